@@ -3,7 +3,7 @@
 (fit: kernel matrix + Cholesky + inverse factor + alpha;  sweep: cross-kernel + triangular
 contraction + EI/UCB/PI + arg-max) over a synthetic batch that is resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W [--config c3]
+    python bench.py --gpus N --steps K --warmup W [--config c3] [--full] [--dump-outputs DIR]
 
 N > 1: one rank per GPU under torch.distributed.run.  The driver starts the ranks itself; invoked
 plainly (`python bench.py --gpus 8`, no RANK in the environment) this script starts them as a CHILD
@@ -13,6 +13,11 @@ SURVEY.md 8e shard it; --weak gives every GPU M candidates of its own instead); 
 is one all-gather of the per-rank winner records (RCCL), read from the device buffer the sweep
 packed them into.
 Rank 0 prints ONE JSON line (contract in the task statement; BASELINE.json names the metric).
+
+A plain run sets up, warms up, times the steps and prints the line.  Everything else it can measure -- the opt-in
+schedule and arithmetic, the full-vector sweep, the plugin-class leg, the CPU baselines, the hyper objective's
+per-stage event loop -- runs only under --full.  --dump-outputs DIR writes what the last timed step handed back
+(winner, fit scalars) as DIR/<name>.npy in float64, for comparing two builds output for output.
 """
 import argparse
 import json
@@ -91,7 +96,7 @@ def build_step(gp, cfg, X, y, ls, inc, world, offset, rec, backend, m_local=None
     empty = m_local is not None and m_local == 0
 
     def step():
-        gp.fit(X, y, cfg["kind"], 1.0, ls, cfg["noise"], 1e-10, True)
+        fit = gp.fit(X, y, cfg["kind"], 1.0, ls, cfg["noise"], 1e-10, True)
         if empty:
             r = dict(best_val=float("-inf"), best_idx=0, n_clamped=0, sweep_ms=0.0)
             if rec is not None:
@@ -107,8 +112,16 @@ def build_step(gp, cfg, X, y, ls, inc, world, offset, rec, backend, m_local=None
             else:
                 v, row, gi = exchange_winner(gp, r, rec, offset, backend)
             r = dict(r, job_best_val=v, job_best_row=row, job_best_idx=gi)
+        r["fit"] = fit
         return r
     return step
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one float64 .npy per named output of the timed path's last step"""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64).reshape(-1))
 
 
 def plugin_leg(cfg, X, y, ls, inc, device, c_abi_ms, reps=3):
@@ -289,6 +302,19 @@ def hyper_bench(args):
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
     call_dev_ms = float(np.median([t["fit_ms"] for t in tim]))      # a polled call (up to N = 4096): the WHOLE evaluation, from the kernels' own clock
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"lml": lml, "grad": grad})
+    out = {
+        "metric": "hyper-parameter objective evaluations/sec (log marginal likelihood + gradient, N training)",
+        "value": 1.0 / dt, "unit": "evals/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "hyper: one tgp_fit_grad evaluation, 16D matern52 ARD, N=%d" % N, "N": N, "D": D},
+        "call_device_ms": call_dev_ms,
+    }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
     # The stage times come from event records between the launches, which a polled call does not make: a second, shorter
     # loop with the per-launch profiling on (tgp_profile_enable: round 5's events + stream synchronisation) supplies them.
     # `value` / `ms_per_step` belong to the default calls above.
@@ -315,13 +341,8 @@ def hyper_bench(args):
              "ms": med["grad_kinv_ms"], "algorithmic_flops": kinv_flops,
              "achieved": kinv_flops / (med["grad_kinv_ms"] * 1e-3) / 1e12,
              "frac": kinv_flops / (med["grad_kinv_ms"] * 1e-3) / 1e12 / PEAK_TFLOPS["f64"]})
-    out = {
-        "metric": "hyper-parameter objective evaluations/sec (log marginal likelihood + gradient, N training)",
-        "value": 1.0 / dt, "unit": "evals/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "hyper: one tgp_fit_grad evaluation, 16D matern52 ARD, N=%d" % N, "N": N, "D": D},
-        "device_ms": dev_ms, "stages_ms": med, "call_device_ms": call_dev_ms,
+    out.update({
+        "device_ms": dev_ms, "stages_ms": med,
         "ms_per_step_with_events": dt_events * 1e3,
         "stages_note": "stages_ms / device_ms: from event records between the launches (tgp_profile_enable on, a separate loop of %d evaluations); "
                        "ms_per_step / value: the default calls (polled up to N = 4096, no events), call_device_ms their kernels' own start-to-doorbell time" % n_ev,
@@ -332,8 +353,8 @@ def hyper_bench(args):
                      "dominant_grad_kernel": kinv,
                      "fit": {"ms": med["fit_ms"], "algorithmic_flops": 2.0 * float(N) ** 3 / 3.0,
                              "frac": 2.0 * float(N) ** 3 / 3.0 / (med["fit_ms"] * 1e-3) / 1e12 / PEAK_TFLOPS["f64"]}},
-    }
-    if not args.no_cpu_baseline:
+    })
+    if not args.no_cpu_baseline:      # (--full only: the plain run has returned above)
         from oracle import gp_oracle as o
         try:
             from threadpoolctl import threadpool_info
@@ -416,6 +437,13 @@ def main():
     ap.add_argument("--no-plugin", action="store_true",
                     help="skip the untimed-for-the-headline `plugin` leg (the same step through HipGPSurrogate / EI|PI|UCB / "
                          "CandidateSweep, three candidate sources)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the opt-in schedule and f32h2 arithmetic, the "
+                         "full-vector sweep, the plugin leg, the CPU baselines (--config hyper: the per-stage event loop "
+                         "and its roofline).  Off by default: a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (winner value / index / row, the fit's LML, y mean "
+                         "and y std; --config hyper: LML and gradient) as DIR/<name>.npy in float64")
     ap.add_argument("--shard-of", type=int, default=1, metavar="G",
                     help="ONE GPU running rank 0's share of a G-way strong split (ceil(M / G) candidates, no exchange): "
                          "the compute side of the scaling curve measured where no multi-GPU node is at hand; the line "
@@ -516,8 +544,9 @@ def main():
     fit_ms, sweep_ms = [], []
     fence()
     t0 = time.perf_counter()
+    r_last = None
     for _ in range(args.steps):
-        step()
+        r_last = step()
         p = gp.profile_read()
         fit_ms.append(p["last_fit_ms"])
         sweep_ms.append(p["last_sweep_ms"])
@@ -526,12 +555,19 @@ def main():
     prof1 = prof_now()
     prof = {k: (prof1[k] - prof0[k]) if k in ("trmm_launches", "trmm_ms", "kstar_launches", "kstar_ms", "trmm_flops") else prof1[k] for k in prof1}
     trmm_flops = prof["trmm_flops"]
+    if args.dump_outputs and rank == 0 and r_last is not None:
+        lml, y_mean, y_std = r_last["fit"]
+        if world > 1:
+            best = {"best_val": r_last["job_best_val"], "best_idx": r_last["job_best_idx"], "best_row": r_last["job_best_row"]}
+        else:
+            best = {"best_val": r_last["best_val"], "best_idx": r_last["best_idx"], "best_row": gp.get_candidate(r_last["best_idx"])}
+        dump_outputs(args.dump_outputs, dict(best, n_clamped=r_last["n_clamped"], lml=lml, y_mean=y_mean, y_std=y_std))
     # Outside the timed region: a few steps under the strictly SERIAL schedule, so that the line also carries the fit's and
     # the sweep's own durations (under --overlap the fit's event bracket contains the sweep's front): what roofline.fit and
     # amdahl_bound are formed from.  Never part of `value`.
     serial = None
     overlapped = None
-    if args.overlap == 0 and hasattr(gp, "set_overlap") and not standin and m_local > 0:
+    if args.full and args.overlap == 0 and hasattr(gp, "set_overlap") and not standin and m_local > 0:
         # the opt-in schedule (tgp_set_overlap(2): CandidateSweep(prefetch_next=True) arms it) on the same handle, outside
         # the timed region: never part of `value`
         gp.set_overlap(2)
@@ -549,7 +585,7 @@ def main():
                       "evals_per_s": m_job / float(np.median(ts[1:])),
                       "note": "tgp_set_overlap(2) on the same handle, 3 steps outside the timed region (rank 0's own clock): the front of the "
                               "sweep runs inside the fit; opt-in (CandidateSweep(prefetch_next=True)), NOT the headline"}
-    if args.overlap > 0 and hasattr(gp, "set_overlap") and not standin:
+    if args.full and args.overlap > 0 and hasattr(gp, "set_overlap") and not standin:
         gp.set_overlap(0)
         ts, fs, ss = [], [], []
         for _ in range(4):
@@ -566,11 +602,11 @@ def main():
     # also the variant that hands the whole (M,) acquisition vector to the host
     # (outside the timed region; wall clock around the call, D2H included)
     full_s = []
-    for _ in range(3 if m_local > 0 else 0):
+    for _ in range(3 if (args.full and m_local > 0) else 0):
         t1 = time.perf_counter()
         gp.sweep(ACQ_ENUM[cfg["acq"]], -1.0, inc, cfg["param"], want_acq=True)
         full_s.append(time.perf_counter() - t1)
-    full_vec_s = float(np.median(full_s)) if full_s else float("inf")
+    full_vec_s = float(np.median(full_s)) if full_s else None
     prof_all = prof_now()
     gp.profile_enable(False)
 
@@ -584,7 +620,7 @@ def main():
     # (f32 accuracy from two scaled fp16 planes on the fp16 matrix pipe), same
     # shard, same protocol, and whether it picks the same winner.  Reported under "opt_in".
     opt_in = None
-    if cfg["dtype"] == "f32" and not args.no_opt_in and not standin:
+    if args.full and cfg["dtype"] == "f32" and not args.no_opt_in and not standin:
         r_main = step()
         gp2 = ta.NativeGP(local_rank, "f32h2")
         gp2.fit(X, y, cfg["kind"], 1.0, ls, cfg["noise"], 1e-10, True)
@@ -693,7 +729,7 @@ def main():
             "sweep_evals_per_s": (total / (sweep_med * 1e-3)) if sweep_med > 0 else None,
             "amdahl_bound": {"speedup_max_by_gpus": amdahl, "fit_ms_replicated": fit_own, "sweep_ms_one_gpu": sweep_1gpu,
                              "note": "fixed M over G GPUs with the fit replicated: (fit + sweep) / (fit + sweep / G) of the SERIAL schedule, before any exchange"},
-            "sweep_full_vector_evals_per_s_per_gpu": m_local / full_vec_s,
+            "sweep_full_vector_evals_per_s_per_gpu": (m_local / full_vec_s) if full_vec_s else (0.0 if args.full else None),
             "roofline": {"bound": "mfma", "kernel": ("trmm_sumsq_bf16x3_kernel (6 bf16 MFMA flops per algorithmic flop, bf16 dense peak)" if cfg["dtype"] == "f32x3" else "trmm_sumsq_f16x2_kernel (3 fp16 MFMA flops per algorithmic flop, fp16 dense peak)") if x3 else "trmm_sumsq_glds[_big]_kernel",
                          "achieved": achieved, "peak": peak, "unit": "TFLOP/s",
                          "frac": achieved / peak, "traffic": traffic, "traffic_source": traffic_source,
@@ -716,9 +752,9 @@ def main():
         if standin:
             out["standin"] = "%s: a CPU stand-in context of the test suite, NOT a measurement" % standin
             out["value"] = None
-        if world == 1 and not args.no_plugin and not standin and args.shard_of == 1 and args.dtype is None:
+        if args.full and world == 1 and not args.no_plugin and not standin and args.shard_of == 1 and args.dtype is None:
             out["plugin"] = plugin_leg(cfg, X, y, ls, inc, local_rank, ms_per_step)
-        if world == 1 and not args.no_cpu_baseline and not standin:
+        if args.full and world == 1 and not args.no_cpu_baseline and not standin:
             out["cpu_baseline"] = cpu_baseline(cfg, X, y, Xc, ls)
             sk = sklearn_leg(cfg, X, y, Xc, ls)
             if sk is not None:

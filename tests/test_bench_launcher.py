@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -31,6 +33,30 @@ def test_bench_gpus2_starts_its_own_ranks_and_prints_one_line():
     assert out["scaling"] == "strong" and out["config"]["M_per_gpu"] == 32768 and out["config"]["M_total"] == 65536
     assert set(out["amdahl_bound"]["speedup_max_by_gpus"]) == {"2", "4", "8"}
     assert "standin" in out and out["value"] is None      # a rehearsal says so and carries no number
+
+
+def test_bench_dump_outputs_are_the_last_steps_and_repeat_run_to_run(tmp_path):
+    """--dump-outputs DIR: the job's winner (value, global index, row) and the fit's LML / y mean / y std as float64
+    .npy files, identical from run to run (fixed seeds), the row the one at that index of the config's batch"""
+    sys.path.insert(0, ROOT)
+    import bench
+    env = {"BENCH_BACKEND": "gloo", "BENCH_TEST_CONTEXT": "oracle_context:OracleBackedContext", "OMP_NUM_THREADS": "2"}
+    dumps = []
+    for run in ("a", "b"):
+        res = _run(env, "--gpus", "2", "--config", "c1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / run))
+        assert res.returncode == 0, res.stderr[-3000:]
+        out = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        assert out["sweep_full_vector_evals_per_s_per_gpu"] is None      # (a --full leg)
+        names = sorted(os.listdir(str(tmp_path / run)))
+        assert names == sorted(k + ".npy" for k in ("best_val", "best_idx", "best_row", "n_clamped", "lml", "y_mean", "y_std"))
+        dumps.append({n: np.load(str(tmp_path / run / n)) for n in names})
+    for n, a in dumps[0].items():
+        assert a.dtype == np.float64
+        np.testing.assert_array_equal(a, dumps[1][n])
+    cfg = bench.CONFIGS["c1"]
+    Xc = bench.synth(cfg, 0, cfg["M"])[2]
+    np.testing.assert_array_equal(dumps[0]["best_row.npy"], Xc[int(dumps[0]["best_idx.npy"][0])])
 
 
 def test_bench_launcher_hands_back_the_ranks_failure():

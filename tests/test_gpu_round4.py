@@ -81,6 +81,34 @@ def test_bench_gpus2_launches_its_own_ranks_on_the_gpu_box():
     assert out["roofline"]["launches"] > 0
 
 
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """`python bench.py --config c1 --steps 3 --warmup 1 --dump-outputs DIR` on one GPU: the plain line (no --full legs),
+    `steps` timed steps, and the dumped winner and fit scalars held to the oracle on the same synthetic inputs"""
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import gp_oracle as o
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c1", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["dtype"] == "f64"
+    assert not {"cpu_baseline", "plugin", "opt_in"} & set(out) and out["overlapped_schedule"] is None
+    d = {k: np.load(str(tmp_path / (k + ".npy"))) for k in ("best_val", "best_idx", "best_row", "n_clamped", "lml", "y_mean", "y_std")}
+    assert all(a.dtype == np.float64 for a in d.values())
+    cfg = dict(bench.CONFIGS["c1"])
+    X, y, Xc, ls = bench.synth(cfg, 0, cfg["M"])
+    om = o.fit(X, y, cfg["kind"], 1.0, ls, cfg["noise"], 1e-10, True)
+    mu, sg = o.predict(om, Xc, True, chunk=16384)
+    acq = o.acquisition(cfg["acq"], mu, sg, "min", cfg["param"], float(y.min()))
+    bi = int(d["best_idx"][0])
+    np.testing.assert_array_equal(d["best_row"], Xc[bi])
+    assert d["best_val"][0] == pytest.approx(acq[bi], rel=1e-6) and d["best_val"][0] >= acq.max() - 1e-6 * abs(acq.max())
+    assert d["lml"][0] == pytest.approx(om.lml, rel=1e-8)
+    assert d["y_mean"][0] == pytest.approx(float(y.mean()), rel=1e-12) and d["y_std"][0] == pytest.approx(float(y.std()), rel=1e-12)
+
+
 # ---- the one-launch sweep for 128 < N <= 512 (mid_sweep_kernel: 64 candidates per workgroup up to N = 256, 32 above) ----
 RTOL = 1e-5          # BASELINE.json north_star: 1e-5 rtol (fp64) on mean / variance / acquisition
 VAR_ATOL = 1e-9      # x (c + noise) y_std^2: the variance cancels near observed points
