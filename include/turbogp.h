@@ -252,6 +252,35 @@ int tgp_winner_wait(tgp_handle h, void *stream);
 int tgp_acq_grad(tgp_handle h, const double *Xq, int64_t m, int acq, double sf, double incumbent,
                  double param, double *val, double *grad);
 
+/* Greedy selection of q candidates for W parallel workers, conditioned on P trials still running.  The reference stubs
+ * this out (turbo/optimiser.py:44-45 `#self.parallel_strategy = None#TODO`, the commented-out run_async /
+ * _next_async_trial of :361-396); the author's older library documents the strategies
+ * (old_library/bayesian_optimiser.py:76-103) and implements Kriging Believer at :527-566.
+ * From the fitted handle and the resident candidate batch (M rows): condition on the pending points Xp (P, D) in order,
+ * then select q rows one after the other.  Each new point z gets a fantasy value in raw units --
+ *   TGP_BATCH_KB  the posterior mean at z given every earlier point (Kriging Believer)
+ *   TGP_BATCH_CL  `lie` (Constant Liar; finite)
+ * -- and conditioning is exactly what a refit on the augmented data would predict with the kernel hyper-parameters,
+ * the jitter and y_mean / y_std of the real observations held (the fantasy enters as (y - y_mean) / y_std, noise and
+ * jitter on the augmented diagonal, no noise in the cross-kernel).  For EI / PI the incumbent after each fantasy is
+ * the best of (incumbent, fantasies so far) in the direction of sf (old_library/bayesian_optimiser.py:509); UCB and
+ * TGP_ACQ_SIGMA do not use it; TGP_ACQ_NONE is TGP_BAD_ARG.  Each selection is the arg-max over the rows not yet
+ * selected in this call (lowest index on ties, NaN never wins); with q = 1 and P = 0 it is tgp_sweep's best_idx /
+ * best_val bit for bit.  The fit and the batch are unchanged by the call.
+ *   q          1 <= q <= M, P + q <= 64 (else TGP_BAD_ARG)
+ *   Xp         (P, D) pending points, NULL when P == 0
+ *   idx_out, val_out   (q) candidate index and acquisition value of each selection
+ *   x_out      (q, D) the selected rows (nullable);  fantasy_out (P + q) the fantasies, pending first (nullable)
+ *   mu_out, sigma_out  (M) posterior after all P + q points (nullable; asking for them costs one more pass)
+ *   n_clamped  (nullable) variances clamped at 0, summed over the sweep and every step
+ * TGP_NOT_PD when a pivot of the augmented factor is <= 0 or not finite (a pending point duplicating a training point
+ * with noise 0).  The step arithmetic is f64 whatever the handle's dtype.  GPU only: TGP_BAD_ARG
+ * on host handles. */
+enum tgp_batch_strategy { TGP_BATCH_KB = 0, TGP_BATCH_CL = 1 };
+int tgp_sweep_batch(tgp_handle h, int64_t q, int strategy, double lie, const double *Xp, int64_t P, int acq, double sf,
+                    double incumbent, double param, int64_t *idx_out, double *val_out, double *x_out,
+                    double *fantasy_out, double *mu_out, double *sigma_out, int64_t *n_clamped);
+
 /* The sweep of tgp_sweep, returning the k <= 64 BEST candidates instead of the single best:
  * vals[0..k) descending, idxs[0..k) their indices (lowest index first among equal values, NaN
  * last, -1 when the batch holds fewer than k candidates).  This is

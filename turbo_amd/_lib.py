@@ -32,6 +32,7 @@ F64, F32, F32X3, F32H2 = 0, 1, 2, 3
 KERNELS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3}
 ACQ_NONE, ACQ_UCB, ACQ_PI, ACQ_EI, ACQ_SIGMA = 0, 1, 2, 3, 4
 BUF_K, BUF_L, BUF_LINV, BUF_ALPHA = 0, 1, 2, 3
+BATCH_KB, BATCH_CL = 0, 1    # tgp_sweep_batch strategies: Kriging Believer, Constant Liar
 
 # every symbol include/turbogp.h declares
 SYMBOLS = (
@@ -40,7 +41,7 @@ SYMBOLS = (
     "tgp_fit_append", "tgp_export_state", "tgp_import_state", "tgp_export_factor_dev", "tgp_import_factor_dev", "tgp_debug_read",
     "tgp_set_candidates", "tgp_set_candidates_dev", "tgp_gen_candidates", "tgp_gen_candidates_lhs", "tgp_lhs_design",
     "tgp_read_candidates", "tgp_get_candidate",
-    "tgp_sweep", "tgp_sweep_topk", "tgp_set_winner_out", "tgp_winner_wait", "tgp_acq_grad", "tgp_acq_refine", "tgp_acq_lbfgsb",
+    "tgp_sweep", "tgp_sweep_batch", "tgp_sweep_topk", "tgp_set_winner_out", "tgp_winner_wait", "tgp_acq_grad", "tgp_acq_refine", "tgp_acq_lbfgsb",
     "tgp_evaluate", "tgp_predict_batch", "tgp_predict", "tgp_profile_enable", "tgp_profile_read", "tgp_profile_reset",
     "tgp_sweep_geometry", "tgp_last_timings",
     "tgp_multi_create", "tgp_multi_destroy", "tgp_multi_last_error", "tgp_multi_size", "tgp_multi_handle",
@@ -133,6 +134,8 @@ def _argtypes():
         "tgp_get_candidate": [_vp, c.c_int64, _dp],
         "tgp_sweep": [_vp, c.c_int, c.c_double, c.c_double, c.c_double, _dp, _dp, _dp, _dp, _i64p, _i64p],
         "tgp_sweep_topk": [_vp, c.c_int, c.c_double, c.c_double, c.c_double, c.c_int64, _dp, _i64p, _i64p],
+        "tgp_sweep_batch": [_vp, c.c_int64, c.c_int, c.c_double, _dp, c.c_int64, c.c_int, c.c_double, c.c_double,
+                            c.c_double, _i64p, _dp, _dp, _dp, _dp, _dp, _i64p],
         "tgp_acq_refine": [_vp, _dp, c.c_int64, _dp, _dp, c.c_int, c.c_double, c.c_double, c.c_double,
                            c.c_int64, _dp, _dp, _i64p, _i64p],
         "tgp_acq_lbfgsb": [_vp, _dp, c.c_int64, _dp, _dp, c.c_int, c.c_double, c.c_double, c.c_double,
@@ -651,6 +654,31 @@ class NativeGP:
                                        ctypes.byref(bi), ctypes.byref(nc)))
         return dict(mu=mu, sigma=sg, acq=aq, best_val=bv.value, best_idx=bi.value,
                     n_clamped=nc.value, sweep_ms=self.profile_read()['last_sweep_ms'])
+
+    def sweep_batch(self, q, strategy=BATCH_KB, lie=0.0, pending=None, acq=ACQ_EI, sf=1.0, incumbent=0.0, param=0.0,
+                    want_posterior=False):
+        """``tgp_sweep_batch``: q resident candidates chosen greedily under Kriging Believer / Constant Liar, conditioned
+        on the pending points (P, D) first.  Returns a dict: idx (q,), val (q,), x (q, D), fantasies (P + q,) pending
+        first, mu / sigma (M,) after all P + q points (want_posterior) or None, n_clamped"""
+        q = int(q)
+        Xp = None if pending is None else _f64c(np.atleast_2d(pending))
+        if Xp is not None and Xp.size == 0:
+            Xp = None
+        P = 0 if Xp is None else Xp.shape[0]
+        if Xp is not None:
+            assert Xp.ndim == 2 and Xp.shape[1] == self.D, "pending points must be (P, %d)" % self.D
+        idx = np.empty(max(q, 1), dtype=np.int64)
+        val = np.empty(max(q, 1))
+        x = np.empty((max(q, 1), self.D))
+        fant = np.empty(max(P + q, 1))
+        mu = np.empty(self.M) if want_posterior else None
+        sg = np.empty(self.M) if want_posterior else None
+        nc = ctypes.c_int64(0)
+        self._check(self.lib.tgp_sweep_batch(self._h, q, int(strategy), float(lie), _ptr(Xp), P, int(acq), float(sf),
+                                             float(incumbent), float(param), idx.ctypes.data_as(_i64p), _ptr(val),
+                                             _ptr(x), _ptr(fant), _ptr(mu), _ptr(sg), ctypes.byref(nc)))
+        return dict(idx=idx[:q], val=val[:q], x=x[:q], fantasies=fant[:P + q], mu=mu, sigma=sg, n_clamped=nc.value,
+                    sweep_ms=self.profile_read()['last_sweep_ms'])
 
     def sweep_topk(self, k, acq, sf=1.0, incumbent=0.0, param=0.0):
         """the k best resident candidates: (indices (k,), values (k,)), best first"""

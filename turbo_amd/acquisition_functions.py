@@ -136,6 +136,40 @@ class AcquisitionFunction:
             keep = idx >= 0
             return idx[keep], vals[keep]
 
+        BATCH_STRATEGIES = {'kriging_believer': _lib.BATCH_KB, 'constant_liar': _lib.BATCH_CL}
+
+        def maximise_batch(self, X, q, strategy='kriging_believer', lie='min', pending=None, want_posterior=False):
+            """q rows of X chosen greedily for q parallel workers (``tgp_sweep_batch``), conditioned first on the
+            ``pending`` points (P, D) -- trials still under evaluation.  Every chosen or pending point is given a
+            fantasy value -- 'kriging_believer': the posterior mean there; 'constant_liar': ``lie``, a float in raw y
+            units or 'min' / 'max' / 'mean' of the model's observed y -- and the model is conditioned on it with the
+            hyper-parameters held (old_library/bayesian_optimiser.py:76-103, :527-566).  X None: the batch already
+            resident on the model's GPU context.  Returns the dict of ``NativeGP.sweep_batch`` (idx, val, x, fantasies,
+            mu, sigma, n_clamped, sweep_ms)."""
+            if not _is_native(self.model):
+                raise NotImplementedError('maximise_batch runs on the GPU only: it needs a model built by HipGPSurrogate '
+                                          '(got {!r})'.format(type(self.model)))
+            if strategy not in self.BATCH_STRATEGIES:
+                raise ValueError('strategy must be one of {}'.format(sorted(self.BATCH_STRATEGIES)))
+            acq, incumbent, param = self._native_args()
+            lie_value = 0.0
+            if strategy == 'constant_liar':
+                y = np.asarray(self.model.y, dtype=np.float64)
+                if isinstance(lie, str):
+                    if lie not in ('min', 'max', 'mean'):
+                        raise ValueError("lie must be a float or one of 'min', 'max', 'mean'")
+                    lie_value = float(getattr(np, lie)(y))
+                else:
+                    lie_value = float(lie)
+            ctx = self.model._ensure_resident()
+            if X is not None:
+                ctx.set_candidates(np.asarray(X, dtype=np.float64))
+            res = ctx.sweep_batch(q, self.BATCH_STRATEGIES[strategy], lie_value, pending, acq, self.scale_factor,
+                                  incumbent, param, want_posterior=want_posterior)
+            self.last_sweep_ms = res.get('sweep_ms')
+            res['lie'] = lie_value if strategy == 'constant_liar' else None
+            return res
+
         def refine(self, starting_points, bounds, max_iter=200):
             """the gradient stage on the GPU (``tgp_acq_refine``): every restart refined by a projected
             L-BFGS, together (N <= 128: each in its own workgroup of one launch); returns

@@ -146,6 +146,47 @@ class CandidateSweep:
         self.last_batches = None
         self._calls = 0
 
+    def select_batch(self, latent_bounds, acq, q, strategy='kriging_believer', lie='min', pending=None):
+        """q points for q parallel workers from ONE batch of candidates, drawn exactly as ``__call__`` draws it, chosen
+        greedily with Kriging Believer / Constant Liar and conditioned first on ``pending`` (P, D): the trials still
+        running (``FunctionInstance.maximise_batch``, ``tgp_sweep_batch``).  Returns (x (q, D), info) with info =
+        {'max_acq' (q,), 'candidate_indices' (q,), 'fantasies' (q,), 'pending_fantasies' (P,), 'strategy'}."""
+        if self.grad_restarts > 0:
+            raise NotImplementedError('select_batch: no gradient refinement of the selected points (grad_restarts > 0)')
+        rank, world = dist_info() if self.shard else (0, 1)
+        if world > 1:
+            raise NotImplementedError('select_batch: one process only (a batch sharded over ranks needs an all-gather '
+                                      'per selection)')
+        if not hasattr(acq, 'maximise_batch') or not _native_acq(acq) or getattr(acq, 'model', None) is None:
+            raise NotImplementedError('select_batch needs a native acquisition over a model built by HipGPSurrogate '
+                                      '(got {!r})'.format(type(getattr(acq, 'model', acq))))
+        bounds = [(lb[1], lb[2]) for lb in latent_bounds.ordered]
+        if pending is not None:
+            pending = np.asarray(pending, dtype=np.float64).reshape(-1, len(bounds))
+        if self.device_rng_seed is not None:
+            # the batch maximise_generated would draw for this call (or has prefetched), left resident
+            low, high = zip(*bounds)
+            ctx = acq.model._ensure_resident()
+            seed, lhs_total = self.device_rng_seed + self._calls, (self.num_random if self.device_design == 'lhs' else None)
+            lo_b, hi_b = np.asarray(low, dtype=np.float64).tobytes(), np.asarray(high, dtype=np.float64).tobytes()
+            key = ("lhs" if lhs_total is not None else "uniform", int(seed), 0, int(self.num_random),
+                   int(lhs_total) if lhs_total is not None else None, lo_b, hi_b)
+            if getattr(ctx, 'gen_key', None) != key:
+                if lhs_total is not None:
+                    ctx.gen_candidates_lhs(seed, 0, self.num_random, lhs_total, low, high)
+                else:
+                    ctx.gen_candidates(seed, 0, self.num_random, low, high)
+            res = acq.maximise_batch(None, q, strategy, lie, pending)
+        else:
+            res = acq.maximise_batch(self.gen_random(self.num_random, latent_bounds), q, strategy, lie, pending)
+        self._calls += 1
+        P = 0 if pending is None else len(pending)
+        info = {'max_acq': res['val'], 'candidate_indices': res['idx'], 'fantasies': res['fantasies'][P:],
+                'pending_fantasies': res['fantasies'][:P], 'strategy': strategy}
+        if res.get('sweep_ms') is not None:
+            info['sweep_ms'] = res['sweep_ms']
+        return np.asarray(res['x'], dtype=np.float64), info
+
     def __call__(self, latent_bounds, acq):
         """Returns: x (1, num_attribs) within the bounds, {'max_acq': value}"""
         bounds = [(lb[1], lb[2]) for lb in latent_bounds.ordered]

@@ -1,0 +1,471 @@
+// batch_kernels.hip -- greedy selection of q candidates with Kriging Believer / Constant Liar (tgp_sweep_batch).
+//
+// The reference stubs batch selection out (turbo/optimiser.py:44-45, :361-396); the author's older library shipped it
+// (old_library/bayesian_optimiser.py:76-103, Kriging Believer :527-566, the incumbent over real AND hypothesised costs
+// :509).  With the hyper-parameters and the normalisation held, conditioning on one more (fantasised) observation z_j
+// changes every candidate's posterior by a rank-1 update (normalised units; G (M x j) holds the scaled cross-covariance
+// columns of the points conditioned so far, R (j x j) their block of the augmented factor):
+//
+//   w_j     = K^-1 k*(z_j)                                       (launch_query_front: two triangular products with Linv)
+//   R[j,i]  = (S[j,i] - sum_{l<i} R[j,l] R[i,l]) / R[i,i],   R[j,j] = sqrt(S[j,j] - sum_{l<j} R[j,l]^2)
+//             with S[j,i] = c k(z_j, z_i) - k*(z_i).w_j  and  S[j,j] = c + noise + jitter - k*(z_j).w_j
+//   c(x)    = c k(x, z_j) - k*(x).w_j - sum_{i<j} G[x,i] R[j,i]                    (every candidate x)
+//   G[x,j]  = c(x) / R[j,j],   var(x) -= G[x,j]^2 (clamped at 0, counted),   mu(x) += G[x,j] e_j
+//   e_j     = (y~_j - mu~_{j-1}(z_j)) / R[j,j],   mu~_{j-1}(z_j) = k*(z_j).alpha + sum_{i<j} R[j,i] e_i   (KB: e_j = 0)
+//
+// bt_small_kernel forms the R row, the fantasy and e_j for one point (one workgroup); bt_pass_kernel is the one O(M N D)
+// pass per point -- kstar_kernel's tiles (sweep_kernels.hip) with w_j in place of alpha and no slab written; bt_update_kernel
+// applies the update, evaluates the acquisition with finalize_kernel's arithmetic and leaves per-block arg-max partials
+// that bt_argmax_kernel turns into the next selection, in device memory.  Everything here is f64, whatever the handle's
+// sweep dtype.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "pairwise.hpp"
+#include "tgp_internal.hpp"
+
+namespace tgp {
+
+#define TGP_TRY(x)                         \
+    do {                                   \
+        hipError_t e_ = (x);               \
+        if (e_ != hipSuccess) return e_;   \
+    } while (0)
+
+constexpr int BT_CT = 64;          // candidates per tile of the pass (AR = 4)
+constexpr int BT_BLOCK = 256;      // candidates per block of the update = per arg-max partial
+
+// Cs (Mpad, Dp) = candidates / length scales, rows >= M and columns >= D zero
+__global__ __launch_bounds__(256) void bt_prep_kernel(const double *__restrict__ cand, const double *__restrict__ ls,
+                                                      double *__restrict__ Cs, long M, long Mpad, int D, int Dp) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= Mpad * Dp) return;
+    const long r = e / Dp;
+    const int d = (int)(e - r * Dp);
+    Cs[e] = (r < M && d < D) ? cand[r * D + d] / ls[d] : 0.0;
+}
+
+// the state the steps update: var~ = (sigma / s_y)^2 of the first sweep, its means, no row selected
+__global__ __launch_bounds__(256) void bt_init_kernel(const double *__restrict__ mu0, const double *__restrict__ sg0,
+                                                      double *__restrict__ mu, double *__restrict__ var,
+                                                      unsigned char *__restrict__ mask, long M, double y_std) {
+    const long x = (long)blockIdx.x * 256 + threadIdx.x;
+    if (x >= M) return;
+    const double s = sg0[x] / y_std;
+    mu[x] = mu0[x];
+    var[x] = s * s;
+    mask[x] = 0;
+}
+
+
+// selection k's candidate row -> the raw coordinates of conditioned point j.  from_rec: selection 0 is the first sweep's
+// arg-max, read from its result record [value, index, clamp count]
+__global__ __launch_bounds__(64) void bt_point_kernel(const double *__restrict__ rec, BtSmall s, int k,
+                                                      const double *__restrict__ cand, double *__restrict__ zraw,
+                                                      unsigned char *__restrict__ mask, long M, int D) {
+    long long idx;
+    if (rec) {
+        idx = (long long)rec[1];
+        if (idx < 0 || idx >= M) idx = 0;
+        if (threadIdx.x == 0) {
+            s.sel_idx[k] = idx;
+            s.sel_val[k] = rec[0];
+            mask[idx] = 1;
+        }
+    } else {
+        idx = s.sel_idx[k];
+    }
+    for (int d = threadIdx.x; d < D; d += 64) zraw[d] = cand[idx * D + d];
+}
+
+__device__ __forceinline__ double bt_block_sum(double v, double *red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// one workgroup: R row j, the fantasy of point j, e_j, the incumbent
+template <int KIND>
+__global__ __launch_bounds__(256) void bt_small_kernel(const double *__restrict__ Kz, const double *__restrict__ w,
+                                                       const double *__restrict__ alpha, const double *__restrict__ Zs,
+                                                       BtSmall s, int j, int N, int Np, int Dp, double constant,
+                                                       double noise, double jitter, double y_mean, double y_std,
+                                                       int kb, double lie, double sf) {
+    __shared__ double red[256];
+    __shared__ double S[BT_MAXP + 1];
+    const int tid = threadIdx.x;
+    for (int i = 0; i <= j; ++i) {
+        const double *k = Kz + (long)i * Np;
+        double a = 0.0;
+        for (int n = tid; n < N; n += 256) a = fma(k[n], w[n], a);
+        a = bt_block_sum(a, red);
+        if (tid == 0) S[i] = a;
+    }
+    {
+        const double *k = Kz + (long)j * Np;
+        double a = 0.0;
+        for (int n = tid; n < N; n += 256) a = fma(k[n], alpha[n], a);
+        a = bt_block_sum(a, red);
+        if (tid == 0) S[BT_MAXP] = a;   // k*(z_j).alpha
+    }
+    __syncthreads();
+    // the cross-kernel between z_j and the earlier points (no noise term)
+    if (tid < j) {
+        const double *zj = Zs + (long)j * Dp, *zi = Zs + (long)tid * Dp;
+        double d2 = 0.0;
+        for (int d = 0; d < Dp; ++d) {
+            const double df = zj[d] - zi[d];
+            d2 = fma(df, df, d2);
+        }
+        S[tid] = kernel_value<double, KIND>(d2, constant) - S[tid];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double *Rj = s.R + (long)j * BT_MAXP;
+        double m = S[BT_MAXP];
+        double piv = ((constant + noise) + jitter) - S[j];
+        for (int i = 0; i < j; ++i) {
+            const double *Ri = s.R + (long)i * BT_MAXP;
+            double t = S[i];
+            for (int l = 0; l < i; ++l) t -= Rj[l] * Ri[l];
+            t /= Ri[i];
+            Rj[i] = t;
+            piv -= t * t;
+            m += t * s.e[i];
+        }
+        if (!(piv > 0.0) || !isfinite(piv)) {
+            if (s.flag[0] == 0) s.flag[0] = j + 1;
+            piv = NAN;
+        }
+        const double rjj = sqrt(piv);
+        Rj[j] = rjj;
+        const double f = kb ? y_std * m + y_mean : lie;
+        s.fant[j] = f;
+        s.e[j] = kb ? 0.0 : ((f - y_mean) / y_std - m) / rjj;
+        const double inc = s.inc[0];
+        s.inc[0] = sf > 0.0 ? (f > inc ? f : inc) : (f < inc ? f : inc);
+    }
+}
+
+// part[s][x] = sum over the training points of split s of c k0(x, X_n) w_n: kstar_kernel's 128 x 128 tiles (f64, AR = 8,
+// direct sums of squared differences from LDS-staged, transposed point blocks) with w in place of alpha, nothing else written
+template <int KIND>
+__global__ __launch_bounds__(256, 2) void bt_pass_kernel(const double *__restrict__ Cs, const double *__restrict__ Xs,
+                                                         const double *__restrict__ w, double *__restrict__ part, int rows,
+                                                         int N, int Np, int Dp, double constant, long ldpart) {
+    using St = KsStage<double>;
+    constexpr int DC = St::DC, LD = St::LD, AR = 4;   // (64 f64 accumulators do not fit: 4 x 8, as kstar_kernel in f64)
+    __shared__ __attribute__((aligned(16))) double Ct[DC][LD];
+    __shared__ __attribute__((aligned(16))) double Xt[DC][LD];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int c0 = blockIdx.x * BT_CT;
+    const int njt = Np / 128;
+    const int per = (njt + (int)gridDim.y - 1) / (int)gridDim.y;
+    const int jt0 = blockIdx.y * per;
+    int jt_end = jt0 + per;
+    if (jt_end > njt) jt_end = njt;
+    const int jt_real = (N + 127) / 128;
+    const int jt_live = jt_end < jt_real ? jt_end : jt_real;
+    auto crow = [&](int a) { return (a < 4 ? 0 : 60) + 4 * ty + a; };
+    auto jcol = [&](int b) { return ((b >> 1) << 5) + 2 * tx + (b & 1); };
+    double pm[AR];
+#pragma unroll
+    for (int a = 0; a < AR; ++a) pm[a] = 0.0;
+    const int nch = (Dp + DC - 1) / DC;
+    const int nsteps = (jt_live > jt0 ? jt_live - jt0 : 0) * nch;
+    const bool one_pass = (nch == 1);
+    const int crows = c0 + BT_CT < rows ? c0 + BT_CT : rows;
+    St sp, sq;
+    double d2[AR][8];
+    if (nsteps > 0) {
+        sp.load(Cs, c0, crows, Dp, 0);
+        sq.load(Xs, jt0 * 128, Np, Dp, 0);
+        sp.store(Ct);
+        sq.store(Xt);
+    }
+    __syncthreads();
+    for (int st = 0; st < nsteps; ++st) {
+        const int jt = jt0 + st / nch, ch = st - (st / nch) * nch;
+        const int j0 = jt * 128;
+        const bool more = (st + 1) < nsteps;
+        if (more) {
+            const int jn = jt0 + (st + 1) / nch, cn = (st + 1) - ((st + 1) / nch) * nch;
+            if (!one_pass) sp.load(Cs, c0, crows, Dp, cn * DC);
+            sq.load(Xs, jn * 128, Np, Dp, cn * DC);
+        }
+        if (ch == 0) {
+#pragma unroll
+            for (int a = 0; a < AR; ++a)
+#pragma unroll
+                for (int b = 0; b < 8; ++b) d2[a][b] = 0.0;
+        }
+        {
+            int dn = Dp - ch * DC;
+            if (dn > DC) dn = DC;
+#pragma unroll 1
+            for (int d4 = 0; d4 < dn; d4 += 4) {
+#pragma unroll
+                for (int dd = 0; dd < 4; ++dd) {
+                    const int d = d4 + dd;
+                    double cv[AR], xv[8];
+#pragma unroll
+                    for (int a = 0; a < AR; ++a) cv[a] = Ct[d][crow(a) + St::rot(d4)];
+#pragma unroll
+                    for (int b = 0; b < 8; ++b) xv[b] = Xt[d][jcol(b) + St::rot(d4)];
+#pragma unroll
+                    for (int a = 0; a < AR; ++a)
+#pragma unroll
+                        for (int b = 0; b < 8; ++b) {
+                            const double df = cv[a] - xv[b];
+                            d2[a][b] = fma(df, df, d2[a][b]);
+                        }
+                }
+            }
+        }
+        if (ch == nch - 1) {
+            double wl[8];
+            const bool edge = j0 + 128 > N;
+#pragma unroll
+            for (int b = 0; b < 8; ++b) wl[b] = (!edge || j0 + jcol(b) < N) ? w[j0 + jcol(b)] : 0.0;
+#pragma unroll
+            for (int a = 0; a < AR; ++a)
+#pragma unroll
+                for (int b = 0; b < 8; ++b) {
+                    const double kv = kernel_value<double, KIND>(d2[a][b], constant);
+                    pm[a] = fma(kv, wl[b], pm[a]);
+                }
+        }
+        if (more) {
+            __syncthreads();
+            if (!one_pass) sp.store(Ct);
+            sq.store(Xt);
+            __syncthreads();
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < AR; ++a) {
+        double s = pm[a];
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (tx == 0) part[(long)blockIdx.y * ldpart + c0 + crow(a)] = s;
+    }
+}
+
+__device__ __forceinline__ double bt_ndtr(double a) {
+    // scipy.special.ndtr (cephes ndtr.c), as finalize_kernel (sweep_kernels.hip)
+    const double x = a * 0.70710678118654752440;
+    const double z = fabs(x);
+    double y;
+    if (z < 0.70710678118654752440) {
+        y = 0.5 + 0.5 * erf(x);
+    } else {
+        y = 0.5 * erfc(z);
+        if (x > 0) y = 1.0 - y;
+    }
+    return y;
+}
+
+struct BtUpd {
+    const double *cand, *ls, *zs;     // raw candidates (M, D), length scales, scaled z_j (Dp)
+    const double *part; int njs; long ldpart;
+    double *G; long ldG; int j; int store;   // column j of G at G + j ldG (store: a later point reads it)
+    BtSmall s;
+    double *mu, *var; unsigned char *mask;
+    long M; int D;
+    double constant, y_mean, y_std;
+    int acq; double sf, param;        // acq == TGP_ACQ_NONE: no selection follows this point
+    double *bval; long long *bidx; unsigned long long *clamp;
+    double *mu_out, *sigma_out;       // nullable: the posterior after the last point
+};
+
+template <int KIND>
+__global__ __launch_bounds__(BT_BLOCK) void bt_update_kernel(BtUpd u) {
+    __shared__ double sv[BT_BLOCK];
+    __shared__ long long si[BT_BLOCK];
+    __shared__ int sclamp;
+    const int tid = threadIdx.x;
+    if (tid == 0) sclamp = 0;
+    __syncthreads();
+    const long x = (long)blockIdx.x * BT_BLOCK + tid;
+    double best = -INFINITY;
+    long long bi = 0x7fffffffffffffffLL;
+    if (x < u.M) {
+        double kdot = 0.0;
+        for (int s = 0; s < u.njs; ++s) kdot += u.part[(long)s * u.ldpart + x];
+        double d2 = 0.0;
+        for (int d = 0; d < u.D; ++d) {
+            const double df = u.cand[x * u.D + d] / u.ls[d] - u.zs[d];
+            d2 = fma(df, df, d2);
+        }
+        double cx = kernel_value<double, KIND>(d2, u.constant) - kdot;
+        const double *Rj = u.s.R + (long)u.j * BT_MAXP;
+        for (int i = 0; i < u.j; ++i) cx -= u.G[(long)i * u.ldG + x] * Rj[i];
+        const double g = cx / Rj[u.j];
+        if (u.store) u.G[(long)u.j * u.ldG + x] = g;
+        double var = u.var[x] - g * g;
+        if (var < 0.0) { var = 0.0; atomicAdd(&sclamp, 1); }
+        u.var[x] = var;
+        double mu = u.mu[x];
+        const double e = u.s.e[u.j];
+        if (e != 0.0) { mu += u.y_std * (g * e); u.mu[x] = mu; }
+        const double sigma = sqrt(var * (u.y_std * u.y_std));
+        if (u.mu_out) u.mu_out[x] = mu;
+        if (u.sigma_out) u.sigma_out[x] = sigma;
+        if (u.acq != TGP_ACQ_NONE && !u.mask[x]) {
+            const double incumbent = u.s.inc[0];
+            double a = 0.0;
+            if (u.acq == TGP_ACQ_UCB) {
+                a = u.sf * mu + u.param * sigma;
+            } else if (u.acq == TGP_ACQ_SIGMA) {
+                a = sigma;
+            } else if (sigma != 0.0) {
+                const double diff = u.sf * (mu - incumbent) - u.param;
+                const double Z = diff / sigma;
+                if (u.acq == TGP_ACQ_PI) {
+                    a = bt_ndtr(Z);
+                } else {
+                    const double pdf = exp(-(Z * Z) / 2.0) / 2.5066282746310002;
+                    a = diff * bt_ndtr(Z) + sigma * pdf;
+                }
+            }
+            if (!isnan(a)) best = a;
+            bi = x;
+        }
+    }
+    sv[tid] = best;
+    si[tid] = bi;
+    __syncthreads();
+    for (int o = BT_BLOCK / 2; o > 0; o >>= 1) {
+        if (tid < o) {
+            const double v2 = sv[tid + o];
+            const long long i2 = si[tid + o];
+            if (v2 > sv[tid] || (v2 == sv[tid] && i2 < si[tid])) { sv[tid] = v2; si[tid] = i2; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        if (u.acq != TGP_ACQ_NONE) { u.bval[blockIdx.x] = sv[0]; u.bidx[blockIdx.x] = si[0]; }
+        if (sclamp) atomicAdd(u.clamp, (unsigned long long)sclamp);
+    }
+}
+
+// selection k = the (value, lowest index) of the partials; the row is masked for the rest of the call
+__global__ __launch_bounds__(256) void bt_argmax_kernel(const double *__restrict__ bval, const long long *__restrict__ bidx,
+                                                        long nblk, BtSmall s, int k, unsigned char *__restrict__ mask,
+                                                        long M) {
+    __shared__ double sv[256];
+    __shared__ long long si[256];
+    double v = -INFINITY;
+    long long i = 0x7fffffffffffffffLL;
+    for (long b = threadIdx.x; b < nblk; b += 256) {
+        const double v2 = bval[b];
+        const long long i2 = bidx[b];
+        if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
+    }
+    sv[threadIdx.x] = v;
+    si[threadIdx.x] = i;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            const double v2 = sv[threadIdx.x + o];
+            const long long i2 = si[threadIdx.x + o];
+            if (v2 > sv[threadIdx.x] || (v2 == sv[threadIdx.x] && i2 < si[threadIdx.x])) {
+                sv[threadIdx.x] = v2;
+                si[threadIdx.x] = i2;
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        long long w = si[0];
+        if (w < 0 || w >= M) w = M - 1;   // (never: q <= M leaves an unmasked row, and every unmasked row takes part)
+        s.sel_idx[k] = w;
+        s.sel_val[k] = sv[0];
+        mask[w] = 1;
+    }
+}
+
+// ---- launchers ----
+#define BT_KIND_DISPATCH(kernel_tmpl, grid, block, ...)                                                          \
+    do {                                                                                                         \
+        switch (c.kernel) {                                                                                      \
+            case TGP_RBF: hipLaunchKernelGGL(kernel_tmpl<TGP_RBF>, grid, block, 0, c.stream, __VA_ARGS__); break; \
+            case TGP_MATERN12: hipLaunchKernelGGL(kernel_tmpl<TGP_MATERN12>, grid, block, 0, c.stream, __VA_ARGS__); break; \
+            case TGP_MATERN32: hipLaunchKernelGGL(kernel_tmpl<TGP_MATERN32>, grid, block, 0, c.stream, __VA_ARGS__); break; \
+            default: hipLaunchKernelGGL(kernel_tmpl<TGP_MATERN52>, grid, block, 0, c.stream, __VA_ARGS__); break; \
+        }                                                                                                        \
+    } while (0)
+
+int bt_pass_splits(const Context &c, int64_t M) {
+    const int64_t tiles = (M + BT_CT - 1) / BT_CT;
+    const int live = (int)((c.N + 127) / 128);
+    int js = (int)std::max<int64_t>(1, 1024 / std::max<int64_t>(tiles, 1));   // about four workgroups per CU
+    return std::min(std::min(js, live), KS_JS);
+}
+
+hipError_t launch_bt_prep(Context &c, double *Cs, int64_t Mpad) {
+    const long n = (long)Mpad * c.Dp;
+    hipLaunchKernelGGL(bt_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.stream, c.d_cand, c.d_ls, Cs,
+                       (long)c.M, (long)Mpad, (int)c.D, (int)c.Dp);
+    return hipGetLastError();
+}
+
+hipError_t launch_bt_init(Context &c, double *mu, double *var, unsigned char *mask) {
+    hipLaunchKernelGGL(bt_init_kernel, dim3((unsigned)((c.M + 255) / 256)), dim3(256), 0, c.stream, c.d_mu, c.d_sigma,
+                       mu, var, mask, (long)c.M, c.y_std);
+    return hipGetLastError();
+}
+
+hipError_t launch_bt_point(Context &c, const double *rec, const BtSmall &s, int k, double *zraw, unsigned char *mask) {
+    hipLaunchKernelGGL(bt_point_kernel, dim3(1), dim3(64), 0, c.stream, rec, s, k, c.d_cand, zraw, mask, (long)c.M,
+                       (int)c.D);
+    return hipGetLastError();
+}
+
+// the front of point j (its vectors into slot j of Kz / Zs) and its small side
+hipError_t launch_bt_condition(Context &c, const BtSmall &s, int j, const double *zraw, double *Kz, double *Zs,
+                               double *hw, double *v, double *w, int kb, double lie, double sf) {
+    TGP_TRY(launch_query_front(c, zraw, Zs + (long)j * c.Dp, Kz + (long)j * c.Np, hw, v, w));
+    BT_KIND_DISPATCH(bt_small_kernel, dim3(1), dim3(256), Kz, w, c.d_alpha, Zs, s, j, (int)c.N, (int)c.Np, (int)c.Dp,
+                     c.constant, c.noise, c.jitter, c.y_mean, c.y_std, kb, lie, sf);
+    return hipGetLastError();
+}
+
+// the pass over every candidate for point j, its update, and (acq != NONE) selection k from the result
+hipError_t launch_bt_step(Context &c, const BtSmall &s, int j, const double *Cs, int64_t ldpart, const double *Zs,
+                          const double *w, double *part, double *G, int store, double *mu, double *var,
+                          unsigned char *mask, int acq, double sf, double param, double *bval, long long *bidx,
+                          unsigned long long *clamp, double *mu_out, double *sigma_out, int k) {
+    const int js = bt_pass_splits(c, c.M);
+    const dim3 gp((unsigned)((c.M + BT_CT - 1) / BT_CT), (unsigned)js);
+    BT_KIND_DISPATCH(bt_pass_kernel, gp, dim3(256), Cs, c.d_Xs, w, part, (int)c.M, (int)c.N, (int)c.Np, (int)c.Dp,
+                     c.constant, (long)ldpart);
+    TGP_TRY(hipGetLastError());
+    BtUpd u{};
+    u.cand = c.d_cand; u.ls = c.d_ls; u.zs = Zs + (long)j * c.Dp;
+    u.part = part; u.njs = js; u.ldpart = ldpart;
+    u.G = G; u.ldG = (long)c.M; u.j = j; u.store = store;
+    u.s = s;
+    u.mu = mu; u.var = var; u.mask = mask;
+    u.M = (long)c.M; u.D = (int)c.D;
+    u.constant = c.constant; u.y_mean = c.y_mean; u.y_std = c.y_std;
+    u.acq = acq; u.sf = sf; u.param = param;
+    u.bval = bval; u.bidx = bidx; u.clamp = clamp;
+    u.mu_out = mu_out; u.sigma_out = sigma_out;
+    const long nblk = (long)((c.M + BT_BLOCK - 1) / BT_BLOCK);
+    BT_KIND_DISPATCH(bt_update_kernel, dim3((unsigned)nblk), dim3(BT_BLOCK), u);
+    TGP_TRY(hipGetLastError());
+    if (acq != TGP_ACQ_NONE) {
+        hipLaunchKernelGGL(bt_argmax_kernel, dim3(1), dim3(256), 0, c.stream, bval, bidx, nblk, s, k, mask, (long)c.M);
+        TGP_TRY(hipGetLastError());
+    }
+    return hipSuccess;
+}
+
+}  // namespace tgp

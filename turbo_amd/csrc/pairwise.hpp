@@ -136,4 +136,40 @@ __device__ __forceinline__ void pairwise_sqdist(const T *__restrict__ P, int p0,
     }
 }
 
+// The 128-point staging of kstar_kernel (sweep_kernels.hip) and bt_pass_kernel (batch_kernels.hip).
+// f32 staging rows: 140 floats, and the rows of dimensions 8 g .. 8 g + 7 start 4 g floats further
+// right (rot): the transposing stores of each half wave (4 points x 8 four-dimension vectors) then
+// fall on 32 distinct banks, where rows of 132 floats put four lanes on each (1.97 M conflict
+// cycles per launch in round 1's counters; 0.66 M with a two-step shift, which this model also predicts).
+template <typename T> struct KsStage {
+    static constexpr int DC = PwCfg<T>::DC, VEC = PwCfg<T>::VEC;
+    static constexpr int LD = 128 + (sizeof(T) == 4 ? 12 : 2);
+    // (f64: rows of 130 doubles, dimensions 8..15 two doubles further right)
+    __device__ static __forceinline__ int rot(int d) { return sizeof(T) == 4 ? ((d >> 3) << 2) : ((d >> 3) << 1); }
+    static constexpr int VPP = DC / VEC;              // 16-byte vectors per point per pass (8)
+    static constexpr int PASSES = 128 * VPP / 256;    // 4
+    typedef T vec_t __attribute__((ext_vector_type(VEC)));
+    vec_t v[PASSES];
+    __device__ __forceinline__ void load(const T *__restrict__ M, int r0, int n, int ld, int d0) {
+#pragma unroll
+        for (int p = 0; p < PASSES; ++p) {
+            const int idx = (int)threadIdx.x + 256 * p;
+            const int r = idx / VPP, dv = (idx % VPP) * VEC;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) v[p][e] = (T)0;
+            if ((d0 + dv) < ld && (r0 + r) < n)
+                v[p] = *reinterpret_cast<const vec_t *>(M + (long)(r0 + r) * ld + d0 + dv);
+        }
+    }
+    __device__ __forceinline__ void store(T (*S)[LD]) const {
+#pragma unroll
+        for (int p = 0; p < PASSES; ++p) {
+            const int idx = (int)threadIdx.x + 256 * p;
+            const int r = idx / VPP, dv = (idx % VPP) * VEC;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) S[dv + e][r + rot(dv)] = v[p][e];   // (dv is a multiple of VEC: one rot per vector)
+        }
+    }
+};
+
 }  // namespace tgp

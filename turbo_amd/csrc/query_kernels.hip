@@ -516,4 +516,41 @@ hipError_t launch_query(Context &c, const double *d_Xq, int m, int acq, double s
     return hipGetLastError();
 }
 
+// The front of launch_query for ONE point, its vectors left where the caller wants them (tgp_sweep_batch: the point
+// conditioned on next, batch_kernels.hip): uq = x / l (Dp), ks = c k0(x, X) (Np, 0 from N on), v = Linv ks,
+// w = Linv^T v = K^-1 k* -- on the matrix-core products whatever TGP_QUERY_MFMA says (one split of w, nothing to add).
+hipError_t launch_query_front(Context &c, const double *d_xq, double *uq, double *ks, double *hw, double *v, double *w) {
+    hipStream_t s = c.stream;
+    const int N = (int)c.N, Np = (int)c.Np, D = (int)c.D, Dp = (int)c.Dp;
+    const dim3 g1((Np + 255) / 256, 1);
+    const size_t sh = (size_t)Dp * sizeof(double);
+    unsigned long long *stamp = nullptr;
+    switch (c.kernel) {
+        case TGP_RBF: hipLaunchKernelGGL(q_kvec_kernel<TGP_RBF>, g1, dim3(256), sh, s, d_xq, c.d_ls, c.d_Xs, uq, ks, hw, N, Np, D, Dp, c.constant, stamp); break;
+        case TGP_MATERN12: hipLaunchKernelGGL(q_kvec_kernel<TGP_MATERN12>, g1, dim3(256), sh, s, d_xq, c.d_ls, c.d_Xs, uq, ks, hw, N, Np, D, Dp, c.constant, stamp); break;
+        case TGP_MATERN32: hipLaunchKernelGGL(q_kvec_kernel<TGP_MATERN32>, g1, dim3(256), sh, s, d_xq, c.d_ls, c.d_Xs, uq, ks, hw, N, Np, D, Dp, c.constant, stamp); break;
+        default: hipLaunchKernelGGL(q_kvec_kernel<TGP_MATERN52>, g1, dim3(256), sh, s, d_xq, c.d_ls, c.d_Xs, uq, ks, hw, N, Np, D, Dp, c.constant, stamp); break;
+    }
+    TGP_TRY(hipGetLastError());
+    const dim3 gr(Np / 16, 1), gc((N + 15) / 16, 1);
+    switch (query_waves(Np)) {
+        case 4:
+            hipLaunchKernelGGL(q_rows_mfma_kernel<4>, gr, dim3(256), 0, s, c.d_Linv, ks, v, Np, 1);
+            TGP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(q_cols_mfma_kernel<4>, gc, dim3(256), 0, s, c.d_Linv, v, w, N, Np, 1);
+            break;
+        case 8:
+            hipLaunchKernelGGL(q_rows_mfma_kernel<8>, gr, dim3(512), 0, s, c.d_Linv, ks, v, Np, 1);
+            TGP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(q_cols_mfma_kernel<8>, gc, dim3(512), 0, s, c.d_Linv, v, w, N, Np, 1);
+            break;
+        default:
+            hipLaunchKernelGGL(q_rows_mfma_kernel<16>, gr, dim3(1024), 0, s, c.d_Linv, ks, v, Np, 1);
+            TGP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(q_cols_mfma_kernel<16>, gc, dim3(1024), 0, s, c.d_Linv, v, w, N, Np, 1);
+            break;
+    }
+    return hipGetLastError();
+}
+
 }  // namespace tgp

@@ -266,6 +266,7 @@ static void free_ws(Context &c) {
     dfree(c.d_Cs); dfree(c.d_Ks[0]); dfree(c.d_Ks[1]); dfree(c.d_part); dfree(c.d_mupart);
     dfree(c.d_topv); dfree(c.d_topi); c.cap_topv = c.cap_topi = 0;
     dfree(c.d_batch); c.cap_batch = 0;
+    dfree(c.d_bt); dfree(c.d_btm); dfree(c.d_bti); c.cap_bt = c.cap_btm = c.cap_bti = 0;
     c.cap_Cs = c.cap_Ks[0] = c.cap_Ks[1] = c.cap_part = c.cap_mupart = 0;
     c.ws_Mpad = 0;
 }
@@ -1628,6 +1629,149 @@ int tgp_acq_grad(tgp_handle h, const double *Xq, int64_t m, int acq, double sf, 
     API_HIP(hipMemcpyAsync(val, d_val, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H val");
     API_HIP(hipMemcpyAsync(grad, d_grad, (size_t)(m * c.D) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H grad");
     API_HIP(hipStreamSynchronize(c.stream), "query sync");
+    return TGP_OK;
+} TGP_CATCH
+
+// Greedy batch selection (include/turbogp.h).  The first step IS tgp_sweep's launch path with the posterior kept on the
+// device; every conditioned point then costs its O(N^2) front (w_j = K^-1 k*(z_j)), a one-workgroup small side and --
+// unless it is the last one and no posterior is asked for -- one O(M N D) pass over the candidates with the update and
+// the next selection's arg-max (batch_kernels.hip).  Every step reads the previous winner from device memory: the host
+// issues everything, then waits once.
+int tgp_sweep_batch(tgp_handle h, int64_t q, int strategy, double lie, const double *Xp, int64_t P, int acq, double sf,
+                    double incumbent, double param, int64_t *idx_out, double *val_out, double *x_out,
+                    double *fantasy_out, double *mu_out, double *sigma_out, int64_t *n_clamped) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_sweep_batch");
+    Context &c = h->c;
+    if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_sweep_batch: no fitted model");
+    if (!c.d_cand || c.M < 1) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: no candidates set");
+    if (q < 1 || q > c.M) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: need 1 <= q <= M");
+    if (P < 0 || P + q > BT_MAXP) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: need P >= 0 and P + q <= 64");
+    if (P > 0 && !Xp) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: Xp is NULL with P > 0");
+    if (strategy != TGP_BATCH_KB && strategy != TGP_BATCH_CL) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: unknown strategy");
+    if (strategy == TGP_BATCH_CL && !std::isfinite(lie)) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: the lie must be finite");
+    if (acq < TGP_ACQ_UCB || acq > TGP_ACQ_SIGMA) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: acq must be UCB, PI, EI or SIGMA");
+    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: sf must be +1 or -1");
+    if (!idx_out || !val_out) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: idx_out and val_out are required");
+    API_HIP(hipSetDevice(c.device), "hipSetDevice");
+    const bool had_front = c.pre.front;
+    API_HIP(pre_join(c), "hipStreamWaitEvent");
+
+    // ---- the first sweep: tgp_sweep's path, means and deviations left in c.d_mu / c.d_sigma, its record in the mapped
+    // result buffer (read by the first selection on the device)
+    const bool small = c.small && c.N <= 2 * NB;
+    const bool mid = mid_sweep_cpw(c, c.M) != 0;
+    int rc = (small || mid) ? ensure_small_workspace(c) : ensure_workspace(c);
+    if (rc != TGP_OK) return rc;
+    c.pre.usable = !small && !mid && had_front && c.pre.gen == c.fit_gen && c.pre.cand == c.d_cand && c.pre.M == c.M &&
+                   c.pre.Mpad == c.ws_Mpad && c.pre.launch_rows == c.launch_rows && c.pre.chunk == c.chunk;
+    c.pre.front = false;
+    if ((rc = ensure_outputs(c, true, true, false)) != TGP_OK) return rc;
+    const int64_t D = c.D, Dp = c.Dp, Np = c.Np, M = c.M, J = P + q;
+    if ((rc = ensure_pinned(c, (size_t)(P * D + 8) * sizeof(double), 8 * sizeof(double))) != TGP_OK) return rc;
+
+    // ---- the call's buffers
+    const int64_t Mpad = ((M + 63) / 64) * 64;        // rows of the scaled candidates and of the pass partials
+    const int64_t nblk = (M + 255) / 256;             // arg-max partials of the update
+    const int js = bt_pass_splits(c, M);
+    const size_t n_bt = (size_t)(BT_MAXP * D + BT_MAXP * Dp + BT_MAXP * Np + 3 * Np + BT_MAXP * BT_MAXP + 4 * BT_MAXP + 8);
+    const size_t n_btm = (size_t)(Mpad * Dp + js * Mpad + 2 * M + nblk + J * M);
+    const size_t n_bti = (size_t)(BT_MAXP + 2 + nblk) * sizeof(long long) + (size_t)M;
+    if ((rc = grow(c, c.d_bt, c.cap_bt, n_bt * sizeof(double), "hipMalloc batch state")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_btm, c.cap_btm, n_btm * sizeof(double), "hipMalloc batch arrays")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_bti, c.cap_bti, n_bti, "hipMalloc batch indices")) != TGP_OK) return rc;
+    double *Zraw = c.d_bt, *Zs = Zraw + BT_MAXP * D, *Kz = Zs + BT_MAXP * Dp, *hw = Kz + BT_MAXP * Np, *v = hw + Np,
+           *w = v + Np, *Rb = w + Np, *eb = Rb + BT_MAXP * BT_MAXP, *fant = eb + BT_MAXP, *selv = fant + BT_MAXP,
+           *inc = selv + BT_MAXP;
+    double *Cs = c.d_btm, *part = Cs + Mpad * Dp, *bmu = part + js * Mpad, *bvar = bmu + M, *bval = bvar + M,
+           *G = bval + nblk;
+    long long *seli = c.d_bti, *clampw = seli + BT_MAXP, *flagw = clampw + 1, *bidx = flagw + 1;
+    unsigned char *mask = reinterpret_cast<unsigned char *>(bidx + nblk);
+    const BtSmall s{Rb, eb, fant, inc, selv, seli, reinterpret_cast<int *>(flagw)};
+
+    const hipEvent_t e0 = c.ev0, e1 = c.ev1;
+    const auto t_host0 = std::chrono::steady_clock::now();
+    API_HIP(hipEventRecord(e0, c.stream), "hipEventRecord");
+    double *winner_keep = c.d_winner;   // the winner record of tgp_set_winner_out belongs to tgp_sweep
+    c.d_winner = nullptr;
+    hipError_t le;
+    if (mid) {
+        le = launch_mid_sweep(c, c.d_cand, acq, sf, incumbent, param, c.d_mu, c.d_sigma, nullptr, c.d_pin_out);
+    } else if (small) {
+        le = launch_small_sweep(c, c.d_cand, acq, sf, incumbent, param, c.d_mu, c.d_sigma, nullptr);
+        if (le == hipSuccess) le = launch_argmax_final(c, (long)((c.M + NB - 1) / NB), c.d_pin_out);
+    } else {
+        c.sweep_res_host = c.d_pin_out;
+        le = launch_sweep(c, acq, sf, incumbent, param, true, true, false);
+        c.sweep_res_host = nullptr;
+        c.pre.usable = false;
+    }
+    c.d_winner = winner_keep;
+    if (le != hipSuccess) return hip_fail(c, le, "tgp_sweep_batch: sweep");
+
+    // ---- the steps
+    double *pin = c.h_pin_in;
+    if (P > 0) memcpy(pin, Xp, (size_t)(P * D) * sizeof(double));
+    pin[P * D] = incumbent;
+    if (P > 0) API_HIP(hipMemcpyAsync(Zraw, pin, (size_t)(P * D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D pending");
+    API_HIP(hipMemcpyAsync(inc, pin + P * D, sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D incumbent");
+    API_HIP(hipMemsetAsync(w, 0, (size_t)Np * sizeof(double), c.stream), "memset w");
+    API_HIP(hipMemsetAsync(clampw, 0, 2 * sizeof(long long), c.stream), "memset counters");
+    if ((le = launch_bt_prep(c, Cs, Mpad)) != hipSuccess) return hip_fail(c, le, "launch_bt_prep");
+    if ((le = launch_bt_init(c, bmu, bvar, mask)) != hipSuccess) return hip_fail(c, le, "launch_bt_init");
+    const int kb = strategy == TGP_BATCH_KB;
+    const bool want_post = mu_out || sigma_out;
+    for (int64_t j = 0; j < J; ++j) {
+        double *zj = Zraw + j * D;
+        if (j >= P) {   // selection k = j - P: the first sweep's winner, or the previous step's
+            const int64_t k = j - P;
+            le = launch_bt_point(c, (P == 0 && k == 0) ? c.d_pin_out : nullptr, s, (int)k, zj, mask);
+            if (le != hipSuccess) return hip_fail(c, le, "launch_bt_point");
+        }
+        if ((le = launch_bt_condition(c, s, (int)j, zj, Kz, Zs, hw, v, w, kb, lie, sf)) != hipSuccess)
+            return hip_fail(c, le, "launch_bt_condition");
+        const bool last = j == J - 1;
+        if (last && !want_post) break;
+        const int64_t knext = j + 1 - P;              // the selection this step's update feeds, if any
+        const bool select = !last && knext >= 0 && knext < q;
+        le = launch_bt_step(c, s, (int)j, Cs, Mpad, Zs, w, part, G, last ? 0 : 1, bmu, bvar, mask,
+                            select ? acq : TGP_ACQ_NONE, sf, param, bval, bidx,
+                            reinterpret_cast<unsigned long long *>(clampw), last ? c.d_mu : nullptr,
+                            last ? c.d_sigma : nullptr, (int)knext);
+        if (le != hipSuccess) return hip_fail(c, le, "launch_bt_step");
+    }
+    API_HIP(hipEventRecord(e1, c.stream), "hipEventRecord");
+
+    // ---- one wait
+    std::vector<double> hs((size_t)(BT_MAXP * D + 2 * BT_MAXP));
+    std::vector<long long> hi((size_t)BT_MAXP + 2);
+    API_HIP(hipMemcpyAsync(hs.data(), Zraw, (size_t)(BT_MAXP * D) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H points");
+    API_HIP(hipMemcpyAsync(hs.data() + BT_MAXP * D, fant, (size_t)(2 * BT_MAXP) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H fantasies");
+    API_HIP(hipMemcpyAsync(hi.data(), seli, (size_t)(BT_MAXP + 2) * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H indices");
+    const size_t bytes = (size_t)M * sizeof(double);
+    if (mu_out) API_HIP(hipMemcpyAsync(mu_out, c.d_mu, bytes, hipMemcpyDeviceToHost, c.stream), "D2H mu");
+    if (sigma_out) API_HIP(hipMemcpyAsync(sigma_out, c.d_sigma, bytes, hipMemcpyDeviceToHost, c.stream), "D2H sigma");
+    API_HIP(hipStreamSynchronize(c.stream), "sweep_batch sync");
+    {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        c.last_sweep_ms = ms;
+        (void)t_host0;
+    }
+    const int flag = (int)(hi[BT_MAXP + 1] & 0xffffffff);
+    if (flag != 0) {
+        char buf[200];
+        snprintf(buf, sizeof buf, "tgp_sweep_batch: the augmented kernel matrix is not positive definite (%s point %d)",
+                 flag - 1 < P ? "pending" : "selected", flag - 1 < P ? flag - 1 : (int)(flag - 1 - P));
+        return fail(c, TGP_NOT_PD, buf);
+    }
+    for (int64_t k = 0; k < q; ++k) {
+        idx_out[k] = (int64_t)hi[k];
+        val_out[k] = hs[BT_MAXP * D + BT_MAXP + k];
+        if (x_out) memcpy(x_out + k * D, hs.data() + (P + k) * D, (size_t)D * sizeof(double));
+    }
+    if (fantasy_out) memcpy(fantasy_out, hs.data() + BT_MAXP * D, (size_t)J * sizeof(double));
+    if (n_clamped) *n_clamped = (int64_t)c.h_pin_out[2] + (int64_t)hi[BT_MAXP];
     return TGP_OK;
 } TGP_CATCH
 

@@ -93,6 +93,10 @@ struct Context {
     size_t cap_rf = 0;
     double *d_batch = nullptr;     // tgp_predict_batch: per-model workspaces, outputs, counters
     size_t cap_batch = 0;
+    double *d_bt = nullptr;        // tgp_sweep_batch: the small state and the conditioned points' vectors
+    double *d_btm = nullptr;       // ... its per-candidate arrays (scaled candidates, pass partials, G, mean, variance)
+    long long *d_bti = nullptr;    // ... its indices, counters and the selection mask
+    size_t cap_bt = 0, cap_btm = 0, cap_bti = 0;   // bytes
     double *d_topv = nullptr;      // top-k workspace (tgp_sweep_topk)
     long long *d_topi = nullptr;
     size_t cap_topv = 0, cap_topi = 0;
@@ -270,5 +274,29 @@ hipError_t presweep_rows(Context &c, hipStream_t st, int rows_final, int budget1
 // returns the event's index or -1 (profiling off); prof_seg names the launch between two marks.
 int prof_mark(Context &c, hipStream_t s);
 void prof_seg(Context &c, int a, int b, int kind, double flops = 0.0);
+
+// tgp_sweep_batch (batch_kernels.hip): greedy batch selection with Kriging Believer / Constant Liar, all on the device
+constexpr int BT_MAXP = 64;        // P + q <= 64 conditioned points per call
+struct BtSmall {                   // the small state of one call (device memory)
+    double *R;                     // (64, 64) rows of the new block of the augmented factor
+    double *e;                     // (64) e_j = (y~_j - mu~_{j-1}(z_j)) / R[j,j]
+    double *fant;                  // (64) fantasies, raw units
+    double *inc;                   // [0] incumbent after the fantasies so far
+    double *sel_val;               // (64) acquisition at each selection
+    long long *sel_idx;            // (64) candidate index of each selection
+    int *flag;                     // first point whose pivot failed + 1, or 0
+};
+// launch_query's front for one point: uq = x / l, ks = k*(x), v = Linv ks, w = Linv^T v (query_kernels.hip)
+hipError_t launch_query_front(Context &c, const double *d_xq, double *uq, double *ks, double *hw, double *v, double *w);
+int bt_pass_splits(const Context &c, int64_t M);   // training-point splits of the pass = rows of its partials
+hipError_t launch_bt_prep(Context &c, double *Cs, int64_t Mpad);
+hipError_t launch_bt_init(Context &c, double *mu, double *var, unsigned char *mask);   // from c.d_mu / c.d_sigma of the first sweep
+hipError_t launch_bt_point(Context &c, const double *rec, const BtSmall &s, int k, double *zraw, unsigned char *mask);
+hipError_t launch_bt_condition(Context &c, const BtSmall &s, int j, const double *zraw, double *Kz, double *Zs,
+                               double *hw, double *v, double *w, int kb, double lie, double sf);
+hipError_t launch_bt_step(Context &c, const BtSmall &s, int j, const double *Cs, int64_t ldpart, const double *Zs,
+                          const double *w, double *part, double *G, int store, double *mu, double *var,
+                          unsigned char *mask, int acq, double sf, double param, double *bval, long long *bidx,
+                          unsigned long long *clamp, double *mu_out, double *sigma_out, int k);
 
 }  // namespace tgp
