@@ -28,7 +28,10 @@ def select_batch(model, Xc, q, strategy, lie, pending, acq_kind, desired_extremu
     """The greedy loop.  ``forced`` (q,): teacher forcing -- take these candidate rows instead of this loop's own
     arg-max (the acquisition of every step is still recorded).  Returns a dict: idx (q,), val (q,) = acquisition at
     each taken row, best (q,) = the step's best unmasked acquisition, acq (list of q (M,) vectors, masked rows -inf),
-    fantasies (P + q,), mu / sigma (M,) after all P + q points, not_pd (bool)."""
+    fantasies (P + q,), mu / sigma (M,) after all P + q points, not_pd (bool), n_clamped_steps = the (candidate, point)
+    pairs of the P + q updates whose variance fell below 0 before the clamp (the first sweep's clamps not included),
+    min_abs_prevar = the smallest |variance before the clamp| of those updates (normalised units): where it is far above
+    the rounding of the variance, the count does not depend on the arithmetic's last digits."""
     Xc = np.atleast_2d(np.asarray(Xc, dtype=np.float64))
     M = Xc.shape[0]
     pending = np.zeros((0, Xc.shape[1])) if pending is None else np.atleast_2d(np.asarray(pending, dtype=np.float64))
@@ -46,7 +49,7 @@ def select_batch(model, Xc, q, strategy, lie, pending, acq_kind, desired_extremu
     Z, kZ, fant = [], [], []
     inc = float(incumbent) if incumbent is not None else 0.0
     mask = np.zeros(M, dtype=bool)
-    out = dict(idx=[], val=[], best=[], acq=[], not_pd=False)
+    out = dict(idx=[], val=[], best=[], acq=[], not_pd=False, n_clamped_steps=0, min_abs_prevar=np.inf)
 
     def condition(z):
         j = len(Z)
@@ -73,6 +76,8 @@ def select_batch(model, Xc, q, strategy, lie, pending, acq_kind, desired_extremu
         g = cx / R[j, j]
         Gc[:, j] = g
         var[:] = var - g * g
+        out["n_clamped_steps"] += int(np.count_nonzero(var < 0))
+        out["min_abs_prevar"] = min(out["min_abs_prevar"], float(np.min(np.abs(var))))
         var[var < 0] = 0.0
         mu_n[:] = mu_n + g * e[j]
         Z.append(z.copy())
@@ -88,7 +93,9 @@ def select_batch(model, Xc, q, strategy, lie, pending, acq_kind, desired_extremu
         a = G.acquisition(acq_kind, mu, sg, desired_extremum, param, inc)
         a = np.where(np.isnan(a), -np.inf, a)
         a[mask] = -np.inf
-        i = int(np.argmax(a)) if forced is None else int(forced[k])
+        # (the lowest unmasked index among the largest values: a masked row never wins, even when every value is -inf)
+        free = np.flatnonzero(~mask)
+        i = int(free[np.argmax(a[free])]) if forced is None else int(forced[k])
         out["acq"].append(a)
         out["best"].append(float(np.max(a)))
         out["idx"].append(i)

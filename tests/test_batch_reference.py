@@ -51,19 +51,66 @@ def _check_against_refits(om, yn, Xc, strategy, lie, Xp, acq, desired, param, in
     return ref
 
 
-@pytest.mark.parametrize("kind,ard", [("rbf", True), ("matern52", True), ("rbf", False)])
+# every acquisition in both directions, each with a lie: "opp" = the opposite extreme of y, the mean, or "below" = a float
+# under every observation; ("ucb", inf) is TGP_ACQ_SIGMA (UCB(beta=inf), acquisition_functions.py)
+ACQ_ROWS = (("ei", "min", 0.01, "opp"), ("pi", "max", 0.0, "opp"), ("ucb", "max", 2.0, "opp"),
+            ("ei", "max", 0.01, "mean"), ("pi", "min", 0.0, "below"), ("ucb", "min", 2.0, "mean"),
+            ("ucb", "max", np.inf, "below"))
+
+
+# (kind, ard) -> (constant, normalize_y)
+SETTINGS = {("rbf", True): (1.2, True), ("matern52", True): (1.2, True), ("rbf", False): (1.2, True),
+            ("matern12", True): (0.3, True), ("matern32", False): (4.0, True), ("matern12", False): (4.0, False),
+            ("matern32", True): (0.3, False)}
+
+
+@pytest.mark.parametrize("kind,ard", list(SETTINGS))
 @pytest.mark.parametrize("noise", [1e-3, 0.0])
 @pytest.mark.parametrize("strategy", [br.KB, br.CL])
 @pytest.mark.parametrize("pending", [False, True])
 def test_rank_updates_equal_literal_refits(kind, ard, noise, strategy, pending):
+    constant, normalize_y = SETTINGS[(kind, ard)]
     X, y, ls, Xc, Xp = _problem(kind, 3, 25, 400, noise, ard, 3)
     jitter = 1e-10 if noise > 0 else 1e-8
-    om = o.fit(X, y, kind, 1.2, ls, noise, jitter, True)
+    om = o.fit(X, y, kind, constant, ls, noise, jitter, normalize_y)
     yn = (y - om.y_mean) / om.y_std
-    for acq, desired, param in (("ei", "min", 0.01), ("pi", "max", 0.0), ("ucb", "max", 2.0)):
+    for acq, desired, param, lie in ACQ_ROWS:
         inc = float(y.min() if desired == "min" else y.max())
-        lie = br.resolve_lie("max" if desired == "min" else "min", y)
+        lie = br.resolve_lie({"opp": "max" if desired == "min" else "min", "below": float(y.min()) - 1.0}.get(lie, lie), y)
         _check_against_refits(om, yn, Xc, strategy, lie, Xp if pending else None, acq, desired, param, inc, 5)
+
+
+@pytest.mark.parametrize("strategy", [br.KB, br.CL])
+def test_sixty_four_conditioned_points_equal_literal_refits(strategy):
+    """P + q = 64 (BT_MAXP): 40 pending points, then 24 selections -- 64 refits of the augmented data"""
+    rng = np.random.RandomState(21)
+    X, y, ls, Xc, _ = _problem("matern52", 3, 25, 400, 1e-3, True, 4)
+    Xp = rng.uniform(0, 1, (40, 3))
+    om = o.fit(X, y, "matern52", 1.2, ls, 1e-3, 1e-10, True)
+    yn = (y - om.y_mean) / om.y_std
+    ref = _check_against_refits(om, yn, Xc, strategy, float(np.mean(y)), Xp, "ei", "min", 0.01, float(y.min()), 24)
+    assert len(ref["fantasies"]) == 64
+
+
+def test_duplicate_rows_lowest_index_first_and_the_duplicate_is_not_next():
+    """ties: every candidate row twice (row i + 20 duplicates row i) gives identical values; the lower index is taken
+    first, and once a row is conditioned on, its duplicate's sigma falls to the noise level, so SIGMA does not take it
+    next"""
+    X, y, ls, C, _ = _problem("rbf", 2, 15, 20, 1e-3, False, 5)
+    Xc = np.vstack([C, C])
+    om = o.fit(X, y, "rbf", 1.0, ls, 1e-3, 1e-10, True)
+    yn = (y - om.y_mean) / om.y_std
+    for acq, desired, param in (("ucb", "max", np.inf), ("ei", "min", 0.01), ("ucb", "max", 2.0)):
+        ref = br.select_batch(om, Xc, 6, br.KB, 0.0, None, acq, desired, param, float(y.min()))
+        a0 = ref["acq"][0]
+        assert a0[:20].tobytes() == a0[20:].tobytes()
+        assert ref["idx"][0] < 20
+        assert all(i < 20 or i - 20 in ref["idx"][:k] for k, i in enumerate(ref["idx"])), ref["idx"]
+        if np.isinf(param):
+            dup = ref["idx"][0] + 20
+            assert ref["idx"][1] != dup
+            assert ref["acq"][1][dup] < 2 * np.sqrt(om.noise + om.jitter) * om.y_std
+        _check_against_refits(om, yn, Xc, br.KB, 0.0, None, acq, desired, param, float(y.min()), 6)
 
 
 def test_lies_masking_and_the_incumbent_rule():
