@@ -281,6 +281,34 @@ int tgp_sweep_batch(tgp_handle h, int64_t q, int strategy, double lie, const dou
                     double incumbent, double param, int64_t *idx_out, double *val_out, double *x_out,
                     double *fantasy_out, double *mu_out, double *sigma_out, int64_t *n_clamped);
 
+/* Thompson sampling: the acquisition the author's older library names but leaves unimplemented
+ * (old_library/acquisition_functions.py:20-21, bayesian_optimiser.py:137-138, :263-264) and its 'asyTS' batch
+ * strategy (:102-104).  tgp_ts_draw draws S sample paths of the fitted model by pathwise conditioning with F random
+ * Fourier features (Wilson et al. 2020), in normalised units (u = x / l, c the constant):
+ *   f_prior_s(x) = sqrt(2c/F) sum_i W[s,i] cos(omega_i . u + b_i)   (omega, b shared by the samples)
+ *   f_s(x)       = f_prior_s(x) + sum_n c k0(x, X_n) v_s[n],  v_s = K^-1 (y~ - f_prior_s(X) - eps_s)
+ *   raw value    = y_mean + y_std f_s(x)
+ * omega_i ~ N(0, I) for RBF and z sqrt(2 nu / chi2_{2 nu}) for Matern nu; b_i ~ U[0, 2 pi); W, eps standard normal,
+ * eps scaled by sqrt(noise + jitter).  The samples are of the LATENT function: their variance is the posterior
+ * variance without the WhiteKernel noise, and their mean is the posterior mean exactly whatever F is.  Random numbers
+ * are Philox-4x32-10 keyed by the seed, counter (element lo, element hi, stream, tag); W is indexed s F + i and eps
+ * s N + n, so sample s does not depend on S (the layout: csrc/ts_kernels.hip).  All arithmetic is f64 whatever the
+ * handle's dtype.  A draw belongs to one fit: after any later fit, append or factor import the three other entries
+ * return TGP_BAD_ARG until the next draw (as they do before the first).  The fit, the candidates, the winner record
+ * and tgp_sweep / tgp_sweep_batch are not touched.  GPU only: TGP_BAD_ARG on host handles.
+ *   tgp_ts_draw   1 <= S <= 64, F a multiple of 64 in [64, 16384]; stored in the handle until the next draw
+ *   tgp_ts_sweep  over the resident candidates: per sample the arg-max of sf * raw value (sf = +1 or -1; lowest index
+ *                 on ties, NaN never wins); distinct != 0: sample s takes the best row not taken by samples < s (needs
+ *                 S <= M).  idx_out, val_out (S): index and RAW sampled value; x_out (S, D) the rows and f_out (M, S)
+ *                 every raw value: nullable
+ *   tgp_ts_eval   the paths at m <= 4096 host points Xq (m, D): f_out (m, S) raw values, grad_out (m, S, D) d f / d x
+ *                 (nullable)
+ *   tgp_ts_read   the draw itself: omega (F, D) in scaled coordinates, b (F), W (S, F), eps (S, N); each nullable */
+int tgp_ts_draw(tgp_handle h, uint64_t seed, int64_t S, int64_t F);
+int tgp_ts_sweep(tgp_handle h, double sf, int distinct, int64_t *idx_out, double *val_out, double *x_out, double *f_out);
+int tgp_ts_eval(tgp_handle h, const double *Xq, int64_t m, double *f_out, double *grad_out);
+int tgp_ts_read(tgp_handle h, double *omega, double *b, double *W, double *eps);
+
 /* The sweep of tgp_sweep, returning the k <= 64 BEST candidates instead of the single best:
  * vals[0..k) descending, idxs[0..k) their indices (lowest index first among equal values, NaN
  * last, -1 when the batch holds fewer than k candidates).  This is

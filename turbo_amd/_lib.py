@@ -41,7 +41,7 @@ SYMBOLS = (
     "tgp_fit_append", "tgp_export_state", "tgp_import_state", "tgp_export_factor_dev", "tgp_import_factor_dev", "tgp_debug_read",
     "tgp_set_candidates", "tgp_set_candidates_dev", "tgp_gen_candidates", "tgp_gen_candidates_lhs", "tgp_lhs_design",
     "tgp_read_candidates", "tgp_get_candidate",
-    "tgp_sweep", "tgp_sweep_batch", "tgp_sweep_topk", "tgp_set_winner_out", "tgp_winner_wait", "tgp_acq_grad", "tgp_acq_refine", "tgp_acq_lbfgsb",
+    "tgp_sweep", "tgp_sweep_batch", "tgp_ts_draw", "tgp_ts_sweep", "tgp_ts_eval", "tgp_ts_read", "tgp_sweep_topk", "tgp_set_winner_out", "tgp_winner_wait", "tgp_acq_grad", "tgp_acq_refine", "tgp_acq_lbfgsb",
     "tgp_evaluate", "tgp_predict_batch", "tgp_predict", "tgp_profile_enable", "tgp_profile_read", "tgp_profile_reset",
     "tgp_sweep_geometry", "tgp_last_timings",
     "tgp_multi_create", "tgp_multi_destroy", "tgp_multi_last_error", "tgp_multi_size", "tgp_multi_handle",
@@ -136,6 +136,10 @@ def _argtypes():
         "tgp_sweep_topk": [_vp, c.c_int, c.c_double, c.c_double, c.c_double, c.c_int64, _dp, _i64p, _i64p],
         "tgp_sweep_batch": [_vp, c.c_int64, c.c_int, c.c_double, _dp, c.c_int64, c.c_int, c.c_double, c.c_double,
                             c.c_double, _i64p, _dp, _dp, _dp, _dp, _dp, _i64p],
+        "tgp_ts_draw": [_vp, c.c_uint64, c.c_int64, c.c_int64],
+        "tgp_ts_sweep": [_vp, c.c_double, c.c_int, _i64p, _dp, _dp, _dp],
+        "tgp_ts_eval": [_vp, _dp, c.c_int64, _dp, _dp],
+        "tgp_ts_read": [_vp, _dp, _dp, _dp, _dp],
         "tgp_acq_refine": [_vp, _dp, c.c_int64, _dp, _dp, c.c_int, c.c_double, c.c_double, c.c_double,
                            c.c_int64, _dp, _dp, _i64p, _i64p],
         "tgp_acq_lbfgsb": [_vp, _dp, c.c_int64, _dp, _dp, c.c_int, c.c_double, c.c_double, c.c_double,
@@ -344,6 +348,7 @@ class NativeGP:
     """One GPU context (tgp_handle).  Thin, stateful, not thread-safe per handle.
     ``device=DEVICE_HOST`` makes a host context instead (``self.host``): fit / predict / acquisition of
     a reloaded model without a GPU, nothing else."""
+    ts_S = ts_F = 0    # shape of the last Thompson draw (ts_draw)
 
     def __init__(self, device=0, dtype="f64"):
         self._h = None
@@ -679,6 +684,42 @@ class NativeGP:
                                              _ptr(x), _ptr(fant), _ptr(mu), _ptr(sg), ctypes.byref(nc)))
         return dict(idx=idx[:q], val=val[:q], x=x[:q], fantasies=fant[:P + q], mu=mu, sigma=sg, n_clamped=nc.value,
                     sweep_ms=self.profile_read()['last_sweep_ms'])
+
+    def ts_draw(self, seed, S=1, F=2048):
+        """``tgp_ts_draw``: S <= 64 posterior sample paths of the fitted model with F random Fourier features (a multiple
+        of 64 in [64, 16384]), kept in the handle until the next draw or fit"""
+        self._check(self.lib.tgp_ts_draw(self._h, int(seed) % (1 << 64), int(S), int(F)))
+        self.ts_S, self.ts_F = int(S), int(F)
+
+    def ts_sweep(self, sf=1.0, distinct=False, want_f=False):
+        """``tgp_ts_sweep``: per drawn sample the arg-max of sf * raw value over the resident candidates (distinct: sample
+        s skips the rows of samples < s).  Returns a dict: idx (S,), val (S,) raw sampled values, x (S, D), f (M, S) raw
+        values (want_f) or None"""
+        S = self.ts_S
+        idx = np.empty(S, dtype=np.int64)
+        val = np.empty(S)
+        x = np.empty((S, self.D))
+        f = np.empty((self.M, S)) if want_f else None
+        self._check(self.lib.tgp_ts_sweep(self._h, float(sf), 1 if distinct else 0, idx.ctypes.data_as(_i64p), _ptr(val),
+                                          _ptr(x), _ptr(f)))
+        return dict(idx=idx, val=val, x=x, f=f, sweep_ms=self.profile_read()['last_sweep_ms'])
+
+    def ts_eval(self, Xq, want_grad=False):
+        """``tgp_ts_eval``: the drawn paths at m <= 4096 points; returns f (m, S) raw values and grad (m, S, D) or None"""
+        Xq = _f64c(np.atleast_2d(Xq))
+        assert Xq.ndim == 2 and Xq.shape[1] == self.D, "points must be (m, %d)" % self.D
+        m, S = Xq.shape[0], self.ts_S
+        f = np.empty((m, S))
+        g = np.empty((m, S, self.D)) if want_grad else None
+        self._check(self.lib.tgp_ts_eval(self._h, _ptr(Xq), m, _ptr(f), _ptr(g)))
+        return f, g
+
+    def ts_read(self):
+        """``tgp_ts_read``: the draw itself -- omega (F, D) in scaled coordinates, b (F,), W (S, F), eps (S, N)"""
+        S, F = self.ts_S, self.ts_F
+        om, b, W, eps = np.empty((F, self.D)), np.empty(F), np.empty((S, F)), np.empty((S, self.N))
+        self._check(self.lib.tgp_ts_read(self._h, _ptr(om), _ptr(b), _ptr(W), _ptr(eps)))
+        return dict(omega=om, b=b, W=W, eps=eps)
 
     def sweep_topk(self, k, acq, sf=1.0, incumbent=0.0, param=0.0):
         """the k best resident candidates: (indices (k,), values (k,)), best first"""

@@ -364,3 +364,166 @@ class EI(AcquisitionFunction):
 
         def _native_args(self):
             return _lib.ACQ_EI, self.incumbent_cost, self.xi
+
+
+class TS(AcquisitionFunction):
+    """Thompson sampling: maximise ONE sample path of the GP posterior, drawn on the GPU (``tgp_ts_draw``).
+
+    The author's older library names this acquisition (old_library/bayesian_optimiser.py:137-138, :263-264) and its
+    'asyTS' batch strategy (:102-104) but leaves both as ``raise NotImplementedError()``.  A path is drawn by pathwise
+    conditioning with ``n_features`` random Fourier features (csrc/ts_kernels.hip): a sample of the latent function,
+    whose mean is the posterior mean.  Trial ``trial_num`` draws with seed ``(seed + trial_num * 0x9E3779B97F4A7C15) mod
+    2**64``; ``seed=None`` takes one ``np.random.randint(0, 2**63)`` from NumPy's global RNG per trial, so a seeded run
+    stays reproducible."""
+
+    GOLDEN = 0x9E3779B97F4A7C15
+
+    def __init__(self, seed=None, n_features=2048):
+        n_features = int(n_features)
+        if n_features < 64 or n_features > 16384 or n_features % 64 != 0:
+            raise ValueError('n_features must be a multiple of 64 in [64, 16384]')
+        self.seed = seed
+        self.n_features = n_features
+
+    def get_type(self):
+        return 'optimism'
+
+    def construct_function(self, trial_num, model, desired_extremum):
+        if not _is_native(model):
+            raise NotImplementedError('TS draws its sample paths on the GPU: it needs a model built by HipGPSurrogate '
+                                      '(got {!r})'.format(type(model)))
+        base = int(np.random.randint(0, 2**63)) if self.seed is None else int(self.seed)
+        seed = (base + int(trial_num) * TS.GOLDEN) % (1 << 64)
+        acq_info = {'seed': seed, 'n_features': self.n_features}
+        return TS.FunctionInstance(model, desired_extremum, seed, self.n_features), acq_info
+
+    class FunctionInstance(AcquisitionFunction.FunctionInstance):
+        """sf * (the sampled path's raw value): sample 0 of the draw with this instance's seed"""
+
+        is_thompson = True
+        sweep_dtype = 'f64'      # every Thompson entry is f64 whatever the handle's dtype
+
+        def __init__(self, model, desired_extremum, seed, n_features):
+            super().__init__(model, desired_extremum)
+            self.seed = int(seed)
+            self.n_features = int(n_features)
+            self._token = object()
+
+        def get_name(self):
+            return 'TS'
+
+        def _native_args(self):
+            raise NotImplementedError('TS has no posterior-formula arguments: it maximises a sampled path')
+
+        def _ctx(self, S=1):
+            """the model's context holding THIS instance's draw of S paths (drawn again after any refit: the same seed
+            gives the same paths)"""
+            f = self.model._factory
+            refit = f._resident is not self.model
+            ctx = self.model._ensure_resident()
+            key = (self._token, int(S))
+            if refit or getattr(ctx, '_ts_owner', None) != key:
+                ctx._ts_owner = None
+                ctx.ts_draw(self.seed, S, self.n_features)
+                ctx._ts_owner = key
+            return ctx
+
+        def _as_points(self, X):
+            X = np.asarray(X, dtype=np.float64)
+            if X.ndim == 1:
+                X = X.reshape(1, -1)
+            assert X.ndim == 2 and X.shape[1] == self.model.X.shape[1], \
+                'X must have shape (num_points, {})'.format(self.model.X.shape[1])
+            return X
+
+        def _values(self, X):
+            """raw sampled values at the rows of X"""
+            X = self._as_points(X)
+            if X.shape[0] == 0:
+                return np.empty(0)
+            ctx = self._ctx()
+            if X.shape[0] <= 64:
+                f, _ = ctx.ts_eval(X)
+                return f[:, 0]
+            ctx.set_candidates(X)
+            return ctx.ts_sweep(self.scale_factor, want_f=True)['f'][:, 0]
+
+        def __call__(self, X):
+            return self.scale_factor * self._values(X)
+
+        def value_and_grad(self, X):
+            """sf * sampled value (m,) and its gradient (m, D) in closed form (``tgp_ts_eval``)"""
+            X = self._as_points(X)
+            ctx = self._ctx()
+            vals, grads = [], []
+            for i in range(0, X.shape[0], 4096):
+                f, g = ctx.ts_eval(X[i:i + 4096], want_grad=True)
+                vals.append(f[:, 0])
+                grads.append(g[:, 0, :])
+            return self.scale_factor * np.concatenate(vals), self.scale_factor * np.concatenate(grads)
+
+        def maximise(self, X):
+            """arg-max of sf * sampled value over the rows of X: (index, value); lowest index wins ties"""
+            X = self._as_points(X)
+            ctx = self._ctx()
+            ctx.set_candidates(X)
+            res = ctx.ts_sweep(self.scale_factor)
+            self.last_sweep_ms = res.get('sweep_ms')
+            return int(res['idx'][0]), self.scale_factor * float(res['val'][0])
+
+        def maximise_topk(self, X, k):
+            """the k best rows of X for the sampled path: (indices (k,), values (k,)), best first"""
+            v = self(X)
+            v = np.where(np.isnan(v), -np.inf, v)
+            order = np.argsort(-v, kind='stable')[:min(int(k), 64)]
+            return order.astype(np.int64), v[order]
+
+        def maximise_generated(self, num_points, low, high, seed, first_candidate=0, lhs_total=None, prefetch_seed=None):
+            """draw ``num_points`` candidates on the GPU (uniform, or rows of an ``lhs_total``-point Latin hypercube) and
+            return the sampled path's best: (x (D,), sf * value, index)"""
+            if prefetch_seed is not None:
+                raise NotImplementedError('TS: no prefetched batch (the overlap starts an EI / UCB sweep inside the fit)')
+            ctx = self._ctx()
+            if lhs_total is not None:
+                ctx.gen_candidates_lhs(seed, first_candidate, num_points, lhs_total, low, high)
+            else:
+                ctx.gen_candidates(seed, first_candidate, num_points, low, high)
+            res = ctx.ts_sweep(self.scale_factor)
+            self.last_sweep_ms = res.get('sweep_ms')
+            return res['x'][0].copy(), self.scale_factor * float(res['val'][0]), int(res['idx'][0])
+
+        def maximise_host_stream(self, num_points, low, high, topk=0, first=0, count=None):
+            return None     # nothing drawn: the caller draws on the host and calls maximise / maximise_topk
+
+        def maximise_batch(self, X, q, strategy='thompson', lie=None, pending=None, want_posterior=False):
+            """q distinct rows of X for q parallel workers: row s maximises sample path s of ONE draw of q paths, skipping
+            the rows of paths < s (asynchronous Thompson sampling: ``pending`` trials are ignored,
+            old_library/bayesian_optimiser.py:102-104).  X None: the batch already resident.  Path 0 is this instance's
+            own path, so the first row is ``maximise(X)``'s.  Returns a dict: idx (q,), val (q,) raw sampled values,
+            x (q, D), pending_ignored, seed, n_features, sweep_ms"""
+            if strategy != 'thompson':
+                raise ValueError("a TS acquisition selects batches with strategy='thompson' only")
+            q = int(q)
+            if q < 1 or q > 64:
+                raise ValueError('q must be in [1, 64]')
+            ctx = self._ctx(q)
+            if X is not None:
+                ctx.set_candidates(self._as_points(X))
+            res = ctx.ts_sweep(self.scale_factor, distinct=True)
+            self.last_sweep_ms = res.get('sweep_ms')
+            P = 0 if pending is None else int(np.asarray(pending).reshape(-1, self.model.X.shape[1]).shape[0])
+            return dict(idx=res['idx'], val=res['val'], x=res['x'], pending_ignored=P, seed=self.seed,
+                        n_features=self.n_features, sweep_ms=res.get('sweep_ms'))
+
+        def _refuse(self, what):
+            raise NotImplementedError('TS: {} is not available for sample paths (use CandidateSweep with '
+                                      "lockstep='scipy' or lockstep=False for gradient restarts)".format(what))
+
+        def refine(self, starting_points, bounds, max_iter=200):
+            self._refuse('the on-device optimiser (on_device=True, tgp_acq_refine)')
+
+        def lbfgsb(self, starting_points, bounds, max_iter=15000):
+            self._refuse('the in-library L-BFGS-B (lockstep=True, tgp_acq_lbfgsb)')
+
+        def winner_record(self, global_offset):
+            self._refuse('the sharded multi-rank sweep')

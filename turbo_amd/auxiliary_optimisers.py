@@ -150,7 +150,16 @@ class CandidateSweep:
         """q points for q parallel workers from ONE batch of candidates, drawn exactly as ``__call__`` draws it, chosen
         greedily with Kriging Believer / Constant Liar and conditioned first on ``pending`` (P, D): the trials still
         running (``FunctionInstance.maximise_batch``, ``tgp_sweep_batch``).  Returns (x (q, D), info) with info =
-        {'max_acq' (q,), 'candidate_indices' (q,), 'fantasies' (q,), 'pending_fantasies' (P,), 'strategy'}."""
+        {'max_acq' (q,), 'candidate_indices' (q,), 'fantasies' (q,), 'pending_fantasies' (P,), 'strategy'}.
+
+        strategy='thompson' with a ``TS`` acquisition: q distinct rows, row s the best of sample path s of one draw of q
+        paths (asynchronous Thompson sampling: ``pending`` is accepted and ignored).  info = {'max_acq' (q,) sf * sampled
+        value, 'candidate_indices' (q,), 'sample_values' (q,) raw, 'strategy', 'seed', 'n_features', 'pending_ignored'}."""
+        thompson = bool(getattr(acq, 'is_thompson', False))
+        if strategy == 'thompson' and not thompson:
+            raise ValueError("strategy='thompson' needs a TS acquisition (got {!r})".format(type(acq)))
+        if thompson and strategy != 'thompson':
+            raise ValueError("a TS acquisition selects batches with strategy='thompson' only (got {!r})".format(strategy))
         if self.grad_restarts > 0:
             raise NotImplementedError('select_batch: no gradient refinement of the selected points (grad_restarts > 0)')
         rank, world = dist_info() if self.shard else (0, 1)
@@ -181,6 +190,13 @@ class CandidateSweep:
             res = acq.maximise_batch(self.gen_random(self.num_random, latent_bounds), q, strategy, lie, pending)
         self._calls += 1
         P = 0 if pending is None else len(pending)
+        if thompson:
+            info = {'max_acq': acq.scale_factor * np.asarray(res['val']), 'candidate_indices': res['idx'],
+                    'sample_values': res['val'], 'strategy': strategy, 'seed': res['seed'],
+                    'n_features': res['n_features'], 'pending_ignored': res['pending_ignored']}
+            if res.get('sweep_ms') is not None:
+                info['sweep_ms'] = res['sweep_ms']
+            return np.asarray(res['x'], dtype=np.float64), info
         info = {'max_acq': res['val'], 'candidate_indices': res['idx'], 'fantasies': res['fantasies'][P:],
                 'pending_fantasies': res['fantasies'][:P], 'strategy': strategy}
         if res.get('sweep_ms') is not None:
@@ -195,6 +211,8 @@ class CandidateSweep:
         # contiguous shards of ONE batch of num_random candidates; global index =
         # offset + local index, so the tie rule (lowest index) does not depend on the world size
         m_local, offset, _ = shard_plan(self.num_random, world, rank)
+        if world > 1 and getattr(acq, 'is_thompson', False):
+            raise NotImplementedError('TS: one process only (the sharded multi-rank sweep is not available for sample paths)')
         # with RCCL the winner record [value, global index, row] is packed on the GPU by the sweep
         # itself and all-gathered from there
         rec = None

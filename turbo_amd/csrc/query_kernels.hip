@@ -553,4 +553,31 @@ hipError_t launch_query_front(Context &c, const double *d_xq, double *uq, double
     return hipGetLastError();
 }
 
+// z = Linv r and w = Linv^T z for m vectors at once (tgp_ts_draw: the S residuals, ts_kernels.hip), on the matrix-core
+// products in groups of 16; r is zero from N on, as q_kvec_kernel leaves ks
+hipError_t launch_linv_solve(Context &c, const double *r, double *z, double *w, int m) {
+    hipStream_t s = c.stream;
+    const int N = (int)c.N, Np = (int)c.Np;
+    const unsigned groups = (unsigned)((m + QM_PTS - 1) / QM_PTS);
+    const dim3 gr(Np / 16, groups), gc((N + 15) / 16, groups);
+    switch (query_waves(Np)) {
+        case 4:
+            hipLaunchKernelGGL(q_rows_mfma_kernel<4>, gr, dim3(256), 0, s, c.d_Linv, r, z, Np, m);
+            TGP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(q_cols_mfma_kernel<4>, gc, dim3(256), 0, s, c.d_Linv, z, w, N, Np, m);
+            break;
+        case 8:
+            hipLaunchKernelGGL(q_rows_mfma_kernel<8>, gr, dim3(512), 0, s, c.d_Linv, r, z, Np, m);
+            TGP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(q_cols_mfma_kernel<8>, gc, dim3(512), 0, s, c.d_Linv, z, w, N, Np, m);
+            break;
+        default:
+            hipLaunchKernelGGL(q_rows_mfma_kernel<16>, gr, dim3(1024), 0, s, c.d_Linv, r, z, Np, m);
+            TGP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(q_cols_mfma_kernel<16>, gc, dim3(1024), 0, s, c.d_Linv, z, w, N, Np, m);
+            break;
+    }
+    return hipGetLastError();
+}
+
 }  // namespace tgp

@@ -16,6 +16,7 @@
 
 #include "mfma_gemm.hpp"
 #include "pairwise.hpp"
+#include "philox.hpp"
 #include "tgp_internal.hpp"
 #include "trmm_sweep.hpp"
 #include "trmm_bf16x3.hpp"
@@ -49,22 +50,6 @@ __global__ __launch_bounds__(256) void prep_candidates_kernel(const double *__re
 // the (M, D) batch takes draw e >> 1, half e & 1, so the stream does not depend on how the batch
 // is sharded over GPUs.  x = lo + (hi - lo) * u, as numpy.random.uniform
 // (turbo/modules/naive_selectors.py:39-46 draws column-wise from the global NumPy RNG instead).
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                              uint32_t k0, uint32_t k1, uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-        const uint32_t n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        const uint32_t n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 __global__ __launch_bounds__(256) void gen_candidates_kernel(double *__restrict__ Xc, long total,
                                                              unsigned long long first, int D,
                                                              unsigned long long seed,

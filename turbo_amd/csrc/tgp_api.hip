@@ -267,6 +267,7 @@ static void free_ws(Context &c) {
     dfree(c.d_topv); dfree(c.d_topi); c.cap_topv = c.cap_topi = 0;
     dfree(c.d_batch); c.cap_batch = 0;
     dfree(c.d_bt); dfree(c.d_btm); dfree(c.d_bti); c.cap_bt = c.cap_btm = c.cap_bti = 0;
+    dfree(c.d_ts); dfree(c.d_tsm); c.cap_ts = c.cap_tsm = 0; c.ts_gen = -1;
     c.cap_Cs = c.cap_Ks[0] = c.cap_Ks[1] = c.cap_part = c.cap_mupart = 0;
     c.ws_Mpad = 0;
 }
@@ -1772,6 +1773,153 @@ int tgp_sweep_batch(tgp_handle h, int64_t q, int strategy, double lie, const dou
     }
     if (fantasy_out) memcpy(fantasy_out, hs.data() + BT_MAXP * D, (size_t)J * sizeof(double));
     if (n_clamped) *n_clamped = (int64_t)c.h_pin_out[2] + (int64_t)hi[BT_MAXP];
+    return TGP_OK;
+} TGP_CATCH
+
+// ---- Thompson sampling (include/turbogp.h, ts_kernels.hip) ----
+// d_ts: [omega (F Dp) | b (F) | W (Spad F) | V (Spad Np) | eps (S N) | priorX (N S) | R (S Np) | Z (S Np)], every
+// part starting on a 32-byte boundary (V is read in 32-byte vectors)
+static int64_t ts_al4(int64_t n) { return (n + 3) & ~(int64_t)3; }
+static TsDraw ts_view(Context &c, double **priorX = nullptr, double **R = nullptr, double **Z = nullptr) {
+    TsDraw t{};
+    t.S = c.ts_S; t.F = c.ts_F;
+    const int64_t Spad = ts_spad(t.S);
+    double *p = c.d_ts;
+    t.omega = p; p += ts_al4(t.F * c.Dp);
+    t.b = p; p += ts_al4(t.F);
+    t.W = p; p += ts_al4(Spad * t.F);
+    t.V = p; p += ts_al4(Spad * c.Np);
+    t.eps = p; p += ts_al4(t.S * c.N);
+    if (priorX) *priorX = p;
+    p += ts_al4(c.N * t.S);
+    if (R) *R = p;
+    p += ts_al4(t.S * c.Np);
+    if (Z) *Z = p;
+    return t;
+}
+static int64_t ts_doubles(const Context &c, int64_t S, int64_t F) {
+    const int64_t Spad = ts_spad(S);
+    return ts_al4(F * c.Dp) + ts_al4(F) + ts_al4(Spad * F) + ts_al4(Spad * c.Np) + ts_al4(S * c.N) + ts_al4(c.N * S) +
+           2 * ts_al4(S * c.Np);
+}
+static int ts_check_draw(Context &c, const char *fn) {
+    if (!c.fitted) return fail(c, TGP_BAD_ARG, std::string(fn) + ": no fitted model");
+    if (c.ts_gen < 0 || c.ts_gen != c.fit_gen)
+        return fail(c, TGP_BAD_ARG, std::string(fn) + ": no draw for the resident fit (tgp_ts_draw after the last fit)");
+    return TGP_OK;
+}
+
+int tgp_ts_draw(tgp_handle h, uint64_t seed, int64_t S, int64_t F) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_ts_draw");
+    Context &c = h->c;
+    if (!c.fitted) return fail(c, TGP_BAD_ARG, "tgp_ts_draw: no fitted model");
+    if (S < 1 || S > 64) return fail(c, TGP_BAD_ARG, "tgp_ts_draw: need 1 <= S <= 64");
+    if (F < 64 || F > 16384 || F % 64 != 0) return fail(c, TGP_BAD_ARG, "tgp_ts_draw: F must be a multiple of 64 in [64, 16384]");
+    API_HIP(hipSetDevice(c.device), "hipSetDevice");
+    API_HIP(pre_join(c), "hipStreamWaitEvent");
+    c.ts_gen = -1;
+    int rc = grow(c, c.d_ts, c.cap_ts, (size_t)ts_doubles(c, S, F) * sizeof(double), "hipMalloc Thompson draw");
+    if (rc != TGP_OK) return rc;
+    c.ts_S = S; c.ts_F = F;
+    double *priorX, *R, *Z;
+    const TsDraw t = ts_view(c, &priorX, &R, &Z);
+    hipError_t le = launch_ts_draw(c, t, (unsigned long long)seed, priorX, R, Z);
+    if (le != hipSuccess) return hip_fail(c, le, "launch_ts_draw");
+    API_HIP(hipStreamSynchronize(c.stream), "ts_draw sync");
+    c.ts_gen = c.fit_gen;
+    return TGP_OK;
+} TGP_CATCH
+
+// one pass over the resident candidates, S arg-max reductions in device memory, one wait
+int tgp_ts_sweep(tgp_handle h, double sf, int distinct, int64_t *idx_out, double *val_out, double *x_out, double *f_out) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_ts_sweep");
+    Context &c = h->c;
+    int rc = ts_check_draw(c, "tgp_ts_sweep");
+    if (rc != TGP_OK) return rc;
+    if (!c.d_cand || c.M < 1) return fail(c, TGP_BAD_ARG, "tgp_ts_sweep: no candidates set");
+    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_ts_sweep: sf must be +1 or -1");
+    if (distinct && c.ts_S > c.M) return fail(c, TGP_BAD_ARG, "tgp_ts_sweep: distinct needs S <= M");
+    if (!idx_out || !val_out) return fail(c, TGP_BAD_ARG, "tgp_ts_sweep: idx_out and val_out are required");
+    API_HIP(hipSetDevice(c.device), "hipSetDevice");
+    API_HIP(pre_join(c), "hipStreamWaitEvent");
+    const TsDraw t = ts_view(c);
+    const int64_t S = t.S, M = c.M, D = c.D;
+    const int64_t Mpad = ((M + 63) / 64) * 64, nblk = (M + 255) / 256;
+    // [Cs (Mpad Dp) | f (M S) | bval (S nblk) | sel_val (S) | sel_x (S D) | bidx (S nblk) | sel_idx (S) | mask (M bytes)]
+    const int64_t nd = ts_al4(Mpad * c.Dp) + ts_al4(M * S) + ts_al4(S * nblk) + ts_al4(S) + ts_al4(S * D) + S * nblk + S;
+    const size_t bytes = (size_t)nd * sizeof(double) + (size_t)M;
+    if ((rc = grow(c, c.d_tsm, c.cap_tsm, bytes, "hipMalloc Thompson sweep")) != TGP_OK) return rc;
+    double *Cs = c.d_tsm, *f = Cs + ts_al4(Mpad * c.Dp), *bval = f + ts_al4(M * S), *selv = bval + ts_al4(S * nblk),
+           *selx = selv + ts_al4(S);
+    long long *bidx = reinterpret_cast<long long *>(selx + ts_al4(S * D)), *seli = bidx + S * nblk;
+    unsigned char *mask = reinterpret_cast<unsigned char *>(seli + S);
+    const auto t_host0 = std::chrono::steady_clock::now();
+    API_HIP(hipEventRecord(c.ev0, c.stream), "hipEventRecord");
+    hipError_t le = launch_bt_prep(c, Cs, Mpad);
+    if (le != hipSuccess) return hip_fail(c, le, "launch_bt_prep");
+    if ((le = launch_ts_pass(c, t, Cs, M, true, f, c.y_mean, c.y_std)) != hipSuccess) return hip_fail(c, le, "launch_ts_pass");
+    if ((le = launch_ts_select(c, t, f, sf, distinct ? 1 : 0, mask, bval, bidx, seli, selv, selx)) != hipSuccess)
+        return hip_fail(c, le, "launch_ts_select");
+    API_HIP(hipEventRecord(c.ev1, c.stream), "hipEventRecord");
+    std::vector<long long> hi((size_t)S);
+    API_HIP(hipMemcpyAsync(hi.data(), seli, (size_t)S * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H indices");
+    API_HIP(hipMemcpyAsync(val_out, selv, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H values");
+    if (x_out) API_HIP(hipMemcpyAsync(x_out, selx, (size_t)(S * D) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H rows");
+    if (f_out) API_HIP(hipMemcpyAsync(f_out, f, (size_t)(M * S) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H f");
+    API_HIP(hipStreamSynchronize(c.stream), "ts_sweep sync");
+    {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, c.ev0, c.ev1);
+        c.last_sweep_ms = ms;
+        (void)t_host0;
+    }
+    for (int64_t s = 0; s < S; ++s) idx_out[s] = (int64_t)hi[s];
+    return TGP_OK;
+} TGP_CATCH
+
+int tgp_ts_eval(tgp_handle h, const double *Xq, int64_t m, double *f_out, double *grad_out) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_ts_eval");
+    Context &c = h->c;
+    int rc = ts_check_draw(c, "tgp_ts_eval");
+    if (rc != TGP_OK) return rc;
+    if (!Xq || !f_out || m < 1 || m > 4096) return fail(c, TGP_BAD_ARG, "tgp_ts_eval: need Xq, f_out and 1 <= m <= 4096");
+    if (ts_eval_lds_bytes(c, c.ts_S) > 65536) return fail(c, TGP_BAD_ARG, "tgp_ts_eval: S (1 + D) too large for one workgroup's LDS");
+    API_HIP(hipSetDevice(c.device), "hipSetDevice");
+    API_HIP(pre_join(c), "hipStreamWaitEvent");
+    const TsDraw t = ts_view(c);
+    const int64_t S = t.S, D = c.D;
+    // [Xq (m D) | f (m S) | grad (m S D)] in the per-call region the sweep uses too
+    const int64_t nd = ts_al4(m * D) + ts_al4(m * S) + m * S * D;
+    if ((rc = grow(c, c.d_tsm, c.cap_tsm, (size_t)nd * sizeof(double), "hipMalloc Thompson eval")) != TGP_OK) return rc;
+    double *dX = c.d_tsm, *df = dX + ts_al4(m * D), *dg = df + ts_al4(m * S);
+    API_HIP(hipMemcpyAsync(dX, Xq, (size_t)(m * D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D Xq");
+    hipError_t le = launch_ts_eval(c, t, dX, (int)m, df, grad_out ? dg : nullptr);
+    if (le != hipSuccess) return hip_fail(c, le, "launch_ts_eval");
+    API_HIP(hipMemcpyAsync(f_out, df, (size_t)(m * S) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H f");
+    if (grad_out) API_HIP(hipMemcpyAsync(grad_out, dg, (size_t)(m * S * D) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H grad");
+    API_HIP(hipStreamSynchronize(c.stream), "ts_eval sync");
+    return TGP_OK;
+} TGP_CATCH
+
+int tgp_ts_read(tgp_handle h, double *omega, double *b, double *W, double *eps) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_ts_read");
+    Context &c = h->c;
+    int rc = ts_check_draw(c, "tgp_ts_read");
+    if (rc != TGP_OK) return rc;
+    API_HIP(hipSetDevice(c.device), "hipSetDevice");
+    API_HIP(pre_join(c), "hipStreamWaitEvent");
+    const TsDraw t = ts_view(c);
+    const size_t d8 = sizeof(double);
+    if (omega) API_HIP(hipMemcpy2DAsync(omega, (size_t)c.D * d8, t.omega, (size_t)c.Dp * d8, (size_t)c.D * d8, (size_t)t.F,
+                                        hipMemcpyDeviceToHost, c.stream), "D2H omega");
+    if (b) API_HIP(hipMemcpyAsync(b, t.b, (size_t)t.F * d8, hipMemcpyDeviceToHost, c.stream), "D2H b");
+    if (W) API_HIP(hipMemcpyAsync(W, t.W, (size_t)(t.S * t.F) * d8, hipMemcpyDeviceToHost, c.stream), "D2H W");
+    if (eps) API_HIP(hipMemcpyAsync(eps, t.eps, (size_t)(t.S * c.N) * d8, hipMemcpyDeviceToHost, c.stream), "D2H eps");
+    API_HIP(hipStreamSynchronize(c.stream), "ts_read sync");
     return TGP_OK;
 } TGP_CATCH
 

@@ -97,6 +97,11 @@ struct Context {
     double *d_btm = nullptr;       // ... its per-candidate arrays (scaled candidates, pass partials, G, mean, variance)
     long long *d_bti = nullptr;    // ... its indices, counters and the selection mask
     size_t cap_bt = 0, cap_btm = 0, cap_bti = 0;   // bytes
+    double *d_ts = nullptr;        // tgp_ts_draw: the draw (omega, b, W, eps, V) and its workspace
+    double *d_tsm = nullptr;       // tgp_ts_sweep / tgp_ts_eval: per-call arrays (scaled candidates, f, partials, points)
+    size_t cap_ts = 0, cap_tsm = 0;   // bytes
+    int64_t ts_S = 0, ts_F = 0;    // the resident draw's shape ...
+    long ts_gen = -1;              // ... and the fit_gen it belongs to (-1: none)
     double *d_topv = nullptr;      // top-k workspace (tgp_sweep_topk)
     long long *d_topi = nullptr;
     size_t cap_topv = 0, cap_topi = 0;
@@ -298,5 +303,31 @@ hipError_t launch_bt_step(Context &c, const BtSmall &s, int j, const double *Cs,
                           const double *w, double *part, double *G, int store, double *mu, double *var,
                           unsigned char *mask, int acq, double sf, double param, double *bval, long long *bidx,
                           unsigned long long *clamp, double *mu_out, double *sigma_out, int k);
+
+
+// Thompson sampling (ts_kernels.hip): S <= 64 sample paths of the fitted model, F random Fourier features
+struct TsDraw {
+    int64_t S, F;
+    double *omega;                 // (F, Dp) in scaled coordinates, columns >= D zero
+    double *b;                     // (F)
+    double *W;                     // (ts_spad(S), F), rows >= S zero
+    double *eps;                   // (S, N)
+    double *V;                     // (ts_spad(S), Np): v_s = K^-1 (y~ - f_prior_s(X) - eps_s), zero from N on and from row S on
+};
+int ts_spad(int64_t S);            // rows of W / V: S rounded up to 16, 32 or 64
+// z = Linv r, w = Linv^T z for m vectors (rows of stride Np, zero from N on) on the matrix-core products (query_kernels.hip)
+hipError_t launch_linv_solve(Context &c, const double *r, double *z, double *w, int m);
+// fill the draw; priorX (N, S), R and Z (S, Np) are its workspace
+hipError_t launch_ts_draw(Context &c, const TsDraw &t, unsigned long long seed, double *priorX, double *R, double *Z);
+// out[row * S + s] = o0 + o1 f_s(P[row]) for scaled points P (rows up to the 64-row tile's end readable, Dp stride);
+// update = false: the prior alone
+hipError_t launch_ts_pass(Context &c, const TsDraw &t, const double *P, int64_t rows, bool update, double *out, double o0,
+                          double o1);
+// per sample the (sf f, lowest index) arg-max over the resident candidates, from f (M, S); distinct: sample s skips the
+// rows of samples < s.  bval / bidx: S * ceil(M / 256) partials; sel_x (S, D) the winners' rows
+hipError_t launch_ts_select(Context &c, const TsDraw &t, const double *f, double sf, int distinct, unsigned char *mask,
+                            double *bval, long long *bidx, long long *sel_idx, double *sel_val, double *sel_x);
+size_t ts_eval_lds_bytes(const Context &c, int64_t S);
+hipError_t launch_ts_eval(Context &c, const TsDraw &t, const double *Xq, int m, double *fout, double *gout);
 
 }  // namespace tgp
