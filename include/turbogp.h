@@ -550,7 +550,10 @@ int tgp_profile_reset(tgp_handle h);
  *  arithmetic, -1 before the first sweep: what CandidateSweep asks before it re-forms the winner's value in f64].
  * The short polled calls (small fit, fit + gradient; doorbell.hpp) report the kernels' own wall_clock64() span;
  * slots [7..11] (a debugging aid) hold that kernel's phase stamps in microseconds from its start: inputs staged,
- * first kernel-matrix tile in LDS, first block factored, fit done, call done (0 when the last fit was not polled). */
+ * first kernel-matrix tile in LDS, first block factored, fit done, call done (0 when the last fit was not polled).
+ * Slots [12..14] (not times): what the last tgp_sweep did about pruning -- -1 not eligible, -2 gated off by the
+ * noise, 0 the pruned schedule ran, 1 it fell back to every candidate -- and the candidates of its lb set and its
+ * survivors (TGP_SWEEP_PRUNE). */
 int tgp_last_timings(tgp_handle h, double *out, int64_t n);
 /* Candidates per trmm launch (chunk) and padded N used by the sweep, for the roofline maths. */
 int tgp_sweep_geometry(tgp_handle h, int64_t *chunk, int64_t *n_padded);

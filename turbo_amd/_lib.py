@@ -844,6 +844,15 @@ class NativeGP:
         return dict(fit_ms=v[0], sweep_ms=v[1], grad_kinv_ms=v[2], grad_pairwise_ms=v[3], grad_ard_ms=v[4],
                     trmm_flops=v[5], sweep_f64=int(v[6]), small_fit_phases_us=[float(x) for x in v[7:12]])
 
+    def last_prune(self):
+        """what the last ``sweep`` did about pruning (``tgp_last_timings`` slots 12-14): state -1 = not eligible (outputs
+        asked for, another acquisition or dtype, N <= 256, TGP_SWEEP_PRUNE=0), -2 = gated off (the noise is too small
+        for the contraction's rounding), 0 = the pruned schedule ran, 1 = too many survivors: every candidate was
+        contracted; lb_set / survivors = candidates of its two exact sets"""
+        v = np.zeros(15)
+        self._check(self.lib.tgp_last_timings(self._h, _ptr(v), 15))
+        return dict(state=int(v[12]), lb_set=int(v[13]), survivors=int(v[14]))
+
     def sweep_geometry(self):
         ch, npad = ctypes.c_int64(), ctypes.c_int64()
         self._check(self.lib.tgp_sweep_geometry(self._h, ctypes.byref(ch), ctypes.byref(npad)))

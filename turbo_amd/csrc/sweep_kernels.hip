@@ -207,6 +207,9 @@ hipError_t launch_mt19937_columns(Context &c, const void *d_words, double *dst, 
 // MU: also accumulate the partial means Ks . alpha (the split-operand dtypes and the register-staged A/B contraction;
 // round 5: the f64 / f32 contraction does it itself -- MeanAcc in mfma_gemm.hpp -- so that this kernel needs nothing
 // of a fit but Xs and can run inside it)
+// XP == 4: the BOUND pass of the pruned sweep (sweep_pruned): no slab at all; the partial means Ks . alpha and the partial
+// sums |Ks| . |alpha| (the scale of their rounding error) go to mupart and to `Ks` read as (splits, ldpart) doubles --
+// from the very k values the slab-writing instantiations produce
 template <typename T, int KIND, int AR, int XP = 0, bool MU = true>
 __global__ __launch_bounds__(256, 2) void kstar_kernel(const T *__restrict__ Cs,
                                                           const T *__restrict__ Xs,
@@ -216,6 +219,7 @@ __global__ __launch_bounds__(256, 2) void kstar_kernel(const T *__restrict__ Cs,
                                                           int N, int Np, int Dp, double constant,
                                                           long ldpart, long pstride = 0, float xscale = 1.f) {
     constexpr bool X3 = XP == 3;
+    constexpr bool BND = XP == 4;
     using St = KsStage<T>;
     constexpr int DC = St::DC, LD = St::LD;
     __shared__ __attribute__((aligned(16))) T Ct[DC][LD];
@@ -237,7 +241,7 @@ __global__ __launch_bounds__(256, 2) void kstar_kernel(const T *__restrict__ Cs,
     // same banks: 4.2 M conflict cycles per launch at C2)
     auto jcol = [&](int b) { return sizeof(T) == 4 ? (b < 4 ? 0 : 60) + 4 * tx + b : ((b >> 1) << 5) + 2 * tx + (b & 1); };
     // tiles that hold only padding: zero-filled
-    for (int jt = (jt_live > jt0 ? jt_live : jt0); jt < jt_end; ++jt) {
+    for (int jt = (jt_live > jt0 ? jt_live : jt0); !BND && jt < jt_end; ++jt) {
 #pragma unroll
         for (int a = 0; a < AR; ++a)
 #pragma unroll
@@ -261,9 +265,9 @@ __global__ __launch_bounds__(256, 2) void kstar_kernel(const T *__restrict__ Cs,
                 }
             }
     }
-    double pm[AR];
+    double pm[AR], pa[AR];
 #pragma unroll
-    for (int a = 0; a < AR; ++a) pm[a] = 0.0;
+    for (int a = 0; a < AR; ++a) pm[a] = pa[a] = 0.0;
     const T cst = (T)constant;
     const float log2c = log2f((float)constant);
     const int nch = (Dp + DC - 1) / DC;
@@ -351,7 +355,10 @@ __global__ __launch_bounds__(256, 2) void kstar_kernel(const T *__restrict__ Cs,
 #pragma unroll
                         for (int b = 0; b < 4; ++b) pm[a] = fma((double)kv[b], al[4 * hb + b], pm[a]);
                     }
-                    if (XP == 2) {
+                    if (BND) {
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) pa[a] = fma(fabs((double)kv[b]), fabs(al[4 * hb + b]), pa[a]);
+                    } else if (XP == 2) {
                         unsigned pk[2][2];
                         split2_f16x2((float)kv[0], (float)kv[1], xscale, pk[0][0], pk[1][0]);
                         split2_f16x2((float)kv[2], (float)kv[3], xscale, pk[0][1], pk[1][1]);
@@ -398,6 +405,12 @@ __global__ __launch_bounds__(256, 2) void kstar_kernel(const T *__restrict__ Cs,
 #pragma unroll
             for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
             if (tx == 0) mupart[(long)blockIdx.y * ldpart + c0 + crow(a)] = s;
+            if (BND) {
+                double t = pa[a];
+#pragma unroll
+                for (int o = 8; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+                if (tx == 0) reinterpret_cast<double *>(Ks)[(long)blockIdx.y * ldpart + c0 + crow(a)] = t;
+            }
         }
     }
 }
@@ -435,6 +448,8 @@ struct FinArgs {
     int acq; double sf, incumbent, param;
     double *mu, *sigma, *acqv; // nullable (M,) outputs
     double *bval; long long *bidx; long long *counters;   // counters[1] += clamped
+    const long long *gidx;     // null, or the batch index of each of the m rows (a gathered subset, sweep_pruned); `off` then only
+                               // places the block partials
 };
 
 __global__ __launch_bounds__(FIN_BLOCK) void finalize_kernel(FinArgs f) {
@@ -478,7 +493,7 @@ __global__ __launch_bounds__(FIN_BLOCK) void finalize_kernel(FinArgs f) {
                 }
             }
         }
-        const long gc = f.off + c;
+        const long gc = f.gidx ? (long)f.gidx[c] : f.off + c;
         if (f.mu) f.mu[gc] = mu;
         if (f.sigma) f.sigma[gc] = sigma;
         if (f.acqv) f.acqv[gc] = a;
@@ -696,21 +711,31 @@ static hipError_t issue_prep(Context &c, hipStream_t st) {
 // the cross-kernel slab of launch pair n (rows padded to `tile_n`, the widest candidate tile any contraction of this
 // pair uses)
 template <typename T>
+using KstarFn = void (*)(const T *, const T *, const double *, T *, double *, int, int, int, int, double, long, long, float);
+constexpr int kstar_ar(size_t bytes) { return bytes == 4 ? 8 : 4; }   // candidate rows per thread: tiles of 128 (f32) / 64 (f64)
+
+// the cross-kernel instantiation for the handle's kernel: split-operand slab (h2 / x3), slab without / with the partial
+// means (nomu), or the pruned sweep's bound pass (bound)
+template <typename T>
+static KstarFn<T> kstar_fn(int kernel, bool h2, bool x3, bool nomu, bool bound) {
+    constexpr int KAR = kstar_ar(sizeof(T));
+    constexpr int P3 = sizeof(T) == 4 ? 3 : 0, P2 = sizeof(T) == 4 ? 2 : 0;
+    switch (kernel) {
+        case TGP_RBF: return bound ? kstar_kernel<T, TGP_RBF, KAR, 4> : h2 ? kstar_kernel<T, TGP_RBF, KAR, P2> : x3 ? kstar_kernel<T, TGP_RBF, KAR, P3> : nomu ? kstar_kernel<T, TGP_RBF, KAR, 0, false> : kstar_kernel<T, TGP_RBF, KAR>;
+        case TGP_MATERN12: return bound ? kstar_kernel<T, TGP_MATERN12, KAR, 4> : h2 ? kstar_kernel<T, TGP_MATERN12, KAR, P2> : x3 ? kstar_kernel<T, TGP_MATERN12, KAR, P3> : nomu ? kstar_kernel<T, TGP_MATERN12, KAR, 0, false> : kstar_kernel<T, TGP_MATERN12, KAR>;
+        case TGP_MATERN32: return bound ? kstar_kernel<T, TGP_MATERN32, KAR, 4> : h2 ? kstar_kernel<T, TGP_MATERN32, KAR, P2> : x3 ? kstar_kernel<T, TGP_MATERN32, KAR, P3> : nomu ? kstar_kernel<T, TGP_MATERN32, KAR, 0, false> : kstar_kernel<T, TGP_MATERN32, KAR>;
+        default: return bound ? kstar_kernel<T, TGP_MATERN52, KAR, 4> : h2 ? kstar_kernel<T, TGP_MATERN52, KAR, P2> : x3 ? kstar_kernel<T, TGP_MATERN52, KAR, P3> : nomu ? kstar_kernel<T, TGP_MATERN52, KAR, 0, false> : kstar_kernel<T, TGP_MATERN52, KAR>;
+    }
+}
+
+template <typename T>
 static hipError_t issue_kstar(Context &c, const SweepPlan<T> &p, int64_t n, int sl, int tile_n, hipStream_t st) {
     const int N = (int)c.N, Np = (int)c.Np, Dp = (int)c.Dp;
     const T *Xs = reinterpret_cast<const T *>(sizeof(T) == 8 ? (const void *)c.d_Xs : (const void *)c.d_Xs32);
     const PairRows r = pair_rows(c, n, tile_n);
-    void (*kst)(const T *, const T *, const double *, T *, double *, int, int, int, int, double, long, long, float);
-    constexpr int KAR = sizeof(T) == 4 ? 8 : 4;
-    constexpr int P3 = sizeof(T) == 4 ? 3 : 0, P2 = sizeof(T) == 4 ? 2 : 0;
+    constexpr int KAR = kstar_ar(sizeof(T));
     const dim3 kgrid((unsigned)(r.rows / (16 * KAR)), (unsigned)p.njs);
-    const bool h2 = p.h2, x3 = p.x3, nomu = p.mean_in_trmm;
-    switch (c.kernel) {
-        case TGP_RBF: kst = h2 ? kstar_kernel<T, TGP_RBF, KAR, P2> : x3 ? kstar_kernel<T, TGP_RBF, KAR, P3> : nomu ? kstar_kernel<T, TGP_RBF, KAR, 0, false> : kstar_kernel<T, TGP_RBF, KAR>; break;
-        case TGP_MATERN12: kst = h2 ? kstar_kernel<T, TGP_MATERN12, KAR, P2> : x3 ? kstar_kernel<T, TGP_MATERN12, KAR, P3> : nomu ? kstar_kernel<T, TGP_MATERN12, KAR, 0, false> : kstar_kernel<T, TGP_MATERN12, KAR>; break;
-        case TGP_MATERN32: kst = h2 ? kstar_kernel<T, TGP_MATERN32, KAR, P2> : x3 ? kstar_kernel<T, TGP_MATERN32, KAR, P3> : nomu ? kstar_kernel<T, TGP_MATERN32, KAR, 0, false> : kstar_kernel<T, TGP_MATERN32, KAR>; break;
-        default: kst = h2 ? kstar_kernel<T, TGP_MATERN52, KAR, P2> : x3 ? kstar_kernel<T, TGP_MATERN52, KAR, P3> : nomu ? kstar_kernel<T, TGP_MATERN52, KAR, 0, false> : kstar_kernel<T, TGP_MATERN52, KAR>; break;
-    }
+    const KstarFn<T> kst = kstar_fn<T>(c.kernel, p.h2, p.x3, p.mean_in_trmm, false);
     hipLaunchKernelGGL(kst, kgrid, dim3(256), 0, st, reinterpret_cast<const T *>(c.d_Cs) + r.off * Dp, Xs, c.d_alpha,
                        reinterpret_cast<T *>(c.d_Ks[sl]), c.d_mupart + r.off, (int)r.rows, N, Np, Dp, c.constant,
                        (long)c.ws_Mpad, (long)Np / 16, p.h2_sb);   // (Np / 16: 16-k blocks per row of the pre-tiled split-operand slabs)
@@ -775,6 +800,340 @@ static hipError_t presweep_rows_t(Context &c, hipStream_t st, int rows_final, in
     return hipSuccess;
 }
 
+// ---- the pruned sweep: contract only the candidates that can still win ----------------------------------
+// An arg-max-only sweep (no mean, deviation or acquisition vector asked for) needs a candidate's variance only if its
+// acquisition could still be the largest.  c + s^2 - q lies in [s^2, c + s^2] (q = k^T K^-1 k in [0, c]), and for a fixed
+// mean EI and UCB (param >= 0) increase with sigma, PI increases or decreases with it by the sign of its argument -- so
+// the mean alone bounds each candidate's acquisition from above, at the larger of its values at the interval's ends:
+//   1. bound pass: kstar (XP = 4) over all M without a slab -> Ks.alpha and |Ks|.|alpha| -> prune_bound_kernel: the mean
+//      moved by its rounding-error bound the way that raises the acquisition, then a relative margin on top;
+//   2. lb set: the largest bound of each of prune_top groups of consecutive candidates, contracted exactly (kstar, the
+//      128 x 128 contraction, finalize on the gathered rows); its best value is the bar lb;
+//   3. survivors: every other candidate whose bound reaches lb (less the margin), compacted in index order and contracted
+//      the same way; ONE arg-max over both sets with the batch indices, so the lowest index still wins a tie.
+// A contracted candidate goes through the full sweep's arithmetic (same Ks bits, MeanAcc's one summation order, the same
+// units in finalize whichever tiling ran): the winner's value and index are the full sweep's, bit for bit.  The clamp gate
+// s^2 / (c + s^2) >= prune_tau * u (u: the contraction's unit roundoff; measured |q - q_f64| / c stays below 122 u,
+// DESIGN §4) keeps every computed variance above 0.99 s^2: no skipped candidate could have clamped, and 0.99 s^2 is a valid
+// lower end of the interval.  More than prune_frac of the batch surviving: the full schedule runs instead.
+__device__ __forceinline__ double acq_at(int acq, double sf, double incumbent, double param, double mu, double sigma) {
+    // finalize_kernel's formulas
+    if (acq == TGP_ACQ_UCB) return sf * mu + param * sigma;
+    if (sigma == 0.0) return 0.0;
+    const double diff = sf * (mu - incumbent) - param;
+    const double Z = diff / sigma;
+    if (acq == TGP_ACQ_PI) return ndtr_dev(Z);
+    const double pdf = exp(-(Z * Z) / 2.0) / 2.5066282746310002;
+    return diff * ndtr_dev(Z) + sigma * pdf;
+}
+
+struct BoundArgs {
+    const double *mupart, *abspart; long ldpart; int njs;   // the bound pass's partial sums, njs rows each
+    long m;
+    double err_scale;          // |the contraction's K*.alpha - this sum| <= err_scale * sum |k| |alpha| (two orders of the same products)
+    double y_mean, y_std;
+    double sig_lo, sig_hi;     // every candidate's computed sigma lies in [sig_lo, sig_hi]
+    int acq; double sf, incumbent, param, margin;
+    double *ub;                // (m,) the bound; NaN -> +inf (always contracted)
+};
+
+__global__ __launch_bounds__(256) void prune_bound_kernel(BoundArgs b) {
+    const long c = (long)blockIdx.x * 256 + threadIdx.x;
+    if (c >= b.m) return;
+    double mun = 0.0, s = 0.0;
+    for (int j = 0; j < b.njs; ++j) {
+        mun += b.mupart[(long)j * b.ldpart + c];
+        s += b.abspart[(long)j * b.ldpart + c];
+    }
+    const double e = b.err_scale * s;
+    const double mu = b.y_std * (b.sf > 0.0 ? mun + e : mun - e) + b.y_mean;
+    const double a_lo = acq_at(b.acq, b.sf, b.incumbent, b.param, mu, b.sig_lo);
+    const double a_hi = acq_at(b.acq, b.sf, b.incumbent, b.param, mu, b.sig_hi);
+    double a = a_lo > a_hi ? a_lo : a_hi;
+    // margin against the rounding of the formulas themselves (UCB: relative to its terms, which may cancel)
+    double scale = fabs(a);
+    if (b.acq == TGP_ACQ_UCB) scale += fabs(mu) + fabs(b.param) * b.sig_hi;
+    a += b.margin * scale;
+    b.ub[c] = (isnan(a_lo) || isnan(a_hi) || isnan(a)) ? INFINITY : a;
+}
+
+// the lb set: per group of gs consecutive candidates the one with the largest bound (lowest index on ties)
+__global__ __launch_bounds__(256) void prune_pick_kernel(const double *__restrict__ ub, long m, long gs,
+                                                         long long *__restrict__ pick) {
+    __shared__ double sv[256];
+    __shared__ long long si[256];
+    const long g0 = (long)blockIdx.x * gs;
+    const long g1 = g0 + gs < m ? g0 + gs : m;
+    double v = -INFINITY;
+    long long i = 0x7fffffffffffffffLL;
+    for (long c = g0 + threadIdx.x; c < g1; c += 256) {
+        const double u = ub[c];
+        if (u > v) { v = u; i = c; }
+    }
+    sv[threadIdx.x] = v;
+    si[threadIdx.x] = i;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) {
+            const double v2 = sv[threadIdx.x + o];
+            const long long i2 = si[threadIdx.x + o];
+            if (v2 > sv[threadIdx.x] || (v2 == sv[threadIdx.x] && i2 < si[threadIdx.x])) { sv[threadIdx.x] = v2; si[threadIdx.x] = i2; }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) pick[blockIdx.x] = si[0] == 0x7fffffffffffffffLL ? g0 : si[0];   // (all bounds -inf: the group's first)
+}
+
+// rows idx[0..n) of the scaled candidates into a dense block of `rows` rows (rows >= n zero)
+template <typename T>
+__global__ __launch_bounds__(256) void prune_gather_kernel(const T *__restrict__ Cs, int Dp, const long long *__restrict__ idx,
+                                                           long n, long rows, T *__restrict__ out) {
+    const long total = rows * Dp;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const long r = i / Dp;
+        const int d = (int)(i - r * Dp);
+        out[i] = r < n ? Cs[idx[r] * Dp + d] : (T)0;
+    }
+}
+
+struct SurvArgs {
+    const double *ub; long m;
+    const long long *pick; long gs;   // the lb set (already contracted: not a survivor)
+    const double *lb; double margin;  // lb: the lb set's best exact value (device)
+    int *bcnt; const int *boff;       // survivors per 256-candidate block / exclusive offsets
+    long long *sidx;                  // survivors' batch indices, in order
+};
+
+__device__ __forceinline__ bool prune_survives(const SurvArgs &s, long c) {
+    const double lb = s.lb[0];
+    const double bar = isinf(lb) ? lb : lb - s.margin * fabs(lb);
+    return c < s.m && s.ub[c] >= bar && s.pick[c / s.gs] != c;
+}
+
+__global__ __launch_bounds__(256) void prune_count_kernel(SurvArgs s) {
+    __shared__ int wsum[4];
+    const long c = (long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long bal = __ballot(prune_survives(s, c));
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __popcll(bal);
+    __syncthreads();
+    if (threadIdx.x == 0) s.bcnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+__global__ __launch_bounds__(1024) void prune_scan_kernel(const int *__restrict__ bcnt, int nb, int *__restrict__ boff,
+                                                          long long *__restrict__ total) {
+    __shared__ int part[1024];
+    const int per = (nb + 1023) / 1024;
+    const int b0 = (int)threadIdx.x * per;
+    const int b1 = b0 + per < nb ? b0 + per : nb;
+    int s = 0;
+    for (int b = b0; b < b1; ++b) s += bcnt[b];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const int v = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int run = part[threadIdx.x] - s;
+    for (int b = b0; b < b1; ++b) { boff[b] = run; run += bcnt[b]; }
+    if (threadIdx.x == 1023) total[0] = part[1023];
+}
+
+__global__ __launch_bounds__(256) void prune_scatter_kernel(SurvArgs s) {
+    __shared__ int wsum[4];
+    const long c = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool keep = prune_survives(s, c);
+    const unsigned long long bal = __ballot(keep);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) wsum[w] = __popcll(bal);
+    __syncthreads();
+    int off = s.boff[blockIdx.x];
+    for (int k = 0; k < w; ++k) off += wsum[k];
+    if (keep) s.sidx[off + __popcll(bal & ((1ull << lane) - 1ull))] = c;
+}
+
+// the pruned sweep's own workspace (grow-only): bounds, lb set, survivors, block counts, the gathered scaled rows
+struct PruneWs {
+    double *ub; long long *pick, *sidx, *misc; int *bcnt, *boff; void *cs;
+};
+static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+template <typename T>
+static hipError_t prune_workspace(Context &c, int64_t npick, int64_t rows_cap, PruneWs &w) {
+    const int64_t M = c.M, nb = (M + 255) / 256;
+    const size_t o_pick = al256((size_t)M * 8), o_sidx = o_pick + al256((size_t)npick * 8), o_misc = o_sidx + al256((size_t)M * 8),
+                 o_bcnt = o_misc + 256, o_boff = o_bcnt + al256((size_t)nb * 4), o_cs = o_boff + al256((size_t)nb * 4);
+    const size_t need = o_cs + (size_t)rows_cap * c.Dp * sizeof(T);
+    if (need > c.cap_prune) {
+        TGP_TRY(hipStreamSynchronize(c.stream));
+        if (c.d_prune) TGP_TRY(hipFree(c.d_prune));
+        c.d_prune = nullptr;
+        c.cap_prune = 0;
+        TGP_TRY(hipMalloc((void **)&c.d_prune, need));
+        c.cap_prune = need;
+    }
+    char *b = c.d_prune;
+    w.ub = reinterpret_cast<double *>(b);
+    w.pick = reinterpret_cast<long long *>(b + o_pick);
+    w.sidx = reinterpret_cast<long long *>(b + o_sidx);
+    w.misc = reinterpret_cast<long long *>(b + o_misc);
+    w.bcnt = reinterpret_cast<int *>(b + o_bcnt);
+    w.boff = reinterpret_cast<int *>(b + o_boff);
+    w.cs = b + o_cs;
+    return hipSuccess;
+}
+
+// n gathered rows: per launch_rows of them the cross-kernel into slot 0, then the 128 x 128 contraction over every row
+// tile with the mean inside (part / mupart rows [0, n))
+template <typename T>
+static hipError_t contract_rows(Context &c, const SweepPlan<T> &p, const T *cs, int64_t n, hipStream_t st, int &mark) {
+    const int N = (int)c.N, Np = (int)c.Np, Dp = (int)c.Dp;
+    constexpr int KAR = kstar_ar(sizeof(T));
+    const T *Xs = reinterpret_cast<const T *>(sizeof(T) == 8 ? (const void *)c.d_Xs : (const void *)c.d_Xs32);
+    const KstarFn<T> kst = kstar_fn<T>(c.kernel, false, false, true, false);
+    for (int64_t off = 0; off < n; off += c.launch_rows) {
+        const int64_t m = n - off < c.launch_rows ? n - off : c.launch_rows;
+        const int64_t rows = ((m + 127) / 128) * 128;
+        hipLaunchKernelGGL(kst, dim3((unsigned)(rows / (16 * KAR)), (unsigned)p.njs), dim3(256), 0, st, cs + off * Dp, Xs,
+                           c.d_alpha, reinterpret_cast<T *>(c.d_Ks[0]), c.d_mupart + off, (int)rows, N, Np, Dp, c.constant,
+                           (long)c.ws_Mpad, (long)Np / 16, 1.f);
+        TGP_TRY(hipGetLastError());
+        int m2 = prof_mark(c, st);
+        prof_seg(c, mark, m2, 1);
+        mark = m2;
+        GemmArgs g{};
+        g.A = sizeof(T) == 8 ? (const void *)c.d_Linv : (const void *)c.d_Linv32; g.lda = Np;
+        g.B = c.d_Ks[0]; g.ldb = Np;
+        g.part = c.d_part + off; g.ldpart = c.ws_Mpad;
+        g.prm = 1;
+        g.tm0 = 0; g.ntm = p.n128; g.ntn = (int)(rows / 128); g.ntn_group = 0;
+        g.K = p.n128 * 128;
+        g.mu_alpha = c.d_alpha; g.mu = c.d_mupart + off;
+        hipLaunchKernelGGL(p.early.kern, dim3((unsigned)(g.ntm * g.ntn)), dim3(256), trmm_glds_lds_bytes(), st, g);
+        TGP_TRY(hipGetLastError());
+        m2 = prof_mark(c, st);
+        prof_seg(c, mark, m2, 0, (double)m * (double)N * (double)N);
+        mark = m2;
+    }
+    return hipSuccess;
+}
+
+// done = false: too many survivors -- the caller runs the full schedule (nothing of this call's results is left behind)
+template <typename T>
+static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, int acq, double sf, double incumbent, double param,
+                               bool &done) {
+    done = false;
+    const Tuning &tu = tuning();
+    const int64_t M = c.M, Mpad = c.ws_Mpad;
+    const int N = (int)c.N, Dp = (int)c.Dp;
+    hipStream_t st = c.stream;
+    const int64_t top = tu.prune_top < 1 ? 1 : tu.prune_top;
+    const int64_t gs = (M + top - 1) / top, npick = (M + gs - 1) / gs;
+    const double frac = tuning_prune_frac_now();
+    const int64_t keep = frac < 0.0 ? -1 : (frac >= 1.0 ? M : (int64_t)(frac * (double)M));   // most survivors taken
+    const int64_t rows_cap = (((npick > keep ? npick : keep) + 127) / 128) * 128;
+    PruneWs w;
+    TGP_TRY(prune_workspace<T>(c, npick, rows_cap, w));
+    TGP_TRY(lds_opt_in(c, p.early.kern, p.early.lds));   // (the request the fit's early row tiles make of the same kernel)
+    const T *Cs = reinterpret_cast<const T *>(c.d_Cs);
+    T *cs = reinterpret_cast<T *>(w.cs);
+
+    // 1. the bound of every candidate
+    if (!c.pre.usable) TGP_TRY(issue_prep<T>(c, st));   // (a fit's front has scaled them already)
+    int mark = prof_mark(c, st);
+    {
+        constexpr int KAR = kstar_ar(sizeof(T));
+        const T *Xs = reinterpret_cast<const T *>(sizeof(T) == 8 ? (const void *)c.d_Xs : (const void *)c.d_Xs32);
+        hipLaunchKernelGGL(kstar_fn<T>(c.kernel, false, false, false, true), dim3((unsigned)(Mpad / (16 * KAR)), (unsigned)p.njs),
+                           dim3(256), 0, st, Cs, Xs, c.d_alpha, reinterpret_cast<T *>(c.d_part), c.d_mupart, (int)Mpad, N,
+                           (int)c.Np, Dp, c.constant, (long)Mpad, 0L, 1.f);
+        TGP_TRY(hipGetLastError());
+        const int m2 = prof_mark(c, st);
+        prof_seg(c, mark, m2, 1);
+        mark = m2;
+    }
+    BoundArgs b{};
+    b.mupart = c.d_mupart; b.abspart = c.d_part; b.ldpart = Mpad; b.njs = p.njs;
+    b.m = M;
+    b.err_scale = 4.0 * (double)(N + 8) * 0x1p-53;
+    b.y_mean = c.y_mean; b.y_std = c.y_std;
+    b.sig_lo = sqrt((0.99 * c.noise) * (c.y_std * c.y_std));
+    b.sig_hi = sqrt((c.constant + c.noise) * (c.y_std * c.y_std));
+    b.acq = acq; b.sf = sf; b.incumbent = incumbent; b.param = param; b.margin = tu.prune_margin;
+    b.ub = w.ub;
+    hipLaunchKernelGGL(prune_bound_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, b);
+    TGP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(prune_pick_kernel, dim3((unsigned)npick), dim3(256), 0, st, w.ub, (long)M, (long)gs, w.pick);
+    TGP_TRY(hipGetLastError());
+
+    auto gather = [&](const long long *idx, int64_t n) -> hipError_t {
+        const long total = (long)(((n + 127) / 128) * 128) * Dp;
+        const long blocks = (total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192;
+        hipLaunchKernelGGL(prune_gather_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, Cs, Dp, idx, (long)n,
+                           (long)(((n + 127) / 128) * 128), cs);
+        return hipGetLastError();
+    };
+    auto finalize = [&](const long long *idx, int64_t n, int64_t blk0) -> hipError_t {
+        FinArgs f{};
+        f.part = c.d_part; f.ldpart = Mpad;
+        f.nunits = p.nunits; f.n128 = p.n128;
+        f.base_pairs = p.nunits;   // 128-row tiles throughout
+        f.mupart = c.d_mupart; f.njs = 1;
+        f.off = blk0 * FIN_BLOCK; f.m = n;
+        f.kss = c.constant + c.noise;
+        f.y_mean = c.y_mean; f.y_std = c.y_std;
+        f.acq = acq; f.sf = sf; f.incumbent = incumbent; f.param = param;
+        f.bval = c.d_bval; f.bidx = c.d_bidx; f.counters = c.d_besti;
+        f.gidx = idx;
+        hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n + FIN_BLOCK - 1) / FIN_BLOCK)), dim3(FIN_BLOCK), 0, st, f);
+        return hipGetLastError();
+    };
+
+    // 2. the lb set, exactly; its best value is the bar (d_best)
+    TGP_TRY(gather(w.pick, npick));
+    TGP_TRY(contract_rows<T>(c, p, cs, npick, st, mark));
+    TGP_TRY(finalize(w.pick, npick, 0));
+    const int64_t nblk_a = (npick + FIN_BLOCK - 1) / FIN_BLOCK;
+    hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, st, c.d_bval, c.d_bidx, (long)nblk_a, c.d_best, c.d_besti,
+                       nullptr, c.d_cand, (int)c.D, (long)M, 0LL, nullptr, Bell{nullptr, 0, nullptr});
+    TGP_TRY(hipGetLastError());
+
+    // 3. the survivors, in index order
+    const int64_t nb = (M + 255) / 256;
+    SurvArgs s{w.ub, (long)M, w.pick, (long)gs, c.d_best, tu.prune_margin, w.bcnt, w.boff, w.sidx};
+    hipLaunchKernelGGL(prune_count_kernel, dim3((unsigned)nb), dim3(256), 0, st, s);
+    TGP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(1024), 0, st, w.bcnt, (int)nb, w.boff, w.misc);
+    TGP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(prune_scatter_kernel, dim3((unsigned)nb), dim3(256), 0, st, s);
+    TGP_TRY(hipGetLastError());
+    long long nsurv = 0;
+    TGP_TRY(hipMemcpyAsync(&nsurv, w.misc, sizeof(long long), hipMemcpyDeviceToHost, st));
+    TGP_TRY(hipStreamSynchronize(st));   // (the launches below are sized by the count)
+    c.prune_lbset = npick;
+    c.prune_surv = nsurv;
+    if (nsurv > keep) {
+        // the full schedule instead: it counts the lb set's clamps again (the counter was zero when this sweep began)
+        c.prune_state = 1;
+        return hipMemsetAsync(c.d_besti + 1, 0, sizeof(long long), st);
+    }
+    int64_t nblk_b = 0;
+    if (nsurv > 0) {
+        TGP_TRY(gather(w.sidx, nsurv));
+        TGP_TRY(contract_rows<T>(c, p, cs, nsurv, st, mark));
+        TGP_TRY(finalize(w.sidx, nsurv, nblk_a));
+        nblk_b = (nsurv + FIN_BLOCK - 1) / FIN_BLOCK;
+    }
+    hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, st, c.d_bval, c.d_bidx, (long)(nblk_a + nblk_b), c.d_best,
+                       c.d_besti, c.d_winner, c.d_cand, (int)c.D, (long)M, (long long)c.winner_offset, c.sweep_res_host,
+                       Bell{nullptr, 0, nullptr});
+    TGP_TRY(hipGetLastError());
+    c.prune_state = 0;
+    done = true;
+    return hipSuccess;
+}
+
 template <typename T, int BK>
 static hipError_t sweep_chunks(Context &c, int acq, double sf, double incumbent, double param,
                                bool want_mu, bool want_sigma, bool want_acq) {
@@ -783,6 +1142,21 @@ static hipError_t sweep_chunks(Context &c, int acq, double sf, double incumbent,
     TGP_TRY((make_plan<T, BK>(c, p)));
     const TrmmVariant &v = p.main;
     const bool x3 = p.x3, h2 = p.h2;
+    // an arg-max-only EI / PI / UCB sweep in f32 / f64 first tries the pruned schedule (TGP_SWEEP_PRUNE)
+    bool fell_back = false;
+    if (!want_mu && !want_sigma && !want_acq && (acq == TGP_ACQ_EI || acq == TGP_ACQ_PI || acq == TGP_ACQ_UCB) &&
+        (c.dtype == TGP_F32 || c.dtype == TGP_F64) && p.mean_in_trmm && tuning_sweep_prune_now() != 0 &&
+        c.M > tuning().prune_top && (double)c.M * (double)c.N * (double)c.N >= tuning_prune_min_work_now()) {
+        const double u = sizeof(T) == 4 ? 0x1p-24 : 0x1p-53;
+        if (c.noise > 0.0 && c.noise / (c.constant + c.noise) >= tuning().prune_tau * u) {
+            bool done = false;
+            TGP_TRY(sweep_pruned<T>(c, p, acq, sf, incumbent, param, done));
+            if (done) return hipSuccess;
+            fell_back = true;
+        } else {
+            c.prune_state = -2;
+        }
+    }
 
     // One pass over the batch: scale all candidates once, then per chunk the cross-kernel slab and
     // its contraction, then ONE finalize + arg-max over all M.  The partial sums live in (Np / 128, Mpad)
@@ -793,7 +1167,8 @@ static hipError_t sweep_chunks(Context &c, int acq, double sf, double incumbent,
     const int64_t Mpad = c.ws_Mpad;
     // what the last fit already started for this very batch (tgp_set_overlap): the scaling, launch pair 0's
     // cross-kernel and the first pre128 row tiles of its contraction
-    const bool pre = c.pre.usable && p.mean_in_trmm;
+    // (after a fall-back from the pruned schedule the slab and the partial sums hold its rows: the front is spent)
+    const bool pre = c.pre.usable && p.mean_in_trmm && !fell_back;
     const int pre128 = pre ? c.pre.rows128 : 0;
     if (!pre) TGP_TRY(issue_prep<T>(c, sa));
     if (h2 && (c.linv16_gen != c.fit_gen || c.linv16_sb != p.h2_sb)) {

@@ -264,6 +264,7 @@ static void free_fit(Context &c) {
 }
 static void free_ws(Context &c) {
     dfree(c.d_Cs); dfree(c.d_Ks[0]); dfree(c.d_Ks[1]); dfree(c.d_part); dfree(c.d_mupart);
+    dfree(c.d_prune); c.cap_prune = 0;
     dfree(c.d_topv); dfree(c.d_topi); c.cap_topv = c.cap_topi = 0;
     dfree(c.d_batch); c.cap_batch = 0;
     dfree(c.d_bt); dfree(c.d_btm); dfree(c.d_bti); c.cap_bt = c.cap_btm = c.cap_bti = 0;
@@ -1513,6 +1514,8 @@ int tgp_sweep(tgp_handle h, int acq, double sf, double incumbent, double param, 
     const Bell bell = ((small || mid) && !mu && !sigma && !acq_out) ? bell_next(c) : Bell{nullptr, 0, nullptr};
     const auto t_host0 = std::chrono::steady_clock::now();
     if (!bell.word) API_HIP(hipEventRecord(e0, c.stream), "hipEventRecord");
+    c.prune_state = -1;
+    c.prune_lbset = c.prune_surv = 0;
     hipError_t le;
     if (mid) {
         le = launch_mid_sweep(c, c.d_cand, acq, sf, incumbent, param, mu ? c.d_mu : nullptr,
@@ -2621,7 +2624,7 @@ int tgp_last_timings(tgp_handle h, double *out, int64_t n) try {
     if (!h) return TGP_BAD_ARG;
     if (h->host) {
         if (!out || n < 1) { h->host->err = "tgp_last_timings: need out and n >= 1"; return TGP_BAD_ARG; }
-        for (int64_t i = 0; i < n; ++i) out[i] = i == 0 ? h->host->last_fit_ms : (i == 1 ? h->host->last_sweep_ms : (i == 6 ? 1.0 : 0.0));   // [6]: the host backend is float64 throughout
+        for (int64_t i = 0; i < n; ++i) out[i] = i == 0 ? h->host->last_fit_ms : (i == 1 ? h->host->last_sweep_ms : (i == 6 ? 1.0 : (i == 12 ? -1.0 : 0.0)));   // [6]: the host backend is float64 throughout; [12]: it never prunes
         return TGP_OK;
     }
     Context &c = h->c;
@@ -2630,14 +2633,17 @@ int tgp_last_timings(tgp_handle h, double *out, int64_t n) try {
     // kernels), 0 when it ran in the handle's arithmetic, -1 before the first sweep
     // [7..11] (round 6, a debugging aid): phase stamps of the last POLLED small fit in microseconds from the kernel's start --
     // inputs staged, first kernel-matrix tile in LDS, first block factored, fit done, call done (0 when the call was not polled)
-    double v[12] = {c.last_fit_ms, c.last_sweep_ms, c.last_grad_ms[0], c.last_grad_ms[1], c.last_grad_ms[2], c.trmm_flops,
-                    (double)c.last_sweep_f64, 0.0, 0.0, 0.0, 0.0, 0.0};
+    // [12..14]: what the last tgp_sweep did about pruning (sweep_pruned): -1 not eligible, -2 gated off, 0 pruned, 1 fell
+    // back to every candidate; the candidates of its lb set; its survivors
+    double v[15] = {c.last_fit_ms, c.last_sweep_ms, c.last_grad_ms[0], c.last_grad_ms[1], c.last_grad_ms[2], c.trmm_flops,
+                    (double)c.last_sweep_f64, 0.0, 0.0, 0.0, 0.0, 0.0, (double)c.prune_state, (double)c.prune_lbset,
+                    (double)c.prune_surv};
     if (c.h_bell && c.h_bell[1]) {
         const unsigned long long t0 = c.h_bell[1];
         const int src[5] = {3, 4, 5, 6, 2};
         for (int k = 0; k < 5; ++k) v[7 + k] = c.h_bell[src[k]] >= t0 ? (double)(c.h_bell[src[k]] - t0) * 1e-2 : 0.0;
     }
-    for (int64_t i = 0; i < n; ++i) out[i] = i < 12 ? v[i] : 0.0;
+    for (int64_t i = 0; i < n; ++i) out[i] = i < 15 ? v[i] : 0.0;
     return TGP_OK;
 } TGP_CATCH
 

@@ -153,6 +153,10 @@ struct Context {
     size_t cap_Cs = 0, cap_Ks[2] = {0, 0}, cap_part = 0, cap_mupart = 0, cap_bval = 0, cap_bidx = 0;   // bytes
     double *d_mu = nullptr, *d_sigma = nullptr, *d_acq = nullptr;   // (M,) optional outputs
     int64_t out_cap = 0;
+    char *d_prune = nullptr;      // the pruned sweep's workspace (sweep_kernels.hip, sweep_pruned)
+    size_t cap_prune = 0;         // bytes
+    int prune_state = -1;         // the last sweep: -1 not eligible, -2 gated off, 0 pruned, 1 fell back to every candidate
+    int64_t prune_lbset = 0, prune_surv = 0;   // ... candidates in its lb set / survivors
     double *d_bval = nullptr;     // per finalize block arg-max value
     long long *d_bidx = nullptr;  // per finalize block arg-max index
     double *sweep_res_host = nullptr;   // set by tgp_sweep around launch_sweep: device-mapped [best value, best index, clamp count] the sweep's last kernel fills (no D2H copy, no memset behind it), or null

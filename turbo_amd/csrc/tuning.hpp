@@ -35,6 +35,12 @@ namespace tgp {
     X(INT, pre_cus, "TGP_PRE_CUS", -1, "CUs of the third stream, which carries the sweep's front inside a fit (-1 = three quarters of the device, 0 = unmasked)") \
     X(INT, pre_cu0, "TGP_PRE_CU0", 0, "first CU of that mask")                                                                 \
     X(INT, pre_lds_kb, "TGP_PRE_LDS_KB", 81, "KiB of LDS requested per workgroup of the early contraction (64 = two per CU, 81 = one)") \
+    X(INT, sweep_prune, "TGP_SWEEP_PRUNE", 1, "1 = an arg-max-only EI / PI / UCB sweep (f32 / f64, N > 256) contracts only the candidates whose acquisition bound can still win (sweep_pruned); 0 = every candidate [per call]") \
+    X(INT, prune_top, "TGP_PRUNE_TOP", 256, "candidates of the pruned sweep's lb set (the best bound of each of this many groups): its best exact value is the bar") \
+    X(DBL, prune_frac, "TGP_PRUNE_FRAC", 0.25, "the pruned sweep runs the full schedule when more than this share of the batch survives (< 0: always) [per call]") \
+    X(DBL, prune_min_work, "TGP_PRUNE_MIN_WORK", 1e11, "the pruned sweep runs only when M * N^2 (the full contraction's multiply-adds) reaches this: below, its fixed cost is more than it saves [per call]") \
+    X(DBL, prune_tau, "TGP_PRUNE_TAU", 2e4, "the pruned sweep needs s^2 / (c + s^2) >= this * the contraction's unit roundoff (no skipped candidate can clamp)") \
+    X(DBL, prune_margin, "TGP_PRUNE_MARGIN", 1e-6, "relative slack of the pruned sweep's bounds against the bar (rounding of the acquisition formulas)") \
     X(INT, mid, "TGP_MID", 1, "0 = 128 < N <= 256 down the general sweep instead of the one-launch kernel")                      \
     X(INT, mid_maxm, "TGP_MID_MAXM", 0, "largest batch that takes the one-launch sweep for 256 < N <= 512 (0 = never) [per call]") \
     X(INT, small, "TGP_SMALL", 1, "0 = N <= 128 down the blocked path instead of the one-workgroup kernels")                     \
@@ -129,8 +135,11 @@ inline const Tuning &tuning() {
 // NOT a switch of this library: the HIP runtime's own variable, reported by tgp_stream_status (0 = unset)
 inline int runtime_hw_queues_env() { const char *v = getenv("GPU_MAX_HW_QUEUES"); return v ? atoi(v) : 0; }
 
-// the two rows tests flip inside one process: looked up at every call
+// the rows tests flip inside one process: looked up at every call
 inline int tuning_chunk_now() { const char *v = getenv("TGP_CHUNK"); return v ? atoi(v) : 0; }
 inline int tuning_mid_maxm_now() { const char *v = getenv("TGP_MID_MAXM"); return v ? atoi(v) : 0; }
+inline int tuning_sweep_prune_now() { const char *v = getenv("TGP_SWEEP_PRUNE"); return v ? atoi(v) : 1; }
+inline double tuning_prune_frac_now() { const char *v = getenv("TGP_PRUNE_FRAC"); return v ? atof(v) : 0.25; }
+inline double tuning_prune_min_work_now() { const char *v = getenv("TGP_PRUNE_MIN_WORK"); return v ? atof(v) : 1e11; }
 
 }  // namespace tgp
