@@ -225,23 +225,24 @@ int tgp_sweep(tgp_handle h, int acq, double sf, double incumbent, double param,
 /* Sharded arg-max (the candidate batch is cut into contiguous shards, one per GPU,
  * and the per-shard winners are combined; the reference's own arg-max is the argsort/[0] of
  * turbo/modules/auxiliary_optimisers.py:63-66 over the whole batch).  Attach a DEVICE buffer of
- * D + 2 doubles on this GPU: every later tgp_sweep with an acquisition also packs
+ * D + 2 doubles on this GPU: every later single-winner sweep with an acquisition (tgp_sweep,
+ * tgp_evaluate, tgp_sweep_topk; not tgp_sweep_batch) also packs
  *     [best value, (double)(global_offset + best index), candidate row (D)]
- * into it, on the device and before tgp_sweep returns, so the all-gather between GPUs (RCCL) can
+ * into it, on the device and before the call returns, so the all-gather between GPUs (RCCL) can
  * read it in place -- no D2H of the row, no host-built tensor.  global_offset = global index of
- * candidate 0 of this handle's shard.  The record is written on the library's stream and complete
- * when tgp_sweep returns (the call synchronises that stream), which is what lets another stream --
- * RCCL on the caller's -- read it without an event.  The buffer is borrowed (checked like
+ * candidate 0 of this handle's shard.  The record is written on the library's stream; another
+ * stream -- RCCL on the caller's -- is ordered behind it by tgp_winner_wait.  The buffer is borrowed (checked like
  * tgp_set_candidates_dev) until replaced, detached with rec_dev == NULL, a fit with another D,
  * or tgp_destroy. */
 int tgp_set_winner_out(tgp_handle h, void *rec_dev, int64_t global_offset);
 /* (round 6) Make `stream` -- a hipStream_t of the CALLER on this handle's device, passed as a plain pointer; NULL is
- * the legacy default stream -- wait for the winner record of the last tgp_sweep: the library records an event on its
- * own stream right behind the kernel that packs the record, and this call is one hipStreamWaitEvent on it.  It makes
- * the cross-stream ordering of the multi-GPU exchange explicit (the record is written on the library's stream and
- * read by RCCL on the caller's, turbo_amd/distributed.py): correct today because tgp_sweep returns only after a
- * synchronisation of its stream, and correct tomorrow if a sweep ever returns earlier.  No sweep with a record
- * yet: nothing to wait for, TGP_OK.  No record attached: TGP_BAD_ARG. */
+ * the legacy default stream -- wait for the winner record of the last sweep that packed one: the library records an
+ * event on its own stream behind every kernel chain that packs the record (tgp_sweep, tgp_evaluate, tgp_sweep_topk),
+ * and this call is one hipStreamWaitEvent on it.  The record is written on the library's stream and read by RCCL on
+ * the caller's (turbo_amd/distributed.py); the polled sweeps return on their doorbell, without a synchronisation of the
+ * library's stream, so this event is what orders the caller's stream behind the record.  Nothing has packed a record
+ * into the attached buffer yet (tgp_set_winner_out starts a buffer afresh): nothing to wait for, TGP_OK.  No record
+ * attached: TGP_BAD_ARG. */
 int tgp_winner_wait(tgp_handle h, void *stream);
 
 /* Acquisition value AND gradient with respect to the query point for a small batch (m <= 4096)

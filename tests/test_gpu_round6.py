@@ -201,6 +201,81 @@ def test_winner_wait_orders_another_stream_behind_the_record():
     np.testing.assert_array_equal(got[2:], Xc[r["best_idx"]])
 
 
+def _winner_model(N):
+    import turbo_amd as ta
+    rng = np.random.RandomState(N)
+    X = rng.uniform(0, 1, (N, 4))
+    y = np.sin(3 * X.sum(1))
+    gp = ta.NativeGP(0, "f64")
+    gp.fit(X, y, "matern52", 1.0, 0.8, 1e-3, 1e-10, True)
+    return gp, rng.uniform(0, 1, (3000, 4)), float(y.min())
+
+
+# N = 100: the one-workgroup kernels, N = 200: the one-launch sweep (both polled: the call returns on the doorbell, without
+# a stream synchronisation), N = 700: the general sweep
+@pytest.mark.parametrize("entry,N", [("evaluate", 100), ("evaluate", 200), ("sweep_topk", 100), ("sweep_topk", 200),
+                                     ("sweep_topk", 700)])
+def test_winner_wait_orders_another_stream_behind_every_entry_that_packs_the_record(entry, N):
+    """tgp_evaluate's mapped-memory path and tgp_sweep_topk pack the winner record like tgp_sweep does, so the event
+    tgp_winner_wait waits on is recorded behind them too: a clone issued on another stream behind winner_wait holds
+    [best value, offset + best index, row] of the call that just returned"""
+    import torch
+    import turbo_amd as ta
+    gp, Xc, inc = _winner_model(N)
+    rec = torch.zeros(6, dtype=torch.float64, device="cuda:0")
+    side = torch.cuda.Stream()
+    if entry == "evaluate":
+        gp.set_winner_out(rec.data_ptr(), 1000, keepalive=rec)
+        r = gp.evaluate(Xc, ta._lib.ACQ_EI, -1.0, inc, 0.01)
+        best_val, best_idx = r["best_val"], r["best_idx"]
+    else:
+        gp.set_candidates(Xc)
+        gp.set_winner_out(rec.data_ptr(), 1000, keepalive=rec)
+        idxs, vals = gp.sweep_topk(5, ta._lib.ACQ_EI, -1.0, inc, 0.01)
+        best_val, best_idx = vals[0], int(idxs[0])
+    gp.winner_wait(side.cuda_stream)
+    with torch.cuda.stream(side):
+        got = rec.clone()                          # issued on the side stream, behind the event
+    side.synchronize()
+    got = got.cpu().numpy()
+    assert got[0] == best_val and int(got[1]) == 1000 + best_idx
+    np.testing.assert_array_equal(got[2:], Xc[best_idx])
+
+
+def test_a_fresh_winner_buffer_has_nothing_to_wait_for():
+    """tgp_set_winner_out forgets the event of the buffer it replaces: no record has been packed into the new one"""
+    import torch
+    import turbo_amd as ta
+    gp, Xc, inc = _winner_model(300)
+    gp.set_candidates(Xc)
+    rec = torch.zeros(6, dtype=torch.float64, device="cuda:0")
+    gp.set_winner_out(rec.data_ptr(), 0, keepalive=rec)
+    gp.sweep(ta._lib.ACQ_EI, -1.0, inc, 0.01)        # records the event behind the old buffer's record
+    fresh = torch.full((6,), -7.25, dtype=torch.float64, device="cuda:0")
+    torch.cuda.synchronize()
+    gp.set_winner_out(fresh.data_ptr(), 0, keepalive=fresh)
+    side = torch.cuda.Stream()
+    gp.winner_wait(side.cuda_stream)                 # TGP_OK (anything else raises)
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(fresh.cpu().numpy(), np.full(6, -7.25))
+
+
+@pytest.mark.parametrize("N", [100, 200, 700])
+def test_sweep_batch_leaves_an_attached_winner_record_alone(N):
+    """the winner record belongs to the single-winner sweeps: tgp_sweep_batch's first sweep does not pack it"""
+    import torch
+    import turbo_amd as ta
+    gp, Xc, inc = _winner_model(N)
+    gp.set_candidates(Xc)
+    rec = torch.full((6,), -7.25, dtype=torch.float64, device="cuda:0")
+    torch.cuda.synchronize()
+    gp.set_winner_out(rec.data_ptr(), 1000, keepalive=rec)
+    r = gp.sweep_batch(3, ta._lib.BATCH_KB, acq=ta._lib.ACQ_EI, sf=-1.0, incumbent=inc, param=0.01)
+    assert len(set(r["idx"].tolist())) == 3
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(rec.cpu().numpy(), np.full(6, -7.25))
+
+
 @pytest.mark.parametrize("N,D,kind,dtype,M", [(40, 3, "matern52", "f64", 3000), (100, 4, "rbf", "f32", 3000),
                                              (200, 5, "matern32", "f32", 4000), (700, 6, "matern52", "f64", 5000),
                                              (1300, 8, "rbf", "f32", 6000), (700, 6, "rbf", "f32h2", 5000)])

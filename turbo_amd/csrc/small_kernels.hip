@@ -1427,28 +1427,26 @@ static hipError_t launch_mid_sweep_as(Context &c, const SmallSweepArgs &a, const
     return hipGetLastError();
 }
 
-hipError_t launch_mid_sweep(Context &c, const double *cand, int acq, double sf, double incumbent,
-                            double param, double *mu, double *sigma, double *acqv, double *res_host, const Bell &bell) {
+static SmallSweepArgs sweep_args(const Context &c, const SweepCall &s) {
     SmallSweepArgs a{};
-    a.cand = cand; a.ls = c.d_ls; a.Xs = c.d_Xs; a.Linv = c.d_Linv; a.alpha = c.d_alpha;
-    a.mu = mu; a.sigma = sigma; a.acqv = acqv;
+    a.cand = c.d_cand; a.ls = c.d_ls; a.Xs = c.d_Xs; a.Linv = c.d_Linv; a.alpha = c.d_alpha;
+    a.mu = s.mu; a.sigma = s.sigma; a.acqv = s.acqv;
     a.bval = c.d_bval; a.bidx = c.d_bidx; a.counters = c.d_besti;
     a.M = (long)c.M; a.N = (int)c.N; a.D = (int)c.D; a.Dp = (int)c.Dp; a.Np = (int)c.Np;
     a.constant = c.constant; a.kss = c.constant + c.noise; a.y_mean = c.y_mean; a.y_std = c.y_std;
-    a.acq = acq; a.sf = sf; a.incumbent = incumbent; a.param = param;
-    const MidFinal f{c.d_best, c.d_winner, res_host, (long long)c.winner_offset, bell};
-    return mid_sweep_cpw(c, c.M) == 64 ? launch_mid_sweep_as<64>(c, a, f) : launch_mid_sweep_as<32>(c, a, f);
+    a.acq = s.acq; a.sf = s.sf; a.incumbent = s.incumbent; a.param = s.param;
+    return a;
 }
 
-hipError_t launch_small_sweep(Context &c, const double *cand, int acq, double sf, double incumbent,
-                              double param, double *mu, double *sigma, double *acqv) {
-    SmallSweepArgs a{};
-    a.cand = cand; a.ls = c.d_ls; a.Xs = c.d_Xs; a.Linv = c.d_Linv; a.alpha = c.d_alpha;
-    a.mu = mu; a.sigma = sigma; a.acqv = acqv;
-    a.bval = c.d_bval; a.bidx = c.d_bidx; a.counters = c.d_besti;
-    a.M = (long)c.M; a.N = (int)c.N; a.D = (int)c.D; a.Dp = (int)c.Dp; a.Np = (int)c.Np;
-    a.constant = c.constant; a.kss = c.constant + c.noise; a.y_mean = c.y_mean; a.y_std = c.y_std;
-    a.acq = acq; a.sf = sf; a.incumbent = incumbent; a.param = param;
+hipError_t launch_mid_sweep(Context &c, const SweepCall &s) {
+    const SmallSweepArgs a = sweep_args(c, s);
+    const MidFinal f{c.d_best, s.winner, s.res, (long long)c.winner_offset, s.bell};
+    // (mid_sweep_cpw of a model that takes this path: 64 candidates per workgroup up to N = 256, i.e. Np = 256, else 32)
+    return c.Np == 4 * NB ? launch_mid_sweep_as<64>(c, a, f) : launch_mid_sweep_as<32>(c, a, f);
+}
+
+hipError_t launch_small_sweep(Context &c, const SweepCall &s) {
+    const SmallSweepArgs a = sweep_args(c, s);
     void (*k)(SmallSweepArgs);
     switch (c.kernel) {
         case TGP_RBF: k = small_sweep_kernel<TGP_RBF>; break;

@@ -1021,9 +1021,10 @@ static hipError_t contract_rows(Context &c, const SweepPlan<T> &p, const T *cs, 
 
 // done = false: too many survivors -- the caller runs the full schedule (nothing of this call's results is left behind)
 template <typename T>
-static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, int acq, double sf, double incumbent, double param,
-                               bool &done) {
+static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCall &call, bool front_usable, bool &done) {
     done = false;
+    const int acq = call.acq;
+    const double sf = call.sf, incumbent = call.incumbent, param = call.param;
     const Tuning &tu = tuning();
     const int64_t M = c.M, Mpad = c.ws_Mpad;
     const int N = (int)c.N, Dp = (int)c.Dp;
@@ -1040,7 +1041,7 @@ static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, int acq, doubl
     T *cs = reinterpret_cast<T *>(w.cs);
 
     // 1. the bound of every candidate
-    if (!c.pre.usable) TGP_TRY(issue_prep<T>(c, st));   // (a fit's front has scaled them already)
+    if (!front_usable) TGP_TRY(issue_prep<T>(c, st));   // (a fit's front has scaled them already)
     int mark = prof_mark(c, st);
     {
         constexpr int KAR = kstar_ar(sizeof(T));
@@ -1126,7 +1127,7 @@ static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, int acq, doubl
         nblk_b = (nsurv + FIN_BLOCK - 1) / FIN_BLOCK;
     }
     hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, st, c.d_bval, c.d_bidx, (long)(nblk_a + nblk_b), c.d_best,
-                       c.d_besti, c.d_winner, c.d_cand, (int)c.D, (long)M, (long long)c.winner_offset, c.sweep_res_host,
+                       c.d_besti, call.winner, c.d_cand, (int)c.D, (long)M, (long long)c.winner_offset, call.res,
                        Bell{nullptr, 0, nullptr});
     TGP_TRY(hipGetLastError());
     c.prune_state = 0;
@@ -1135,22 +1136,22 @@ static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, int acq, doubl
 }
 
 template <typename T, int BK>
-static hipError_t sweep_chunks(Context &c, int acq, double sf, double incumbent, double param,
-                               bool want_mu, bool want_sigma, bool want_acq) {
+static hipError_t sweep_chunks(Context &c, const SweepCall &call, bool front_usable) {
     const int Np = (int)c.Np, D = (int)c.D;
+    const int acq = call.acq;
     SweepPlan<T> p;
     TGP_TRY((make_plan<T, BK>(c, p)));
     const TrmmVariant &v = p.main;
     const bool x3 = p.x3, h2 = p.h2;
     // an arg-max-only EI / PI / UCB sweep in f32 / f64 first tries the pruned schedule (TGP_SWEEP_PRUNE)
     bool fell_back = false;
-    if (!want_mu && !want_sigma && !want_acq && (acq == TGP_ACQ_EI || acq == TGP_ACQ_PI || acq == TGP_ACQ_UCB) &&
+    if (!call.mu && !call.sigma && !call.acqv && (acq == TGP_ACQ_EI || acq == TGP_ACQ_PI || acq == TGP_ACQ_UCB) &&
         (c.dtype == TGP_F32 || c.dtype == TGP_F64) && p.mean_in_trmm && tuning_sweep_prune_now() != 0 &&
         c.M > tuning().prune_top && (double)c.M * (double)c.N * (double)c.N >= tuning_prune_min_work_now()) {
         const double u = sizeof(T) == 4 ? 0x1p-24 : 0x1p-53;
         if (c.noise > 0.0 && c.noise / (c.constant + c.noise) >= tuning().prune_tau * u) {
             bool done = false;
-            TGP_TRY(sweep_pruned<T>(c, p, acq, sf, incumbent, param, done));
+            TGP_TRY(sweep_pruned<T>(c, p, call, front_usable, done));
             if (done) return hipSuccess;
             fell_back = true;
         } else {
@@ -1168,7 +1169,7 @@ static hipError_t sweep_chunks(Context &c, int acq, double sf, double incumbent,
     // what the last fit already started for this very batch (tgp_set_overlap): the scaling, launch pair 0's
     // cross-kernel and the first pre128 row tiles of its contraction
     // (after a fall-back from the pruned schedule the slab and the partial sums hold its rows: the front is spent)
-    const bool pre = c.pre.usable && p.mean_in_trmm && !fell_back;
+    const bool pre = front_usable && p.mean_in_trmm && !fell_back;
     const int pre128 = pre ? c.pre.rows128 : 0;
     if (!pre) TGP_TRY(issue_prep<T>(c, sa));
     if (h2 && (c.linv16_gen != c.fit_gen || c.linv16_sb != p.h2_sb)) {
@@ -1224,30 +1225,30 @@ static hipError_t sweep_chunks(Context &c, int acq, double sf, double incumbent,
         f.off = 0; f.m = c.M;
         f.kss = c.constant + c.noise;
         f.y_mean = c.y_mean; f.y_std = c.y_std;
-        f.acq = acq; f.sf = sf; f.incumbent = incumbent; f.param = param;
-        f.mu = want_mu ? c.d_mu : nullptr;
-        f.sigma = want_sigma ? c.d_sigma : nullptr;
-        f.acqv = want_acq ? c.d_acq : nullptr;
+        f.acq = acq; f.sf = call.sf; f.incumbent = call.incumbent; f.param = call.param;
+        f.mu = call.mu; f.sigma = call.sigma; f.acqv = call.acqv;
         f.bval = c.d_bval; f.bidx = c.d_bidx; f.counters = c.d_besti;
         hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((c.M + FIN_BLOCK - 1) / FIN_BLOCK)),
                            dim3(FIN_BLOCK), 0, sa, f);
         TGP_TRY(hipGetLastError());
     }
-    if (acq != TGP_ACQ_NONE || c.sweep_res_host) {
+    if (acq != TGP_ACQ_NONE || call.res) {
         // (without an acquisition the launch only hands the clamp count over and zeroes the counter)
         const long nblk = acq != TGP_ACQ_NONE ? (long)((c.M + FIN_BLOCK - 1) / FIN_BLOCK) : 0L;
         hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, sa, c.d_bval, c.d_bidx, nblk,
-                           c.d_best, c.d_besti, acq != TGP_ACQ_NONE ? c.d_winner : nullptr, c.d_cand, D, (long)c.M,
-                           (long long)c.winner_offset, c.sweep_res_host, Bell{nullptr, 0, nullptr});
+                           c.d_best, c.d_besti, acq != TGP_ACQ_NONE ? call.winner : nullptr, c.d_cand, D, (long)c.M,
+                           (long long)c.winner_offset, call.res, Bell{nullptr, 0, nullptr});
         TGP_TRY(hipGetLastError());
     }
     return hipSuccess;
 }
 
-hipError_t launch_argmax_final(Context &c, long nblk, double *res_host, const Bell &bell) {
+// behind launch_small_sweep (64 candidates per arg-max partial; without an acquisition only the clamp count is handed over)
+hipError_t launch_argmax_final(Context &c, const SweepCall &call) {
+    const long nblk = call.acq != TGP_ACQ_NONE ? (long)((c.M + NB - 1) / NB) : 0L;
     hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, c.stream, c.d_bval, c.d_bidx, nblk,
-                       c.d_best, c.d_besti, c.d_winner, c.d_cand, (int)c.D, (long)c.M,
-                       (long long)c.winner_offset, res_host, bell);
+                       c.d_best, c.d_besti, call.winner, c.d_cand, (int)c.D, (long)c.M,
+                       (long long)c.winner_offset, call.res, call.bell);
     return hipGetLastError();
 }
 
@@ -1265,9 +1266,8 @@ hipError_t launch_argmax_final(Context &c, long nblk, double *res_host, const Be
         return fn<double, 16>(__VA_ARGS__);                                          \
     } while (0)
 
-hipError_t launch_sweep(Context &c, int acq, double sf, double incumbent, double param,
-                        bool want_mu, bool want_sigma, bool want_acq) {
-    TGP_SWEEP_DISPATCH(sweep_chunks, c, acq, sf, incumbent, param, want_mu, want_sigma, want_acq);
+hipError_t launch_sweep(Context &c, const SweepCall &call, bool front_usable) {
+    TGP_SWEEP_DISPATCH(sweep_chunks, c, call, front_usable);
 }
 
 hipError_t presweep_front(Context &c, hipStream_t st) { TGP_SWEEP_DISPATCH(presweep_front_t, c, st); }

@@ -233,6 +233,41 @@ static double bell_ms(const Context &c) {
     return t1 >= t0 ? (double)(t1 - t0) * 1e-5 : 0.0;
 }
 
+// ---- one call's clock and its one wait ----
+// A polled call (live bell) is timed on the host clock, launch to doorbell, and records no event; any other call is
+// bracketed by ev0 / ev1 on its stream and ends in a stream synchronisation.
+struct CallClock {
+    Bell bell{nullptr, 0, nullptr};
+    std::chrono::steady_clock::time_point t0{};
+    bool stopped = false;      // ev1 is out
+};
+static int call_begin(Context &c, CallClock &k) {
+    k.t0 = std::chrono::steady_clock::now();
+    if (!k.bell.word) API_HIP(hipEventRecord(c.ev0, c.stream), "hipEventRecord");
+    return TGP_OK;
+}
+// optional: ev1 HERE, so that what the entry queues behind it (copies back to the caller) is not timed
+static int call_stop(Context &c, CallClock &k) {
+    if (!k.bell.word && !k.stopped) API_HIP(hipEventRecord(c.ev1, c.stream), "hipEventRecord");
+    k.stopped = true;
+    return TGP_OK;
+}
+// wait for the call and leave its time in last_ms (c.last_fit_ms / c.last_sweep_ms)
+static int call_finish(Context &c, CallClock &k, double &last_ms, const char *where) {
+    if (k.bell.word) {
+        const int rc = bell_wait(c, k.bell, where);
+        if (rc == TGP_OK) last_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - k.t0).count();
+        return rc;
+    }
+    const int rc = call_stop(c, k);
+    if (rc != TGP_OK) return rc;
+    API_HIP(hipStreamSynchronize(c.stream), where);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, c.ev0, c.ev1);
+    last_ms = ms;
+    return TGP_OK;
+}
+
 // No C++ exception may cross the C boundary: every entry is a function-try-block.
 static int exception_status(tgp_handle h, const char *fn, const char *what, int code) {
     try {
@@ -810,7 +845,7 @@ static int fit_impl(tgp_handle h, const double *X, int64_t N, int64_t D, const d
         // not by a sweep)
         const int mode = grad_mode ? 0 : std::min(c.pre.mode, tuning().overlap);
         if (mode > 0 && c.d_cand && c.M > 0 && !c.stream_own && (c.dtype == TGP_F64 || c.dtype == TGP_F32) &&
-            mid_sweep_cpw(c, c.M) == 0) {
+            sweep_path(c, c.M) == SweepPath::General) {
             int rc = ensure_workspace(c);
             if (rc != TGP_OK) return rc;
             c.pre.issue = mode;
@@ -914,8 +949,9 @@ int tgp_fit_append(tgp_handle h, const double *X, int64_t N, int64_t D, const do
     std::vector<double> xrow((size_t)Dp, 0.0);
     for (int64_t d = 0; d < D; ++d) xrow[d] = X[(size_t)n_old * D + d] / c.ls[d];
 
-    const hipEvent_t e0 = c.ev0, e1 = c.ev1;
-    API_HIP(hipEventRecord(e0, c.stream), "hipEventRecord");
+    CallClock clk;
+    int rc = call_begin(c, clk);
+    if (rc != TGP_OK) return rc;
     API_HIP(hipMemcpyAsync(c.d_Xs + n_old * Dp, xrow.data(), (size_t)Dp * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D x row");
     API_HIP(hipMemcpyAsync(c.d_yn, yn.data(), (size_t)Np * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D yn");
     c.linv_extent = std::max<int64_t>(c.linv_extent, ((N + NB - 1) / NB) * NB);   // the appended row of Linv
@@ -925,11 +961,7 @@ int tgp_fit_append(tgp_handle h, const double *X, int64_t N, int64_t D, const do
     double scal[4] = {0.0, 0.0, 0.0, 0.0};
     API_HIP(hipMemcpyAsync(&flag, c.d_flag, sizeof(int), hipMemcpyDeviceToHost, c.stream), "D2H flag");
     API_HIP(hipMemcpyAsync(scal, c.d_scal, 4 * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H scal");
-    API_HIP(hipEventRecord(e1, c.stream), "hipEventRecord");
-    API_HIP(hipStreamSynchronize(c.stream), "append sync");
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    c.last_fit_ms = ms;
+    if ((rc = call_finish(c, clk, c.last_fit_ms, "append sync")) != TGP_OK) return rc;
     if (flag != 0) {
         char buf[160];
         snprintf(buf, sizeof buf, "kernel matrix is not positive definite (pivot %d of %lld <= 0)", flag - 1, (long long)N);
@@ -1392,7 +1424,7 @@ int tgp_set_winner_out(tgp_handle h, void *rec_dev, int64_t global_offset) try {
     if (!h) return TGP_BAD_ARG;
     HOST_NA("tgp_set_winner_out");
     Context &c = h->c;
-    if (!rec_dev) { c.d_winner = nullptr; c.winner_offset = 0; return TGP_OK; }
+    if (!rec_dev) { c.d_winner = nullptr; c.winner_offset = 0; c.winner_recorded = false; return TGP_OK; }
     if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_set_winner_out: fit first (D is taken from the model)");
     if (global_offset < 0 || global_offset > ((int64_t)1 << 52)) return fail(c, TGP_BAD_ARG, "tgp_set_winner_out: global_offset must be in [0, 2^52]");
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
@@ -1400,6 +1432,7 @@ int tgp_set_winner_out(tgp_handle h, void *rec_dev, int64_t global_offset) try {
     if (rc != TGP_OK) return rc;
     c.d_winner = reinterpret_cast<double *>(rec_dev);
     c.winner_offset = global_offset;
+    c.winner_recorded = false;   // a new buffer holds no record yet: nothing for tgp_winner_wait to wait for
     return TGP_OK;
 } TGP_CATCH
 
@@ -1408,7 +1441,7 @@ int tgp_winner_wait(tgp_handle h, void *stream) try {
     HOST_NA("tgp_winner_wait");
     Context &c = h->c;
     if (!c.d_winner) return fail(c, TGP_BAD_ARG, "tgp_winner_wait: no winner record attached (tgp_set_winner_out)");
-    if (!c.winner_recorded) return TGP_OK;      // no sweep has packed a record yet: nothing to wait for
+    if (!c.winner_recorded) return TGP_OK;      // nothing has packed a record into this buffer yet: nothing to wait for
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
     API_HIP(hipStreamWaitEvent(static_cast<hipStream_t>(stream), c.ev_winner, 0), "hipStreamWaitEvent");
     return TGP_OK;
@@ -1478,6 +1511,41 @@ static int ensure_small_workspace(Context &c) {
     return TGP_OK;
 }
 
+// One sweep of the resident candidates with the resident model, for every entry of the family: picks the kernel
+// family, sees to its workspace, starts the call's clock in front of the first launch, launches, and records the winner
+// event behind whatever packed the record.  The entry keeps its argument checks, its own buffers and what it copies back.
+static int run_sweep(Context &c, const SweepCall &s, CallClock &clk) {
+    const SweepPath path = sweep_path(c, c.M);
+    int rc = path == SweepPath::General ? ensure_workspace(c) : ensure_small_workspace(c);
+    if (rc != TGP_OK) return rc;
+    // the front a fit started (tgp_set_overlap) is used when it belongs to the resident fit, batch and workspace geometry
+    const bool front = path == SweepPath::General && s.may_use_front && c.pre.gen == c.fit_gen && c.pre.cand == c.d_cand &&
+                       c.pre.M == c.M && c.pre.Mpad == c.ws_Mpad && c.pre.launch_rows == c.launch_rows && c.pre.chunk == c.chunk;
+    c.pre.front = false;   // one sweep per front: the slab it filled is overwritten from here on
+    c.last_sweep_f64 = path != SweepPath::General || c.dtype == TGP_F64;   // (the one-workgroup / one-launch kernels only exist in f64)
+    c.prune_state = -1;
+    c.prune_lbset = c.prune_surv = 0;
+    if ((rc = call_begin(c, clk)) != TGP_OK) return rc;
+    hipError_t le;
+    if (path == SweepPath::OneLaunch) {
+        le = launch_mid_sweep(c, s);
+    } else if (path == SweepPath::OneWorkgroup) {
+        le = launch_small_sweep(c, s);
+        if (le == hipSuccess) le = launch_argmax_final(c, s);
+    } else {
+        le = launch_sweep(c, s, front);
+    }
+    if (le != hipSuccess) return hip_fail(c, le, "launch_sweep");
+    if (s.winner && s.acq != TGP_ACQ_NONE) {
+        // the winner record is packed: what tgp_winner_wait makes another stream (RCCL's) wait for -- a polled call
+        // returns without a stream synchronisation, so the ordering rests on this event
+        if (!c.ev_winner) API_HIP(hipEventCreateWithFlags(&c.ev_winner, hipEventDisableTiming), "hipEventCreate");
+        API_HIP(hipEventRecord(c.ev_winner, c.stream), "hipEventRecord");
+        c.winner_recorded = true;
+    }
+    return TGP_OK;
+}
+
 int tgp_sweep(tgp_handle h, int acq, double sf, double incumbent, double param, double *mu,
               double *sigma, double *acq_out, double *best_val, int64_t *best_idx,
               int64_t *n_clamped) try {
@@ -1489,48 +1557,27 @@ int tgp_sweep(tgp_handle h, int acq, double sf, double incumbent, double param, 
     if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_SIGMA) return fail(c, TGP_BAD_ARG, "tgp_sweep: unknown acquisition");
     if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_sweep: sf must be +1 or -1");
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
-    const bool had_front = c.pre.front;
+    SweepCall s;
+    s.acq = acq; s.sf = sf; s.incumbent = incumbent; s.param = param;
+    s.may_use_front = c.pre.front;
     API_HIP(pre_join(c), "hipStreamWaitEvent");
-    const bool small = c.small && c.N <= 2 * NB;
-    const bool mid = mid_sweep_cpw(c, c.M) != 0;
-    c.last_sweep_f64 = small || mid || c.dtype == TGP_F64;   // (the one-workgroup / one-launch kernels only exist in f64)
-    int rc = (small || mid) ? ensure_small_workspace(c) : ensure_workspace(c);
+    int rc = ensure_outputs(c, mu != nullptr, sigma != nullptr, acq_out != nullptr);
     if (rc != TGP_OK) return rc;
-    // the front a fit started (tgp_set_overlap) is used when it belongs to the resident fit, batch and workspace geometry
-    c.pre.usable = !small && !mid && had_front && c.pre.gen == c.fit_gen && c.pre.cand == c.d_cand && c.pre.M == c.M &&
-                   c.pre.Mpad == c.ws_Mpad && c.pre.launch_rows == c.launch_rows && c.pre.chunk == c.chunk;
-    c.pre.front = false;   // one sweep per front: the slab it filled is overwritten from here on
-    rc = ensure_outputs(c, mu != nullptr, sigma != nullptr, acq_out != nullptr);
-    if (rc != TGP_OK) return rc;
-
+    s.mu = mu ? c.d_mu : nullptr; s.sigma = sigma ? c.d_sigma : nullptr; s.acqv = acq_out ? c.d_acq : nullptr;
+    s.winner = c.d_winner;
+    // (the one question about the kernel family: only the one-workgroup / one-launch kernels can ring a doorbell, and
+    // they always write the mapped record)
+    const bool can_ring = sweep_path(c, c.M) != SweepPath::General;
     // every sweep's last kernel leaves [best value, best index, clamp count] in device-mapped host memory and
     // hands the counters back at zero: no D2H copy, no memset behind it (TGP_SWEEP_ZC=0: the copies, A/B)
-    const bool zc_off = tuning().sweep_zc == 0;
-    const bool zc = small || mid || !zc_off;
+    const bool zc = can_ring || tuning().sweep_zc != 0;
     if (zc && (rc = ensure_pinned(c, 0, 8 * sizeof(double))) != TGP_OK) return rc;
-    const hipEvent_t e0 = c.ev0, e1 = c.ev1;
+    s.res = zc ? c.d_pin_out : nullptr;
     // (round 6) the small-problem sweep that only returns its record -- the arg-max of a trial -- is a polled call: the
     // last kernel rings the doorbell, no event, no stream synchronisation (doorbell.hpp)
-    const Bell bell = ((small || mid) && !mu && !sigma && !acq_out) ? bell_next(c) : Bell{nullptr, 0, nullptr};
-    const auto t_host0 = std::chrono::steady_clock::now();
-    if (!bell.word) API_HIP(hipEventRecord(e0, c.stream), "hipEventRecord");
-    c.prune_state = -1;
-    c.prune_lbset = c.prune_surv = 0;
-    hipError_t le;
-    if (mid) {
-        le = launch_mid_sweep(c, c.d_cand, acq, sf, incumbent, param, mu ? c.d_mu : nullptr,
-                              sigma ? c.d_sigma : nullptr, acq_out ? c.d_acq : nullptr, c.d_pin_out, bell);
-    } else if (small) {
-        le = launch_small_sweep(c, c.d_cand, acq, sf, incumbent, param, mu ? c.d_mu : nullptr,
-                                sigma ? c.d_sigma : nullptr, acq_out ? c.d_acq : nullptr);
-        if (le == hipSuccess) le = launch_argmax_final(c, acq != TGP_ACQ_NONE ? (long)((c.M + NB - 1) / NB) : 0L, c.d_pin_out, bell);
-    } else {
-        c.sweep_res_host = zc ? c.d_pin_out : nullptr;
-        le = launch_sweep(c, acq, sf, incumbent, param, mu != nullptr, sigma != nullptr, acq_out != nullptr);
-        c.sweep_res_host = nullptr;
-        c.pre.usable = false;
-    }
-    if (le != hipSuccess) return hip_fail(c, le, "launch_sweep");
+    if (can_ring && !mu && !sigma && !acq_out) s.bell = bell_next(c);
+    CallClock clk{s.bell};
+    if ((rc = run_sweep(c, s, clk)) != TGP_OK) return rc;
     double bv = 0.0;
     long long bi[2] = {0, 0};
     if (!zc) {
@@ -1538,28 +1585,12 @@ int tgp_sweep(tgp_handle h, int acq, double sf, double incumbent, double param, 
         API_HIP(hipMemcpyAsync(bi, c.d_besti, 2 * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H besti");
         API_HIP(hipMemsetAsync(c.d_besti, 0, 4 * sizeof(long long), c.stream), "memset counters");   // zero between calls
     }
-    if (!bell.word) API_HIP(hipEventRecord(e1, c.stream), "hipEventRecord");
-    if (c.d_winner && acq != TGP_ACQ_NONE) {
-        // the winner record is packed: what tgp_winner_wait makes another stream (RCCL's) wait for -- the ordering no
-        // longer rests on this call ending in a stream synchronisation
-        if (!c.ev_winner) API_HIP(hipEventCreateWithFlags(&c.ev_winner, hipEventDisableTiming), "hipEventCreate");
-        API_HIP(hipEventRecord(c.ev_winner, c.stream), "hipEventRecord");
-        c.winner_recorded = true;
-    }
+    if ((rc = call_stop(c, clk)) != TGP_OK) return rc;   // (last_sweep_ms leaves the copies of the (M,) outputs out)
     const size_t bytes = (size_t)c.M * sizeof(double);
     if (mu) API_HIP(hipMemcpyAsync(mu, c.d_mu, bytes, hipMemcpyDeviceToHost, c.stream), "D2H mu");
     if (sigma) API_HIP(hipMemcpyAsync(sigma, c.d_sigma, bytes, hipMemcpyDeviceToHost, c.stream), "D2H sigma");
     if (acq_out) API_HIP(hipMemcpyAsync(acq_out, c.d_acq, bytes, hipMemcpyDeviceToHost, c.stream), "D2H acq");
-    if (bell.word) {
-        const int wrc = bell_wait(c, bell, "sweep sync");
-        if (wrc != TGP_OK) return wrc;
-        c.last_sweep_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();   // (launch to doorbell, host clock)
-    } else {
-        API_HIP(hipStreamSynchronize(c.stream), "sweep sync");
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        c.last_sweep_ms = ms;
-    }
+    if ((rc = call_finish(c, clk, c.last_sweep_ms, "sweep sync")) != TGP_OK) return rc;
     if (c.profiling) prof_collect(c);
     if (zc) { bv = c.h_pin_out[0]; bi[0] = (long long)c.h_pin_out[1]; bi[1] = (long long)c.h_pin_out[2]; }
     if (acq != TGP_ACQ_NONE) {
@@ -1636,7 +1667,7 @@ int tgp_acq_grad(tgp_handle h, const double *Xq, int64_t m, int acq, double sf, 
     return TGP_OK;
 } TGP_CATCH
 
-// Greedy batch selection (include/turbogp.h).  The first step IS tgp_sweep's launch path with the posterior kept on the
+// Greedy batch selection (include/turbogp.h).  The first step IS a sweep (run_sweep) with the posterior kept on the
 // device; every conditioned point then costs its O(N^2) front (w_j = K^-1 k*(z_j)), a one-workgroup small side and --
 // unless it is the last one and no posterior is asked for -- one O(M N D) pass over the candidates with the update and
 // the next selection's arg-max (batch_kernels.hip).  Every step reads the previous winner from device memory: the host
@@ -1658,21 +1689,17 @@ int tgp_sweep_batch(tgp_handle h, int64_t q, int strategy, double lie, const dou
     if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: sf must be +1 or -1");
     if (!idx_out || !val_out) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: idx_out and val_out are required");
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
-    const bool had_front = c.pre.front;
+    // ---- the first sweep: means and deviations left in c.d_mu / c.d_sigma, its record in the mapped result buffer (read
+    // by the first selection on the device); the winner record of tgp_set_winner_out is not this call's to pack
+    SweepCall first;
+    first.acq = acq; first.sf = sf; first.incumbent = incumbent; first.param = param;
+    first.may_use_front = c.pre.front;
     API_HIP(pre_join(c), "hipStreamWaitEvent");
-
-    // ---- the first sweep: tgp_sweep's path, means and deviations left in c.d_mu / c.d_sigma, its record in the mapped
-    // result buffer (read by the first selection on the device)
-    const bool small = c.small && c.N <= 2 * NB;
-    const bool mid = mid_sweep_cpw(c, c.M) != 0;
-    int rc = (small || mid) ? ensure_small_workspace(c) : ensure_workspace(c);
-    if (rc != TGP_OK) return rc;
-    c.pre.usable = !small && !mid && had_front && c.pre.gen == c.fit_gen && c.pre.cand == c.d_cand && c.pre.M == c.M &&
-                   c.pre.Mpad == c.ws_Mpad && c.pre.launch_rows == c.launch_rows && c.pre.chunk == c.chunk;
-    c.pre.front = false;
+    int rc;
     if ((rc = ensure_outputs(c, true, true, false)) != TGP_OK) return rc;
     const int64_t D = c.D, Dp = c.Dp, Np = c.Np, M = c.M, J = P + q;
     if ((rc = ensure_pinned(c, (size_t)(P * D + 8) * sizeof(double), 8 * sizeof(double))) != TGP_OK) return rc;
+    first.mu = c.d_mu; first.sigma = c.d_sigma; first.res = c.d_pin_out;
 
     // ---- the call's buffers
     const int64_t Mpad = ((M + 63) / 64) * 64;        // rows of the scaled candidates and of the pass partials
@@ -1693,25 +1720,9 @@ int tgp_sweep_batch(tgp_handle h, int64_t q, int strategy, double lie, const dou
     unsigned char *mask = reinterpret_cast<unsigned char *>(bidx + nblk);
     const BtSmall s{Rb, eb, fant, inc, selv, seli, reinterpret_cast<int *>(flagw)};
 
-    const hipEvent_t e0 = c.ev0, e1 = c.ev1;
-    const auto t_host0 = std::chrono::steady_clock::now();
-    API_HIP(hipEventRecord(e0, c.stream), "hipEventRecord");
-    double *winner_keep = c.d_winner;   // the winner record of tgp_set_winner_out belongs to tgp_sweep
-    c.d_winner = nullptr;
+    CallClock clk;
+    if ((rc = run_sweep(c, first, clk)) != TGP_OK) return rc;
     hipError_t le;
-    if (mid) {
-        le = launch_mid_sweep(c, c.d_cand, acq, sf, incumbent, param, c.d_mu, c.d_sigma, nullptr, c.d_pin_out);
-    } else if (small) {
-        le = launch_small_sweep(c, c.d_cand, acq, sf, incumbent, param, c.d_mu, c.d_sigma, nullptr);
-        if (le == hipSuccess) le = launch_argmax_final(c, (long)((c.M + NB - 1) / NB), c.d_pin_out);
-    } else {
-        c.sweep_res_host = c.d_pin_out;
-        le = launch_sweep(c, acq, sf, incumbent, param, true, true, false);
-        c.sweep_res_host = nullptr;
-        c.pre.usable = false;
-    }
-    c.d_winner = winner_keep;
-    if (le != hipSuccess) return hip_fail(c, le, "tgp_sweep_batch: sweep");
 
     // ---- the steps
     double *pin = c.h_pin_in;
@@ -1744,7 +1755,7 @@ int tgp_sweep_batch(tgp_handle h, int64_t q, int strategy, double lie, const dou
                             last ? c.d_sigma : nullptr, (int)knext);
         if (le != hipSuccess) return hip_fail(c, le, "launch_bt_step");
     }
-    API_HIP(hipEventRecord(e1, c.stream), "hipEventRecord");
+    if ((rc = call_stop(c, clk)) != TGP_OK) return rc;
 
     // ---- one wait
     std::vector<double> hs((size_t)(BT_MAXP * D + 2 * BT_MAXP));
@@ -1755,13 +1766,7 @@ int tgp_sweep_batch(tgp_handle h, int64_t q, int strategy, double lie, const dou
     const size_t bytes = (size_t)M * sizeof(double);
     if (mu_out) API_HIP(hipMemcpyAsync(mu_out, c.d_mu, bytes, hipMemcpyDeviceToHost, c.stream), "D2H mu");
     if (sigma_out) API_HIP(hipMemcpyAsync(sigma_out, c.d_sigma, bytes, hipMemcpyDeviceToHost, c.stream), "D2H sigma");
-    API_HIP(hipStreamSynchronize(c.stream), "sweep_batch sync");
-    {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        c.last_sweep_ms = ms;
-        (void)t_host0;
-    }
+    if ((rc = call_finish(c, clk, c.last_sweep_ms, "sweep_batch sync")) != TGP_OK) return rc;
     const int flag = (int)(hi[BT_MAXP + 1] & 0xffffffff);
     if (flag != 0) {
         char buf[200];
@@ -1858,26 +1863,20 @@ int tgp_ts_sweep(tgp_handle h, double sf, int distinct, int64_t *idx_out, double
            *selx = selv + ts_al4(S);
     long long *bidx = reinterpret_cast<long long *>(selx + ts_al4(S * D)), *seli = bidx + S * nblk;
     unsigned char *mask = reinterpret_cast<unsigned char *>(seli + S);
-    const auto t_host0 = std::chrono::steady_clock::now();
-    API_HIP(hipEventRecord(c.ev0, c.stream), "hipEventRecord");
+    CallClock clk;
+    if ((rc = call_begin(c, clk)) != TGP_OK) return rc;
     hipError_t le = launch_bt_prep(c, Cs, Mpad);
     if (le != hipSuccess) return hip_fail(c, le, "launch_bt_prep");
     if ((le = launch_ts_pass(c, t, Cs, M, true, f, c.y_mean, c.y_std)) != hipSuccess) return hip_fail(c, le, "launch_ts_pass");
     if ((le = launch_ts_select(c, t, f, sf, distinct ? 1 : 0, mask, bval, bidx, seli, selv, selx)) != hipSuccess)
         return hip_fail(c, le, "launch_ts_select");
-    API_HIP(hipEventRecord(c.ev1, c.stream), "hipEventRecord");
+    if ((rc = call_stop(c, clk)) != TGP_OK) return rc;
     std::vector<long long> hi((size_t)S);
     API_HIP(hipMemcpyAsync(hi.data(), seli, (size_t)S * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H indices");
     API_HIP(hipMemcpyAsync(val_out, selv, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H values");
     if (x_out) API_HIP(hipMemcpyAsync(x_out, selx, (size_t)(S * D) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H rows");
     if (f_out) API_HIP(hipMemcpyAsync(f_out, f, (size_t)(M * S) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H f");
-    API_HIP(hipStreamSynchronize(c.stream), "ts_sweep sync");
-    {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, c.ev0, c.ev1);
-        c.last_sweep_ms = ms;
-        (void)t_host0;
-    }
+    if ((rc = call_finish(c, clk, c.last_sweep_ms, "ts_sweep sync")) != TGP_OK) return rc;
     for (int64_t s = 0; s < S; ++s) idx_out[s] = (int64_t)hi[s];
     return TGP_OK;
 } TGP_CATCH
@@ -1938,62 +1937,45 @@ int tgp_sweep_topk(tgp_handle h, int acq, double sf, double incumbent, double pa
     if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_sweep_topk: sf must be +1 or -1");
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
     API_HIP(pre_join(c), "hipStreamWaitEvent");
-    const bool small = c.small && c.N <= 2 * NB;
-    const bool mid = mid_sweep_cpw(c, c.M) != 0;
-    c.last_sweep_f64 = small || mid || c.dtype == TGP_F64;   // (the one-workgroup / one-launch kernels only exist in f64)
-    int rc = (small || mid) ? ensure_small_workspace(c) : ensure_workspace(c);
-    if (rc != TGP_OK) return rc;
-    rc = ensure_outputs(c, false, false, true);           // the (M,) acquisition vector stays on the device
+    int rc = ensure_outputs(c, false, false, true);           // the (M,) acquisition vector stays on the device
     if (rc != TGP_OK) return rc;
     const int64_t nb = (c.M + 4095) / 4096;
     const size_t ents = (size_t)(2 * nb * k);
     if ((rc = grow(c, c.d_topv, c.cap_topv, ents * sizeof(double), "hipMalloc topk values")) != TGP_OK) return rc;
     if ((rc = grow(c, c.d_topi, c.cap_topi, ents * sizeof(long long), "hipMalloc topk indices")) != TGP_OK) return rc;
     // (round 6) small and one-launch models: a polled call -- the top-k's final pass leaves values, indices and the clamp
-    // count in mapped host memory, hands the counters back at zero and rings; no D2H copy, memset, event or synchronisation
-    Bell bell{nullptr, 0, nullptr};
-    if (small || mid) {
-        bell = bell_next(c);
-        if (bell.word && (rc = ensure_pinned(c, 0, (size_t)(8 + 2 * k + 1) * sizeof(double))) != TGP_OK) return rc;
+    // count in mapped host memory, hands the counters back at zero and rings; no D2H copy, memset, event or synchronisation.
+    // (The one question about the kernel family: that final pass is only wired up behind the two f64 families.)
+    CallClock clk;
+    if (sweep_path(c, c.M) != SweepPath::General) {
+        clk.bell = bell_next(c);
+        if (clk.bell.word && (rc = ensure_pinned(c, 0, (size_t)(8 + 2 * k + 1) * sizeof(double))) != TGP_OK) return rc;
     }
-    const auto t_host0 = std::chrono::steady_clock::now();
-    if (!bell.word) API_HIP(hipEventRecord(c.ev0, c.stream), "hipEventRecord");
-    hipError_t le;
-    if (mid) {
-        le = launch_mid_sweep(c, c.d_cand, acq, sf, incumbent, param, nullptr, nullptr, c.d_acq, nullptr);
-    } else if (small) {
-        le = launch_small_sweep(c, c.d_cand, acq, sf, incumbent, param, nullptr, nullptr, c.d_acq);
-        if (le == hipSuccess) le = launch_argmax_final(c, (long)((c.M + NB - 1) / NB), nullptr);
-    } else {
-        le = launch_sweep(c, acq, sf, incumbent, param, false, false, true);
-    }
-    if (le != hipSuccess) return hip_fail(c, le, "launch_sweep");
+    const bool polled = clk.bell.word != nullptr;
+    SweepCall s;      // (no record, no bell: the top-k pass behind it ends the call)
+    s.acq = acq; s.sf = sf; s.incumbent = incumbent; s.param = param;
+    s.acqv = c.d_acq;
+    s.winner = c.d_winner;
+    if ((rc = run_sweep(c, s, clk)) != TGP_OK) return rc;
     long off = 0;
-    le = launch_topk(c, c.d_acq, (long)c.M, (int)k, c.d_topv, c.d_topi, &off, bell.word ? c.d_pin_out + 8 : nullptr, bell);
+    hipError_t le = launch_topk(c, c.d_acq, (long)c.M, (int)k, c.d_topv, c.d_topi, &off, polled ? c.d_pin_out + 8 : nullptr, clk.bell);
     if (le != hipSuccess) return hip_fail(c, le, "launch_topk");
-    if (bell.word) {
-        const int wrc = bell_wait(c, bell, "topk sync");
-        if (wrc != TGP_OK) return wrc;
-        c.last_sweep_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
+    long long hi[64], bi[2] = {0, 0};
+    if (!polled) {
+        API_HIP(hipMemcpyAsync(vals, c.d_topv + off, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H topk values");
+        API_HIP(hipMemcpyAsync(hi, c.d_topi + off, (size_t)k * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H topk indices");
+        API_HIP(hipMemcpyAsync(bi, c.d_besti, 2 * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H besti");
+        API_HIP(hipMemsetAsync(c.d_besti, 0, 4 * sizeof(long long), c.stream), "memset counters");
+    }
+    if ((rc = call_finish(c, clk, c.last_sweep_ms, "topk sync")) != TGP_OK) return rc;
+    if (c.profiling) prof_collect(c);
+    if (polled) {
         const double *rec = c.h_pin_out + 8;
         for (int64_t i = 0; i < k; ++i) { vals[i] = rec[i]; idxs[i] = (int64_t)rec[k + i]; }     // (-1: fewer than k candidates)
         if (n_clamped) *n_clamped = (int64_t)rec[2 * k];
-        if (c.profiling) prof_collect(c);
         return TGP_OK;
     }
-    std::vector<long long> hi((size_t)k);
-    long long bi[2] = {0, 0};
-    API_HIP(hipMemcpyAsync(vals, c.d_topv + off, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H topk values");
-    API_HIP(hipMemcpyAsync(hi.data(), c.d_topi + off, (size_t)k * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H topk indices");
-    API_HIP(hipMemcpyAsync(bi, c.d_besti, 2 * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H besti");
-    API_HIP(hipMemsetAsync(c.d_besti, 0, 4 * sizeof(long long), c.stream), "memset counters");
-    API_HIP(hipEventRecord(c.ev1, c.stream), "hipEventRecord");
-    API_HIP(hipStreamSynchronize(c.stream), "topk sync");
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, c.ev0, c.ev1);
-    c.last_sweep_ms = ms;
-    if (c.profiling) prof_collect(c);
-    for (int64_t i = 0; i < k; ++i) idxs[i] = (hi[(size_t)i] == 0x7fffffffffffffffLL) ? -1 : (int64_t)hi[(size_t)i];   // -1: fewer than k candidates
+    for (int64_t i = 0; i < k; ++i) idxs[i] = (hi[i] == 0x7fffffffffffffffLL) ? -1 : (int64_t)hi[i];   // -1: fewer than k candidates
     if (n_clamped) *n_clamped = (int64_t)bi[1];
     return TGP_OK;
 } TGP_CATCH
@@ -2025,16 +2007,13 @@ int tgp_acq_refine(tgp_handle h, const double *X0, int64_t R, const double *lo, 
         memcpy(c.h_pin_in + R * D, lo, (size_t)D * sizeof(double));
         memcpy(c.h_pin_in + R * D + D, hi, (size_t)D * sizeof(double));
         double *o_x = c.d_pin_out + 8, *o_v = o_x + R * D, *o_info = o_v + R;
-        API_HIP(hipEventRecord(c.ev0, c.stream), "hipEventRecord");
+        CallClock clk;
+        if ((prc = call_begin(c, clk)) != TGP_OK) return prc;
         hipError_t le = launch_small_refine(c, c.d_pin_in, c.d_pin_in + R * D, c.d_pin_in + R * D + D, (int)R, acq, sf,
                                             incumbent, param, (int)std::min<int64_t>(max_iter, 1 << 30), 1e-5,
                                             2.220446049250313e-09, o_x, o_v, o_info);
         if (le != hipSuccess) return hip_fail(c, le, "launch_small_refine");
-        API_HIP(hipEventRecord(c.ev1, c.stream), "hipEventRecord");
-        API_HIP(hipStreamSynchronize(c.stream), "refine sync");
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, c.ev0, c.ev1);
-        c.last_sweep_ms = ms;
+        if ((prc = call_finish(c, clk, c.last_sweep_ms, "refine sync")) != TGP_OK) return prc;
         const double *h_x = c.h_pin_out + 8, *h_v = h_x + R * D, *h_info = h_v + R;
         memcpy(x_out, h_x, (size_t)(R * D) * sizeof(double));
         memcpy(val_out, h_v, (size_t)R * sizeof(double));
@@ -2066,7 +2045,8 @@ int tgp_acq_refine(tgp_handle h, const double *X0, int64_t R, const double *lo, 
     double *d_state = c.d_rf, *d_lo = d_state + R * stride + hist, *d_hi = d_lo + D, *d_xo = d_hi + D;
     double *d_vo = d_xo + R * D, *d_info = d_vo + R;
     int *d_active = reinterpret_cast<int *>(d_info + 2 * R);
-    API_HIP(hipEventRecord(c.ev0, c.stream), "hipEventRecord");
+    CallClock clk;
+    if ((rc = call_begin(c, clk)) != TGP_OK) return rc;
     API_HIP(hipMemcpyAsync(d_Xq, X0, (size_t)(R * D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D X0");
     API_HIP(hipMemcpyAsync(d_lo, lo, (size_t)D * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D lo");
     API_HIP(hipMemcpyAsync(d_hi, hi, (size_t)D * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D hi");
@@ -2097,11 +2077,7 @@ int tgp_acq_refine(tgp_handle h, const double *X0, int64_t R, const double *lo, 
     API_HIP(hipMemcpyAsync(x_out, d_xo, (size_t)(R * D) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H x");
     API_HIP(hipMemcpyAsync(val_out, d_vo, (size_t)R * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H values");
     API_HIP(hipMemcpyAsync(info.data(), d_info, (size_t)(2 * R) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H info");
-    API_HIP(hipEventRecord(c.ev1, c.stream), "hipEventRecord");
-    API_HIP(hipStreamSynchronize(c.stream), "refine sync");
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, c.ev0, c.ev1);
-    c.last_sweep_ms = ms;
+    if ((rc = call_finish(c, clk, c.last_sweep_ms, "refine sync")) != TGP_OK) return rc;
     if (status_out)
         for (int64_t r = 0; r < R; ++r) status_out[r] = (int64_t)info[(size_t)(2 * r)];
     if (iterations) *iterations = it;
@@ -2373,17 +2349,14 @@ int tgp_fit_optimise(tgp_handle h, const double *X, int64_t N, int64_t D, const 
     // away by HSA_CU_MASK or by another process on the card) invalidates the launch: nothing of it reaches
     // the caller, and the fit runs once more with one workgroup per start -- no barrier, no way to wait.
     for (int attempt = 0; attempt < 2; ++attempt) {
-        API_HIP(hipEventRecord(c.ev0, c.stream), "hipEventRecord");
+        CallClock clk;
+        if ((rc = call_begin(c, clk)) != TGP_OK) return rc;
         hipError_t le = launch_small_hyper(c, kernel, d_in, d_in + N * D, d_in + N * D + N, d_in + N * D + N + S * P,
                                            d_in + N * D + N + S * P + P, (int)S, (int)N, (int)D, (int)Dp, (int)n_ls,
                                            (int)std::min<int64_t>(max_iter, 1 << 30), jitter, c.d_rf, o_theta, o_f, o_info,
                                            attempt > 0);
         if (le != hipSuccess) return hip_fail(c, le, "launch_small_hyper");
-        API_HIP(hipEventRecord(c.ev1, c.stream), "hipEventRecord");
-        API_HIP(hipStreamSynchronize(c.stream), "hyper sync");
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, c.ev0, c.ev1);
-        c.last_fit_ms = ms;
+        if ((rc = call_finish(c, clk, c.last_fit_ms, "hyper sync")) != TGP_OK) return rc;
         timed_out = false;
         for (int64_t s = 0; s < S; ++s) timed_out = timed_out || (int64_t)h_info[3 * s] == 3;
         if (!timed_out) break;
@@ -2414,9 +2387,9 @@ int tgp_evaluate(tgp_handle h, const double *Xc, int64_t M, int acq, double sf, 
     if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_SIGMA) return fail(c, TGP_BAD_ARG, "tgp_evaluate: unknown acquisition");
     if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_evaluate: sf must be +1 or -1");
     const size_t in_bytes = (size_t)M * (size_t)c.D * sizeof(double);
-    const bool mid = mid_sweep_cpw(c, M) != 0;
-    const bool zero_copy = ((c.small && c.N <= 2 * NB) || mid) && in_bytes <= ((size_t)8 << 20) && M <= 262144;
-    if (zero_copy) c.last_sweep_f64 = true;   // (otherwise tgp_sweep below says)
+    // (the one question about the kernel family: only the one-workgroup / one-launch kernels write their outputs straight
+    // into mapped host memory)
+    const bool zero_copy = sweep_path(c, M) != SweepPath::General && in_bytes <= ((size_t)8 << 20) && M <= 262144;
     if (!zero_copy) {
         int rc = tgp_set_candidates(h, Xc, M);
         if (rc != TGP_OK) return rc;
@@ -2441,37 +2414,20 @@ int tgp_evaluate(tgp_handle h, const double *Xc, int64_t M, int acq, double sf, 
     memcpy(c.h_pin_cand, Xc, in_bytes);
     c.d_cand = c.d_pin_cand;              // resident (in host memory the GPU can read) until replaced
     c.M = M;
-    rc = ensure_small_workspace(c);
-    if (rc != TGP_OK) return rc;
-    double *o_res = c.d_pin_out, *o_mu = c.d_pin_out + 8, *o_sg = o_mu + M, *o_aq = o_sg + M;
     // (round 6) a polled call.  N <= 128: the record's kernel is a launch of its own behind the sweep, so when it rings every
     // mean / deviation / acquisition value the sweep wrote into mapped host memory is out.  The one-launch sweep of
     // 128 < N <= 256: every workgroup's output stores come from the wave that takes its ticket behind a system-scope
     // fence, and the last workgroup rings
-    const Bell bell = bell_next(c);
-    const auto t_host0 = std::chrono::steady_clock::now();
-    if (!bell.word) API_HIP(hipEventRecord(c.ev0, c.stream), "hipEventRecord");
-    hipError_t le;
-    if (mid) {   // one launch: the last workgroup writes the result record
-        le = launch_mid_sweep(c, c.d_cand, acq, sf, incumbent, param, mu ? o_mu : nullptr, sigma ? o_sg : nullptr,
-                              acq_out ? o_aq : nullptr, o_res, bell);
-    } else {
-        le = launch_small_sweep(c, c.d_cand, acq, sf, incumbent, param, mu ? o_mu : nullptr,
-                                sigma ? o_sg : nullptr, acq_out ? o_aq : nullptr);
-        if (le == hipSuccess) le = launch_argmax_final(c, acq != TGP_ACQ_NONE ? (long)((M + NB - 1) / NB) : 0L, o_res, bell);
-    }
-    if (le != hipSuccess) return hip_fail(c, le, "launch_small_sweep");
-    if (bell.word) {
-        const int wrc = bell_wait(c, bell, "evaluate sync");
-        if (wrc != TGP_OK) return wrc;
-        c.last_sweep_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
-    } else {
-        API_HIP(hipEventRecord(c.ev1, c.stream), "hipEventRecord");
-        API_HIP(hipStreamSynchronize(c.stream), "evaluate sync");
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, c.ev0, c.ev1);
-        c.last_sweep_ms = ms;
-    }
+    SweepCall s;
+    s.acq = acq; s.sf = sf; s.incumbent = incumbent; s.param = param;
+    double *o_mu = c.d_pin_out + 8, *o_sg = o_mu + M, *o_aq = o_sg + M;
+    s.mu = mu ? o_mu : nullptr; s.sigma = sigma ? o_sg : nullptr; s.acqv = acq_out ? o_aq : nullptr;
+    s.res = c.d_pin_out;
+    s.winner = c.d_winner;
+    s.bell = bell_next(c);
+    CallClock clk{s.bell};
+    if ((rc = run_sweep(c, s, clk)) != TGP_OK) return rc;
+    if ((rc = call_finish(c, clk, c.last_sweep_ms, "evaluate sync")) != TGP_OK) return rc;
     const double *res = c.h_pin_out;
     if (mu) memcpy(mu, res + 8, (size_t)M * sizeof(double));
     if (sigma) memcpy(sigma, res + 8 + M, (size_t)M * sizeof(double));
@@ -2544,7 +2500,8 @@ int tgp_predict_batch(tgp_handle h, int64_t T, const int64_t *Ns, int64_t D, con
             d_xc, d_mu + t * M, sigma ? d_sg + t * M : nullptr, N, D, Dp, M, constants[t], noises[t], jitters[t],
             ymean[(size_t)t], ystd[(size_t)t]);
     }
-    API_HIP(hipEventRecord(c.ev0, c.stream), "hipEventRecord");
+    CallClock clk;
+    if ((rc = call_begin(c, clk)) != TGP_OK) return rc;
     API_HIP(hipMemsetAsync(d_cnt, 0, (size_t)(4 * T) * sizeof(long long), c.stream), "memset counters");
     API_HIP(hipMemcpyAsync(d_xc, Xc, (size_t)(M * D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D points");
     hipError_t le = mid ? launch_mid_batch(c, kernel, pin_dev + args_off, pin_dev + args_off + (size_t)T * fa, T, M)
@@ -2554,11 +2511,7 @@ int tgp_predict_batch(tgp_handle h, int64_t T, const int64_t *Ns, int64_t D, con
     API_HIP(hipMemcpyAsync(mu, d_mu, (size_t)(T * M) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H mu");
     if (sigma) API_HIP(hipMemcpyAsync(sigma, d_sg, (size_t)(T * M) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H sigma");
     API_HIP(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)(4 * T) * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H counters");
-    API_HIP(hipEventRecord(c.ev1, c.stream), "hipEventRecord");
-    API_HIP(hipStreamSynchronize(c.stream), "batch sync");
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, c.ev0, c.ev1);
-    c.last_sweep_ms = ms;
+    if ((rc = call_finish(c, clk, c.last_sweep_ms, "batch sync")) != TGP_OK) return rc;
     int64_t clamped = 0;
     for (int64_t t = 0; t < T; ++t) {
         const double *res = c.h_pin_out + 8 + 3 * t;

@@ -33,7 +33,6 @@ struct PreSweep {
     const double *cand = nullptr;
     int64_t M = 0, Mpad = 0, launch_rows = 0, chunk = 0;   // the batch and workspace geometry it was issued for
     bool pending = false;     // work on the device's third stream the main stream has not been told to wait for
-    bool usable = false;      // set by tgp_sweep around launch_sweep: the front belongs to the resident fit, batch and geometry
     hipEvent_t ev = nullptr;     // third stream: end of the front
     hipEvent_t ev_in = nullptr;  // main stream: Xs / length scales staged
 };
@@ -159,7 +158,6 @@ struct Context {
     int64_t prune_lbset = 0, prune_surv = 0;   // ... candidates in its lb set / survivors
     double *d_bval = nullptr;     // per finalize block arg-max value
     long long *d_bidx = nullptr;  // per finalize block arg-max index
-    double *sweep_res_host = nullptr;   // set by tgp_sweep around launch_sweep: device-mapped [best value, best index, clamp count] the sweep's last kernel fills (no D2H copy, no memset behind it), or null
     double *d_winner = nullptr;   // borrowed (D + 2) record [value, global index, row] or null (tgp_set_winner_out)
     int64_t winner_offset = 0;    // global index of candidate 0 of the resident batch
     hipEvent_t ev_winner = nullptr;   // recorded on the stream behind the kernel that packs the record (tgp_winner_wait)
@@ -260,18 +258,37 @@ void fill_small_batch_args(void *fit_args, void *sweep_args, int64_t t, const do
                            double noise, double jitter, double y_mean, double y_std);
 hipError_t launch_small_batch(Context &c, int kernel, const void *fit_args_dev, const void *sweep_args_dev,
                               int64_t T, int64_t M, bool fit, bool sweep);
-hipError_t launch_argmax_final(Context &c, long nblk, double *res_host, const Bell &bell = Bell{nullptr, 0, nullptr});   // bell.word != null: rings when the record is out (the call's last kernel)
-// 128 < N <= 512: the whole sweep -- cross-kernel tile, contraction, acquisition, arg-max, winner record -- in ONE launch
-// (small_kernels.hip, mid_sweep_kernel); res_host: optional zero-copy record [best value, best index, clamp count].
-// mid_sweep_cpw: candidates per workgroup (64 up to N = 256, 32 up to N = 512 and moderate batches), 0 = the general sweep
+// One sweep of the resident candidates with the resident model: what the C-ABI entries ask of run_sweep (tgp_api.hip)
+// and the launchers below read.  Nothing of it travels through the handle.
+struct SweepCall {
+    int acq = TGP_ACQ_NONE;
+    double sf = 1.0, incumbent = 0.0, param = 0.0;
+    double *mu = nullptr, *sigma = nullptr, *acqv = nullptr;   // (M,) optional outputs: device memory, or device-mapped host memory behind the one-workgroup / one-launch kernels
+    double *res = nullptr;          // device-mapped [best value, best index, clamp count] the sweep's last kernel fills, handing the counters back at zero (no D2H copy, no memset behind it), or null
+    double *winner = nullptr;       // the (D + 2) record [value, global index, row] to pack (tgp_set_winner_out), or null
+    Bell bell{nullptr, 0, nullptr}; // word != null: the one-workgroup / one-launch family's last kernel rings when the record is out (the general sweep never rings)
+    bool may_use_front = false;     // the caller saw c.pre.front before pre_join discarded it: the front a fit issued may serve this sweep
+};
+// which kernel family sweeps a batch of M candidates with the resident model
+enum class SweepPath {
+    OneWorkgroup,   // N <= 128 off small_fit_kernel: small_sweep_kernel + the arg-max's final kernel (f64)
+    OneLaunch,      // 128 < N <= 512: mid_sweep_kernel, everything in one launch (f64)
+    General         // the cross-kernel / contraction / finalize schedule in the handle's arithmetic (sweep_kernels.hip)
+};
+// mid_sweep_cpw: candidates per workgroup of the one-launch sweep (64 up to N = 256, 32 up to N = 512 and moderate
+// batches), 0 = not that family
 int mid_sweep_cpw(const Context &c, int64_t M);   // M: the batch about to be swept
-hipError_t launch_mid_sweep(Context &c, const double *cand, int acq, double sf, double incumbent,
-                            double param, double *mu, double *sigma, double *acqv, double *res_host,
-                            const Bell &bell = Bell{nullptr, 0, nullptr});   // bell.word != null: the last workgroup rings when the record is out
-hipError_t launch_small_sweep(Context &c, const double *cand, int acq, double sf, double incumbent,
-                              double param, double *mu, double *sigma, double *acqv);
-hipError_t launch_sweep(Context &c, int acq, double sf, double incumbent, double param,
-                        bool want_mu, bool want_sigma, bool want_acq);
+inline SweepPath sweep_path(const Context &c, int64_t M) {
+    if (c.small && c.N <= 2 * NB) return SweepPath::OneWorkgroup;
+    return mid_sweep_cpw(c, M) != 0 ? SweepPath::OneLaunch : SweepPath::General;
+}
+// the three families' launchers, on c.stream over c.d_cand / c.M.  One-workgroup: launch_small_sweep, then
+// launch_argmax_final (record, winner, bell).  One-launch: launch_mid_sweep does all of it.  General: launch_sweep;
+// front_usable: the front a fit issued belongs to the resident fit, batch and workspace geometry
+hipError_t launch_small_sweep(Context &c, const SweepCall &s);
+hipError_t launch_argmax_final(Context &c, const SweepCall &s);
+hipError_t launch_mid_sweep(Context &c, const SweepCall &s);
+hipError_t launch_sweep(Context &c, const SweepCall &s, bool front_usable);
 // inside launch_fit, on the third stream (c.pre.mode > 0, candidates resident, workspace ensured): the candidate scaling and
 // launch pair 0's cross-kernel (needs Xs, the length scales) / the contraction's 128-row tiles whose rows of Linv are
 // final (rows < rows_final), at most budget128 of them in all
