@@ -984,7 +984,24 @@ static hipError_t prune_workspace(Context &c, int64_t npick, int64_t rows_cap, P
     return hipSuccess;
 }
 
-// n gathered rows: per launch_rows of them the cross-kernel into slot 0, then the 128 x 128 contraction over every row
+// The contraction of `rows` gathered candidates (a multiple of 128) over ntm 128-row tiles: the widest candidate tile of
+// 128 / 64 / 32 that still gives CONTRACT_MIN_WGS workgroups, else the narrowest.  A launch with fewer workgroups than
+// CUs lasts as long as its heaviest wave, and the narrow variants (trmm_sweep.hpp) cut that wave's share of a row tile
+// from 128 x 32 to 32 x 64 / 32 x 32; they write the 128 x 128 kernel's bits, so the choice never shows in a result.
+template <typename T>
+static TrmmVariant contract_variant(const SweepPlan<T> &p, int64_t rows, int ntm) {
+    TrmmVariant v;
+    v.kern = p.early.kern; v.lds = trmm_glds_lds_bytes(); v.tile_m = 128; v.tile_n = 128; v.threads = 256;
+    if ((rows / 128) * ntm >= CONTRACT_MIN_WGS) return v;
+    if ((rows / 64) * ntm >= CONTRACT_MIN_WGS) {
+        v.kern = trmm_sumsq_glds_narrow_kernel<T, 64>; v.lds = trmm_narrow_lds_bytes<64>(); v.tile_n = 64;
+    } else {
+        v.kern = trmm_sumsq_glds_narrow_kernel<T, 32>; v.lds = trmm_narrow_lds_bytes<32>(); v.tile_n = 32;
+    }
+    return v;
+}
+
+// n gathered rows: per launch_rows of them the cross-kernel into slot 0, then the 128-row contraction over every row
 // tile with the mean inside (part / mupart rows [0, n))
 template <typename T>
 static hipError_t contract_rows(Context &c, const SweepPlan<T> &p, const T *cs, int64_t n, hipStream_t st, int &mark) {
@@ -1007,10 +1024,11 @@ static hipError_t contract_rows(Context &c, const SweepPlan<T> &p, const T *cs, 
         g.B = c.d_Ks[0]; g.ldb = Np;
         g.part = c.d_part + off; g.ldpart = c.ws_Mpad;
         g.prm = 1;
-        g.tm0 = 0; g.ntm = p.n128; g.ntn = (int)(rows / 128); g.ntn_group = 0;
+        const TrmmVariant v = contract_variant<T>(p, rows, p.n128);
+        g.tm0 = 0; g.ntm = p.n128; g.ntn = (int)(rows / v.tile_n); g.ntn_group = 0;
         g.K = p.n128 * 128;
         g.mu_alpha = c.d_alpha; g.mu = c.d_mupart + off;
-        hipLaunchKernelGGL(p.early.kern, dim3((unsigned)(g.ntm * g.ntn)), dim3(256), trmm_glds_lds_bytes(), st, g);
+        hipLaunchKernelGGL(v.kern, dim3((unsigned)(g.ntm * g.ntn)), dim3(v.threads), v.lds, st, g);
         TGP_TRY(hipGetLastError());
         m2 = prof_mark(c, st);
         prof_seg(c, mark, m2, 0, (double)m * (double)N * (double)N);
@@ -1043,10 +1061,18 @@ static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCal
     // 1. the bound of every candidate
     if (!front_usable) TGP_TRY(issue_prep<T>(c, st));   // (a fit's front has scaled them already)
     int mark = prof_mark(c, st);
+    // Splits of the training points over the bound pass's grid: a big batch fills the chip with its candidate tiles
+    // alone, and every split costs a workgroup its prologue (candidate tile staged, first barrier), 2 x 8 shuffled
+    // partial sums and a row of each partial array for prune_bound_kernel to read.  (Any split is covered by
+    // err_scale: it bounds the distance between two summation orders of the same products.)
+    int njs_b = 1;
     {
         constexpr int KAR = kstar_ar(sizeof(T));
+        const int64_t xb = Mpad / (16 * KAR);
+        while (njs_b < p.njs && xb * njs_b < BOUND_MIN_WGS) njs_b *= 2;
+        if (njs_b > p.njs) njs_b = p.njs;
         const T *Xs = reinterpret_cast<const T *>(sizeof(T) == 8 ? (const void *)c.d_Xs : (const void *)c.d_Xs32);
-        hipLaunchKernelGGL(kstar_fn<T>(c.kernel, false, false, false, true), dim3((unsigned)(Mpad / (16 * KAR)), (unsigned)p.njs),
+        hipLaunchKernelGGL(kstar_fn<T>(c.kernel, false, false, false, true), dim3((unsigned)xb, (unsigned)njs_b),
                            dim3(256), 0, st, Cs, Xs, c.d_alpha, reinterpret_cast<T *>(c.d_part), c.d_mupart, (int)Mpad, N,
                            (int)c.Np, Dp, c.constant, (long)Mpad, 0L, 1.f);
         TGP_TRY(hipGetLastError());
@@ -1055,7 +1081,7 @@ static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCal
         mark = m2;
     }
     BoundArgs b{};
-    b.mupart = c.d_mupart; b.abspart = c.d_part; b.ldpart = Mpad; b.njs = p.njs;
+    b.mupart = c.d_mupart; b.abspart = c.d_part; b.ldpart = Mpad; b.njs = njs_b;
     b.m = M;
     b.err_scale = 4.0 * (double)(N + 8) * 0x1p-53;
     b.y_mean = c.y_mean; b.y_std = c.y_std;

@@ -20,6 +20,8 @@ constexpr int SW_BM = 128;      // sweep tile: rows of Linv
 constexpr int SW_BN = 128;      // sweep tile: candidates
 constexpr int KS_JS = 8;        // most training-point splits of the cross-kernel grid (rows of mupart)
 constexpr int FIN_BLOCK = 256;  // finalize block = candidates per arg-max partial
+constexpr int CONTRACT_MIN_WGS = 512;   // a gathered set's contraction takes the widest candidate tile that still gives this many workgroups (two per CU)
+constexpr int BOUND_MIN_WGS = 2048;     // the bound pass splits the training points only as far as its grid needs to reach this many workgroups
 
 struct ProfSeg { int a, b, kind; double flops; };   // pooled events a -> b bracket one launch; kind: 0 trmm, 1 kstar; flops: the contraction's algorithmic flops of that launch (a launch a fit took row tiles of has fewer)
 

@@ -191,6 +191,192 @@ __global__ __launch_bounds__(256, 2) void trmm_sumsq_glds_kernel(GemmArgs g) {
 
 constexpr size_t trmm_glds_lds_bytes() { return (size_t)2 * 2 * 128 * 128; }
 
+// ------------------------------------------------------------------------------------------
+// Narrow variant for a few hundred to a few thousand gathered candidates (the pruned sweep's lb set and
+// survivors): 128 rows x BN candidates (BN = 32 or 64) per workgroup, and the four waves split the ROWS -- wave w
+// owns rows [32 w, 32 w + 32) against all BN candidates -- so 256 candidates give 256 (BN = 32) workgroups whose
+// waves each carry a quarter of the 128 x 128 kernel's MFMA chain per wave (there a wave owns 128 rows x 32
+// candidates, and a launch of fewer workgroups than CUs lasts as long as that one wave).
+// `part` and the mean are those of the 128 x 128 kernel bit for bit:
+//   * an accumulator element's k-chain is the MFMA's own and does not depend on who owns the fragment;
+//   * the sum of squares of a column goes, per 64-row half, through ONE in-lane fma chain over the half's row
+//     fragments in ascending order, then the cross-lane adds, then half 0 + half 1.  Here a half's chain starts in
+//     wave 2 hh and is handed through LDS to wave 2 hh + 1, which continues it from that value -- the same fmas
+//     in the same order -- and does the cross-lane adds; one thread per column adds the halves;
+//   * the mean keeps MeanAcc's four partial sums per candidate (chunks {2g, 2g + 1}, k ascending) and their
+//     (p0 + p1) + (p2 + p3), on 4 BN threads.
+// ------------------------------------------------------------------------------------------
+template <typename T, int BN>
+__global__ __launch_bounds__(256, 2) void trmm_sumsq_glds_narrow_kernel(GemmArgs g) {
+    using MF = Mfma<T>;
+    using vec_t = typename MF::vec_t;
+    using acc_t = typename MF::acc_t;
+    constexpr int EPL = MF::EPL;
+    constexpr int BM = 128;
+    constexpr int BK = 128 / (int)sizeof(T);
+    constexpr int NFM = 32 / MF::FM, NFN = BN / MF::FN;   // fragments per wave: its 32 rows x all BN candidates
+    constexpr int NG = 64 / MF::FM;
+    constexpr int KSTEPS = 8 / NG;
+    constexpr int A_BYTES = BM * 128, B_BYTES = BN * 128;
+    constexpr int BUF_BYTES = A_BYTES + B_BYTES;
+    constexpr int BP = BN / 32;                           // 8-row pieces of the B tile per wave
+    constexpr int EPC = 16 / (int)sizeof(T);              // elements per 16-byte chunk (the mean)
+    static_assert(BN == 32 || BN == 64, "narrow contraction: 32 or 64 candidates per workgroup");
+    static_assert(4 * BN <= 256, "the mean's 4 BN partial sums need a thread each");
+
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];   // [2][A 128 x 128 B | B BN x 128 B]
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+    int tm, tn;
+    sweep_tile(g, (int)blockIdx.x, tm, tn);
+    int ke = (tm + 1) * BM;
+    ke = ke < g.K ? ke : g.K;
+
+    // ---- direct-to-LDS staging, the 128 x 128 kernel's image: A piece (4p + w), B piece (BP w + p) ------------
+    const int srow = lane >> 3;
+    const int schunk = lane & 7;
+    const char *asrc[4];
+    const char *bsrc[BP];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int row = (4 * p + wave) * 8 + srow;
+        const int src_chunk = schunk ^ ((row >> 1) & 7);
+        asrc[p] = reinterpret_cast<const char *>(reinterpret_cast<const T *>(g.A) + ((long)tm * BM + row) * g.lda) + src_chunk * 16;
+    }
+#pragma unroll
+    for (int p = 0; p < BP; ++p) {
+        const int row = (BP * wave + p) * 8 + srow;
+        const int src_chunk = schunk ^ ((row >> 1) & 7);
+        bsrc[p] = reinterpret_cast<const char *>(reinterpret_cast<const T *>(g.B) + ((long)tn * BN + row) * g.ldb) + src_chunk * 16;
+    }
+    auto stage = [&](int buf, int k0) {
+        const long koff = (long)k0 * (long)sizeof(T);
+        char *base = smem_raw + buf * BUF_BYTES;
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+            __builtin_amdgcn_global_load_lds((gbl_void_t *)(asrc[p] + koff), (lds_void_t *)(base + (4 * p + wave) * 8 * 128), 16, 0, 0);
+#pragma unroll
+        for (int p = 0; p < BP; ++p)
+            __builtin_amdgcn_global_load_lds((gbl_void_t *)(bsrc[p] + koff), (lds_void_t *)(base + A_BYTES + (BP * wave + p) * 8 * 128), 16, 0, 0);
+    };
+
+    acc_t acc[NFM][NFN];
+#pragma unroll
+    for (int i = 0; i < NFM; ++i)
+#pragma unroll
+        for (int j = 0; j < NFN; ++j)
+#pragma unroll
+            for (int r = 0; r < MF::NACC; ++r) acc[i][j][r] = (T)0;
+
+    const int fidx = MF::ab_idx(lane);
+    const int grp = MF::ab_kg(lane);
+    const int swz = (fidx >> 1) & 7;                  // row offsets are multiples of 16
+    const int a_row_off = (wave * 32 + fidx) * 128;
+    const int b_row_off = A_BYTES + fidx * 128;
+
+    // rows 0..63 (waves 0, 1) have nothing but zeros right of the diagonal block's first half: the 128 x 128 kernel's cut
+    const int ke_lo = (tm * BM + 64) < ke ? (tm * BM + 64) : ke;
+    const int ke_wave = wave < 2 ? ke_lo : ke;
+    const bool do_mean = g.mu != nullptr && ke >= g.K;
+    const bool mean_thread = do_mean && tid < 4 * BN;
+    const int mrow = tid % BN, mgrp = tid / BN;       // (threads >= 4 BN: unused)
+    const int mswz = (mrow >> 1) & 7;
+    double ms = 0.0;
+    int buf = 0;
+    stage(0, 0);
+    __syncthreads();
+    for (int k0 = 0; k0 < ke; k0 += BK) {
+        double mal[2 * EPC];
+        if (mean_thread) {
+#pragma unroll
+            for (int e = 0; e < 2 * EPC; ++e) mal[e] = g.mu_alpha[k0 + mgrp * 2 * EPC + e];
+        }
+        if (k0 + BK < ke) stage(buf ^ 1, k0 + BK);
+        const char *base = smem_raw + buf * BUF_BYTES;
+        if (k0 < ke_wave) {
+#pragma unroll
+            for (int s = 0; s < KSTEPS; ++s) {
+                const int coff = ((s * NG + grp) ^ swz) * 16;
+                vec_t a[NFM], b[NFN];
+#pragma unroll
+                for (int i = 0; i < NFM; ++i)
+                    a[i] = *reinterpret_cast<const vec_t *>(base + a_row_off + i * MF::FM * 128 + coff);
+#pragma unroll
+                for (int j = 0; j < NFN; ++j)
+                    b[j] = *reinterpret_cast<const vec_t *>(base + b_row_off + j * MF::FN * 128 + coff);
+#pragma unroll
+                for (int e = 0; e < EPL; ++e)
+#pragma unroll
+                    for (int i = 0; i < NFM; ++i)
+#pragma unroll
+                        for (int j = 0; j < NFN; ++j) acc[i][j] = MF::mma(a[i][e], b[j][e], acc[i][j]);
+            }
+        }
+        if (mean_thread) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                typedef T mvec_t __attribute__((ext_vector_type(EPC)));
+                const mvec_t v = *reinterpret_cast<const mvec_t *>(base + A_BYTES + mrow * 128 + (((2 * mgrp + q) ^ mswz) << 4));
+#pragma unroll
+                for (int e = 0; e < EPC; ++e) ms = fma((double)v[e], mal[q * EPC + e], ms);
+            }
+        }
+        __syncthreads();
+        buf ^= 1;
+    }
+    // (the k-loop's last barrier is behind every wave: LDS is free)
+    double *mred = reinterpret_cast<double *>(smem_raw);              // [4][BN]    the mean's partial sums
+    double *hand = mred + 4 * BN;                                     // [2][NFN][64] a half's chain, wave 2 hh -> wave 2 hh + 1
+    double *half = hand + 2 * NFN * 64;                               // [2][BN]    the halves' column sums
+    if (mean_thread) mred[mgrp * BN + mrow] = ms;
+
+    const int hh = wave >> 1;
+    double s[NFN];
+    if ((wave & 1) == 0) {
+#pragma unroll
+        for (int j = 0; j < NFN; ++j) {
+            s[j] = 0.0;
+#pragma unroll
+            for (int i = 0; i < NFM; ++i)
+#pragma unroll
+                for (int r = 0; r < MF::NACC; ++r) {
+                    const double v = (double)acc[i][j][r];
+                    s[j] = fma(v, v, s[j]);
+                }
+            hand[(hh * NFN + j) * 64 + lane] = s[j];
+        }
+    }
+    __syncthreads();
+    if (wave & 1) {
+#pragma unroll
+        for (int j = 0; j < NFN; ++j) {
+            s[j] = hand[(hh * NFN + j) * 64 + lane];
+#pragma unroll
+            for (int i = 0; i < NFM; ++i)
+#pragma unroll
+                for (int r = 0; r < MF::NACC; ++r) {
+                    const double v = (double)acc[i][j][r];
+                    s[j] = fma(v, v, s[j]);
+                }
+#pragma unroll
+            for (int o = MF::COL_LANE_STRIDE; o < 64; o <<= 1) s[j] += __shfl_xor(s[j], o, 64);
+            if (lane < MF::COL_LANE_STRIDE) half[hh * BN + j * MF::FN + lane] = s[j];
+        }
+    }
+    __syncthreads();
+    if (tid < BN) {
+        g.part[(long)tm * g.prm * g.ldpart + (long)tn * BN + tid] = half[tid] + half[BN + tid];
+        if (do_mean)
+            g.mu[(long)tn * BN + tid] = (mred[tid] + mred[BN + tid]) + (mred[2 * BN + tid] + mred[3 * BN + tid]);
+    }
+}
+
+template <int BN>
+constexpr size_t trmm_narrow_lds_bytes() { return (size_t)2 * (128 + BN) * 128; }
+
 }  // namespace tgp
 
 namespace tgp {
