@@ -282,6 +282,41 @@ int tgp_sweep_batch(tgp_handle h, int64_t q, int strategy, double lie, const dou
                     double incumbent, double param, int64_t *idx_out, double *val_out, double *x_out,
                     double *fantasy_out, double *mu_out, double *sigma_out, int64_t *n_clamped);
 
+/* The Monte Carlo parallel strategy of the author's older library (old_library/bayesian_optimiser.py:76-106,
+ * _max_mc_acq_suggestion :568-624): S simulations of the outcomes of the P pending and the selected points, and the
+ * AVERAGE of the S acquisition functions maximised.  Arguments and rules as tgp_sweep_batch without strategy / lie.  In
+ * normalised units, with R the new block of the augmented factor and G the scaled cross-covariance columns of
+ * tgp_sweep_batch (hyper-parameters, jitter, y_mean / y_std held):
+ *   y~[s,j]  = mu~_{s,j-1}(z_j) + R[j,j] eps[s,j],  eps[s,j] ~ N(0,1)   a draw of the OBSERVATION y at z_j given simulation
+ *                                                                      s's own earlier draws (noise + jitter in R[j,j]^2)
+ *   mu~_s(x) = mu0(x) + sum_{i<=j} G[x,i] eps[s,i];   sigma~(x) is tgp_sweep_batch's and shared by the simulations
+ *   inc_s    = best(incumbent, raw fantasies of simulation s so far) in the direction of sf      (EI / PI only)
+ *   a(x)     = (1/S) sum_s acq(y_mean + y_std mu~_s(x), y_std sigma~(x); inc_s), summed in the order s = 0, 1, ...
+ * which is what S literal refits on the augmented data give.  The draw is JOINT (sequential conditioning); the old
+ * library draws each pending point on its own (:582-585), which ignores that two nearby pending points come out alike --
+ * with one pending point the two coincide.  TGP_ACQ_SIGMA does not depend on the simulations: a(x) = sigma~(x).
+ *   S          1 <= S <= 64 simulations
+ *   eps_in     NULL: eps[s,j] is a Philox-4x32-10 normal keyed by `seed`, counter (element lo, element hi, 0, tag),
+ *              element s 64 + j with j counted pending-first, the 53-bit uniforms and the Box-Muller branch of the
+ *              Thompson draw (csrc/philox.hpp) -- simulation s does not depend on S, the draw for point j not on P or q.
+ *              Else (S, P + q) finite standard normals used as they are (quasi-random or common random numbers)
+ *   idx_out, val_out   (q) candidate index and AVERAGED acquisition of each selection (lowest index on ties, NaN never
+ *              wins, taken rows masked); with P = 0 the first selection is tgp_sweep's launch path, so q = 1, P = 0
+ *              returns tgp_sweep's best_idx / best_val bit for bit
+ *   x_out      (q, D) the selected rows;  fantasy_out (S, P + q) the fantasies, raw units;  eps_out (S, P + q) the
+ *              normals used;  acq_out (q, M) every step's averaged acquisition with the rows already taken (and NaN)
+ *              at -inf -- row 0 with P = 0 holds the values of tgp_sweep's acq_out, so in the handle's arithmetic
+ *              (f32 on an f32 handle; every other row is f64);  sigma_out (M) after all P + q points (costs one more
+ *              pass).  All nullable
+ *   n_clamped  (nullable) variances clamped at 0, summed over the sweep and every step, once per (candidate, point)
+ * TGP_NOT_PD as tgp_sweep_batch (the pivot does not depend on the simulation).  f64 whatever the handle's dtype.  The
+ * fit, the candidates, the winner record, a Thompson draw and later sweeps are untouched.  GPU only: TGP_BAD_ARG on host
+ * handles. */
+int tgp_sweep_batch_mc(tgp_handle h, int64_t q, int64_t S, uint64_t seed, const double *eps_in, const double *Xp, int64_t P,
+                       int acq, double sf, double incumbent, double param, int64_t *idx_out, double *val_out,
+                       double *x_out, double *fantasy_out, double *eps_out, double *acq_out, double *sigma_out,
+                       int64_t *n_clamped);
+
 /* Thompson sampling: the acquisition the author's older library names but leaves unimplemented
  * (old_library/acquisition_functions.py:20-21, bayesian_optimiser.py:137-138, :263-264) and its 'asyTS' batch
  * strategy (:102-104).  tgp_ts_draw draws S sample paths of the fitted model by pathwise conditioning with F random

@@ -7,12 +7,21 @@ One JSON line per (config, q, pending): the median wall time of one tgp_sweep_ba
 the same q points by q x (tgp_fit_append of the fantasised point + tgp_sweep) after appending the pending points, and
 (Branin size only) of the same loop as a NumPy / SciPy refit on the host.  One tgp_sweep of the same batch is timed as
 the yardstick (batch_over_sweep, per_point_over_sweep = (batch - sweep) / (P + q - 1) / sweep).
+
+    python tools/bench_batch.py --mc 1,16,64 [--mc-literal-S 16] [--configs branin,c2,c3] --q 8 [--out profiles/batch_mc.jsonl]
+
+The Monte Carlo mode: one JSON line per (config, q, pending, S) with the median wall time of one tgp_sweep_batch_mc call
+of S simulations beside one Kriging Believer call on the same handle and candidates (mc_over_kb).  --mc-literal-S S adds,
+once per config without pending points, what the old library's loop costs on the same handle: S x (tgp_fit_append of
+one fantasised point + tgp_sweep) for ONE selection after the first (the refit back to the real data between two
+simulations is timed on its own and subtracted), beside the same step inside tgp_sweep_batch_mc (q = 2 minus q = 1).
 """
 import argparse
 import json
 import os
 import sys
 import time
+from types import SimpleNamespace
 
 import numpy as np
 from scipy.linalg import cho_factor, cho_solve
@@ -77,6 +86,45 @@ def host_refit_loop(X, y, Xc, Xp, q, ls, noise, jitter, param):
     return chosen
 
 
+def mc_mode(a, st, emit):
+    """tgp_sweep_batch_mc beside Kriging Believer, same handle, same candidates, warm.  st: the per-config state main
+    builds (gp, L, fit, X, y, Xc, Xp_all, acq, sf, inc, par, t_sweep, base)"""
+    gp, L, call = st.gp, st.L, (st.acq, st.sf, st.inc, st.par)
+    for P in [int(v) for v in a.pending.split(",")]:
+        Xp = st.Xp_all[:P] if P else None
+        for q in [int(v) for v in a.q.split(",")]:
+            gp.sweep_batch(q, L.BATCH_KB, 0.0, Xp, *call)
+            t_kb = _median_ms(lambda: gp.sweep_batch(q, L.BATCH_KB, 0.0, Xp, *call), a.reps)
+            kb_dev = gp.profile_read()["last_sweep_ms"]
+            for S in [int(v) for v in a.mc.split(",")]:
+                gp.sweep_batch_mc(q, S, 1, None, Xp, *call)
+                t_mc = _median_ms(lambda: gp.sweep_batch_mc(q, S, 1, None, Xp, *call), a.reps)
+                emit(dict(st.base, workload="batch_select_mc", strategy="monte_carlo", q=q, pending=P, S=S,
+                          sweep_ms=round(st.t_sweep, 4), kb_ms=round(t_kb, 4), kb_device_ms=round(kb_dev, 4),
+                          mc_ms=round(t_mc, 4), mc_device_ms=round(gp.profile_read()["last_sweep_ms"], 4),
+                          mc_over_kb=round(t_mc / t_kb, 3)))
+    if a.mc_literal_S > 0:
+        # the old library's loop for ONE selection after the first: per simulation append the fantasised point and sweep.
+        # Each simulation starts from the real data again; that refit is not part of the method, so S x its median time
+        # is subtracted from the loop's.
+        S = a.mc_literal_S
+        res = gp.sweep_batch_mc(2, S, 1, None, None, *call)
+        Xa, fants = np.vstack([st.X, res["x"][0]]), res["fantasies"][:, 0]
+
+        def literal():
+            for s_ in range(S):
+                st.fit(Xa, np.append(st.y, fants[s_]), append=True)
+                gp.sweep(*call, want_acq=True)
+                st.fit(st.X, st.y)
+        t_lit = _median_ms(literal, a.reps) - S * _median_ms(lambda: st.fit(st.X, st.y), a.reps)
+        gp.set_candidates(st.Xc)
+        t_step = _median_ms(lambda: gp.sweep_batch_mc(2, S, 1, None, None, *call), a.reps) \
+            - _median_ms(lambda: gp.sweep_batch_mc(1, S, 1, None, None, *call), a.reps)
+        emit(dict(st.base, workload="batch_select_mc", strategy="monte_carlo_literal", S=S,
+                  literal_one_selection_ms=round(t_lit, 3), mc_one_selection_ms=round(t_step, 4),
+                  literal_over_mc=round(t_lit / max(t_step, 1e-9), 1)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="branin,c1,c2,c3")
@@ -84,11 +132,21 @@ def main():
     ap.add_argument("--pending", default="0,4")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--no-naive", action="store_true", help="time tgp_sweep_batch and tgp_sweep only")
+    ap.add_argument("--mc", default=None, help="Monte Carlo mode: the simulation counts, e.g. 1,16,64")
+    ap.add_argument("--mc-literal-S", type=int, default=0, metavar="S",
+                    help="with --mc: also time the literal alternative for one selection, S x (tgp_fit_append + tgp_sweep)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import turbo_amd as ta
     L = ta._lib
     out = open(a.out, "a") if a.out else None
+
+    def emit(line):
+        s = json.dumps(line)
+        print(s, flush=True)
+        if out:
+            out.write(s + "\n")
+            out.flush()
     for name in a.configs.split(","):
         cfg = BRANIN if name == "branin" else CONFIGS[name]
         if name == "branin":
@@ -111,6 +169,11 @@ def main():
         gp.set_candidates(Xc)
         gp.sweep(acq, sf, inc, par)
         t_sweep = _median_ms(lambda: gp.sweep(acq, sf, inc, par), a.reps)
+        if a.mc:
+            base = dict(config=name, N=cfg["N"], D=cfg["D"], M=cfg["M"], dtype=cfg["dtype"], acq=cfg["acq"])
+            mc_mode(a, SimpleNamespace(gp=gp, L=L, fit=fit, X=X, y=y, Xc=Xc, Xp_all=Xp_all, acq=acq, sf=sf, inc=inc, par=par,
+                                       t_sweep=t_sweep, base=base), emit)
+            continue
         for P in [int(v) for v in a.pending.split(",")]:
             Xp = Xp_all[:P] if P else None
             for q in [int(v) for v in a.q.split(",")]:
@@ -143,11 +206,7 @@ def main():
                     if name == "branin":
                         t_host = _median_ms(lambda: host_refit_loop(X, y, Xc, Xp_all[:P], q, ls, noise, jitter, par), a.reps)
                         line.update(host_refit_ms=round(t_host, 3))
-                s = json.dumps(line)
-                print(s, flush=True)
-                if out:
-                    out.write(s + "\n")
-                    out.flush()
+                emit(line)
     if out:
         out.close()
 

@@ -41,7 +41,7 @@ SYMBOLS = (
     "tgp_fit_append", "tgp_export_state", "tgp_import_state", "tgp_export_factor_dev", "tgp_import_factor_dev", "tgp_debug_read",
     "tgp_set_candidates", "tgp_set_candidates_dev", "tgp_gen_candidates", "tgp_gen_candidates_lhs", "tgp_lhs_design",
     "tgp_read_candidates", "tgp_get_candidate",
-    "tgp_sweep", "tgp_sweep_batch", "tgp_ts_draw", "tgp_ts_sweep", "tgp_ts_eval", "tgp_ts_read", "tgp_sweep_topk", "tgp_set_winner_out", "tgp_winner_wait", "tgp_acq_grad", "tgp_acq_refine", "tgp_acq_lbfgsb",
+    "tgp_sweep", "tgp_sweep_batch", "tgp_sweep_batch_mc", "tgp_ts_draw", "tgp_ts_sweep", "tgp_ts_eval", "tgp_ts_read", "tgp_sweep_topk", "tgp_set_winner_out", "tgp_winner_wait", "tgp_acq_grad", "tgp_acq_refine", "tgp_acq_lbfgsb",
     "tgp_evaluate", "tgp_predict_batch", "tgp_predict", "tgp_profile_enable", "tgp_profile_read", "tgp_profile_reset",
     "tgp_sweep_geometry", "tgp_last_timings",
     "tgp_multi_create", "tgp_multi_destroy", "tgp_multi_last_error", "tgp_multi_size", "tgp_multi_handle",
@@ -136,6 +136,8 @@ def _argtypes():
         "tgp_sweep_topk": [_vp, c.c_int, c.c_double, c.c_double, c.c_double, c.c_int64, _dp, _i64p, _i64p],
         "tgp_sweep_batch": [_vp, c.c_int64, c.c_int, c.c_double, _dp, c.c_int64, c.c_int, c.c_double, c.c_double,
                             c.c_double, _i64p, _dp, _dp, _dp, _dp, _dp, _i64p],
+        "tgp_sweep_batch_mc": [_vp, c.c_int64, c.c_int64, c.c_uint64, _dp, _dp, c.c_int64, c.c_int, c.c_double, c.c_double,
+                               c.c_double, _i64p, _dp, _dp, _dp, _dp, _dp, _dp, _i64p],
         "tgp_ts_draw": [_vp, c.c_uint64, c.c_int64, c.c_int64],
         "tgp_ts_sweep": [_vp, c.c_double, c.c_int, _i64p, _dp, _dp, _dp],
         "tgp_ts_eval": [_vp, _dp, c.c_int64, _dp, _dp],
@@ -683,6 +685,40 @@ class NativeGP:
                                              float(incumbent), float(param), idx.ctypes.data_as(_i64p), _ptr(val),
                                              _ptr(x), _ptr(fant), _ptr(mu), _ptr(sg), ctypes.byref(nc)))
         return dict(idx=idx[:q], val=val[:q], x=x[:q], fantasies=fant[:P + q], mu=mu, sigma=sg, n_clamped=nc.value,
+                    sweep_ms=self.profile_read()['last_sweep_ms'])
+
+    def sweep_batch_mc(self, q, n_sim=16, seed=0, eps=None, pending=None, acq=ACQ_EI, sf=1.0, incumbent=0.0, param=0.0,
+                       want_acq=False, want_sigma=False):
+        """``tgp_sweep_batch_mc``: q resident candidates chosen greedily by the Monte Carlo strategy -- the average of the
+        acquisition over ``n_sim`` <= 64 simulated outcomes of the pending (P, D) and the selected points.  ``eps`` None:
+        the normals come from the Philox stream of ``seed``; else (n_sim, P + q) standard normals used as they are.
+        Returns a dict: idx (q,), val (q,), x (q, D), fantasies (n_sim, P + q) pending first, eps (n_sim, P + q), acq
+        (q, M) every step's averaged acquisition (want_acq) or None, sigma (M,) after all points (want_sigma) or None,
+        n_clamped"""
+        q, S = int(q), int(n_sim)
+        Xp = None if pending is None else _f64c(np.atleast_2d(pending))
+        if Xp is not None and Xp.size == 0:
+            Xp = None
+        P = 0 if Xp is None else Xp.shape[0]
+        if Xp is not None:
+            assert Xp.ndim == 2 and Xp.shape[1] == self.D, "pending points must be (P, %d)" % self.D
+        J, Sa = max(P + q, 1), max(S, 1)
+        if eps is not None:
+            eps = _f64c(np.asarray(eps, dtype=np.float64))
+            assert eps.shape == (S, P + q), "eps must be (n_sim, P + q) = (%d, %d)" % (S, P + q)
+        idx = np.empty(max(q, 1), dtype=np.int64)
+        val = np.empty(max(q, 1))
+        x = np.empty((max(q, 1), self.D))
+        fant = np.empty((Sa, J))
+        eo = np.empty((Sa, J))
+        aq = np.empty((max(q, 1), self.M)) if want_acq else None
+        sg = np.empty(self.M) if want_sigma else None
+        nc = ctypes.c_int64(0)
+        self._check(self.lib.tgp_sweep_batch_mc(self._h, q, S, int(seed) % (1 << 64), _ptr(eps), _ptr(Xp), P, int(acq),
+                                                float(sf), float(incumbent), float(param), idx.ctypes.data_as(_i64p),
+                                                _ptr(val), _ptr(x), _ptr(fant), _ptr(eo), _ptr(aq), _ptr(sg),
+                                                ctypes.byref(nc)))
+        return dict(idx=idx[:q], val=val[:q], x=x[:q], fantasies=fant, eps=eo, acq=aq, sigma=sg, n_clamped=nc.value,
                     sweep_ms=self.profile_read()['last_sweep_ms'])
 
     def ts_draw(self, seed, S=1, F=2048):

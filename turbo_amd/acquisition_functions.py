@@ -138,20 +138,42 @@ class AcquisitionFunction:
 
         BATCH_STRATEGIES = {'kriging_believer': _lib.BATCH_KB, 'constant_liar': _lib.BATCH_CL}
 
-        def maximise_batch(self, X, q, strategy='kriging_believer', lie='min', pending=None, want_posterior=False):
+        def maximise_batch(self, X, q, strategy='kriging_believer', lie='min', pending=None, want_posterior=False,
+                           n_sim=16, seed=None):
             """q rows of X chosen greedily for q parallel workers (``tgp_sweep_batch``), conditioned first on the
             ``pending`` points (P, D) -- trials still under evaluation.  Every chosen or pending point is given a
             fantasy value -- 'kriging_believer': the posterior mean there; 'constant_liar': ``lie``, a float in raw y
             units or 'min' / 'max' / 'mean' of the model's observed y -- and the model is conditioned on it with the
             hyper-parameters held (old_library/bayesian_optimiser.py:76-103, :527-566).  X None: the batch already
             resident on the model's GPU context.  Returns the dict of ``NativeGP.sweep_batch`` (idx, val, x, fantasies,
-            mu, sigma, n_clamped, sweep_ms)."""
+            mu, sigma, n_clamped, sweep_ms).
+
+            'monte_carlo' (``tgp_sweep_batch_mc``; old_library/bayesian_optimiser.py:568-624): ``n_sim`` <= 64
+            simulations of the pending and chosen points' outcomes, drawn jointly from the model, and the AVERAGE of
+            the acquisition over them maximised.  ``seed`` keys the fantasies' random numbers; None takes one
+            ``np.random.randint(0, 2**63)`` from NumPy's global RNG, as ``TS`` does.  Returns the dict of
+            ``NativeGP.sweep_batch_mc`` (fantasies (n_sim, P + q)) plus n_sim and seed; ``lie`` is not used and
+            ``want_posterior`` asks for sigma alone (the S means differ).  The other strategies ignore ``n_sim`` and
+            ``seed``."""
             if not _is_native(self.model):
                 raise NotImplementedError('maximise_batch runs on the GPU only: it needs a model built by HipGPSurrogate '
                                           '(got {!r})'.format(type(self.model)))
-            if strategy not in self.BATCH_STRATEGIES:
-                raise ValueError('strategy must be one of {}'.format(sorted(self.BATCH_STRATEGIES)))
+            if strategy != 'monte_carlo' and strategy not in self.BATCH_STRATEGIES:
+                raise ValueError('strategy must be one of {}'.format(sorted(list(self.BATCH_STRATEGIES) + ['monte_carlo'])))
             acq, incumbent, param = self._native_args()
+            if strategy == 'monte_carlo':
+                n_sim = int(n_sim)
+                if n_sim < 1 or n_sim > 64:
+                    raise ValueError('n_sim must be in [1, 64]')
+                seed = int(np.random.randint(0, 2**63)) if seed is None else int(seed) % (1 << 64)
+                ctx = self.model._ensure_resident()
+                if X is not None:
+                    ctx.set_candidates(np.asarray(X, dtype=np.float64))
+                res = ctx.sweep_batch_mc(q, n_sim, seed, None, pending, acq, self.scale_factor, incumbent, param,
+                                         want_sigma=want_posterior)
+                self.last_sweep_ms = res.get('sweep_ms')
+                res['n_sim'], res['seed'] = n_sim, seed
+                return res
             lie_value = 0.0
             if strategy == 'constant_liar':
                 y = np.asarray(self.model.y, dtype=np.float64)
@@ -495,7 +517,8 @@ class TS(AcquisitionFunction):
         def maximise_host_stream(self, num_points, low, high, topk=0, first=0, count=None):
             return None     # nothing drawn: the caller draws on the host and calls maximise / maximise_topk
 
-        def maximise_batch(self, X, q, strategy='thompson', lie=None, pending=None, want_posterior=False):
+        def maximise_batch(self, X, q, strategy='thompson', lie=None, pending=None, want_posterior=False, n_sim=16,
+                           seed=None):
             """q distinct rows of X for q parallel workers: row s maximises sample path s of ONE draw of q paths, skipping
             the rows of paths < s (asynchronous Thompson sampling: ``pending`` trials are ignored,
             old_library/bayesian_optimiser.py:102-104).  X None: the batch already resident.  Path 0 is this instance's

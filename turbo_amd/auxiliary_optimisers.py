@@ -146,11 +146,18 @@ class CandidateSweep:
         self.last_batches = None
         self._calls = 0
 
-    def select_batch(self, latent_bounds, acq, q, strategy='kriging_believer', lie='min', pending=None):
+    def select_batch(self, latent_bounds, acq, q, strategy='kriging_believer', lie='min', pending=None, n_sim=16,
+                     seed=None):
         """q points for q parallel workers from ONE batch of candidates, drawn exactly as ``__call__`` draws it, chosen
         greedily with Kriging Believer / Constant Liar and conditioned first on ``pending`` (P, D): the trials still
         running (``FunctionInstance.maximise_batch``, ``tgp_sweep_batch``).  Returns (x (q, D), info) with info =
         {'max_acq' (q,), 'candidate_indices' (q,), 'fantasies' (q,), 'pending_fantasies' (P,), 'strategy'}.
+
+        strategy='monte_carlo' (``tgp_sweep_batch_mc``): the average of the acquisition over ``n_sim`` <= 64 joint
+        simulations of the pending and chosen points' outcomes is maximised; ``seed`` keys their random numbers (None:
+        one ``np.random.randint(0, 2**63)`` taken after the candidates are drawn, as ``TS`` takes its seed; with a seed
+        given the NumPy RNG is consumed as by one ``__call__``).  info then holds 'fantasies' (n_sim, q),
+        'pending_fantasies' (n_sim, P), 'n_sim' and 'seed'.  The other strategies ignore both arguments.
 
         strategy='thompson' with a ``TS`` acquisition: q distinct rows, row s the best of sample path s of one draw of q
         paths (asynchronous Thompson sampling: ``pending`` is accepted and ignored).  info = {'max_acq' (q,) sf * sampled
@@ -176,18 +183,19 @@ class CandidateSweep:
             # the batch maximise_generated would draw for this call (or has prefetched), left resident
             low, high = zip(*bounds)
             ctx = acq.model._ensure_resident()
-            seed, lhs_total = self.device_rng_seed + self._calls, (self.num_random if self.device_design == 'lhs' else None)
+            cand_seed, lhs_total = self.device_rng_seed + self._calls, (self.num_random if self.device_design == 'lhs' else None)
             lo_b, hi_b = np.asarray(low, dtype=np.float64).tobytes(), np.asarray(high, dtype=np.float64).tobytes()
-            key = ("lhs" if lhs_total is not None else "uniform", int(seed), 0, int(self.num_random),
+            key = ("lhs" if lhs_total is not None else "uniform", int(cand_seed), 0, int(self.num_random),
                    int(lhs_total) if lhs_total is not None else None, lo_b, hi_b)
             if getattr(ctx, 'gen_key', None) != key:
                 if lhs_total is not None:
-                    ctx.gen_candidates_lhs(seed, 0, self.num_random, lhs_total, low, high)
+                    ctx.gen_candidates_lhs(cand_seed, 0, self.num_random, lhs_total, low, high)
                 else:
-                    ctx.gen_candidates(seed, 0, self.num_random, low, high)
-            res = acq.maximise_batch(None, q, strategy, lie, pending)
+                    ctx.gen_candidates(cand_seed, 0, self.num_random, low, high)
+            res = acq.maximise_batch(None, q, strategy, lie, pending, n_sim=n_sim, seed=seed)
         else:
-            res = acq.maximise_batch(self.gen_random(self.num_random, latent_bounds), q, strategy, lie, pending)
+            res = acq.maximise_batch(self.gen_random(self.num_random, latent_bounds), q, strategy, lie, pending,
+                                     n_sim=n_sim, seed=seed)
         self._calls += 1
         P = 0 if pending is None else len(pending)
         if thompson:
@@ -197,8 +205,13 @@ class CandidateSweep:
             if res.get('sweep_ms') is not None:
                 info['sweep_ms'] = res['sweep_ms']
             return np.asarray(res['x'], dtype=np.float64), info
-        info = {'max_acq': res['val'], 'candidate_indices': res['idx'], 'fantasies': res['fantasies'][P:],
-                'pending_fantasies': res['fantasies'][:P], 'strategy': strategy}
+        if strategy == 'monte_carlo':
+            info = {'max_acq': res['val'], 'candidate_indices': res['idx'], 'fantasies': res['fantasies'][:, P:],
+                    'pending_fantasies': res['fantasies'][:, :P], 'strategy': strategy, 'n_sim': res['n_sim'],
+                    'seed': res['seed']}
+        else:
+            info = {'max_acq': res['val'], 'candidate_indices': res['idx'], 'fantasies': res['fantasies'][P:],
+                    'pending_fantasies': res['fantasies'][:P], 'strategy': strategy}
         if res.get('sweep_ms') is not None:
             info['sweep_ms'] = res['sweep_ms']
         return np.asarray(res['x'], dtype=np.float64), info

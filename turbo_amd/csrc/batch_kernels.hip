@@ -18,10 +18,29 @@
 // applies the update, evaluates the acquisition with finalize_kernel's arithmetic and leaves per-block arg-max partials
 // that bt_argmax_kernel turns into the next selection, in device memory.  Everything here is f64, whatever the handle's
 // sweep dtype.
+//
+// Monte Carlo (tgp_sweep_batch_mc; old_library/bayesian_optimiser.py:76-106, _max_mc_acq_suggestion :568-624): S
+// simulations of the pending and selected points' outcomes, and the AVERAGE of the S acquisition functions maximised.
+// With the hyper-parameters held the variance update above does not depend on the fantasised values and the mean is
+// linear in them through the stored columns of G, so one conditioned point costs one bt_pass_kernel pass whatever S is:
+//
+//   y~[s,j]  = mu~_{s,j-1}(z_j) + R[j,j] eps[s,j],  eps[s,j] ~ N(0,1)        a draw of the OBSERVATION y (R[j,j]^2 holds
+//              mu~_{s,j-1}(z_j) = k*(z_j).alpha + sum_{i<j} R[j,i] eps[s,i]    noise + jitter), so e[s,j] = eps[s,j]
+//   mu~_s(x) = mu0(x) + sum_{i<=j} G[x,i] eps[s,i],   sigma~(x) shared: the update above
+//   inc_s    = best(incumbent, the raw fantasies of simulation s so far) in the direction of sf        (EI / PI)
+//   a(x)     = (1/S) sum_s acq(y_mean + y_std mu~_s(x), y_std sigma~(x); inc_s),   summed in the order s = 0, 1, ...
+//
+// The draw is JOINT: point j is drawn given simulation s's own draws of the points before it.  The old library draws
+// every pending point on its own from the concrete model (:582-585), which ignores that two nearby pending points come
+// out alike; with one pending point the two coincide.  eps[s,j] is a Philox-4x32-10 normal (philox.hpp) keyed by the
+// seed, counter (element lo, element hi, 0, MC_TAG), element s 64 + j with j counted pending-first: simulation s does
+// not depend on S, the draw for point j not on P or q.  mc_small_kernel stands in bt_small_kernel's place and
+// mc_update_kernel in bt_update_kernel's; the point, front, pass and arg-max kernels are shared.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "pairwise.hpp"
+#include "philox.hpp"
 #include "tgp_internal.hpp"
 
 namespace tgp {
@@ -391,6 +410,208 @@ __global__ __launch_bounds__(256) void bt_argmax_kernel(const double *__restrict
     }
 }
 
+// ---- Monte Carlo: S simulations of every conditioned point's outcome ----
+constexpr uint32_t MC_TAG = 0x4D435349u;   // "MCSI": the fourth counter word of the fantasies' normals
+constexpr int MC_SC = 16;                  // simulations whose means a thread holds at a time
+
+// eps (64, 64) POINT-major (eps[j * 64 + s]): the Philox normal of element s 64 + j for s < S, j < J, zero elsewhere;
+// inc[s] = the incumbent
+__global__ __launch_bounds__(256) void mc_init_kernel(double *__restrict__ eps, double *__restrict__ inc, int S, int J,
+                                                      int draw, unsigned long long seed, double incumbent) {
+    const int e = blockIdx.x * 256 + threadIdx.x;   // = j * 64 + s
+    if (e >= BT_MAXP * MC_MAXS) return;
+    const int j = e >> 6, s = e & 63;
+    if (draw) eps[e] = (s < S && j < J) ? philox_normal((unsigned long long)s * 64ull + (unsigned long long)j, 0u, MC_TAG, seed) : 0.0;
+    if (j == 0) inc[s] = incumbent;
+}
+
+// one workgroup: R row j and the pivot test exactly as bt_small_kernel; then per simulation the conditional mean at
+// z_j, the fantasy (a draw of y) and the incumbent
+template <int KIND>
+__global__ __launch_bounds__(256) void mc_small_kernel(const double *__restrict__ Kz, const double *__restrict__ w,
+                                                       const double *__restrict__ alpha, const double *__restrict__ Zs,
+                                                       McSmall s, int j, int N, int Np, int Dp, double constant,
+                                                       double noise, double jitter, double y_mean, double y_std,
+                                                       double sf) {
+    __shared__ double red[256];
+    __shared__ double S[BT_MAXP + 1];
+    __shared__ double Rl[BT_MAXP];
+    const int tid = threadIdx.x;
+    for (int i = 0; i <= j; ++i) {
+        const double *k = Kz + (long)i * Np;
+        double a = 0.0;
+        for (int n = tid; n < N; n += 256) a = fma(k[n], w[n], a);
+        a = bt_block_sum(a, red);
+        if (tid == 0) S[i] = a;
+    }
+    {
+        const double *k = Kz + (long)j * Np;
+        double a = 0.0;
+        for (int n = tid; n < N; n += 256) a = fma(k[n], alpha[n], a);
+        a = bt_block_sum(a, red);
+        if (tid == 0) S[BT_MAXP] = a;   // k*(z_j).alpha
+    }
+    __syncthreads();
+    if (tid < j) {
+        const double *zj = Zs + (long)j * Dp, *zi = Zs + (long)tid * Dp;
+        double d2 = 0.0;
+        for (int d = 0; d < Dp; ++d) {
+            const double df = zj[d] - zi[d];
+            d2 = fma(df, df, d2);
+        }
+        S[tid] = kernel_value<double, KIND>(d2, constant) - S[tid];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double *Rj = s.b.R + (long)j * BT_MAXP;
+        double piv = ((constant + noise) + jitter) - S[j];
+        for (int i = 0; i < j; ++i) {
+            const double *Ri = s.b.R + (long)i * BT_MAXP;
+            double t = S[i];
+            for (int l = 0; l < i; ++l) t -= Rj[l] * Ri[l];
+            t /= Ri[i];
+            Rj[i] = t;
+            Rl[i] = t;
+            piv -= t * t;
+        }
+        if (!(piv > 0.0) || !isfinite(piv)) {
+            if (s.b.flag[0] == 0) s.b.flag[0] = j + 1;
+            piv = NAN;
+        }
+        const double rjj = sqrt(piv);
+        Rj[j] = rjj;
+        Rl[j] = rjj;
+    }
+    __syncthreads();
+    if (tid < s.S) {
+        double m = S[BT_MAXP];
+        for (int i = 0; i < j; ++i) m += Rl[i] * s.eps[i * MC_MAXS + tid];
+        const double yn = m + Rl[j] * s.eps[j * MC_MAXS + tid];
+        const double f = y_std * yn + y_mean;
+        s.fant[j * MC_MAXS + tid] = f;
+        const double inc = s.inc[tid];
+        s.inc[tid] = sf > 0.0 ? (f > inc ? f : inc) : (f < inc ? f : inc);
+    }
+}
+
+struct McUpd {
+    const double *cand, *ls, *zs;     // raw candidates (M, D), length scales, scaled z_j (Dp)
+    const double *part; int njs; long ldpart;
+    double *G; long ldG; int j;       // column j of G at G + j ldG: always stored (the later means read it)
+    McSmall s;
+    const double *mu0;                // the first sweep's means, raw units: never updated
+    double *var; const unsigned char *mask;
+    long M; int D;
+    double constant, y_std;
+    int acq; double sf, param;        // acq == TGP_ACQ_NONE: no selection follows this point
+    double *bval; long long *bidx; unsigned long long *clamp;
+    double *acq_out, *sigma_out;      // nullable: this step's averaged acquisition (taken rows -inf) / sigma after it
+};
+
+// c(x), G[x,j], the variance update and its clamp exactly as bt_update_kernel; then the S means from G[x, 0..j] and
+// eps (LDS), S acquisition values (finalize_kernel's formulas), their mean in the order s = 0, 1, ... and the per-block
+// arg-max partials.  A thread per candidate: G is column-major, so its reads are coalesced; MC_SC means at a time
+// stay in registers (plain f64 FMAs: at S = J = 64 the erf / exp evaluations outweigh the product)
+template <int KIND>
+__global__ __launch_bounds__(BT_BLOCK) void mc_update_kernel(McUpd u) {
+    __shared__ double sv[BT_BLOCK];
+    __shared__ long long si[BT_BLOCK];
+    __shared__ int sclamp;
+    __shared__ __attribute__((aligned(16))) double epsl[BT_MAXP * MC_MAXS];   // [i][s]
+    __shared__ double incl[MC_MAXS];
+    const int tid = threadIdx.x;
+    const int j = u.j, S = u.s.S;
+    if (tid == 0) sclamp = 0;
+    if (u.acq != TGP_ACQ_NONE && u.acq != TGP_ACQ_SIGMA) {
+        for (int e = tid; e < (j + 1) * MC_MAXS; e += BT_BLOCK) epsl[e] = u.s.eps[e];
+        if (tid < MC_MAXS) incl[tid] = u.s.inc[tid];
+    }
+    __syncthreads();
+    const long x = (long)blockIdx.x * BT_BLOCK + tid;
+    double best = -INFINITY;
+    long long bi = 0x7fffffffffffffffLL;
+    if (x < u.M) {
+        double kdot = 0.0;
+        for (int s = 0; s < u.njs; ++s) kdot += u.part[(long)s * u.ldpart + x];
+        double d2 = 0.0;
+        for (int d = 0; d < u.D; ++d) {
+            const double df = u.cand[x * u.D + d] / u.ls[d] - u.zs[d];
+            d2 = fma(df, df, d2);
+        }
+        double cx = kernel_value<double, KIND>(d2, u.constant) - kdot;
+        const double *Rj = u.s.b.R + (long)j * BT_MAXP;
+        for (int i = 0; i < j; ++i) cx -= u.G[(long)i * u.ldG + x] * Rj[i];
+        const double g = cx / Rj[j];
+        u.G[(long)j * u.ldG + x] = g;
+        double var = u.var[x] - g * g;
+        if (var < 0.0) { var = 0.0; atomicAdd(&sclamp, 1); }
+        u.var[x] = var;
+        const double sigma = sqrt(var * (u.y_std * u.y_std));
+        if (u.sigma_out) u.sigma_out[x] = sigma;
+        if (u.acq != TGP_ACQ_NONE) {
+            if (!u.mask[x]) {
+                double a;
+                if (u.acq == TGP_ACQ_SIGMA) {
+                    a = sigma;                 // the same for every simulation: no average to round
+                } else {
+                    const double mu0 = u.mu0[x];
+                    double sum = 0.0;
+                    for (int s0 = 0; s0 < S; s0 += MC_SC) {
+                        double acc[MC_SC];
+#pragma unroll
+                        for (int t = 0; t < MC_SC; ++t) acc[t] = 0.0;
+                        for (int i = 0; i <= j; ++i) {
+                            const double gi = i == j ? g : u.G[(long)i * u.ldG + x];
+                            const double *er = epsl + i * MC_MAXS + s0;
+#pragma unroll
+                            for (int t = 0; t < MC_SC; ++t) acc[t] = fma(gi, er[t], acc[t]);
+                        }
+#pragma unroll
+                        for (int t = 0; t < MC_SC; ++t) {
+                            if (s0 + t < S) {
+                                const double mu = mu0 + u.y_std * acc[t];
+                                double as = 0.0;
+                                if (u.acq == TGP_ACQ_UCB) {
+                                    as = u.sf * mu + u.param * sigma;
+                                } else if (sigma != 0.0) {
+                                    const double diff = u.sf * (mu - incl[s0 + t]) - u.param;
+                                    const double Z = diff / sigma;
+                                    if (u.acq == TGP_ACQ_PI) {
+                                        as = bt_ndtr(Z);
+                                    } else {
+                                        const double pdf = exp(-(Z * Z) / 2.0) / 2.5066282746310002;
+                                        as = diff * bt_ndtr(Z) + sigma * pdf;
+                                    }
+                                }
+                                sum += as;
+                            }
+                        }
+                    }
+                    a = sum / (double)S;
+                }
+                if (!isnan(a)) best = a;
+                bi = x;
+            }
+            if (u.acq_out) u.acq_out[x] = best;
+        }
+    }
+    sv[tid] = best;
+    si[tid] = bi;
+    __syncthreads();
+    for (int o = BT_BLOCK / 2; o > 0; o >>= 1) {
+        if (tid < o) {
+            const double v2 = sv[tid + o];
+            const long long i2 = si[tid + o];
+            if (v2 > sv[tid] || (v2 == sv[tid] && i2 < si[tid])) { sv[tid] = v2; si[tid] = i2; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        if (u.acq != TGP_ACQ_NONE) { u.bval[blockIdx.x] = sv[0]; u.bidx[blockIdx.x] = si[0]; }
+        if (sclamp) atomicAdd(u.clamp, (unsigned long long)sclamp);
+    }
+}
+
 // ---- launchers ----
 #define BT_KIND_DISPATCH(kernel_tmpl, grid, block, ...)                                                          \
     do {                                                                                                         \
@@ -463,6 +684,51 @@ hipError_t launch_bt_step(Context &c, const BtSmall &s, int j, const double *Cs,
     TGP_TRY(hipGetLastError());
     if (acq != TGP_ACQ_NONE) {
         hipLaunchKernelGGL(bt_argmax_kernel, dim3(1), dim3(256), 0, c.stream, bval, bidx, nblk, s, k, mask, (long)c.M);
+        TGP_TRY(hipGetLastError());
+    }
+    return hipSuccess;
+}
+
+// ---- Monte Carlo launchers ----
+hipError_t launch_mc_init(Context &c, const McSmall &s, int J, bool draw, unsigned long long seed, double incumbent) {
+    hipLaunchKernelGGL(mc_init_kernel, dim3(BT_MAXP * MC_MAXS / 256), dim3(256), 0, c.stream, s.eps, s.inc, s.S, J,
+                       draw ? 1 : 0, seed, incumbent);
+    return hipGetLastError();
+}
+
+hipError_t launch_mc_condition(Context &c, const McSmall &s, int j, const double *zraw, double *Kz, double *Zs,
+                               double *hw, double *v, double *w, double sf) {
+    TGP_TRY(launch_query_front(c, zraw, Zs + (long)j * c.Dp, Kz + (long)j * c.Np, hw, v, w));
+    BT_KIND_DISPATCH(mc_small_kernel, dim3(1), dim3(256), Kz, w, c.d_alpha, Zs, s, j, (int)c.N, (int)c.Np, (int)c.Dp,
+                     c.constant, c.noise, c.jitter, c.y_mean, c.y_std, sf);
+    return hipGetLastError();
+}
+
+hipError_t launch_mc_step(Context &c, const McSmall &s, int j, const double *Cs, int64_t ldpart, const double *Zs,
+                          const double *w, double *part, double *G, const double *mu0, double *var,
+                          unsigned char *mask, int acq, double sf, double param, double *bval, long long *bidx,
+                          unsigned long long *clamp, double *acq_out, double *sigma_out, int k) {
+    const int js = bt_pass_splits(c, c.M);
+    const dim3 gp((unsigned)((c.M + BT_CT - 1) / BT_CT), (unsigned)js);
+    BT_KIND_DISPATCH(bt_pass_kernel, gp, dim3(256), Cs, c.d_Xs, w, part, (int)c.M, (int)c.N, (int)c.Np, (int)c.Dp,
+                     c.constant, (long)ldpart);
+    TGP_TRY(hipGetLastError());
+    McUpd u{};
+    u.cand = c.d_cand; u.ls = c.d_ls; u.zs = Zs + (long)j * c.Dp;
+    u.part = part; u.njs = js; u.ldpart = ldpart;
+    u.G = G; u.ldG = (long)c.M; u.j = j;
+    u.s = s;
+    u.mu0 = mu0; u.var = var; u.mask = mask;
+    u.M = (long)c.M; u.D = (int)c.D;
+    u.constant = c.constant; u.y_std = c.y_std;
+    u.acq = acq; u.sf = sf; u.param = param;
+    u.bval = bval; u.bidx = bidx; u.clamp = clamp;
+    u.acq_out = acq_out; u.sigma_out = sigma_out;
+    const long nblk = (long)((c.M + BT_BLOCK - 1) / BT_BLOCK);
+    BT_KIND_DISPATCH(mc_update_kernel, dim3((unsigned)nblk), dim3(BT_BLOCK), u);
+    TGP_TRY(hipGetLastError());
+    if (acq != TGP_ACQ_NONE) {
+        hipLaunchKernelGGL(bt_argmax_kernel, dim3(1), dim3(256), 0, c.stream, bval, bidx, nblk, s.b, k, mask, (long)c.M);
         TGP_TRY(hipGetLastError());
     }
     return hipSuccess;

@@ -1784,6 +1784,151 @@ int tgp_sweep_batch(tgp_handle h, int64_t q, int strategy, double lie, const dou
     return TGP_OK;
 } TGP_CATCH
 
+// The Monte Carlo strategy (include/turbogp.h): tgp_sweep_batch's schedule -- the first sweep, then per conditioned point
+// its front, a one-workgroup small side and one pass with the update and the next arg-max -- with S simulations of
+// every point's outcome carried through the small side and the update (batch_kernels.hip).  One wait.
+int tgp_sweep_batch_mc(tgp_handle h, int64_t q, int64_t S, uint64_t seed, const double *eps_in, const double *Xp, int64_t P,
+                       int acq, double sf, double incumbent, double param, int64_t *idx_out, double *val_out,
+                       double *x_out, double *fantasy_out, double *eps_out, double *acq_out, double *sigma_out,
+                       int64_t *n_clamped) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_sweep_batch_mc");
+    Context &c = h->c;
+    if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_sweep_batch_mc: no fitted model");
+    if (!c.d_cand || c.M < 1) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: no candidates set");
+    if (q < 1 || q > c.M) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: need 1 <= q <= M");
+    if (P < 0 || P + q > BT_MAXP) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: need P >= 0 and P + q <= 64");
+    if (P > 0 && !Xp) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: Xp is NULL with P > 0");
+    if (S < 1 || S > MC_MAXS) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: need 1 <= S <= 64");
+    if (acq < TGP_ACQ_UCB || acq > TGP_ACQ_SIGMA) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: acq must be UCB, PI, EI or SIGMA");
+    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: sf must be +1 or -1");
+    if (!idx_out || !val_out) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: idx_out and val_out are required");
+    const int64_t D = c.D, Dp = c.Dp, Np = c.Np, M = c.M, J = P + q;
+    if (eps_in)
+        for (int64_t i = 0; i < S * J; ++i)
+            if (!std::isfinite(eps_in[i])) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: eps_in must be finite");
+    API_HIP(hipSetDevice(c.device), "hipSetDevice");
+    // ---- the first sweep, as tgp_sweep_batch's (its acquisition vector kept when it is row 0 of acq_out)
+    const bool first_acq = acq_out && P == 0;
+    SweepCall first;
+    first.acq = acq; first.sf = sf; first.incumbent = incumbent; first.param = param;
+    first.may_use_front = c.pre.front;
+    API_HIP(pre_join(c), "hipStreamWaitEvent");
+    int rc;
+    if ((rc = ensure_outputs(c, true, true, first_acq)) != TGP_OK) return rc;
+    constexpr int64_t NE = (int64_t)BT_MAXP * MC_MAXS;
+    // result staging (pinned, so the copies back are not staged): [sweep record (8) | x (q D) | sel_val (64) | eps (J 64) |
+    // fantasies (J 64) | indices, clamp count, flag (66)]
+    const size_t n_pout = (size_t)(8 + q * D + BT_MAXP + 2 * J * MC_MAXS + BT_MAXP + 2);
+    if ((rc = ensure_pinned(c, (size_t)(P * D + NE + 8) * sizeof(double), n_pout * sizeof(double))) != TGP_OK) return rc;
+    first.mu = c.d_mu; first.sigma = c.d_sigma; first.res = c.d_pin_out;
+    if (first_acq) first.acqv = c.d_acq;
+
+    // ---- the call's buffers (tgp_sweep_batch's regions, laid out for this call)
+    const int64_t Mpad = ((M + 63) / 64) * 64;
+    const int64_t nblk = (M + 255) / 256;
+    const int js = bt_pass_splits(c, M);
+    const int64_t n_acq = acq_out ? (first_acq ? q - 1 : q) : 0;   // rows of acq_out the steps write
+    const size_t n_bt = (size_t)(BT_MAXP * D + BT_MAXP * Dp + BT_MAXP * Np + 3 * Np + BT_MAXP * BT_MAXP + BT_MAXP + 2 * NE + MC_MAXS);
+    const size_t n_btm = (size_t)(Mpad * Dp + js * Mpad + 2 * M + nblk + J * M + n_acq * M);
+    const size_t n_bti = (size_t)(BT_MAXP + 2 + nblk) * sizeof(long long) + (size_t)M;
+    if ((rc = grow(c, c.d_bt, c.cap_bt, n_bt * sizeof(double), "hipMalloc batch state")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_btm, c.cap_btm, n_btm * sizeof(double), "hipMalloc batch arrays")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_bti, c.cap_bti, n_bti, "hipMalloc batch indices")) != TGP_OK) return rc;
+    double *Zraw = c.d_bt, *Zs = Zraw + BT_MAXP * D, *Kz = Zs + BT_MAXP * Dp, *hw = Kz + BT_MAXP * Np, *v = hw + Np,
+           *w = v + Np, *Rb = w + Np, *selv = Rb + BT_MAXP * BT_MAXP, *epsd = selv + BT_MAXP, *fant = epsd + NE,
+           *inc = fant + NE;
+    double *Cs = c.d_btm, *part = Cs + Mpad * Dp, *bmu = part + js * Mpad, *bvar = bmu + M, *bval = bvar + M,
+           *G = bval + nblk, *acqd = G + J * M;
+    long long *seli = c.d_bti, *clampw = seli + BT_MAXP, *flagw = clampw + 1, *bidx = flagw + 1;
+    unsigned char *mask = reinterpret_cast<unsigned char *>(bidx + nblk);
+    McSmall s{};
+    s.b = BtSmall{Rb, nullptr, nullptr, nullptr, selv, seli, reinterpret_cast<int *>(flagw)};
+    s.eps = epsd; s.fant = fant; s.inc = inc; s.S = (int)S;
+
+    CallClock clk;
+    if ((rc = run_sweep(c, first, clk)) != TGP_OK) return rc;
+    hipError_t le;
+
+    // ---- the steps
+    double *pin = c.h_pin_in;
+    if (P > 0) {
+        memcpy(pin, Xp, (size_t)(P * D) * sizeof(double));
+        API_HIP(hipMemcpyAsync(Zraw, pin, (size_t)(P * D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D pending");
+    }
+    if (eps_in) {   // (S, J) -> point-major (64, 64), zero elsewhere
+        double *pe = pin + P * D;
+        memset(pe, 0, (size_t)NE * sizeof(double));
+        for (int64_t si = 0; si < S; ++si)
+            for (int64_t j = 0; j < J; ++j) pe[j * MC_MAXS + si] = eps_in[si * J + j];
+        API_HIP(hipMemcpyAsync(epsd, pe, (size_t)NE * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D eps");
+    }
+    API_HIP(hipMemsetAsync(w, 0, (size_t)Np * sizeof(double), c.stream), "memset w");
+    API_HIP(hipMemsetAsync(clampw, 0, 2 * sizeof(long long), c.stream), "memset counters");
+    if ((le = launch_mc_init(c, s, (int)J, eps_in == nullptr, (unsigned long long)seed, incumbent)) != hipSuccess)
+        return hip_fail(c, le, "launch_mc_init");
+    if ((le = launch_bt_prep(c, Cs, Mpad)) != hipSuccess) return hip_fail(c, le, "launch_bt_prep");
+    if ((le = launch_bt_init(c, bmu, bvar, mask)) != hipSuccess) return hip_fail(c, le, "launch_bt_init");
+    for (int64_t j = 0; j < J; ++j) {
+        double *zj = Zraw + j * D;
+        if (j >= P) {   // selection k = j - P: the first sweep's winner, or the previous step's
+            const int64_t k = j - P;
+            le = launch_bt_point(c, (P == 0 && k == 0) ? c.d_pin_out : nullptr, s.b, (int)k, zj, mask);
+            if (le != hipSuccess) return hip_fail(c, le, "launch_bt_point");
+        }
+        if ((le = launch_mc_condition(c, s, (int)j, zj, Kz, Zs, hw, v, w, sf)) != hipSuccess)
+            return hip_fail(c, le, "launch_mc_condition");
+        const bool last = j == J - 1;
+        if (last && !sigma_out) break;
+        const int64_t knext = j + 1 - P;              // the selection this step's update feeds, if any
+        const bool select = !last && knext >= 0 && knext < q;
+        double *arow = (select && acq_out) ? acqd + (knext - (first_acq ? 1 : 0)) * M : nullptr;
+        le = launch_mc_step(c, s, (int)j, Cs, Mpad, Zs, w, part, G, bmu, bvar, mask, select ? acq : TGP_ACQ_NONE, sf,
+                            param, bval, bidx, reinterpret_cast<unsigned long long *>(clampw), arow,
+                            last ? c.d_sigma : nullptr, (int)knext);
+        if (le != hipSuccess) return hip_fail(c, le, "launch_mc_step");
+    }
+    if ((rc = call_stop(c, clk)) != TGP_OK) return rc;
+
+    // ---- one wait: only what was asked for, and of eps / fantasies only the J rows in use (point-major: contiguous)
+    double *h_x = c.h_pin_out + 8, *h_selv = h_x + q * D, *h_eps = h_selv + BT_MAXP, *h_fant = h_eps + J * MC_MAXS;
+    long long *hi = reinterpret_cast<long long *>(h_fant + J * MC_MAXS);
+    const size_t d8 = sizeof(double);
+    if (x_out) API_HIP(hipMemcpyAsync(h_x, Zraw + P * D, (size_t)(q * D) * d8, hipMemcpyDeviceToHost, c.stream), "D2H points");
+    API_HIP(hipMemcpyAsync(h_selv, selv, (size_t)q * d8, hipMemcpyDeviceToHost, c.stream), "D2H values");
+    if (eps_out) API_HIP(hipMemcpyAsync(h_eps, epsd, (size_t)(J * MC_MAXS) * d8, hipMemcpyDeviceToHost, c.stream), "D2H eps");
+    if (fantasy_out) API_HIP(hipMemcpyAsync(h_fant, fant, (size_t)(J * MC_MAXS) * d8, hipMemcpyDeviceToHost, c.stream), "D2H fantasies");
+    API_HIP(hipMemcpyAsync(hi, seli, (size_t)(BT_MAXP + 2) * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H indices");
+    const size_t bytes = (size_t)M * d8;
+    if (first_acq) API_HIP(hipMemcpyAsync(acq_out, c.d_acq, bytes, hipMemcpyDeviceToHost, c.stream), "D2H acq");
+    if (n_acq > 0)
+        API_HIP(hipMemcpyAsync(acq_out + (first_acq ? M : 0), acqd, (size_t)n_acq * bytes, hipMemcpyDeviceToHost, c.stream), "D2H acq");
+    if (sigma_out) API_HIP(hipMemcpyAsync(sigma_out, c.d_sigma, bytes, hipMemcpyDeviceToHost, c.stream), "D2H sigma");
+    if ((rc = call_finish(c, clk, c.last_sweep_ms, "sweep_batch_mc sync")) != TGP_OK) return rc;
+    const int flag = (int)(hi[BT_MAXP + 1] & 0xffffffff);
+    if (flag != 0) {
+        char buf[200];
+        snprintf(buf, sizeof buf, "tgp_sweep_batch_mc: the augmented kernel matrix is not positive definite (%s point %d)",
+                 flag - 1 < P ? "pending" : "selected", flag - 1 < P ? flag - 1 : (int)(flag - 1 - P));
+        return fail(c, TGP_NOT_PD, buf);
+    }
+    for (int64_t k = 0; k < q; ++k) {
+        idx_out[k] = (int64_t)hi[k];
+        val_out[k] = h_selv[k];
+    }
+    if (x_out) memcpy(x_out, h_x, (size_t)(q * D) * d8);
+    if (first_acq)   // row 0 is the first sweep's vector: NaN -> -inf, the convention of the steps' rows
+        for (int64_t x = 0; x < M; ++x)
+            if (std::isnan(acq_out[x])) acq_out[x] = -INFINITY;
+    for (int64_t si = 0; si < S; ++si)
+        for (int64_t j = 0; j < J; ++j) {
+            if (fantasy_out) fantasy_out[si * J + j] = h_fant[j * MC_MAXS + si];
+            if (eps_out) eps_out[si * J + j] = h_eps[j * MC_MAXS + si];
+        }
+    if (n_clamped) *n_clamped = (int64_t)c.h_pin_out[2] + (int64_t)hi[BT_MAXP];
+    return TGP_OK;
+} TGP_CATCH
+
 // ---- Thompson sampling (include/turbogp.h, ts_kernels.hip) ----
 // d_ts: [omega (F Dp) | b (F) | W (Spad F) | V (Spad Np) | eps (S N) | priorX (N S) | R (S Np) | Z (S Np)], every
 // part starting on a 32-byte boundary (V is read in 32-byte vectors)

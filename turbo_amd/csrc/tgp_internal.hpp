@@ -326,7 +326,23 @@ hipError_t launch_bt_step(Context &c, const BtSmall &s, int j, const double *Cs,
                           const double *w, double *part, double *G, int store, double *mu, double *var,
                           unsigned char *mask, int acq, double sf, double param, double *bval, long long *bidx,
                           unsigned long long *clamp, double *mu_out, double *sigma_out, int k);
-
+// tgp_sweep_batch_mc (batch_kernels.hip): the Monte Carlo strategy, S <= 64 simulations of every conditioned point
+constexpr int MC_MAXS = 64;
+struct McSmall {
+    BtSmall b;                     // R, sel_val, sel_idx, flag as tgp_sweep_batch (e, fant, inc unused: null)
+    double *eps;                   // (64, 64) POINT-major: eps[j * 64 + s], zero from S / J on
+    double *fant;                  // (64, 64) point-major fantasies, raw units
+    double *inc;                   // (64) per simulation: the incumbent after its fantasies so far
+    int S;
+};
+// eps from the Philox stream (draw) or left as the caller copied it; inc[s] = incumbent
+hipError_t launch_mc_init(Context &c, const McSmall &s, int J, bool draw, unsigned long long seed, double incumbent);
+hipError_t launch_mc_condition(Context &c, const McSmall &s, int j, const double *zraw, double *Kz, double *Zs,
+                               double *hw, double *v, double *w, double sf);
+hipError_t launch_mc_step(Context &c, const McSmall &s, int j, const double *Cs, int64_t ldpart, const double *Zs,
+                          const double *w, double *part, double *G, const double *mu0, double *var,
+                          unsigned char *mask, int acq, double sf, double param, double *bval, long long *bidx,
+                          unsigned long long *clamp, double *acq_out, double *sigma_out, int k);
 
 // Thompson sampling (ts_kernels.hip): S <= 64 sample paths of the fitted model, F random Fourier features
 struct TsDraw {

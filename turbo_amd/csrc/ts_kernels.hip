@@ -47,19 +47,13 @@ namespace tgp {
 constexpr uint32_t TS_TAG = 0x54534D50u;   // "TSMP": the fourth counter word of every draw
 constexpr double TS_TWO_PI = 6.283185307179586;
 
-__device__ __forceinline__ double ts_u53(uint32_t a, uint32_t b) {
-    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) * (1.0 / 9007199254740992.0);
-}
+// (the uniform, the counter layout and the Box-Muller branch: philox.hpp)
+__device__ __forceinline__ double ts_u53(uint32_t a, uint32_t b) { return philox_u53(a, b); }
 __device__ __forceinline__ void ts_words(unsigned long long e, uint32_t stream, unsigned long long seed, uint32_t r[4]) {
-    philox4x32_10((uint32_t)e, (uint32_t)(e >> 32), stream, TS_TAG, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    philox_words(e, stream, TS_TAG, seed, r);
 }
 __device__ __forceinline__ double ts_normal(unsigned long long e, uint32_t stream, unsigned long long seed) {
-    uint32_t r[4];
-    ts_words(e, stream, seed, r);
-    const double u1 = ts_u53(r[0], r[1]), u2 = ts_u53(r[2], r[3]);
-    const double t = -2.0 * log(1.0 - u1);
-    const double a = TS_TWO_PI * u2;
-    return sqrt(t) * cos(a);
+    return philox_normal(e, stream, TS_TAG, seed);
 }
 
 // omega (F, Dp; columns >= D zero), b (F), W (Spad, F; rows >= S zero), eps (S, N)
