@@ -57,7 +57,10 @@ enum tgp_kernel { TGP_RBF = 0, TGP_MATERN12 = 1, TGP_MATERN32 = 2, TGP_MATERN52 
 
 /* turbo/modules/acquisition_functions.py: UCB :147-158 (TGP_ACQ_SIGMA = its beta=inf branch),
  * PI :225-247, EI :336-358.  TGP_ACQ_NONE = predict only. */
-enum tgp_acq { TGP_ACQ_NONE = 0, TGP_ACQ_UCB = 1, TGP_ACQ_PI = 2, TGP_ACQ_EI = 3, TGP_ACQ_SIGMA = 4 };
+/* TGP_ACQ_MES: max-value entropy search (Wang & Jegelka 2017), which the reference does not have: the average over the
+ * handle's S maxima (tgp_mes_set_maxima / tgp_mes_draw, below) of a closed form of (mu, sigma); `incumbent` and `param`
+ * are ignored.  Accepted by tgp_sweep, tgp_evaluate, tgp_sweep_topk, tgp_acq_grad and tgp_acq_lbfgsb. */
+enum tgp_acq { TGP_ACQ_NONE = 0, TGP_ACQ_UCB = 1, TGP_ACQ_PI = 2, TGP_ACQ_EI = 3, TGP_ACQ_SIGMA = 4, TGP_ACQ_MES = 5 };
 
 /* buffers readable through tgp_debug_read (parity tests only) */
 enum tgp_buffer { TGP_BUF_K = 0, TGP_BUF_L = 1, TGP_BUF_LINV = 2, TGP_BUF_ALPHA = 3 };
@@ -71,8 +74,8 @@ enum tgp_buffer { TGP_BUF_K = 0, TGP_BUF_L = 1, TGP_BUF_LINV = 2, TGP_BUF_ALPHA 
  * whatever process loaded the recorder (turbo/recorder.py:157-163, turbo/plotting/trials.py:192-195,
  * :371, :448, :574-577), which need not own an MI355X.  A host handle serves tgp_fit, tgp_fit_append
  * (as a full fit), tgp_export_state / tgp_import_state (the same blob), tgp_debug_read (L, alpha),
- * tgp_set_candidates, tgp_read_candidates, tgp_get_candidate, tgp_sweep, tgp_evaluate, tgp_predict and
- * the timing queries, always in float64 (csrc/host_backend.cpp: plain C++, its own arithmetic -- not
+ * tgp_set_candidates, tgp_read_candidates, tgp_get_candidate, tgp_sweep, tgp_evaluate, tgp_predict,
+ * tgp_mes_set_maxima and the timing queries, always in float64 (csrc/host_backend.cpp: plain C++, its own arithmetic -- not
  * the HIP kernels, not the test oracle); every other entry returns TGP_BAD_ARG on it. */
 #define TGP_DEVICE_HOST (-1)
 int tgp_create(int device, int dtype, tgp_handle *out);
@@ -265,7 +268,7 @@ int tgp_acq_grad(tgp_handle h, const double *Xq, int64_t m, int acq, double sf, 
  * the jitter and y_mean / y_std of the real observations held (the fantasy enters as (y - y_mean) / y_std, noise and
  * jitter on the augmented diagonal, no noise in the cross-kernel).  For EI / PI the incumbent after each fantasy is
  * the best of (incumbent, fantasies so far) in the direction of sf (old_library/bayesian_optimiser.py:509); UCB and
- * TGP_ACQ_SIGMA do not use it; TGP_ACQ_NONE is TGP_BAD_ARG.  Each selection is the arg-max over the rows not yet
+ * TGP_ACQ_SIGMA do not use it; TGP_ACQ_NONE and TGP_ACQ_MES are TGP_BAD_ARG.  Each selection is the arg-max over the rows not yet
  * selected in this call (lowest index on ties, NaN never wins); with q = 1 and P = 0 it is tgp_sweep's best_idx /
  * best_val bit for bit.  The fit and the batch are unchanged by the call.
  *   q          1 <= q <= M, P + q <= 64 (else TGP_BAD_ARG)
@@ -309,6 +312,7 @@ int tgp_sweep_batch(tgp_handle h, int64_t q, int strategy, double lie, const dou
  *              (f32 on an f32 handle; every other row is f64);  sigma_out (M) after all P + q points (costs one more
  *              pass).  All nullable
  *   n_clamped  (nullable) variances clamped at 0, summed over the sweep and every step, once per (candidate, point)
+ * TGP_ACQ_MES is TGP_BAD_ARG here too.
  * TGP_NOT_PD as tgp_sweep_batch (the pivot does not depend on the simulation).  f64 whatever the handle's dtype.  The
  * fit, the candidates, the winner record, a Thompson draw and later sweeps are untouched.  GPU only: TGP_BAD_ARG on host
  * handles. */
@@ -344,6 +348,27 @@ int tgp_ts_draw(tgp_handle h, uint64_t seed, int64_t S, int64_t F);
 int tgp_ts_sweep(tgp_handle h, double sf, int distinct, int64_t *idx_out, double *val_out, double *x_out, double *f_out);
 int tgp_ts_eval(tgp_handle h, const double *Xq, int64_t m, double *f_out, double *grad_out);
 int tgp_ts_read(tgp_handle h, double *omega, double *b, double *W, double *eps);
+
+/* Max-value entropy search (TGP_ACQ_MES).  With y*_s, s = 0 .. S-1, samples of the optimum's RAW value (maxima for
+ * sf = +1, minima for sf = -1) and mu, sigma tgp_sweep's raw posterior mean and deviation at a candidate:
+ *   sigma_f^2 = max(sigma^2 - noise y_std^2, 0)     the latent deviation: sigma includes the WhiteKernel noise, the y*
+ *                                                   are maxima of the LATENT function (the Thompson section above)
+ *   gamma_s   = sf (y*_s - mu) / sigma_f
+ *   h(gamma)  = gamma phi(gamma) / (2 Phi(gamma)) - log Phi(gamma)
+ *   a         = (1/S) sum_s h(gamma_s), summed in the order s = 0, 1, ...;  a = 0 where sigma_f == 0
+ * always in float64, through the scaled complementary error function: finite for every finite input.
+ *   tgp_mes_set_maxima  stores 1 <= S <= 64 finite raw values in the handle (host handles too).  Like a Thompson draw
+ *                       they belong to ONE fit: any later fit, append, factor import or state import drops them, and
+ *                       TGP_ACQ_MES without maxima is TGP_BAD_ARG.
+ *   tgp_mes_draw        GPU only: tgp_ts_draw(seed, S, F), then the non-distinct tgp_ts_sweep(sf) over the resident
+ *                       candidates; each sampled maximum is moved to `incumbent` where the incumbent is better in the
+ *                       direction of sf (a NaN incumbent skips that), and the result becomes the handle's maxima on
+ *                       the device.  ystar_out (S) is nullable.  The Thompson draw it made STAYS in the handle,
+ *                       replacing an earlier one (tgp_ts_sweep / tgp_ts_eval / tgp_ts_read then see this draw).
+ * An arg-max-only TGP_ACQ_MES sweep always takes the unpruned schedule (tgp_last_timings slot 12 stays -1): the pruned
+ * sweep's bounds are proved for EI / PI / UCB only.  The winner record is packed as for the others. */
+int tgp_mes_set_maxima(tgp_handle h, const double *ystar, int64_t S);
+int tgp_mes_draw(tgp_handle h, uint64_t seed, int64_t S, int64_t F, double sf, double incumbent, double *ystar_out);
 
 /* The sweep of tgp_sweep, returning the k <= 64 BEST candidates instead of the single best:
  * vals[0..k) descending, idxs[0..k) their indices (lowest index first among equal values, NaN
@@ -404,7 +429,7 @@ int tgp_fit_optimise(tgp_handle h, const double *X, int64_t N, int64_t D, const 
  * tgp_acq_grad) and one optimiser step for all restarts in lock-step, all resident on the GPU.
  * Replaces the loop of scipy.optimize.minimize(method='L-BFGS-B') runs over finite-difference
  * gradients at turbo/modules/auxiliary_optimisers.py:80-99.
- *   x_out (R, D), val_out (R): refined points and their acquisition values
+ *   x_out (R, D), val_out (R): refined points and their acquisition values (TGP_ACQ_MES: TGP_BAD_ARG, use tgp_acq_lbfgsb)
  *   status_out (R, nullable): 1 converged, 2 no progress from the start point, 0 stopped by max_iter
  *   iterations (nullable): value + gradient evaluations made (by the slowest restart) */
 int tgp_acq_refine(tgp_handle h, const double *X0, int64_t R, const double *lo, const double *hi,

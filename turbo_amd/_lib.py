@@ -30,7 +30,7 @@ OK, NOT_PD, BAD_ARG, HIP_ERROR, NOT_FITTED, NO_MEMORY, NO_DEVICE = 0, 1, 2, 3, 4
 DEVICE_HOST = -1     # tgp_create(TGP_DEVICE_HOST): the reload path without a GPU (include/turbogp.h)
 F64, F32, F32X3, F32H2 = 0, 1, 2, 3
 KERNELS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3}
-ACQ_NONE, ACQ_UCB, ACQ_PI, ACQ_EI, ACQ_SIGMA = 0, 1, 2, 3, 4
+ACQ_NONE, ACQ_UCB, ACQ_PI, ACQ_EI, ACQ_SIGMA, ACQ_MES = 0, 1, 2, 3, 4, 5
 BUF_K, BUF_L, BUF_LINV, BUF_ALPHA = 0, 1, 2, 3
 BATCH_KB, BATCH_CL = 0, 1    # tgp_sweep_batch strategies: Kriging Believer, Constant Liar
 
@@ -41,7 +41,7 @@ SYMBOLS = (
     "tgp_fit_append", "tgp_export_state", "tgp_import_state", "tgp_export_factor_dev", "tgp_import_factor_dev", "tgp_debug_read",
     "tgp_set_candidates", "tgp_set_candidates_dev", "tgp_gen_candidates", "tgp_gen_candidates_lhs", "tgp_lhs_design",
     "tgp_read_candidates", "tgp_get_candidate",
-    "tgp_sweep", "tgp_sweep_batch", "tgp_sweep_batch_mc", "tgp_ts_draw", "tgp_ts_sweep", "tgp_ts_eval", "tgp_ts_read", "tgp_sweep_topk", "tgp_set_winner_out", "tgp_winner_wait", "tgp_acq_grad", "tgp_acq_refine", "tgp_acq_lbfgsb",
+    "tgp_sweep", "tgp_sweep_batch", "tgp_sweep_batch_mc", "tgp_ts_draw", "tgp_ts_sweep", "tgp_ts_eval", "tgp_ts_read", "tgp_mes_set_maxima", "tgp_mes_draw", "tgp_sweep_topk", "tgp_set_winner_out", "tgp_winner_wait", "tgp_acq_grad", "tgp_acq_refine", "tgp_acq_lbfgsb",
     "tgp_evaluate", "tgp_predict_batch", "tgp_predict", "tgp_profile_enable", "tgp_profile_read", "tgp_profile_reset",
     "tgp_sweep_geometry", "tgp_last_timings",
     "tgp_multi_create", "tgp_multi_destroy", "tgp_multi_last_error", "tgp_multi_size", "tgp_multi_handle",
@@ -142,6 +142,8 @@ def _argtypes():
         "tgp_ts_sweep": [_vp, c.c_double, c.c_int, _i64p, _dp, _dp, _dp],
         "tgp_ts_eval": [_vp, _dp, c.c_int64, _dp, _dp],
         "tgp_ts_read": [_vp, _dp, _dp, _dp, _dp],
+        "tgp_mes_set_maxima": [_vp, _dp, c.c_int64],
+        "tgp_mes_draw": [_vp, c.c_uint64, c.c_int64, c.c_int64, c.c_double, c.c_double, _dp],
         "tgp_acq_refine": [_vp, _dp, c.c_int64, _dp, _dp, c.c_int, c.c_double, c.c_double, c.c_double,
                            c.c_int64, _dp, _dp, _i64p, _i64p],
         "tgp_acq_lbfgsb": [_vp, _dp, c.c_int64, _dp, _dp, c.c_int, c.c_double, c.c_double, c.c_double,
@@ -351,6 +353,7 @@ class NativeGP:
     ``device=DEVICE_HOST`` makes a host context instead (``self.host``): fit / predict / acquisition of
     a reloaded model without a GPU, nothing else."""
     ts_S = ts_F = 0    # shape of the last Thompson draw (ts_draw)
+    fit_gen = 0        # counts the calls that left another fit in the handle (what a draw or MES maxima belong to)
 
     def __init__(self, device=0, dtype="f64"):
         self._h = None
@@ -467,6 +470,7 @@ class NativeGP:
             self.appended = bool(flag.value)
         else:
             self._check(self.lib.tgp_fit(*args))
+        self.fit_gen += 1
         self.N, self.D = X.shape
         return lml.value, ym.value, ys.value
 
@@ -478,6 +482,7 @@ class NativeGP:
         ls = _f64c(np.atleast_1d(length_scale))
         lml, ym, ys = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
         grad = np.zeros(2 + ls.shape[0])
+        self.fit_gen += 1
         self._check(self.lib.tgp_fit_grad(
             self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(y), KERNELS[kind], float(constant),
             _ptr(ls), ls.shape[0], float(noise), float(jitter), 1 if normalize_y else 0,
@@ -514,6 +519,7 @@ class NativeGP:
         st = np.empty(S, dtype=np.int64)
         ev = ctypes.c_int64(0)
         entry = self.lib.tgp_fit_lbfgsb if lbfgsb else self.lib.tgp_fit_optimise
+        self.fit_gen += 1
         self._check(entry(
             self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(y), KERNELS[kind], _ptr(theta0), S, int(n_ls),
             _ptr(lo), _ptr(hi), float(jitter), 1 if normalize_y else 0, int(max_iter), _ptr(theta), _ptr(f),
@@ -533,6 +539,7 @@ class NativeGP:
         blob = bytes(blob)
         lml = ctypes.c_double(0.0)
         buf = ctypes.create_string_buffer(blob, len(blob))
+        self.fit_gen += 1
         self._check(self.lib.tgp_import_state(self._h, ctypes.cast(buf, _vp), len(blob), ctypes.byref(lml)))
         n, d = np.frombuffer(blob, dtype=np.int64, count=2, offset=8)
         self.N, self.D = int(n), int(d)
@@ -549,6 +556,7 @@ class NativeGP:
         """``tgp_import_factor_dev``: receive rows [row0, row0 + rows) of a factor (all of it by default); rows arrive in
         order, the handle is fitted when the last one is in.  Returns True once the factor is complete."""
         rows = int(factor.Np - row0) if rows is None else int(rows)
+        self.fit_gen += 1
         self._check(self.lib.tgp_import_factor_dev(self._h, ctypes.byref(factor), int(row0), rows))
         self.N, self.D = int(factor.N), int(factor.D)
         return row0 + rows == factor.Np
@@ -756,6 +764,22 @@ class NativeGP:
         om, b, W, eps = np.empty((F, self.D)), np.empty(F), np.empty((S, F)), np.empty((S, self.N))
         self._check(self.lib.tgp_ts_read(self._h, _ptr(om), _ptr(b), _ptr(W), _ptr(eps)))
         return dict(omega=om, b=b, W=W, eps=eps)
+
+    def mes_set_maxima(self, ystar):
+        """``tgp_mes_set_maxima``: the 1 <= S <= 64 finite raw values of the optimum that ``ACQ_MES`` averages over; they
+        belong to the resident fit (any later fit, append or import drops them).  Works on host handles too."""
+        ys = _f64c(np.asarray(ystar, dtype=np.float64).reshape(-1))
+        self._check(self.lib.tgp_mes_set_maxima(self._h, _ptr(ys), ys.shape[0]))
+
+    def mes_draw(self, seed, S=8, F=2048, sf=1.0, incumbent=float("nan")):
+        """``tgp_mes_draw``: S maxima of posterior sample paths over the resident candidates (a Thompson draw of F
+        features and its non-distinct sweep), none worse than ``incumbent`` (NaN: no such step), stored as the handle's
+        maxima on the device; returns them (S,).  The Thompson draw stays in the handle."""
+        out = np.empty(max(int(S), 1))
+        self._check(self.lib.tgp_mes_draw(self._h, int(seed) % (1 << 64), int(S), int(F), float(sf), float(incumbent),
+                                          _ptr(out)))
+        self.ts_S, self.ts_F = int(S), int(F)
+        return out[:int(S)]
 
     def sweep_topk(self, k, acq, sf=1.0, incumbent=0.0, param=0.0):
         """the k best resident candidates: (indices (k,), values (k,)), best first"""

@@ -550,3 +550,152 @@ class TS(AcquisitionFunction):
 
         def winner_record(self, global_offset):
             self._refuse('the sharded multi-rank sweep')
+
+
+class MES(AcquisitionFunction):
+    """Max-value entropy search (Wang & Jegelka 2017): the expected reduction of the entropy of the posterior at x from
+    knowing the optimum's VALUE y*, averaged over ``n_samples`` <= 64 samples of y* (``TGP_ACQ_MES``, csrc/mes_math.hpp):
+
+        sigma_f^2 = max(sigma^2 - noise y_std^2, 0),   gamma_s = sf (y*_s - mu) / sigma_f
+        a(x) = (1/S) sum_s [ gamma_s phi(gamma_s) / (2 Phi(gamma_s)) - log Phi(gamma_s) ],   0 where sigma_f == 0
+
+    The y*_s are the maxima (minima for 'min') of ``n_samples`` posterior sample paths over the batch the instance is
+    FIRST asked to maximise or evaluate -- a Thompson draw of ``n_features`` random Fourier features and its sweep
+    (``tgp_mes_draw``) -- none worse than the best observed y; they then stay with the instance (and travel with its
+    pickle), whatever it is asked afterwards.  Seeds as ``TS``: trial ``trial_num`` draws with
+    ``(seed + trial_num * 0x9E3779B97F4A7C15) mod 2**64``, ``seed=None`` takes one ``np.random.randint(0, 2**63)`` per
+    trial.  Native models only: the latent deviation needs the model's noise level and the maxima its sample paths, so
+    ``construct_function`` raises ``ValueError`` for a foreign model.  ``maximise_batch`` and ``refine`` are refused
+    (no MES inside the batch strategies or the one-launch optimiser); an arg-max-only MES sweep is never pruned."""
+
+    def __init__(self, n_samples=8, seed=None, n_features=2048):
+        n_samples, n_features = int(n_samples), int(n_features)
+        if n_samples < 1 or n_samples > 64:
+            raise ValueError('n_samples must be in [1, 64]')
+        if n_features < 64 or n_features > 16384 or n_features % 64 != 0:
+            raise ValueError('n_features must be a multiple of 64 in [64, 16384]')
+        self.n_samples = n_samples
+        self.seed = seed
+        self.n_features = n_features
+
+    def get_type(self):
+        return 'optimism'
+
+    def construct_function(self, trial_num, model, desired_extremum):
+        if not _is_native(model):
+            raise ValueError('MES serves native models only: it needs a model built by HipGPSurrogate (got {!r}) for the '
+                             'noise level and the sample paths its maxima come from'.format(type(model)))
+        base = int(np.random.randint(0, 2**63)) if self.seed is None else int(self.seed)
+        seed = (base + int(trial_num) * TS.GOLDEN) % (1 << 64)
+        acq_info = {'seed': seed, 'n_samples': self.n_samples, 'n_features': self.n_features}
+        return MES.FunctionInstance(model, desired_extremum, seed, self.n_samples, self.n_features), acq_info
+
+    class FunctionInstance(AcquisitionFunction.FunctionInstance):
+        """the S-sample average of h(gamma_s); ``maxima`` (S,) once drawn or given"""
+
+        def __init__(self, model, desired_extremum, seed, n_samples, n_features, maxima=None):
+            super().__init__(model, desired_extremum)
+            self.seed = int(seed)
+            self.n_samples = int(n_samples)
+            self.n_features = int(n_features)
+            self.maxima = None if maxima is None else np.array(maxima, dtype=np.float64).reshape(-1)
+            self._token = object()
+
+        def get_name(self):
+            return 'MES'
+
+        def _native_args(self):
+            return _lib.ACQ_MES, 0.0, 0.0
+
+        def _as_points(self, X):
+            X = np.asarray(X, dtype=np.float64)
+            if X.ndim == 1 and X.size > 0:
+                X = X.reshape(1, -1)
+            return X
+
+        def _prepare(self, X=None):
+            """the model's context with THIS instance's maxima in it.  First use: they are drawn over X (None: the batch
+            already resident).  Later: re-sent only when the handle holds another fit or another instance's maxima."""
+            ctx = self.model._ensure_resident()
+            key = (self._token, getattr(ctx, 'fit_gen', 0))
+            if self.maxima is None:
+                if getattr(ctx, 'host', False):
+                    raise ValueError('MES: the maxima are drawn on the GPU; this instance has none yet and the model is '
+                                     'served by the host backend')
+                if X is not None:
+                    ctx.set_candidates(X)
+                y = np.asarray(self.model.y, dtype=np.float64)
+                best = float(y.max() if self.scale_factor > 0 else y.min())
+                ctx._mes_owner = None
+                self.maxima = ctx.mes_draw(self.seed, self.n_samples, self.n_features, self.scale_factor, best).copy()
+                ctx._mes_owner = key
+            elif getattr(ctx, '_mes_owner', None) != key:
+                ctx._mes_owner = None
+                ctx.mes_set_maxima(self.maxima)
+                ctx._mes_owner = key
+            return ctx
+
+        def __call__(self, X):
+            X = self._as_points(X)
+            if X.shape[0] > 0:
+                self._prepare(X)
+            return super().__call__(X)
+
+        def maximise(self, X):
+            X = self._as_points(X)
+            self._prepare(X)
+            return super().maximise(X)
+
+        def maximise_topk(self, X, k):
+            X = self._as_points(X)
+            self._prepare(X)
+            return super().maximise_topk(X, k)
+
+        def value_and_grad(self, X):
+            X = self._as_points(X)
+            self._prepare(X)
+            return super().value_and_grad(X)
+
+        def lbfgsb(self, starting_points, bounds, max_iter=15000):
+            self._prepare(self._as_points(starting_points))
+            return super().lbfgsb(starting_points, bounds, max_iter)
+
+        def maximise_generated(self, num_points, low, high, seed, first_candidate=0, lhs_total=None, prefetch_seed=None):
+            if self.maxima is None:
+                # the first use: the batch has to be resident before the maxima can be drawn over it (the base method
+                # then finds it there, by its key, and does not draw it again)
+                ctx = self.model._ensure_resident()
+                if lhs_total is not None:
+                    ctx.gen_candidates_lhs(seed, first_candidate, num_points, lhs_total, low, high)
+                else:
+                    ctx.gen_candidates(seed, first_candidate, num_points, low, high)
+            self._prepare(None)
+            return super().maximise_generated(num_points, low, high, seed, first_candidate, lhs_total, prefetch_seed)
+
+        def maximise_host_stream(self, num_points, low, high, topk=0, first=0, count=None):
+            ctx = self.model._ensure_resident()
+            if not hasattr(ctx, 'set_candidates_numpy_stream') or not ctx.set_candidates_numpy_stream(num_points, low, high, first=first, count=count):
+                return None
+            self._prepare(None)
+            acq, incumbent, param = self._native_args()
+            if topk > 0:
+                idx, vals = ctx.sweep_topk(min(int(topk), 64), acq, self.scale_factor, incumbent, param)
+                keep = idx >= 0
+                top = (idx[keep], vals[keep])
+                if len(top[0]) > 0:
+                    return ctx, int(top[0][0]), float(top[1][0]), top
+                return ctx, 0, -np.inf, top
+            res = ctx.sweep(acq, self.scale_factor, incumbent, param)
+            self.last_sweep_ms = res.get('sweep_ms')
+            return ctx, res['best_idx'], res['best_val'], None
+
+        def _refuse(self, what):
+            raise NotImplementedError('MES: {} is not available for max-value entropy search (use CandidateSweep with '
+                                      'the default lockstep=True gradient stage)'.format(what))
+
+        def maximise_batch(self, X, q, strategy='kriging_believer', lie='min', pending=None, want_posterior=False,
+                           n_sim=16, seed=None):
+            self._refuse('batch selection (tgp_sweep_batch / tgp_sweep_batch_mc)')
+
+        def refine(self, starting_points, bounds, max_iter=200):
+            self._refuse('the on-device optimiser (on_device=True, tgp_acq_refine)')

@@ -100,6 +100,11 @@ int tgp_get_candidate(tgp_handle h, int64_t idx, double *out_row) {
     HOST_TRY(h->g.read_candidates(idx, 1, out_row))
 }
 
+int tgp_mes_set_maxima(tgp_handle h, const double *ystar, int64_t S) {
+    if (!h) return TGP_BAD_ARG;
+    HOST_TRY(h->g.mes_set_maxima(ystar, S))
+}
+
 int tgp_sweep(tgp_handle h, int acq, double sf, double incumbent, double param, double *mu, double *sigma,
               double *acq_out, double *best_val, int64_t *best_idx, int64_t *n_clamped) {
     if (!h) return TGP_BAD_ARG;

@@ -99,6 +99,31 @@ inline double ndtr(double a) {
     return x > 0 ? 1.0 - y : y;
 }
 
+// exp(z^2) erfc(z) for z >= 0 (the standard library has none).  Below 3 the product itself (exp's argument is exact to
+// ~z^2 ulp); from 3 on Laplace's continued fraction  1 / (sqrt(pi) (z + (1/2) / (z + 1 / (z + (3/2) / (z + ...))))),
+// evaluated backwards from 50 terms: its error falls like exp(-2 z sqrt(2 n)), below 1e-26 there.
+inline double erfcx_pos(double z) {
+    if (z < 3.0) return exp(z * z) * erfc(z);
+    double k = z;
+    for (int n = 50; n >= 1; --n) k = z + (0.5 * n) / k;
+    return 0.56418958354775629 / k;
+}
+
+// max-value entropy search, the formulas and branches of the HIP kernels (mes_math.hpp):
+// h(g) = g phi(g) / (2 Phi(g)) - log Phi(g), finite for every finite g
+inline double mes_h(double g) {
+    if (g < -50.0) {
+        const double t = 1.0 / (g * g);
+        return log(-g) + 0.41893853320467274 + t * (2.0 + t * (-7.5 + t * (148.0 / 3.0)));
+    }
+    const double z = fabs(g) * 0.70710678118654752440;
+    const double e = erfcx_pos(z);
+    if (g <= 0.0) return 0.5 * g * (0.79788456080286536 / e) - (log(0.5 * e) - z * z);
+    const double ez = exp(-z * z);
+    const double q = 0.5 * e * ez;
+    return 0.5 * g * (0.3989422804014327 * ez / (1.0 - q)) - log1p(-q);
+}
+
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -111,6 +136,7 @@ int HostGP::fit(const double *Xin, int64_t n, int64_t d, const double *yin, int 
                 const double *lsin, int64_t n_ls, double nz, double jit, int norm,
                 double *lml_out, double *ym_out, double *ys_out) {
     fitted = false;
+    mes.clear();   // the maxima of max-value entropy search belong to one fit
     if (!Xin || !yin || !lsin) { err = "tgp_fit: X, y and ls must not be NULL"; return TGP_BAD_ARG; }
     if (n < 1 || d < 1) { err = "tgp_fit: need N >= 1 and D >= 1"; return TGP_BAD_ARG; }
     if (n > 65536 || d > 4096) { err = "tgp_fit: N <= 65536 and D <= 4096 supported"; return TGP_BAD_ARG; }
@@ -285,11 +311,21 @@ int HostGP::read_candidates(int64_t first, int64_t count, double *out) {
     return TGP_OK;
 }
 
+int HostGP::mes_set_maxima(const double *ystar, int64_t S) {
+    if (!fitted) { err = "tgp_mes_set_maxima: no fitted model (the maxima belong to one fit)"; return TGP_NOT_FITTED; }
+    bool ok = ystar && S >= 1 && S <= 64;
+    for (int64_t s = 0; ok && s < S; ++s) ok = isfinite(ystar[s]);
+    if (!ok) { err = "tgp_mes_set_maxima: need 1 <= S <= 64 finite values"; return TGP_BAD_ARG; }
+    mes.assign(ystar, ystar + S);
+    return TGP_OK;
+}
+
 int HostGP::sweep(int acq, double sf, double incumbent, double param, double *mu, double *sigma,
                   double *acq_out, double *best_val, int64_t *best_idx, int64_t *n_clamped) {
     if (!fitted) { err = "tgp_sweep: no fitted model"; return TGP_NOT_FITTED; }
     if (M < 1) { err = "tgp_sweep: no candidates set"; return TGP_BAD_ARG; }
-    if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_SIGMA) { err = "tgp_sweep: unknown acquisition"; return TGP_BAD_ARG; }
+    if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_MES) { err = "tgp_sweep: unknown acquisition"; return TGP_BAD_ARG; }
+    if (acq == TGP_ACQ_MES && mes.empty()) { err = "tgp_sweep: TGP_ACQ_MES needs maxima for the resident fit (tgp_mes_set_maxima after the last fit)"; return TGP_BAD_ARG; }
     if (sf != 1.0 && sf != -1.0) { err = "tgp_sweep: sf must be +1 or -1"; return TGP_BAD_ARG; }
     const double t0 = now_ms();
     const int64_t n = N, d = D, m = M;
@@ -301,6 +337,9 @@ int HostGP::sweep(int acq, double sf, double incumbent, double param, double *mu
     const double kss = constant + noise;   // kernel_.diag(X*): the white noise is in the predictive variance
     const double c = constant, ym = y_mean, ys = y_std;
     const int kern = kernel;
+    const double *ystar = mes.data();
+    const int64_t nstar = (int64_t)mes.size();
+    const double noise_var = noise * (y_std * y_std);   // what sigma^2 holds beyond the latent variance
     double *vb = vbest.data();
     int64_t *ib = ibest.data(), *nc = nclamp.data();
     parallel_for(ntiles, nt, [=](int64_t tb, int64_t te) {
@@ -356,6 +395,14 @@ int HostGP::sweep(int acq, double sf, double incumbent, double param, double *mu
                     const double Z = diff / sg;
                     if (acq == TGP_ACQ_PI) a = ndtr(Z);
                     else a = diff * ndtr(Z) + sg * (exp(-(Z * Z) / 2.0) / 2.5066282746310002);
+                } else if (acq == TGP_ACQ_MES) {
+                    const double v = sg * sg - noise_var;
+                    if (v > 0.0) {
+                        const double sl = sqrt(v);
+                        double sum = 0.0;
+                        for (int64_t s = 0; s < nstar; ++s) sum += mes_h(sf * (ystar[s] - muq) / sl);
+                        a = sum / (double)nstar;
+                    }
                 }
                 const int64_t g = j0 + q;
                 if (mu) mu[g] = muq;

@@ -15,7 +15,9 @@
 //   alpha, LML           _gpr.py:360-364, :584-613 (two triangular substitutions)
 //   predict              _gpr.py:443-494: K*, mu = s_y K* alpha + y_mean, v = L^-1 K*^T by forward
 //                        substitution on tiles of 16 candidates, var = (c + noise) - |v|^2, clamp
-//   acquisition          turbo/modules/acquisition_functions.py UCB :147-158, PI :225-247, EI :336-358
+//   acquisition          turbo/modules/acquisition_functions.py UCB :147-158, PI :225-247, EI :336-358;
+//                        max-value entropy search (TGP_ACQ_MES) from the maxima of mes_set_maxima, with an
+//                        erfcx of its own (the standard library has none)
 #pragma once
 #include <stdint.h>
 
@@ -38,6 +40,7 @@ struct HostGP {
     std::vector<double> alpha;   // (N,)
     std::vector<double> cand;    // (M, D) resident candidates
     int64_t M = 0;
+    std::vector<double> mes;     // the maxima of max-value entropy search; every fit drops them
     double last_fit_ms = 0.0, last_sweep_ms = 0.0;
 
     // all return a tgp_status; err holds the message of a failure
@@ -49,6 +52,7 @@ struct HostGP {
     int debug_read(int which, double *out);
     int set_candidates(const double *Xc, int64_t M);
     int read_candidates(int64_t first, int64_t count, double *out);
+    int mes_set_maxima(const double *ystar, int64_t S);
     int sweep(int acq, double sf, double incumbent, double param, double *mu, double *sigma,
               double *acq_out, double *best_val, int64_t *best_idx, int64_t *n_clamped);
 };

@@ -312,8 +312,15 @@ struct QFinal {
     int m, D, acq;
     double kss, y_mean, y_std, sf, incumbent, param;
     Bell bell;               // word != null: q_reduce_kernel's last workgroup forms value + gradient and rings
+    MesArgs mes;             // TGP_ACQ_MES (the MES instances of the two kernels below): the handle's maxima
 };
-template <typename LD>
+// MES: max-value entropy search is a compile-time case, so the other acquisitions' instances keep their code
+template <bool MES>
+__device__ __forceinline__ AcqCoef q_coef(const QFinal &f, double mu, double sigma) {
+    if constexpr (MES) return mes_coef(f.mes, mu, sigma, f.sf);
+    else return acq_coef(f.acq, mu, sigma, f.sf, f.incumbent, f.param);
+}
+template <bool MES, typename LD>
 __device__ __forceinline__ void q_finalize_point(const QFinal &f, const double *r, int q, LD ld) {
     const int D = f.D;
     const double mu = f.y_std * ld(r) + f.y_mean;
@@ -322,7 +329,7 @@ __device__ __forceinline__ void q_finalize_point(const QFinal &f, const double *
     if (!pos) var = 0.0;
     const double sn = sqrt(var);
     const double sigma = f.y_std * sn;
-    const AcqCoef ac = acq_coef(f.acq, mu, sigma, f.sf, f.incumbent, f.param);
+    const AcqCoef ac = q_coef<MES>(f, mu, sigma);
     const double a = ac.a, cm = ac.cm, cs = ac.cs;
     f.val[q] = a;
     for (int d = 0; d < D; ++d) {
@@ -338,6 +345,7 @@ __device__ __forceinline__ void q_finalize_point(const QFinal &f, const double *
 // Round 6 (fin.bell.word != null, tgp_acq_grad's polled call): the workgroup that draws the last ticket turns the
 // sums of ALL points into value + gradient -- straight into device-mapped host memory -- and rings the call's
 // doorbell: no finalize launch, no D2H copies, no stream synchronisation.  Nobody waits for anybody.
+template <bool MES>
 __global__ __launch_bounds__(256) void q_reduce_kernel(const double *__restrict__ Xs,
                                                        const double *__restrict__ alpha,
                                                        const double *__restrict__ uq,
@@ -409,7 +417,7 @@ __global__ __launch_bounds__(256) void q_reduce_kernel(const double *__restrict_
             const bool pos = var > 0.0;
             if (!pos) var = 0.0;
             const double sn = sqrt(var);
-            const AcqCoef ac = acq_coef(fin.acq, mu, fin.y_std * sn, fin.sf, fin.incumbent, fin.param);
+            const AcqCoef ac = q_coef<MES>(fin, mu, fin.y_std * sn);
             fin.val[qq] = ac.a;
             red[0][threadIdx.x] = ac.cm; red[1][threadIdx.x] = ac.cs; red[2][threadIdx.x] = sn;
             red[3][threadIdx.x] = (pos && sn > 0.0) ? 1.0 : 0.0;
@@ -435,10 +443,11 @@ __global__ __launch_bounds__(256) void q_reduce_kernel(const double *__restrict_
 }
 
 // one thread per query point: value and gradient of the acquisition
+template <bool MES>
 __global__ void q_finalize_kernel(const double *__restrict__ red, QFinal fin) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= fin.m) return;
-    q_finalize_point(fin, red + (long)q * (2 + 2 * fin.D), q, [](const double *a) { return *a; });
+    q_finalize_point<MES>(fin, red + (long)q * (2 + 2 * fin.D), q, [](const double *a) { return *a; });
 }
 
 // doubles of launch_query's workspace per query point
@@ -508,11 +517,15 @@ hipError_t launch_query(Context &c, const double *d_Xq, int m, int acq, double s
     fin.kss = c.constant + c.noise; fin.y_mean = c.y_mean; fin.y_std = c.y_std;
     fin.sf = sf; fin.incumbent = incumbent; fin.param = param;
     fin.bell = d_val ? bell : Bell{nullptr, 0, nullptr};
-    hipLaunchKernelGGL(q_reduce_kernel, dim3(D, m), dim3(256), 0, s, c.d_Xs, c.d_alpha, uq, ks, hw, v, w, red, N, Np, D, Dp, m,
+    const bool is_mes = acq == TGP_ACQ_MES;    // (tgp_acq_grad has checked that the maxima belong to the resident fit)
+    if (is_mes) fin.mes = MesArgs{c.d_mes, c.mes_S, c.noise * (c.y_std * c.y_std)};
+    auto k_red = is_mes ? q_reduce_kernel<true> : q_reduce_kernel<false>;
+    auto k_fin = is_mes ? q_finalize_kernel<true> : q_finalize_kernel<false>;
+    hipLaunchKernelGGL(k_red, dim3(D, m), dim3(256), 0, s, c.d_Xs, c.d_alpha, uq, ks, hw, v, w, red, N, Np, D, Dp, m,
                        mfma ? 1 : QCOLS_SPLIT, fin);
     TGP_TRY(hipGetLastError());
     if (!d_val || fin.bell.word) return hipSuccess;
-    hipLaunchKernelGGL(q_finalize_kernel, dim3((m + 63) / 64), dim3(64), 0, s, red, fin);
+    hipLaunchKernelGGL(k_fin, dim3((m + 63) / 64), dim3(64), 0, s, red, fin);
     return hipGetLastError();
 }
 

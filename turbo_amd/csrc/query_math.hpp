@@ -59,4 +59,12 @@ __device__ __forceinline__ AcqCoef acq_coef(int acq, double mu, double sigma, do
     return r;
 }
 
+// max-value entropy search (mes_math.hpp): the value and its partials from the handle's S maxima, read from device memory
+// at one address for every lane (a query batch is a few points: nothing to stage)
+__device__ __forceinline__ AcqCoef mes_coef(const MesArgs &m, double mu, double sigma, double sf) {
+    AcqCoef r{0.0, 0.0, 0.0};
+    r.a = mes_acq<true>(m.ystar, m.S, m.noise_var, sf, mu, sigma, r.cm, r.cs);
+    return r;
+}
+
 }  // namespace tgp

@@ -717,9 +717,17 @@ __device__ __forceinline__ double ndtr_small(double a) {
 
 constexpr size_t SMALL_SWEEP_LDS = (size_t)(4 * T_SZ + 1024) * sizeof(double);
 
-template <int KIND>
-__device__ __forceinline__ void small_sweep_body(const SmallSweepArgs &p) {
+// MES: the max-value entropy search instance -- a compile-time case of the epilogue (the other instances keep their code);
+// its S maxima are staged in LDS once per workgroup
+template <int KIND, bool MES = false>
+__device__ __forceinline__ void small_sweep_body(const SmallSweepArgs &p, const MesArgs &mes = MesArgs{nullptr, 0, 0.0}) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
+    const double *ys = nullptr;
+    if constexpr (MES) {
+        __shared__ double ysl[MES_MAXS];
+        if ((int)threadIdx.x < mes.S) ysl[threadIdx.x] = mes.ystar[threadIdx.x];   // (read behind the barriers below)
+        ys = ysl;
+    }
     tile_t Ks0 = reinterpret_cast<tile_t>(sm);                  // cross-kernel, candidates x training points 0..63
     tile_t Ks1 = reinterpret_cast<tile_t>(sm + T_SZ);           //                                   ... 64..127
     tile_t Lt = reinterpret_cast<tile_t>(sm + 2 * T_SZ);        // one 64 x 64 block of Linv
@@ -869,6 +877,10 @@ __device__ __forceinline__ void small_sweep_body(const SmallSweepArgs &p) {
                     }
                 }
             }
+            if constexpr (MES) {
+                double cm, cs;
+                a = mes_acq<false>(ys, mes.S, mes.noise_var, p.sf, mu, sigma, cm, cs);
+            }
             if (p.mu) p.mu[gc] = mu;
             if (p.sigma) p.sigma[gc] = sigma;
             if (p.acqv) p.acqv[gc] = a;
@@ -891,6 +903,8 @@ __device__ __forceinline__ void small_sweep_body(const SmallSweepArgs &p) {
 
 template <int KIND>
 __global__ __launch_bounds__(256) void small_sweep_kernel(SmallSweepArgs p) { small_sweep_body<KIND>(p); }
+template <int KIND>
+__global__ __launch_bounds__(256) void small_sweep_mes_kernel(SmallSweepArgs p, MesArgs mes) { small_sweep_body<KIND, true>(p, mes); }
 
 // blockIdx.y = model (tgp_predict_batch)
 template <int KIND>
@@ -1111,9 +1125,15 @@ struct MidFinal {            // what the last workgroup needs to finish the laun
     Bell bell;               // a polled call (round 6): the last workgroup rings when the record is out
 };
 
-template <int KIND, int CPW>
-__device__ __forceinline__ void mid_sweep_body(const SmallSweepArgs &p, const MidFinal &f) {
+template <int KIND, int CPW, bool MES = false>
+__device__ __forceinline__ void mid_sweep_body(const SmallSweepArgs &p, const MidFinal &f, const MesArgs &mes = MesArgs{nullptr, 0, 0.0}) {
     using Cfg = MidCfg<CPW>;
+    const double *ys = nullptr;
+    if constexpr (MES) {          // as small_sweep_body
+        __shared__ double ysl[MES_MAXS];
+        if ((int)threadIdx.x < mes.S) ysl[threadIdx.x] = mes.ystar[threadIdx.x];
+        ys = ysl;
+    }
     constexpr int LDK = Cfg::LDK, CT_LD = Cfg::CT_LD, XT_LD = Cfg::XT_LD;
     constexpr int CA = CPW / 16;                                      // candidates per thread of the cross-kernel phase
     constexpr int NCF = CPW / 16;                                     // 16-candidate column fragments of the contraction
@@ -1296,6 +1316,10 @@ __device__ __forceinline__ void mid_sweep_body(const SmallSweepArgs &p, const Mi
                     }
                 }
             }
+            if constexpr (MES) {
+                double cm, cs;
+                a = mes_acq<false>(ys, mes.S, mes.noise_var, p.sf, mu, sigma, cm, cs);
+            }
             if (p.mu) p.mu[gc] = mu;
             if (p.sigma) p.sigma[gc] = sigma;
             if (p.acqv) p.acqv[gc] = a;
@@ -1371,6 +1395,10 @@ __device__ __forceinline__ void mid_sweep_body(const SmallSweepArgs &p, const Mi
 
 template <int KIND, int CPW>
 __global__ __launch_bounds__(512) void mid_sweep_kernel(SmallSweepArgs p, MidFinal f) { mid_sweep_body<KIND, CPW>(p, f); }
+template <int KIND, int CPW>
+__global__ __launch_bounds__(512) void mid_sweep_mes_kernel(SmallSweepArgs p, MidFinal f, MesArgs mes) {
+    mid_sweep_body<KIND, CPW, true>(p, f, mes);
+}
 
 // blockIdx.y = model (tgp_predict_batch with stored models of 128 < N <= 256): predict only
 template <int KIND>
@@ -1412,6 +1440,22 @@ int mid_sweep_cpw(const Context &c, int64_t M) {
 }
 
 template <int CPW>
+static hipError_t launch_mid_sweep_mes_as(Context &c, const SmallSweepArgs &a, const MidFinal &f, const MesArgs &mes) {
+    void (*k)(SmallSweepArgs, MidFinal, MesArgs);
+    switch (c.kernel) {
+        case TGP_RBF: k = mid_sweep_mes_kernel<TGP_RBF, CPW>; break;
+        case TGP_MATERN12: k = mid_sweep_mes_kernel<TGP_MATERN12, CPW>; break;
+        case TGP_MATERN32: k = mid_sweep_mes_kernel<TGP_MATERN32, CPW>; break;
+        default: k = mid_sweep_mes_kernel<TGP_MATERN52, CPW>; break;
+    }
+    static LdsOptIn opt_in[4];
+    TGP_TRY(opt_in[c.kernel & 3].ensure(reinterpret_cast<const void *>(k), c.device, MidCfg<CPW>::LDS));
+    const unsigned nblk = (unsigned)((c.M + CPW - 1) / CPW);
+    hipLaunchKernelGGL(k, dim3(nblk), dim3(512), MidCfg<CPW>::LDS, c.stream, a, f, mes);
+    return hipGetLastError();
+}
+
+template <int CPW>
 static hipError_t launch_mid_sweep_as(Context &c, const SmallSweepArgs &a, const MidFinal &f) {
     void (*k)(SmallSweepArgs, MidFinal);
     switch (c.kernel) {
@@ -1442,11 +1486,27 @@ hipError_t launch_mid_sweep(Context &c, const SweepCall &s) {
     const SmallSweepArgs a = sweep_args(c, s);
     const MidFinal f{c.d_best, s.winner, s.res, (long long)c.winner_offset, s.bell};
     // (mid_sweep_cpw of a model that takes this path: 64 candidates per workgroup up to N = 256, i.e. Np = 256, else 32)
+    if (s.acq == TGP_ACQ_MES)
+        return c.Np == 4 * NB ? launch_mid_sweep_mes_as<64>(c, a, f, s.mes) : launch_mid_sweep_mes_as<32>(c, a, f, s.mes);
     return c.Np == 4 * NB ? launch_mid_sweep_as<64>(c, a, f) : launch_mid_sweep_as<32>(c, a, f);
 }
 
 hipError_t launch_small_sweep(Context &c, const SweepCall &s) {
     const SmallSweepArgs a = sweep_args(c, s);
+    const unsigned nblk = (unsigned)((c.M + NB - 1) / NB);
+    if (s.acq == TGP_ACQ_MES) {
+        void (*km)(SmallSweepArgs, MesArgs);
+        switch (c.kernel) {
+            case TGP_RBF: km = small_sweep_mes_kernel<TGP_RBF>; break;
+            case TGP_MATERN12: km = small_sweep_mes_kernel<TGP_MATERN12>; break;
+            case TGP_MATERN32: km = small_sweep_mes_kernel<TGP_MATERN32>; break;
+            default: km = small_sweep_mes_kernel<TGP_MATERN52>; break;
+        }
+        static LdsOptIn opt_mes[4];
+        TGP_TRY(opt_mes[c.kernel & 3].ensure(reinterpret_cast<const void *>(km), c.device, SMALL_SWEEP_LDS));
+        hipLaunchKernelGGL(km, dim3(nblk), dim3(256), SMALL_SWEEP_LDS, c.stream, a, s.mes);
+        return hipGetLastError();
+    }
     void (*k)(SmallSweepArgs);
     switch (c.kernel) {
         case TGP_RBF: k = small_sweep_kernel<TGP_RBF>; break;
@@ -1456,7 +1516,6 @@ hipError_t launch_small_sweep(Context &c, const SweepCall &s) {
     }
     static LdsOptIn opt_in[4];
     TGP_TRY(opt_in[c.kernel & 3].ensure(reinterpret_cast<const void *>(k), c.device, SMALL_SWEEP_LDS));
-    const unsigned nblk = (unsigned)((c.M + NB - 1) / NB);
     hipLaunchKernelGGL(k, dim3(nblk), dim3(256), SMALL_SWEEP_LDS, c.stream, a);
     return hipGetLastError();
 }

@@ -452,12 +452,21 @@ struct FinArgs {
                                // places the block partials
 };
 
-__global__ __launch_bounds__(FIN_BLOCK) void finalize_kernel(FinArgs f) {
+// MES: the max-value entropy search instance (finalize_mes_kernel) -- a compile-time case of the epilogue, so the
+// EI / PI / UCB instance keeps its code and its registers; the S maxima are staged in LDS once per workgroup
+template <bool MES>
+__device__ __forceinline__ void finalize_body(const FinArgs &f, const MesArgs &mes) {
     __shared__ double sv[FIN_BLOCK];
     __shared__ long long si[FIN_BLOCK];
     __shared__ int sclamp;
     const int tid = threadIdx.x;
     if (tid == 0) sclamp = 0;
+    const double *ys = nullptr;
+    if constexpr (MES) {
+        __shared__ double ysl[MES_MAXS];
+        if (tid < mes.S) ysl[tid] = mes.ystar[tid];
+        ys = ysl;
+    }
     __syncthreads();
     const long c = (long)blockIdx.x * FIN_BLOCK + tid;
     double best = -INFINITY;
@@ -493,6 +502,10 @@ __global__ __launch_bounds__(FIN_BLOCK) void finalize_kernel(FinArgs f) {
                 }
             }
         }
+        if constexpr (MES) {
+            double cm, cs;
+            a = mes_acq<false>(ys, mes.S, mes.noise_var, f.sf, mu, sigma, cm, cs);
+        }
         const long gc = f.gidx ? (long)f.gidx[c] : f.off + c;
         if (f.mu) f.mu[gc] = mu;
         if (f.sigma) f.sigma[gc] = sigma;
@@ -518,6 +531,9 @@ __global__ __launch_bounds__(FIN_BLOCK) void finalize_kernel(FinArgs f) {
         if (sclamp) atomicAdd((unsigned long long *)&f.counters[1], (unsigned long long)sclamp);
     }
 }
+
+__global__ __launch_bounds__(FIN_BLOCK) void finalize_kernel(FinArgs f) { finalize_body<false>(f, MesArgs{nullptr, 0, 0.0}); }
+__global__ __launch_bounds__(FIN_BLOCK) void finalize_mes_kernel(FinArgs f, MesArgs mes) { finalize_body<true>(f, mes); }
 
 // Final (value, lowest index) of the per-block partials.  When a winner record is attached
 // (tgp_set_winner_out: the sharded arg-max of SURVEY 8e) the same block also packs
@@ -1169,7 +1185,8 @@ static hipError_t sweep_chunks(Context &c, const SweepCall &call, bool front_usa
     TGP_TRY((make_plan<T, BK>(c, p)));
     const TrmmVariant &v = p.main;
     const bool x3 = p.x3, h2 = p.h2;
-    // an arg-max-only EI / PI / UCB sweep in f32 / f64 first tries the pruned schedule (TGP_SWEEP_PRUNE)
+    // an arg-max-only EI / PI / UCB sweep in f32 / f64 first tries the pruned schedule (TGP_SWEEP_PRUNE); its bounds are
+    // proved for those three only, so TGP_ACQ_MES always takes the schedule below (prune_state stays "not eligible")
     bool fell_back = false;
     if (!call.mu && !call.sigma && !call.acqv && (acq == TGP_ACQ_EI || acq == TGP_ACQ_PI || acq == TGP_ACQ_UCB) &&
         (c.dtype == TGP_F32 || c.dtype == TGP_F64) && p.mean_in_trmm && tuning_sweep_prune_now() != 0 &&
@@ -1254,8 +1271,9 @@ static hipError_t sweep_chunks(Context &c, const SweepCall &call, bool front_usa
         f.acq = acq; f.sf = call.sf; f.incumbent = call.incumbent; f.param = call.param;
         f.mu = call.mu; f.sigma = call.sigma; f.acqv = call.acqv;
         f.bval = c.d_bval; f.bidx = c.d_bidx; f.counters = c.d_besti;
-        hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((c.M + FIN_BLOCK - 1) / FIN_BLOCK)),
-                           dim3(FIN_BLOCK), 0, sa, f);
+        const dim3 fgrid((unsigned)((c.M + FIN_BLOCK - 1) / FIN_BLOCK));
+        if (acq == TGP_ACQ_MES) hipLaunchKernelGGL(finalize_mes_kernel, fgrid, dim3(FIN_BLOCK), 0, sa, f, call.mes);
+        else hipLaunchKernelGGL(finalize_kernel, fgrid, dim3(FIN_BLOCK), 0, sa, f);
         TGP_TRY(hipGetLastError());
     }
     if (acq != TGP_ACQ_NONE || call.res) {

@@ -304,6 +304,7 @@ static void free_ws(Context &c) {
     dfree(c.d_batch); c.cap_batch = 0;
     dfree(c.d_bt); dfree(c.d_btm); dfree(c.d_bti); c.cap_bt = c.cap_btm = c.cap_bti = 0;
     dfree(c.d_ts); dfree(c.d_tsm); c.cap_ts = c.cap_tsm = 0; c.ts_gen = -1;
+    dfree(c.d_mes); c.mes_S = 0; c.mes_gen = -1;
     c.cap_Cs = c.cap_Ks[0] = c.cap_Ks[1] = c.cap_part = c.cap_mupart = 0;
     c.ws_Mpad = 0;
 }
@@ -1514,7 +1515,18 @@ static int ensure_small_workspace(Context &c) {
 // One sweep of the resident candidates with the resident model, for every entry of the family: picks the kernel
 // family, sees to its workspace, starts the call's clock in front of the first launch, launches, and records the winner
 // event behind whatever packed the record.  The entry keeps its argument checks, its own buffers and what it copies back.
-static int run_sweep(Context &c, const SweepCall &s, CallClock &clk) {
+// TGP_ACQ_MES needs maxima that belong to the resident fit (tgp_mes_set_maxima / tgp_mes_draw); like a Thompson draw they
+// are dropped by every later fit, append and import
+static int mes_check(Context &c, int acq, const char *fn) {
+    if (acq != TGP_ACQ_MES) return TGP_OK;
+    if (c.mes_gen < 0 || c.mes_gen != c.fit_gen || c.mes_S < 1)
+        return fail(c, TGP_BAD_ARG, std::string(fn) + ": TGP_ACQ_MES needs maxima for the resident fit (tgp_mes_set_maxima or tgp_mes_draw after the last fit)");
+    return TGP_OK;
+}
+
+static int run_sweep(Context &c, const SweepCall &call, CallClock &clk) {
+    SweepCall s = call;
+    if (s.acq == TGP_ACQ_MES) s.mes = MesArgs{c.d_mes, c.mes_S, c.noise * (c.y_std * c.y_std)};
     const SweepPath path = sweep_path(c, c.M);
     int rc = path == SweepPath::General ? ensure_workspace(c) : ensure_small_workspace(c);
     if (rc != TGP_OK) return rc;
@@ -1554,7 +1566,8 @@ int tgp_sweep(tgp_handle h, int acq, double sf, double incumbent, double param, 
     Context &c = h->c;
     if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_sweep: no fitted model");
     if (!c.d_cand || c.M < 1) return fail(c, TGP_BAD_ARG, "tgp_sweep: no candidates set");
-    if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_SIGMA) return fail(c, TGP_BAD_ARG, "tgp_sweep: unknown acquisition");
+    if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_MES) return fail(c, TGP_BAD_ARG, "tgp_sweep: unknown acquisition");
+    if (int mrc = mes_check(c, acq, "tgp_sweep"); mrc != TGP_OK) return mrc;
     if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_sweep: sf must be +1 or -1");
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
     SweepCall s;
@@ -1608,7 +1621,8 @@ int tgp_acq_grad(tgp_handle h, const double *Xq, int64_t m, int acq, double sf, 
     Context &c = h->c;
     if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_acq_grad: no fitted model");
     if (!Xq || !val || !grad || m < 1 || m > 4096) return fail(c, TGP_BAD_ARG, "tgp_acq_grad: need Xq, val, grad and 1 <= m <= 4096");
-    if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_SIGMA) return fail(c, TGP_BAD_ARG, "tgp_acq_grad: unknown acquisition");
+    if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_MES) return fail(c, TGP_BAD_ARG, "tgp_acq_grad: unknown acquisition");
+    if (int mrc = mes_check(c, acq, "tgp_acq_grad"); mrc != TGP_OK) return mrc;
     if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_acq_grad: sf must be +1 or -1");
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
     API_HIP(pre_join(c), "hipStreamWaitEvent");
@@ -1618,7 +1632,8 @@ int tgp_acq_grad(tgp_handle h, const double *Xq, int64_t m, int acq, double sf, 
     // four general kernels with value + gradient formed by the reduction's last workgroup.
     const int64_t D = c.D;
     const size_t zc_in = (size_t)(m * D) * sizeof(double), zc_out = (size_t)(8 + m + m * D) * sizeof(double);
-    const bool small_q = small_refine_fits(c) && small_path_enabled() && tuning().small_query != 0;
+    // (max-value entropy search lives in the general query kernels only: they serve every N)
+    const bool small_q = small_refine_fits(c) && small_path_enabled() && tuning().small_query != 0 && acq != TGP_ACQ_MES;
     Bell bell{nullptr, 0, nullptr};
     if (zc_in <= ((size_t)1 << 20) && zc_out <= ((size_t)1 << 20)) bell = bell_next(c);
     if (bell.word) {
@@ -1955,6 +1970,30 @@ static int64_t ts_doubles(const Context &c, int64_t S, int64_t F) {
     return ts_al4(F * c.Dp) + ts_al4(F) + ts_al4(Spad * F) + ts_al4(Spad * c.Np) + ts_al4(S * c.N) + ts_al4(c.N * S) +
            2 * ts_al4(S * c.Np);
 }
+// tgp_ts_sweep's per-call region over the resident batch, carved from `base`:
+// [Cs (Mpad Dp) | f (M S) | bval (S nblk) | sel_val (S) | sel_x (S D) | bidx (S nblk) | sel_idx (S) | mask (M bytes)]
+struct TsSweepWs {
+    double *Cs, *f, *bval, *selv, *selx;
+    long long *bidx, *seli;
+    unsigned char *mask;
+    int64_t Mpad;
+    size_t bytes;
+};
+static TsSweepWs ts_sweep_ws(const Context &c, double *base, int64_t S) {
+    const int64_t M = c.M, D = c.D, nblk = (M + 255) / 256;
+    TsSweepWs w{};
+    w.Mpad = ((M + 63) / 64) * 64;
+    w.Cs = base;
+    w.f = w.Cs + ts_al4(w.Mpad * c.Dp);
+    w.bval = w.f + ts_al4(M * S);
+    w.selv = w.bval + ts_al4(S * nblk);
+    w.selx = w.selv + ts_al4(S);
+    w.bidx = reinterpret_cast<long long *>(w.selx + ts_al4(S * D));
+    w.seli = w.bidx + S * nblk;
+    w.mask = reinterpret_cast<unsigned char *>(w.seli + S);
+    w.bytes = (size_t)(w.mask - reinterpret_cast<unsigned char *>(base)) + (size_t)M;
+    return w;
+}
 static int ts_check_draw(Context &c, const char *fn) {
     if (!c.fitted) return fail(c, TGP_BAD_ARG, std::string(fn) + ": no fitted model");
     if (c.ts_gen < 0 || c.ts_gen != c.fit_gen)
@@ -1999,15 +2038,12 @@ int tgp_ts_sweep(tgp_handle h, double sf, int distinct, int64_t *idx_out, double
     API_HIP(pre_join(c), "hipStreamWaitEvent");
     const TsDraw t = ts_view(c);
     const int64_t S = t.S, M = c.M, D = c.D;
-    const int64_t Mpad = ((M + 63) / 64) * 64, nblk = (M + 255) / 256;
-    // [Cs (Mpad Dp) | f (M S) | bval (S nblk) | sel_val (S) | sel_x (S D) | bidx (S nblk) | sel_idx (S) | mask (M bytes)]
-    const int64_t nd = ts_al4(Mpad * c.Dp) + ts_al4(M * S) + ts_al4(S * nblk) + ts_al4(S) + ts_al4(S * D) + S * nblk + S;
-    const size_t bytes = (size_t)nd * sizeof(double) + (size_t)M;
-    if ((rc = grow(c, c.d_tsm, c.cap_tsm, bytes, "hipMalloc Thompson sweep")) != TGP_OK) return rc;
-    double *Cs = c.d_tsm, *f = Cs + ts_al4(Mpad * c.Dp), *bval = f + ts_al4(M * S), *selv = bval + ts_al4(S * nblk),
-           *selx = selv + ts_al4(S);
-    long long *bidx = reinterpret_cast<long long *>(selx + ts_al4(S * D)), *seli = bidx + S * nblk;
-    unsigned char *mask = reinterpret_cast<unsigned char *>(seli + S);
+    if ((rc = grow(c, c.d_tsm, c.cap_tsm, ts_sweep_ws(c, nullptr, S).bytes, "hipMalloc Thompson sweep")) != TGP_OK) return rc;
+    const TsSweepWs ws = ts_sweep_ws(c, c.d_tsm, S);
+    const int64_t Mpad = ws.Mpad;
+    double *Cs = ws.Cs, *f = ws.f, *bval = ws.bval, *selv = ws.selv, *selx = ws.selx;
+    long long *bidx = ws.bidx, *seli = ws.seli;
+    unsigned char *mask = ws.mask;
     CallClock clk;
     if ((rc = call_begin(c, clk)) != TGP_OK) return rc;
     hipError_t le = launch_bt_prep(c, Cs, Mpad);
@@ -2070,6 +2106,56 @@ int tgp_ts_read(tgp_handle h, double *omega, double *b, double *W, double *eps) 
     return TGP_OK;
 } TGP_CATCH
 
+// ---- max-value entropy search: the S maxima a TGP_ACQ_MES call averages over (include/turbogp.h) ----
+static bool mes_values_ok(const double *ystar, int64_t S) {
+    if (!ystar || S < 1 || S > MES_MAXS) return false;
+    for (int64_t s = 0; s < S; ++s)
+        if (!std::isfinite(ystar[s])) return false;
+    return true;
+}
+
+int tgp_mes_set_maxima(tgp_handle h, const double *ystar, int64_t S) try {
+    if (!h) return TGP_BAD_ARG;
+    if (h->host) return h->host->mes_set_maxima(ystar, S);
+    Context &c = h->c;
+    if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_mes_set_maxima: no fitted model (the maxima belong to one fit)");
+    if (!mes_values_ok(ystar, S)) return fail(c, TGP_BAD_ARG, "tgp_mes_set_maxima: need 1 <= S <= 64 finite values");
+    API_HIP(hipSetDevice(c.device), "hipSetDevice");
+    c.mes_gen = -1;
+    if (!c.d_mes) API_HIP(hipMalloc((void **)&c.d_mes, MES_MAXS * sizeof(double)), "hipMalloc maxima");
+    API_HIP(hipMemcpyAsync(c.d_mes, ystar, (size_t)S * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D maxima");
+    API_HIP(hipStreamSynchronize(c.stream), "mes_set_maxima sync");
+    c.mes_S = (int)S;
+    c.mes_gen = c.fit_gen;
+    return TGP_OK;
+} TGP_CATCH
+
+int tgp_mes_draw(tgp_handle h, uint64_t seed, int64_t S, int64_t F, double sf, double incumbent, double *ystar_out) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_mes_draw");
+    Context &c = h->c;
+    if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_mes_draw: no fitted model");
+    if (!c.d_cand || c.M < 1) return fail(c, TGP_BAD_ARG, "tgp_mes_draw: no candidates set");
+    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_mes_draw: sf must be +1 or -1");
+    c.mes_gen = -1;
+    int rc = tgp_ts_draw(h, seed, S, F);      // (checks S and F)
+    if (rc != TGP_OK) return rc;
+    int64_t idx[MES_MAXS];
+    double val[MES_MAXS];
+    if ((rc = tgp_ts_sweep(h, sf, 0, idx, val, nullptr, nullptr)) != TGP_OK) return rc;
+    for (int64_t s = 0; s < S; ++s)
+        if (!std::isfinite(val[s])) return fail(c, TGP_BAD_ARG, "tgp_mes_draw: a sample path has no finite value over the candidates");
+    // the sweep's winners are still where it left them on the device: the handle's maxima are formed from there
+    if (!c.d_mes) API_HIP(hipMalloc((void **)&c.d_mes, MES_MAXS * sizeof(double)), "hipMalloc maxima");
+    hipError_t le = launch_mes_take(c, ts_sweep_ws(c, c.d_tsm, S).selv, (int)S, sf, incumbent, c.d_mes);
+    if (le != hipSuccess) return hip_fail(c, le, "launch_mes_take");
+    if (ystar_out) API_HIP(hipMemcpyAsync(ystar_out, c.d_mes, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H maxima");
+    API_HIP(hipStreamSynchronize(c.stream), "mes_draw sync");
+    c.mes_S = (int)S;
+    c.mes_gen = c.fit_gen;
+    return TGP_OK;
+} TGP_CATCH
+
 int tgp_sweep_topk(tgp_handle h, int acq, double sf, double incumbent, double param, int64_t k,
                    double *vals, int64_t *idxs, int64_t *n_clamped) try {
     if (!h) return TGP_BAD_ARG;
@@ -2077,7 +2163,8 @@ int tgp_sweep_topk(tgp_handle h, int acq, double sf, double incumbent, double pa
     Context &c = h->c;
     if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_sweep_topk: no fitted model");
     if (!c.d_cand || c.M < 1) return fail(c, TGP_BAD_ARG, "tgp_sweep_topk: no candidates set");
-    if (acq <= TGP_ACQ_NONE || acq > TGP_ACQ_SIGMA) return fail(c, TGP_BAD_ARG, "tgp_sweep_topk: needs an acquisition");
+    if (acq <= TGP_ACQ_NONE || acq > TGP_ACQ_MES) return fail(c, TGP_BAD_ARG, "tgp_sweep_topk: needs an acquisition");
+    if (int mrc = mes_check(c, acq, "tgp_sweep_topk"); mrc != TGP_OK) return mrc;
     if (k < 1 || k > 64 || !vals || !idxs) return fail(c, TGP_BAD_ARG, "tgp_sweep_topk: need 1 <= k <= 64, vals and idxs");
     if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_sweep_topk: sf must be +1 or -1");
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
@@ -2245,7 +2332,8 @@ int tgp_acq_lbfgsb(tgp_handle h, const double *X0, int64_t R, const double *lo, 
     if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_acq_lbfgsb: no fitted model");
     if (!X0 || !lo || !hi || !x_out || !val_out || R < 1 || R > 4096)
         return fail(c, TGP_BAD_ARG, "tgp_acq_lbfgsb: need X0, lo, hi, x_out, val_out and 1 <= R <= 4096");
-    if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_SIGMA) return fail(c, TGP_BAD_ARG, "tgp_acq_lbfgsb: unknown acquisition");
+    if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_MES) return fail(c, TGP_BAD_ARG, "tgp_acq_lbfgsb: unknown acquisition");
+    if (int mrc = mes_check(c, acq, "tgp_acq_lbfgsb"); mrc != TGP_OK) return mrc;
     if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_acq_lbfgsb: sf must be +1 or -1");
     if (max_iter < 1) return fail(c, TGP_BAD_ARG, "tgp_acq_lbfgsb: max_iter >= 1");
     const int D = (int)c.D;
@@ -2529,7 +2617,8 @@ int tgp_evaluate(tgp_handle h, const double *Xc, int64_t M, int acq, double sf, 
     Context &c = h->c;
     if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_evaluate: no fitted model");
     if (!Xc || M < 1) return fail(c, TGP_BAD_ARG, "tgp_evaluate: need Xc and M >= 1");
-    if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_SIGMA) return fail(c, TGP_BAD_ARG, "tgp_evaluate: unknown acquisition");
+    if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_MES) return fail(c, TGP_BAD_ARG, "tgp_evaluate: unknown acquisition");
+    if (int mrc = mes_check(c, acq, "tgp_evaluate"); mrc != TGP_OK) return mrc;
     if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_evaluate: sf must be +1 or -1");
     const size_t in_bytes = (size_t)M * (size_t)c.D * sizeof(double);
     // (the one question about the kernel family: only the one-workgroup / one-launch kernels write their outputs straight

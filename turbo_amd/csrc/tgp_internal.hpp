@@ -9,6 +9,7 @@
 #include "../../include/turbogp.h"
 #include "doorbell.hpp"
 #include "lds_opt_in.hpp"
+#include "mes_math.hpp"
 #include "tuning.hpp"
 
 namespace tgp {
@@ -103,6 +104,9 @@ struct Context {
     size_t cap_ts = 0, cap_tsm = 0;   // bytes
     int64_t ts_S = 0, ts_F = 0;    // the resident draw's shape ...
     long ts_gen = -1;              // ... and the fit_gen it belongs to (-1: none)
+    double *d_mes = nullptr;       // tgp_mes_set_maxima / tgp_mes_draw: MES_MAXS doubles, the first mes_S are the maxima
+    int mes_S = 0;
+    long mes_gen = -1;             // the fit_gen the maxima belong to (-1: none)
     double *d_topv = nullptr;      // top-k workspace (tgp_sweep_topk)
     long long *d_topi = nullptr;
     size_t cap_topv = 0, cap_topi = 0;
@@ -269,6 +273,7 @@ struct SweepCall {
     double *res = nullptr;          // device-mapped [best value, best index, clamp count] the sweep's last kernel fills, handing the counters back at zero (no D2H copy, no memset behind it), or null
     double *winner = nullptr;       // the (D + 2) record [value, global index, row] to pack (tgp_set_winner_out), or null
     Bell bell{nullptr, 0, nullptr}; // word != null: the one-workgroup / one-launch family's last kernel rings when the record is out (the general sweep never rings)
+    MesArgs mes{nullptr, 0, 0.0};   // TGP_ACQ_MES: the handle's maxima (run_sweep fills it in)
     bool may_use_front = false;     // the caller saw c.pre.front before pre_join discarded it: the front a fit issued may serve this sweep
 };
 // which kernel family sweeps a batch of M candidates with the resident model
@@ -366,6 +371,8 @@ hipError_t launch_ts_pass(Context &c, const TsDraw &t, const double *P, int64_t 
 // rows of samples < s.  bval / bidx: S * ceil(M / 256) partials; sel_x (S, D) the winners' rows
 hipError_t launch_ts_select(Context &c, const TsDraw &t, const double *f, double sf, int distinct, unsigned char *mask,
                             double *bval, long long *bidx, long long *sel_idx, double *sel_val, double *sel_x);
+// tgp_mes_draw: dst[s] = the better of src[s] and incumbent in the direction of sf (a NaN incumbent changes nothing)
+hipError_t launch_mes_take(Context &c, const double *src, int S, double sf, double incumbent, double *dst);
 size_t ts_eval_lds_bytes(const Context &c, int64_t S);
 hipError_t launch_ts_eval(Context &c, const TsDraw &t, const double *Xq, int m, double *fout, double *gout);
 

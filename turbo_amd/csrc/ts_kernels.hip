@@ -507,6 +507,19 @@ hipError_t launch_ts_draw(Context &c, const TsDraw &t, unsigned long long seed, 
     return hipGetLastError();
 }
 
+// the sampled maxima of max-value entropy search (tgp_mes_draw): the Thompson sweep's winners, none worse than the incumbent
+__global__ void mes_take_kernel(const double *__restrict__ src, int S, double sf, double incumbent, double *__restrict__ dst) {
+    const int s = threadIdx.x;
+    if (s >= S) return;
+    const double y = src[s];
+    dst[s] = sf * incumbent > sf * y ? incumbent : y;
+}
+
+hipError_t launch_mes_take(Context &c, const double *src, int S, double sf, double incumbent, double *dst) {
+    hipLaunchKernelGGL(mes_take_kernel, dim3(1), dim3(MES_MAXS), 0, c.stream, src, S, sf, incumbent, dst);
+    return hipGetLastError();
+}
+
 hipError_t launch_ts_select(Context &c, const TsDraw &t, const double *f, double sf, int distinct, unsigned char *mask,
                             double *bval, long long *bidx, long long *sel_idx, double *sel_val, double *sel_x) {
     const long M = (long)c.M, nblk = (M + 255) / 256;
