@@ -76,6 +76,27 @@ def test_zero_eps_is_kriging_believer(N, S):
         assert res["n_clamped"] == kb["n_clamped"]
 
 
+@pytest.mark.parametrize("N", [5, 130])
+def test_one_zero_simulation_is_kriging_believer_to_the_bit(N):
+    """what the two strategies share (the R row, the rank-1 step, the block arg-max and its partials), at the smallest
+    shapes that reach every part: N one below and one above the pass's 128-row split, M = 300 = two update blocks (the
+    second partial), pending points before the selections.  With S = 1 and eps = 0 the mean of one number is that
+    number, so unlike test_zero_eps_is_kriging_believer the values are equal to the bit too.  No ties: the candidates
+    are distinct uniform draws."""
+    L = __import__("turbo_amd")._lib
+    X, y, ls, Xc, Xp = _problem(N, 3, "rbf", 1e-4, 300, 40 + N)
+    gp = _gp("f64", X, y, "rbf", ls, 1e-4, Xc)
+    for acq, sf, par in ((L.ACQ_EI, -1.0, 0.01), (L.ACQ_PI, 1.0, 0.0), (L.ACQ_UCB, 1.0, 2.0)):
+        inc = float(y.min() if sf < 0 else y.max())
+        kb = gp.sweep_batch(3, L.BATCH_KB, 0.0, Xp[:2], acq, sf, inc, par, want_posterior=True)
+        res = gp.sweep_batch_mc(3, 1, 0, np.zeros((1, 5)), Xp[:2], acq, sf, inc, par, want_sigma=True)
+        np.testing.assert_array_equal(res["idx"], kb["idx"])
+        np.testing.assert_array_equal(res["x"], kb["x"])
+        assert res["sigma"].tobytes() == kb["sigma"].tobytes()
+        assert res["n_clamped"] == kb["n_clamped"]
+        assert np.asarray(res["val"], dtype=np.float64).tobytes() == np.asarray(kb["val"], dtype=np.float64).tobytes()
+
+
 CASES = [
     # N, D, kind, noise, M, dtype, pending, acq, sf, S, q
     (32, 2, "matern52", 1e-4, 10000, "f64", False, "ei", -1.0, 1, 8),

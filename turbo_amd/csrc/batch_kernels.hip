@@ -15,8 +15,8 @@
 //
 // bt_small_kernel forms the R row, the fantasy and e_j for one point (one workgroup); bt_pass_kernel is the one O(M N D)
 // pass per point -- kstar_kernel's tiles (sweep_kernels.hip) with w_j in place of alpha and no slab written; bt_update_kernel
-// applies the update, evaluates the acquisition with finalize_kernel's arithmetic and leaves per-block arg-max partials
-// that bt_argmax_kernel turns into the next selection, in device memory.  Everything here is f64, whatever the handle's
+// applies the update (bt_rank1), evaluates the acquisition (acq_value, acq_math.hpp: every sweep's formulas) and leaves
+// per-block arg-max partials that bt_argmax_kernel turns into the next selection, in device memory.  Everything here is f64, whatever the handle's
 // sweep dtype.
 //
 // Monte Carlo (tgp_sweep_batch_mc; old_library/bayesian_optimiser.py:76-106, _max_mc_acq_suggestion :568-624): S
@@ -35,10 +35,12 @@
 // out alike; with one pending point the two coincide.  eps[s,j] is a Philox-4x32-10 normal (philox.hpp) keyed by the
 // seed, counter (element lo, element hi, 0, MC_TAG), element s 64 + j with j counted pending-first: simulation s does
 // not depend on S, the draw for point j not on P or q.  mc_small_kernel stands in bt_small_kernel's place and
-// mc_update_kernel in bt_update_kernel's; the point, front, pass and arg-max kernels are shared.
+// mc_update_kernel in bt_update_kernel's, each pair on one shared body (bt_factor_row; bt_rank1 and bt_finish_block); the
+// point, front, pass and arg-max kernels are shared.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "acq_math.hpp"
 #include "pairwise.hpp"
 #include "philox.hpp"
 #include "tgp_internal.hpp"
@@ -109,15 +111,18 @@ __device__ __forceinline__ double bt_block_sum(double v, double *red) {
     return r;
 }
 
-// one workgroup: R row j, the fantasy of point j, e_j, the incumbent
+// what the two small kernels share, one workgroup: S[i] = k*(z_i).w_j (i <= j), k*(z_j).alpha, the cross-kernel between
+// z_j and the earlier points, then thread 0's R row j, pivot test and flag.  Returns, in thread 0 only, R[j,j] and
+// m = k*(z_j).alpha + sum_{i<j} R[j,i] e[i] (e null: the first term alone) accumulated inside the row loop, i ascending;
+// Rl (nullable, LDS) receives a copy of the row.  red (256), S (BT_MAXP + 1) and Rl (BT_MAXP) are the caller's LDS; the
+// caller synchronises before other threads read S[BT_MAXP] or Rl
+struct BtRow { double m, rjj; };
 template <int KIND>
-__global__ __launch_bounds__(256) void bt_small_kernel(const double *__restrict__ Kz, const double *__restrict__ w,
-                                                       const double *__restrict__ alpha, const double *__restrict__ Zs,
-                                                       BtSmall s, int j, int N, int Np, int Dp, double constant,
-                                                       double noise, double jitter, double y_mean, double y_std,
-                                                       int kb, double lie, double sf) {
-    __shared__ double red[256];
-    __shared__ double S[BT_MAXP + 1];
+__device__ __forceinline__ BtRow bt_factor_row(const double *__restrict__ Kz, const double *__restrict__ w,
+                                               const double *__restrict__ alpha, const double *__restrict__ Zs,
+                                               const BtSmall &s, int j, int N, int Np, int Dp, double constant,
+                                               double noise, double jitter, const double *e, double *red, double *S,
+                                               double *Rl) {
     const int tid = threadIdx.x;
     for (int i = 0; i <= j; ++i) {
         const double *k = Kz + (long)i * Np;
@@ -145,6 +150,7 @@ __global__ __launch_bounds__(256) void bt_small_kernel(const double *__restrict_
         S[tid] = kernel_value<double, KIND>(d2, constant) - S[tid];
     }
     __syncthreads();
+    BtRow r{0.0, 0.0};
     if (tid == 0) {
         double *Rj = s.R + (long)j * BT_MAXP;
         double m = S[BT_MAXP];
@@ -155,8 +161,9 @@ __global__ __launch_bounds__(256) void bt_small_kernel(const double *__restrict_
             for (int l = 0; l < i; ++l) t -= Rj[l] * Ri[l];
             t /= Ri[i];
             Rj[i] = t;
+            if (Rl) Rl[i] = t;
             piv -= t * t;
-            m += t * s.e[i];
+            if (e) m += t * e[i];
         }
         if (!(piv > 0.0) || !isfinite(piv)) {
             if (s.flag[0] == 0) s.flag[0] = j + 1;
@@ -164,9 +171,26 @@ __global__ __launch_bounds__(256) void bt_small_kernel(const double *__restrict_
         }
         const double rjj = sqrt(piv);
         Rj[j] = rjj;
-        const double f = kb ? y_std * m + y_mean : lie;
+        if (Rl) Rl[j] = rjj;
+        r = BtRow{m, rjj};
+    }
+    return r;
+}
+
+// one workgroup: R row j (bt_factor_row), the fantasy of point j, e_j, the incumbent
+template <int KIND>
+__global__ __launch_bounds__(256) void bt_small_kernel(const double *__restrict__ Kz, const double *__restrict__ w,
+                                                       const double *__restrict__ alpha, const double *__restrict__ Zs,
+                                                       BtSmall s, int j, int N, int Np, int Dp, double constant,
+                                                       double noise, double jitter, double y_mean, double y_std,
+                                                       int kb, double lie, double sf) {
+    __shared__ double red[256];
+    __shared__ double S[BT_MAXP + 1];
+    const BtRow r = bt_factor_row<KIND>(Kz, w, alpha, Zs, s, j, N, Np, Dp, constant, noise, jitter, s.e, red, S, nullptr);
+    if (threadIdx.x == 0) {
+        const double f = kb ? y_std * r.m + y_mean : lie;
         s.fant[j] = f;
-        s.e[j] = kb ? 0.0 : ((f - y_mean) / y_std - m) / rjj;
+        s.e[j] = kb ? 0.0 : ((f - y_mean) / y_std - r.m) / r.rjj;
         const double inc = s.inc[0];
         s.inc[0] = sf > 0.0 ? (f > inc ? f : inc) : (f < inc ? f : inc);
     }
@@ -276,31 +300,59 @@ __global__ __launch_bounds__(256, 2) void bt_pass_kernel(const double *__restric
     }
 }
 
-__device__ __forceinline__ double bt_ndtr(double a) {
-    // scipy.special.ndtr (cephes ndtr.c), as finalize_kernel (sweep_kernels.hip)
-    const double x = a * 0.70710678118654752440;
-    const double z = fabs(x);
-    double y;
-    if (z < 0.70710678118654752440) {
-        y = 0.5 + 0.5 * erf(x);
-    } else {
-        y = 0.5 * erfc(z);
-        if (x > 0) y = 1.0 - y;
+// what the two update kernels are given alike (bt_upd_base fills it)
+struct BtUpdBase {
+    const double *cand, *ls, *zs;     // raw candidates (M, D), length scales, scaled z_j (Dp)
+    const double *part; int njs; long ldpart;
+    double *G; long ldG; int j;       // column j of G at G + j ldG
+    double *var; const unsigned char *mask;
+    long M; int D;
+    double constant, y_std;
+    int acq; double sf, param;        // acq == TGP_ACQ_NONE: no selection follows this point
+    double *bval; long long *bidx; unsigned long long *clamp;
+    double *sigma_out;                // nullable: sigma after this point
+};
+
+// candidate x's rank-1 step for point j (R: the call's factor block): c(x), G[x,j] (stored when a later point or mean
+// reads it), the variance update with its clamp (counted in *sclamp, LDS) and sigma in raw units, written where asked
+struct BtRank1 { double g, var, sigma; };
+template <int KIND>
+__device__ __forceinline__ BtRank1 bt_rank1(const BtUpdBase &u, const double *R, long x, int store, int *sclamp) {
+    double kdot = 0.0;
+    for (int s = 0; s < u.njs; ++s) kdot += u.part[(long)s * u.ldpart + x];
+    double d2 = 0.0;
+    for (int d = 0; d < u.D; ++d) {
+        const double df = u.cand[x * u.D + d] / u.ls[d] - u.zs[d];
+        d2 = fma(df, df, d2);
     }
-    return y;
+    double cx = kernel_value<double, KIND>(d2, u.constant) - kdot;
+    const double *Rj = R + (long)u.j * BT_MAXP;
+    for (int i = 0; i < u.j; ++i) cx -= u.G[(long)i * u.ldG + x] * Rj[i];
+    const double g = cx / Rj[u.j];
+    if (store) u.G[(long)u.j * u.ldG + x] = g;
+    double var = u.var[x] - g * g;
+    if (var < 0.0) { var = 0.0; atomicAdd(sclamp, 1); }
+    u.var[x] = var;
+    const double sigma = sqrt(var * (u.y_std * u.y_std));
+    if (u.sigma_out) u.sigma_out[x] = sigma;
+    return BtRank1{g, var, sigma};
+}
+
+// the block's arg-max partial and its clamp count (sv, si: BT_BLOCK entries of LDS each)
+__device__ __forceinline__ void bt_finish_block(const BtUpdBase &u, Best best, double *sv, long long *si, const int *sclamp) {
+    best = block_argmax<BT_BLOCK>(best, sv, si);
+    if (threadIdx.x == 0) {
+        if (u.acq != TGP_ACQ_NONE) { u.bval[blockIdx.x] = best.v; u.bidx[blockIdx.x] = best.i; }
+        if (*sclamp) atomicAdd(u.clamp, (unsigned long long)*sclamp);
+    }
 }
 
 struct BtUpd {
-    const double *cand, *ls, *zs;     // raw candidates (M, D), length scales, scaled z_j (Dp)
-    const double *part; int njs; long ldpart;
-    double *G; long ldG; int j; int store;   // column j of G at G + j ldG (store: a later point reads it)
+    BtUpdBase b;
     BtSmall s;
-    double *mu, *var; unsigned char *mask;
-    long M; int D;
-    double constant, y_mean, y_std;
-    int acq; double sf, param;        // acq == TGP_ACQ_NONE: no selection follows this point
-    double *bval; long long *bidx; unsigned long long *clamp;
-    double *mu_out, *sigma_out;       // nullable: the posterior after the last point
+    int store;                        // column j of G is kept: a later point reads it
+    double *mu;                       // the running means, raw units
+    double *mu_out;                   // nullable: the means after the last point
 };
 
 template <int KIND>
@@ -312,66 +364,17 @@ __global__ __launch_bounds__(BT_BLOCK) void bt_update_kernel(BtUpd u) {
     if (tid == 0) sclamp = 0;
     __syncthreads();
     const long x = (long)blockIdx.x * BT_BLOCK + tid;
-    double best = -INFINITY;
-    long long bi = 0x7fffffffffffffffLL;
-    if (x < u.M) {
-        double kdot = 0.0;
-        for (int s = 0; s < u.njs; ++s) kdot += u.part[(long)s * u.ldpart + x];
-        double d2 = 0.0;
-        for (int d = 0; d < u.D; ++d) {
-            const double df = u.cand[x * u.D + d] / u.ls[d] - u.zs[d];
-            d2 = fma(df, df, d2);
-        }
-        double cx = kernel_value<double, KIND>(d2, u.constant) - kdot;
-        const double *Rj = u.s.R + (long)u.j * BT_MAXP;
-        for (int i = 0; i < u.j; ++i) cx -= u.G[(long)i * u.ldG + x] * Rj[i];
-        const double g = cx / Rj[u.j];
-        if (u.store) u.G[(long)u.j * u.ldG + x] = g;
-        double var = u.var[x] - g * g;
-        if (var < 0.0) { var = 0.0; atomicAdd(&sclamp, 1); }
-        u.var[x] = var;
+    Best best;
+    if (x < u.b.M) {
+        const BtRank1 r = bt_rank1<KIND>(u.b, u.s.R, x, u.store, &sclamp);
         double mu = u.mu[x];
-        const double e = u.s.e[u.j];
-        if (e != 0.0) { mu += u.y_std * (g * e); u.mu[x] = mu; }
-        const double sigma = sqrt(var * (u.y_std * u.y_std));
+        const double e = u.s.e[u.b.j];
+        if (e != 0.0) { mu += u.b.y_std * (r.g * e); u.mu[x] = mu; }
         if (u.mu_out) u.mu_out[x] = mu;
-        if (u.sigma_out) u.sigma_out[x] = sigma;
-        if (u.acq != TGP_ACQ_NONE && !u.mask[x]) {
-            const double incumbent = u.s.inc[0];
-            double a = 0.0;
-            if (u.acq == TGP_ACQ_UCB) {
-                a = u.sf * mu + u.param * sigma;
-            } else if (u.acq == TGP_ACQ_SIGMA) {
-                a = sigma;
-            } else if (sigma != 0.0) {
-                const double diff = u.sf * (mu - incumbent) - u.param;
-                const double Z = diff / sigma;
-                if (u.acq == TGP_ACQ_PI) {
-                    a = bt_ndtr(Z);
-                } else {
-                    const double pdf = exp(-(Z * Z) / 2.0) / 2.5066282746310002;
-                    a = diff * bt_ndtr(Z) + sigma * pdf;
-                }
-            }
-            if (!isnan(a)) best = a;
-            bi = x;
-        }
+        if (u.b.acq != TGP_ACQ_NONE && !u.b.mask[x])
+            best = candidate(acq_value(u.b.acq, u.b.sf, u.s.inc[0], u.b.param, mu, r.sigma), x);
     }
-    sv[tid] = best;
-    si[tid] = bi;
-    __syncthreads();
-    for (int o = BT_BLOCK / 2; o > 0; o >>= 1) {
-        if (tid < o) {
-            const double v2 = sv[tid + o];
-            const long long i2 = si[tid + o];
-            if (v2 > sv[tid] || (v2 == sv[tid] && i2 < si[tid])) { sv[tid] = v2; si[tid] = i2; }
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        if (u.acq != TGP_ACQ_NONE) { u.bval[blockIdx.x] = sv[0]; u.bidx[blockIdx.x] = si[0]; }
-        if (sclamp) atomicAdd(u.clamp, (unsigned long long)sclamp);
-    }
+    bt_finish_block(u.b, best, sv, si, &sclamp);
 }
 
 // selection k = the (value, lowest index) of the partials; the row is masked for the rest of the call
@@ -380,32 +383,12 @@ __global__ __launch_bounds__(256) void bt_argmax_kernel(const double *__restrict
                                                         long M) {
     __shared__ double sv[256];
     __shared__ long long si[256];
-    double v = -INFINITY;
-    long long i = 0x7fffffffffffffffLL;
-    for (long b = threadIdx.x; b < nblk; b += 256) {
-        const double v2 = bval[b];
-        const long long i2 = bidx[b];
-        if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-    }
-    sv[threadIdx.x] = v;
-    si[threadIdx.x] = i;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            const double v2 = sv[threadIdx.x + o];
-            const long long i2 = si[threadIdx.x + o];
-            if (v2 > sv[threadIdx.x] || (v2 == sv[threadIdx.x] && i2 < si[threadIdx.x])) {
-                sv[threadIdx.x] = v2;
-                si[threadIdx.x] = i2;
-            }
-        }
-        __syncthreads();
-    }
+    const Best b = block_argmax<256>(strided_argmax<256>(bval, bidx, nblk), sv, si);
     if (threadIdx.x == 0) {
-        long long w = si[0];
+        long long w = b.i;
         if (w < 0 || w >= M) w = M - 1;   // (never: q <= M leaves an unmasked row, and every unmasked row takes part)
         s.sel_idx[k] = w;
-        s.sel_val[k] = sv[0];
+        s.sel_val[k] = b.v;
         mask[w] = 1;
     }
 }
@@ -425,8 +408,8 @@ __global__ __launch_bounds__(256) void mc_init_kernel(double *__restrict__ eps, 
     if (j == 0) inc[s] = incumbent;
 }
 
-// one workgroup: R row j and the pivot test exactly as bt_small_kernel; then per simulation the conditional mean at
-// z_j, the fantasy (a draw of y) and the incumbent
+// one workgroup: R row j and the pivot test (bt_factor_row, the row also left in LDS); then per simulation the
+// conditional mean at z_j, the fantasy (a draw of y) and the incumbent
 template <int KIND>
 __global__ __launch_bounds__(256) void mc_small_kernel(const double *__restrict__ Kz, const double *__restrict__ w,
                                                        const double *__restrict__ alpha, const double *__restrict__ Zs,
@@ -437,51 +420,7 @@ __global__ __launch_bounds__(256) void mc_small_kernel(const double *__restrict_
     __shared__ double S[BT_MAXP + 1];
     __shared__ double Rl[BT_MAXP];
     const int tid = threadIdx.x;
-    for (int i = 0; i <= j; ++i) {
-        const double *k = Kz + (long)i * Np;
-        double a = 0.0;
-        for (int n = tid; n < N; n += 256) a = fma(k[n], w[n], a);
-        a = bt_block_sum(a, red);
-        if (tid == 0) S[i] = a;
-    }
-    {
-        const double *k = Kz + (long)j * Np;
-        double a = 0.0;
-        for (int n = tid; n < N; n += 256) a = fma(k[n], alpha[n], a);
-        a = bt_block_sum(a, red);
-        if (tid == 0) S[BT_MAXP] = a;   // k*(z_j).alpha
-    }
-    __syncthreads();
-    if (tid < j) {
-        const double *zj = Zs + (long)j * Dp, *zi = Zs + (long)tid * Dp;
-        double d2 = 0.0;
-        for (int d = 0; d < Dp; ++d) {
-            const double df = zj[d] - zi[d];
-            d2 = fma(df, df, d2);
-        }
-        S[tid] = kernel_value<double, KIND>(d2, constant) - S[tid];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double *Rj = s.b.R + (long)j * BT_MAXP;
-        double piv = ((constant + noise) + jitter) - S[j];
-        for (int i = 0; i < j; ++i) {
-            const double *Ri = s.b.R + (long)i * BT_MAXP;
-            double t = S[i];
-            for (int l = 0; l < i; ++l) t -= Rj[l] * Ri[l];
-            t /= Ri[i];
-            Rj[i] = t;
-            Rl[i] = t;
-            piv -= t * t;
-        }
-        if (!(piv > 0.0) || !isfinite(piv)) {
-            if (s.b.flag[0] == 0) s.b.flag[0] = j + 1;
-            piv = NAN;
-        }
-        const double rjj = sqrt(piv);
-        Rj[j] = rjj;
-        Rl[j] = rjj;
-    }
+    bt_factor_row<KIND>(Kz, w, alpha, Zs, s.b, j, N, Np, Dp, constant, noise, jitter, nullptr, red, S, Rl);
     __syncthreads();
     if (tid < s.S) {
         double m = S[BT_MAXP];
@@ -495,23 +434,16 @@ __global__ __launch_bounds__(256) void mc_small_kernel(const double *__restrict_
 }
 
 struct McUpd {
-    const double *cand, *ls, *zs;     // raw candidates (M, D), length scales, scaled z_j (Dp)
-    const double *part; int njs; long ldpart;
-    double *G; long ldG; int j;       // column j of G at G + j ldG: always stored (the later means read it)
+    BtUpdBase b;                      // (column j of G is always stored: the later means read it)
     McSmall s;
     const double *mu0;                // the first sweep's means, raw units: never updated
-    double *var; const unsigned char *mask;
-    long M; int D;
-    double constant, y_std;
-    int acq; double sf, param;        // acq == TGP_ACQ_NONE: no selection follows this point
-    double *bval; long long *bidx; unsigned long long *clamp;
-    double *acq_out, *sigma_out;      // nullable: this step's averaged acquisition (taken rows -inf) / sigma after it
+    double *acq_out;                  // nullable: this step's averaged acquisition (taken rows -inf)
 };
 
-// c(x), G[x,j], the variance update and its clamp exactly as bt_update_kernel; then the S means from G[x, 0..j] and
-// eps (LDS), S acquisition values (finalize_kernel's formulas), their mean in the order s = 0, 1, ... and the per-block
-// arg-max partials.  A thread per candidate: G is column-major, so its reads are coalesced; MC_SC means at a time
-// stay in registers (plain f64 FMAs: at S = J = 64 the erf / exp evaluations outweigh the product)
+// bt_rank1's step; then the S means from G[x, 0..j] and eps (LDS), S acquisition values (acq_value), their mean in the
+// order s = 0, 1, ... and the per-block arg-max partials.  A thread per candidate: G is column-major, so its reads are
+// coalesced; MC_SC means at a time stay in registers (plain f64 FMAs: at S = J = 64 the erf / exp evaluations outweigh
+// the product)
 template <int KIND>
 __global__ __launch_bounds__(BT_BLOCK) void mc_update_kernel(McUpd u) {
     __shared__ double sv[BT_BLOCK];
@@ -520,38 +452,22 @@ __global__ __launch_bounds__(BT_BLOCK) void mc_update_kernel(McUpd u) {
     __shared__ __attribute__((aligned(16))) double epsl[BT_MAXP * MC_MAXS];   // [i][s]
     __shared__ double incl[MC_MAXS];
     const int tid = threadIdx.x;
-    const int j = u.j, S = u.s.S;
+    const int j = u.b.j, S = u.s.S;
     if (tid == 0) sclamp = 0;
-    if (u.acq != TGP_ACQ_NONE && u.acq != TGP_ACQ_SIGMA) {
+    if (u.b.acq != TGP_ACQ_NONE && u.b.acq != TGP_ACQ_SIGMA) {
         for (int e = tid; e < (j + 1) * MC_MAXS; e += BT_BLOCK) epsl[e] = u.s.eps[e];
         if (tid < MC_MAXS) incl[tid] = u.s.inc[tid];
     }
     __syncthreads();
     const long x = (long)blockIdx.x * BT_BLOCK + tid;
-    double best = -INFINITY;
-    long long bi = 0x7fffffffffffffffLL;
-    if (x < u.M) {
-        double kdot = 0.0;
-        for (int s = 0; s < u.njs; ++s) kdot += u.part[(long)s * u.ldpart + x];
-        double d2 = 0.0;
-        for (int d = 0; d < u.D; ++d) {
-            const double df = u.cand[x * u.D + d] / u.ls[d] - u.zs[d];
-            d2 = fma(df, df, d2);
-        }
-        double cx = kernel_value<double, KIND>(d2, u.constant) - kdot;
-        const double *Rj = u.s.b.R + (long)j * BT_MAXP;
-        for (int i = 0; i < j; ++i) cx -= u.G[(long)i * u.ldG + x] * Rj[i];
-        const double g = cx / Rj[j];
-        u.G[(long)j * u.ldG + x] = g;
-        double var = u.var[x] - g * g;
-        if (var < 0.0) { var = 0.0; atomicAdd(&sclamp, 1); }
-        u.var[x] = var;
-        const double sigma = sqrt(var * (u.y_std * u.y_std));
-        if (u.sigma_out) u.sigma_out[x] = sigma;
-        if (u.acq != TGP_ACQ_NONE) {
-            if (!u.mask[x]) {
+    Best best;
+    if (x < u.b.M) {
+        const BtRank1 r = bt_rank1<KIND>(u.b, u.s.b.R, x, 1, &sclamp);
+        const double g = r.g, sigma = r.sigma;
+        if (u.b.acq != TGP_ACQ_NONE) {
+            if (!u.b.mask[x]) {
                 double a;
-                if (u.acq == TGP_ACQ_SIGMA) {
+                if (u.b.acq == TGP_ACQ_SIGMA) {
                     a = sigma;                 // the same for every simulation: no average to round
                 } else {
                     const double mu0 = u.mu0[x];
@@ -561,7 +477,7 @@ __global__ __launch_bounds__(BT_BLOCK) void mc_update_kernel(McUpd u) {
 #pragma unroll
                         for (int t = 0; t < MC_SC; ++t) acc[t] = 0.0;
                         for (int i = 0; i <= j; ++i) {
-                            const double gi = i == j ? g : u.G[(long)i * u.ldG + x];
+                            const double gi = i == j ? g : u.b.G[(long)i * u.b.ldG + x];
                             const double *er = epsl + i * MC_MAXS + s0;
 #pragma unroll
                             for (int t = 0; t < MC_SC; ++t) acc[t] = fma(gi, er[t], acc[t]);
@@ -569,47 +485,19 @@ __global__ __launch_bounds__(BT_BLOCK) void mc_update_kernel(McUpd u) {
 #pragma unroll
                         for (int t = 0; t < MC_SC; ++t) {
                             if (s0 + t < S) {
-                                const double mu = mu0 + u.y_std * acc[t];
-                                double as = 0.0;
-                                if (u.acq == TGP_ACQ_UCB) {
-                                    as = u.sf * mu + u.param * sigma;
-                                } else if (sigma != 0.0) {
-                                    const double diff = u.sf * (mu - incl[s0 + t]) - u.param;
-                                    const double Z = diff / sigma;
-                                    if (u.acq == TGP_ACQ_PI) {
-                                        as = bt_ndtr(Z);
-                                    } else {
-                                        const double pdf = exp(-(Z * Z) / 2.0) / 2.5066282746310002;
-                                        as = diff * bt_ndtr(Z) + sigma * pdf;
-                                    }
-                                }
-                                sum += as;
+                                const double mu = mu0 + u.b.y_std * acc[t];
+                                sum += acq_value(u.b.acq, u.b.sf, incl[s0 + t], u.b.param, mu, sigma);
                             }
                         }
                     }
                     a = sum / (double)S;
                 }
-                if (!isnan(a)) best = a;
-                bi = x;
+                best = candidate(a, x);
             }
-            if (u.acq_out) u.acq_out[x] = best;
+            if (u.acq_out) u.acq_out[x] = best.v;
         }
     }
-    sv[tid] = best;
-    si[tid] = bi;
-    __syncthreads();
-    for (int o = BT_BLOCK / 2; o > 0; o >>= 1) {
-        if (tid < o) {
-            const double v2 = sv[tid + o];
-            const long long i2 = si[tid + o];
-            if (v2 > sv[tid] || (v2 == sv[tid] && i2 < si[tid])) { sv[tid] = v2; si[tid] = i2; }
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        if (u.acq != TGP_ACQ_NONE) { u.bval[blockIdx.x] = sv[0]; u.bidx[blockIdx.x] = si[0]; }
-        if (sclamp) atomicAdd(u.clamp, (unsigned long long)sclamp);
-    }
+    bt_finish_block(u.b, best, sv, si, &sclamp);
 }
 
 // ---- launchers ----
@@ -649,44 +537,58 @@ hipError_t launch_bt_point(Context &c, const double *rec, const BtSmall &s, int 
     return hipGetLastError();
 }
 
-// the front of point j (its vectors into slot j of Kz / Zs) and its small side
-hipError_t launch_bt_condition(Context &c, const BtSmall &s, int j, const double *zraw, double *Kz, double *Zs,
-                               double *hw, double *v, double *w, int kb, double lie, double sf) {
-    TGP_TRY(launch_query_front(c, zraw, Zs + (long)j * c.Dp, Kz + (long)j * c.Np, hw, v, w));
-    BT_KIND_DISPATCH(bt_small_kernel, dim3(1), dim3(256), Kz, w, c.d_alpha, Zs, s, j, (int)c.N, (int)c.Np, (int)c.Dp,
-                     c.constant, c.noise, c.jitter, c.y_mean, c.y_std, kb, lie, sf);
+// the front of point j (its vectors into slot j of Kz / Zs) and its small side: mc_small_kernel when mc is given
+hipError_t launch_bt_condition(Context &c, const BatchWs &ws, const BtSmall &s, const McSmall *mc, int j, int kb,
+                               double lie, double sf) {
+    TGP_TRY(launch_query_front(c, ws.Zraw + (long)j * c.D, ws.Zs + (long)j * c.Dp, ws.Kz + (long)j * c.Np, ws.hw, ws.v, ws.w));
+    if (mc)
+        BT_KIND_DISPATCH(mc_small_kernel, dim3(1), dim3(256), ws.Kz, ws.w, c.d_alpha, ws.Zs, *mc, j, (int)c.N, (int)c.Np,
+                         (int)c.Dp, c.constant, c.noise, c.jitter, c.y_mean, c.y_std, sf);
+    else
+        BT_KIND_DISPATCH(bt_small_kernel, dim3(1), dim3(256), ws.Kz, ws.w, c.d_alpha, ws.Zs, s, j, (int)c.N, (int)c.Np,
+                         (int)c.Dp, c.constant, c.noise, c.jitter, c.y_mean, c.y_std, kb, lie, sf);
     return hipGetLastError();
 }
 
-// the pass over every candidate for point j, its update, and (acq != NONE) selection k from the result
-hipError_t launch_bt_step(Context &c, const BtSmall &s, int j, const double *Cs, int64_t ldpart, const double *Zs,
-                          const double *w, double *part, double *G, int store, double *mu, double *var,
-                          unsigned char *mask, int acq, double sf, double param, double *bval, long long *bidx,
-                          unsigned long long *clamp, double *mu_out, double *sigma_out, int k) {
-    const int js = bt_pass_splits(c, c.M);
-    const dim3 gp((unsigned)((c.M + BT_CT - 1) / BT_CT), (unsigned)js);
-    BT_KIND_DISPATCH(bt_pass_kernel, gp, dim3(256), Cs, c.d_Xs, w, part, (int)c.M, (int)c.N, (int)c.Np, (int)c.Dp,
-                     c.constant, (long)ldpart);
-    TGP_TRY(hipGetLastError());
-    BtUpd u{};
-    u.cand = c.d_cand; u.ls = c.d_ls; u.zs = Zs + (long)j * c.Dp;
-    u.part = part; u.njs = js; u.ldpart = ldpart;
-    u.G = G; u.ldG = (long)c.M; u.j = j; u.store = store;
-    u.s = s;
-    u.mu = mu; u.var = var; u.mask = mask;
+// the pass over every candidate for the point whose w is in ws.w
+static hipError_t launch_bt_pass(Context &c, const BatchWs &ws) {
+    const dim3 gp((unsigned)((c.M + BT_CT - 1) / BT_CT), (unsigned)ws.js);
+    BT_KIND_DISPATCH(bt_pass_kernel, gp, dim3(256), ws.Cs, c.d_Xs, ws.w, ws.part, (int)c.M, (int)c.N, (int)c.Np, (int)c.Dp,
+                     c.constant, (long)ws.Mpad);
+    return hipGetLastError();
+}
+
+static BtUpdBase bt_upd_base(const Context &c, const BatchWs &ws, int j, int acq, double sf, double param, double *sigma_out) {
+    BtUpdBase u{};
+    u.cand = c.d_cand; u.ls = c.d_ls; u.zs = ws.Zs + (long)j * c.Dp;
+    u.part = ws.part; u.njs = ws.js; u.ldpart = (long)ws.Mpad;
+    u.G = ws.G; u.ldG = (long)c.M; u.j = j;
+    u.var = ws.bvar; u.mask = ws.mask;
     u.M = (long)c.M; u.D = (int)c.D;
-    u.constant = c.constant; u.y_mean = c.y_mean; u.y_std = c.y_std;
+    u.constant = c.constant; u.y_std = c.y_std;
     u.acq = acq; u.sf = sf; u.param = param;
-    u.bval = bval; u.bidx = bidx; u.clamp = clamp;
-    u.mu_out = mu_out; u.sigma_out = sigma_out;
-    const long nblk = (long)((c.M + BT_BLOCK - 1) / BT_BLOCK);
-    BT_KIND_DISPATCH(bt_update_kernel, dim3((unsigned)nblk), dim3(BT_BLOCK), u);
+    u.bval = ws.bval; u.bidx = ws.bidx; u.clamp = reinterpret_cast<unsigned long long *>(ws.clampw);
+    u.sigma_out = sigma_out;
+    return u;
+}
+
+// selection k from the update's partials
+static hipError_t launch_bt_select(Context &c, const BatchWs &ws, const BtSmall &s, int k) {
+    hipLaunchKernelGGL(bt_argmax_kernel, dim3(1), dim3(256), 0, c.stream, ws.bval, ws.bidx, (long)ws.nblk, s, k, ws.mask,
+                       (long)c.M);
+    return hipGetLastError();
+}
+
+// the pass for point j, its update, and (acq != NONE) selection k from the result
+hipError_t launch_bt_step(Context &c, const BatchWs &ws, const BtSmall &s, int j, int store, int acq, double sf,
+                          double param, double *mu_out, double *sigma_out, int k) {
+    TGP_TRY(launch_bt_pass(c, ws));
+    BtUpd u{};
+    u.b = bt_upd_base(c, ws, j, acq, sf, param, sigma_out);
+    u.s = s; u.store = store; u.mu = ws.bmu; u.mu_out = mu_out;
+    BT_KIND_DISPATCH(bt_update_kernel, dim3((unsigned)ws.nblk), dim3(BT_BLOCK), u);
     TGP_TRY(hipGetLastError());
-    if (acq != TGP_ACQ_NONE) {
-        hipLaunchKernelGGL(bt_argmax_kernel, dim3(1), dim3(256), 0, c.stream, bval, bidx, nblk, s, k, mask, (long)c.M);
-        TGP_TRY(hipGetLastError());
-    }
-    return hipSuccess;
+    return acq != TGP_ACQ_NONE ? launch_bt_select(c, ws, s, k) : hipSuccess;
 }
 
 // ---- Monte Carlo launchers ----
@@ -696,42 +598,15 @@ hipError_t launch_mc_init(Context &c, const McSmall &s, int J, bool draw, unsign
     return hipGetLastError();
 }
 
-hipError_t launch_mc_condition(Context &c, const McSmall &s, int j, const double *zraw, double *Kz, double *Zs,
-                               double *hw, double *v, double *w, double sf) {
-    TGP_TRY(launch_query_front(c, zraw, Zs + (long)j * c.Dp, Kz + (long)j * c.Np, hw, v, w));
-    BT_KIND_DISPATCH(mc_small_kernel, dim3(1), dim3(256), Kz, w, c.d_alpha, Zs, s, j, (int)c.N, (int)c.Np, (int)c.Dp,
-                     c.constant, c.noise, c.jitter, c.y_mean, c.y_std, sf);
-    return hipGetLastError();
-}
-
-hipError_t launch_mc_step(Context &c, const McSmall &s, int j, const double *Cs, int64_t ldpart, const double *Zs,
-                          const double *w, double *part, double *G, const double *mu0, double *var,
-                          unsigned char *mask, int acq, double sf, double param, double *bval, long long *bidx,
-                          unsigned long long *clamp, double *acq_out, double *sigma_out, int k) {
-    const int js = bt_pass_splits(c, c.M);
-    const dim3 gp((unsigned)((c.M + BT_CT - 1) / BT_CT), (unsigned)js);
-    BT_KIND_DISPATCH(bt_pass_kernel, gp, dim3(256), Cs, c.d_Xs, w, part, (int)c.M, (int)c.N, (int)c.Np, (int)c.Dp,
-                     c.constant, (long)ldpart);
-    TGP_TRY(hipGetLastError());
+hipError_t launch_mc_step(Context &c, const BatchWs &ws, const McSmall &s, int j, int acq, double sf, double param,
+                          double *acq_out, double *sigma_out, int k) {
+    TGP_TRY(launch_bt_pass(c, ws));
     McUpd u{};
-    u.cand = c.d_cand; u.ls = c.d_ls; u.zs = Zs + (long)j * c.Dp;
-    u.part = part; u.njs = js; u.ldpart = ldpart;
-    u.G = G; u.ldG = (long)c.M; u.j = j;
-    u.s = s;
-    u.mu0 = mu0; u.var = var; u.mask = mask;
-    u.M = (long)c.M; u.D = (int)c.D;
-    u.constant = c.constant; u.y_std = c.y_std;
-    u.acq = acq; u.sf = sf; u.param = param;
-    u.bval = bval; u.bidx = bidx; u.clamp = clamp;
-    u.acq_out = acq_out; u.sigma_out = sigma_out;
-    const long nblk = (long)((c.M + BT_BLOCK - 1) / BT_BLOCK);
-    BT_KIND_DISPATCH(mc_update_kernel, dim3((unsigned)nblk), dim3(BT_BLOCK), u);
+    u.b = bt_upd_base(c, ws, j, acq, sf, param, sigma_out);
+    u.s = s; u.mu0 = ws.bmu; u.acq_out = acq_out;
+    BT_KIND_DISPATCH(mc_update_kernel, dim3((unsigned)ws.nblk), dim3(BT_BLOCK), u);
     TGP_TRY(hipGetLastError());
-    if (acq != TGP_ACQ_NONE) {
-        hipLaunchKernelGGL(bt_argmax_kernel, dim3(1), dim3(256), 0, c.stream, bval, bidx, nblk, s.b, k, mask, (long)c.M);
-        TGP_TRY(hipGetLastError());
-    }
-    return hipSuccess;
+    return acq != TGP_ACQ_NONE ? launch_bt_select(c, ws, s.b, k) : hipSuccess;
 }
 
 }  // namespace tgp

@@ -37,11 +37,7 @@ namespace tgp {
 // ---- top-k ---------------------------------------------------------------------------------
 constexpr int TOPK_PER_THREAD = 16;
 constexpr int TOPK_SLICE = 256 * TOPK_PER_THREAD;     // 4096 entries per block
-constexpr long long IDX_NONE = 0x7fffffffffffffffLL;
-
-__device__ __forceinline__ bool topk_better(double v2, long long i2, double v, long long i) {
-    return v2 > v || (v2 == v && i2 < i);
-}
+// (IDX_NONE and better(): acq_math.hpp)
 
 // vals: n entries; idx_in: their global indices (null: entry p of this level is candidate p).
 // Block b writes its k best of entries [b * SLICE, (b + 1) * SLICE) to out_v / out_i [b * k ..],
@@ -77,7 +73,7 @@ __global__ __launch_bounds__(256) void topk_kernel(const double *__restrict__ va
         int bs = 0;
 #pragma unroll
         for (int r = 0; r < TOPK_PER_THREAD; ++r)
-            if (topk_better(v[r], ix[r], bv, bi)) { bv = v[r]; bi = ix[r]; bs = r; }
+            if (better(v[r], ix[r], bv, bi)) { bv = v[r]; bi = ix[r]; bs = r; }
         int own = tid;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
@@ -85,7 +81,7 @@ __global__ __launch_bounds__(256) void topk_kernel(const double *__restrict__ va
             const long long i2 = __shfl_xor(bi, o, 64);
             const int o2 = __shfl_xor(own, o, 64);
             const int s2 = __shfl_xor(bs, o, 64);
-            if (topk_better(v2, i2, bv, bi)) { bv = v2; bi = i2; own = o2; bs = s2; }
+            if (better(v2, i2, bv, bi)) { bv = v2; bi = i2; own = o2; bs = s2; }
         }
         if (lane == 0) { sv[wave] = bv; si[wave] = bi; sown[wave] = own; sslot[wave] = bs; }
         __syncthreads();
@@ -94,7 +90,7 @@ __global__ __launch_bounds__(256) void topk_kernel(const double *__restrict__ va
         int wo = sown[0], ws = sslot[0];
 #pragma unroll
         for (int w = 1; w < 4; ++w)
-            if (topk_better(sv[w], si[w], wv, wi)) { wv = sv[w]; wi = si[w]; wo = sown[w]; ws = sslot[w]; }
+            if (better(sv[w], si[w], wv, wi)) { wv = sv[w]; wi = si[w]; wo = sown[w]; ws = sslot[w]; }
         if (tid == 0) {
             out_v[(long)blockIdx.x * k + round] = wv;
             out_i[(long)blockIdx.x * k + round] = wi;

@@ -21,6 +21,7 @@
 
 #include <algorithm>
 
+#include "acq_math.hpp"
 #include "chol64.hpp"
 #include "lbfgs_wave.hpp"
 #include "lds_opt_in.hpp"
@@ -706,15 +707,6 @@ struct SmallSweepArgs {
     int acq; double sf, incumbent, param;
 };
 
-__device__ __forceinline__ double ndtr_small(double a) {
-    // scipy.special.ndtr (cephes ndtr.c), as finalize_kernel
-    const double x = a * 0.70710678118654752440;
-    const double z = fabs(x);
-    if (z < 0.70710678118654752440) return 0.5 + 0.5 * erf(x);
-    const double y = 0.5 * erfc(z);
-    return x > 0 ? 1.0 - y : y;
-}
-
 constexpr size_t SMALL_SWEEP_LDS = (size_t)(4 * T_SZ + 1024) * sizeof(double);
 
 // MES: the max-value entropy search instance -- a compile-time case of the epilogue (the other instances keep their code);
@@ -849,8 +841,7 @@ __device__ __forceinline__ void small_sweep_body(const SmallSweepArgs &p, const 
     __syncthreads();
 
     // ---- epilogue: as finalize_kernel, one candidate per thread of the first wave ----
-    double best = -INFINITY;
-    long long bi = 0x7fffffffffffffffLL;
+    Best best;
     int clamped = 0;
     if (tid < NB) {
         const long gc = c0 + tid;
@@ -860,23 +851,7 @@ __device__ __forceinline__ void small_sweep_body(const SmallSweepArgs &p, const 
             if (var < 0.0) { var = 0.0; clamped = 1; }
             const double mu = p.y_std * red[128 + tid] + p.y_mean;
             const double sigma = sqrt(var * (p.y_std * p.y_std));
-            double a = 0.0;
-            if (p.acq == TGP_ACQ_UCB) {
-                a = p.sf * mu + p.param * sigma;
-            } else if (p.acq == TGP_ACQ_SIGMA) {
-                a = sigma;
-            } else if (p.acq == TGP_ACQ_PI || p.acq == TGP_ACQ_EI) {
-                if (sigma != 0.0) {
-                    const double diff = p.sf * (mu - p.incumbent) - p.param;
-                    const double Z = diff / sigma;
-                    if (p.acq == TGP_ACQ_PI) {
-                        a = ndtr_small(Z);
-                    } else {
-                        const double pdf = exp(-(Z * Z) / 2.0) / 2.5066282746310002;
-                        a = diff * ndtr_small(Z) + sigma * pdf;
-                    }
-                }
-            }
+            double a = acq_value(p.acq, p.sf, p.incumbent, p.param, mu, sigma);
             if constexpr (MES) {
                 double cm, cs;
                 a = mes_acq<false>(ys, mes.S, mes.noise_var, p.sf, mu, sigma, cm, cs);
@@ -884,18 +859,13 @@ __device__ __forceinline__ void small_sweep_body(const SmallSweepArgs &p, const 
             if (p.mu) p.mu[gc] = mu;
             if (p.sigma) p.sigma[gc] = sigma;
             if (p.acqv) p.acqv[gc] = a;
-            if (p.acq != TGP_ACQ_NONE) { bi = gc; if (!isnan(a)) best = a; }
+            if (p.acq != TGP_ACQ_NONE) best = candidate(a, gc);
         }
         // arg-max of the 64 candidates (value, then lowest index) and the clamp count, in-wave
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double v2 = __shfl_xor(best, o, 64);
-            const long long i2 = __shfl_xor(bi, o, 64);
-            clamped += __shfl_xor(clamped, o, 64);
-            if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
-        }
+        best = wave_argmax(best);
+        clamped = wave_sum(clamped);
         if (tid == 0) {
-            if (p.bval) { p.bval[blockIdx.x] = best; p.bidx[blockIdx.x] = bi; }
+            if (p.bval) { p.bval[blockIdx.x] = best.v; p.bidx[blockIdx.x] = best.i; }
             if (clamped) atomicAdd((unsigned long long *)&p.counters[1], (unsigned long long)clamped);
         }
     }
@@ -1287,8 +1257,7 @@ __device__ __forceinline__ void mid_sweep_body(const SmallSweepArgs &p, const Mi
     // ---- 3. epilogue: as finalize_kernel / small_sweep_kernel, one candidate per thread of the first wave ----
     __shared__ int is_last;
     if (tid < 64) {
-        double best = -INFINITY;
-        long long bi = 0x7fffffffffffffffLL;
+        Best best;
         int clamped = 0;
         const long gc = c0 + tid;
         if (tid < CPW && gc < p.M) {
@@ -1299,23 +1268,7 @@ __device__ __forceinline__ void mid_sweep_body(const SmallSweepArgs &p, const Mi
             if (var < 0.0) { var = 0.0; clamped = 1; }
             const double mu = p.y_std * (mred[tid] + mred[CPW + tid]) + p.y_mean;
             const double sigma = sqrt(var * (p.y_std * p.y_std));
-            double a = 0.0;
-            if (p.acq == TGP_ACQ_UCB) {
-                a = p.sf * mu + p.param * sigma;
-            } else if (p.acq == TGP_ACQ_SIGMA) {
-                a = sigma;
-            } else if (p.acq == TGP_ACQ_PI || p.acq == TGP_ACQ_EI) {
-                if (sigma != 0.0) {
-                    const double diff = p.sf * (mu - p.incumbent) - p.param;
-                    const double Z = diff / sigma;
-                    if (p.acq == TGP_ACQ_PI) {
-                        a = ndtr_small(Z);
-                    } else {
-                        const double pdf = exp(-(Z * Z) / 2.0) / 2.5066282746310002;
-                        a = diff * ndtr_small(Z) + sigma * pdf;
-                    }
-                }
-            }
+            double a = acq_value(p.acq, p.sf, p.incumbent, p.param, mu, sigma);
             if constexpr (MES) {
                 double cm, cs;
                 a = mes_acq<false>(ys, mes.S, mes.noise_var, p.sf, mu, sigma, cm, cs);
@@ -1323,21 +1276,16 @@ __device__ __forceinline__ void mid_sweep_body(const SmallSweepArgs &p, const Mi
             if (p.mu) p.mu[gc] = mu;
             if (p.sigma) p.sigma[gc] = sigma;
             if (p.acqv) p.acqv[gc] = a;
-            if (p.acq != TGP_ACQ_NONE) { bi = gc; if (!isnan(a)) best = a; }
+            if (p.acq != TGP_ACQ_NONE) best = candidate(a, gc);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double v2 = __shfl_xor(best, o, 64);
-            const long long i2 = __shfl_xor(bi, o, 64);
-            clamped += __shfl_xor(clamped, o, 64);
-            if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
-        }
+        best = wave_argmax(best);
+        clamped = wave_sum(clamped);
         if (tid == 0) {
             if (clamped) atomicAdd((unsigned long long *)&p.counters[1], (unsigned long long)clamped);
             is_last = 0;
             if (p.bval) {      // (a batched predict has no arg-max and nothing for a last workgroup to do)
-                p.bval[blockIdx.x] = best;
-                p.bidx[blockIdx.x] = bi;
+                p.bval[blockIdx.x] = best.v;
+                p.bidx[blockIdx.x] = best.i;
                 // the ticket: release my partials, and whoever draws the last one sees everybody's.  (Every store of
                 // this epilogue -- means, deviations, acquisition values -- came from THIS wave, so the fence's wait
                 // covers them; a polled call's outputs are mapped host memory: system scope then)
@@ -1353,26 +1301,15 @@ __device__ __forceinline__ void mid_sweep_body(const SmallSweepArgs &p, const Mi
     // ---- the last workgroup: (value, lowest index) over all workgroups, exactly argmax_final_kernel ----
     double *sv = stage;                                               // [512]
     long long *si = reinterpret_cast<long long *>(stage + 512);       // [512]
-    double v = -INFINITY;
-    long long i = 0x7fffffffffffffffLL;
+    Best all;   // (not strided_argmax: the other workgroups' partials are read with agent-scope atomic loads)
     if (p.acq != TGP_ACQ_NONE) {
         for (long b = tid; b < (long)gridDim.x; b += 512) {
             const double v2 = __hip_atomic_load(p.bval + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const long long i2 = __hip_atomic_load(p.bidx + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
+            take_better(all, v2, i2);
         }
     }
-    sv[tid] = v;
-    si[tid] = i;
-    __syncthreads();
-    for (int o = 256; o > 0; o >>= 1) {
-        if (tid < o) {
-            const double v2 = sv[tid + o];
-            const long long i2 = si[tid + o];
-            if (v2 > sv[tid] || (v2 == sv[tid] && i2 < si[tid])) { sv[tid] = v2; si[tid] = i2; }
-        }
-        __syncthreads();
-    }
+    block_argmax<512>(all, sv, si);
     if (tid == 0) {
         f.best[0] = sv[0];
         p.counters[0] = si[0];

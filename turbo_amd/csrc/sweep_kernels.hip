@@ -14,6 +14,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "acq_math.hpp"
 #include "mfma_gemm.hpp"
 #include "pairwise.hpp"
 #include "philox.hpp"
@@ -415,21 +416,6 @@ __global__ __launch_bounds__(256, 2) void kstar_kernel(const T *__restrict__ Cs,
     }
 }
 
-__device__ __forceinline__ double ndtr_dev(double a) {
-    // scipy.special.ndtr (cephes ndtr.c) behind scipy.stats.norm.cdf
-    // (scipy/stats/_continuous_distns.py:368-369)
-    const double x = a * 0.70710678118654752440;
-    const double z = fabs(x);
-    double y;
-    if (z < 0.70710678118654752440) {
-        y = 0.5 + 0.5 * erf(x);
-    } else {
-        y = 0.5 * erfc(z);
-        if (x > 0) y = 1.0 - y;
-    }
-    return y;
-}
-
 struct FinArgs {
     const double *part; long ldpart;
     // `part` has one row per 128 rows of Linv.  The 128-row-tile kernels fill every row; the 256-row-tile kernels
@@ -469,8 +455,7 @@ __device__ __forceinline__ void finalize_body(const FinArgs &f, const MesArgs &m
     }
     __syncthreads();
     const long c = (long)blockIdx.x * FIN_BLOCK + tid;
-    double best = -INFINITY;
-    long long bi = 0x7fffffffffffffffLL;
+    Best best;
     if (c < f.m) {
         double q = 0.0;
         const int npair = (c < f.pre_m && f.pre_pairs > f.base_pairs) ? f.pre_pairs : f.base_pairs;
@@ -485,23 +470,7 @@ __device__ __forceinline__ void finalize_body(const FinArgs &f, const MesArgs &m
         if (var < 0.0) { var = 0.0; atomicAdd(&sclamp, 1); }
         const double mu = f.y_std * mun + f.y_mean;
         const double sigma = sqrt(var * (f.y_std * f.y_std));
-        double a = 0.0;
-        if (f.acq == TGP_ACQ_UCB) {
-            a = f.sf * mu + f.param * sigma;
-        } else if (f.acq == TGP_ACQ_SIGMA) {
-            a = sigma;
-        } else if (f.acq == TGP_ACQ_PI || f.acq == TGP_ACQ_EI) {
-            if (sigma != 0.0) {
-                const double diff = f.sf * (mu - f.incumbent) - f.param;
-                const double Z = diff / sigma;
-                if (f.acq == TGP_ACQ_PI) {
-                    a = ndtr_dev(Z);
-                } else {
-                    const double pdf = exp(-(Z * Z) / 2.0) / 2.5066282746310002;
-                    a = diff * ndtr_dev(Z) + sigma * pdf;
-                }
-            }
-        }
+        double a = acq_value(f.acq, f.sf, f.incumbent, f.param, mu, sigma);
         if constexpr (MES) {
             double cm, cs;
             a = mes_acq<false>(ys, mes.S, mes.noise_var, f.sf, mu, sigma, cm, cs);
@@ -510,24 +479,13 @@ __device__ __forceinline__ void finalize_body(const FinArgs &f, const MesArgs &m
         if (f.mu) f.mu[gc] = mu;
         if (f.sigma) f.sigma[gc] = sigma;
         if (f.acqv) f.acqv[gc] = a;
-        if (f.acq != TGP_ACQ_NONE && !isnan(a)) { best = a; bi = gc; }
-        else if (f.acq != TGP_ACQ_NONE) { bi = gc; }
+        if (f.acq != TGP_ACQ_NONE) best = candidate(a, gc);
     }
-    sv[tid] = best;
-    si[tid] = bi;
-    __syncthreads();
-    for (int o = FIN_BLOCK / 2; o > 0; o >>= 1) {
-        if (tid < o) {
-            const double v2 = sv[tid + o];
-            const long long i2 = si[tid + o];
-            if (v2 > sv[tid] || (v2 == sv[tid] && i2 < si[tid])) { sv[tid] = v2; si[tid] = i2; }
-        }
-        __syncthreads();
-    }
+    best = block_argmax<FIN_BLOCK>(best, sv, si);
     if (tid == 0) {
         const long gb = f.off / FIN_BLOCK + blockIdx.x;
-        f.bval[gb] = sv[0];
-        f.bidx[gb] = si[0];
+        f.bval[gb] = best.v;
+        f.bidx[gb] = best.i;
         if (sclamp) atomicAdd((unsigned long long *)&f.counters[1], (unsigned long long)sclamp);
     }
 }
@@ -549,27 +507,7 @@ __global__ __launch_bounds__(256) void argmax_final_kernel(const double *__restr
                                                            double *__restrict__ res_host, Bell bell) {
     __shared__ double sv[256];
     __shared__ long long si[256];
-    double v = -INFINITY;
-    long long i = 0x7fffffffffffffffLL;
-    for (long b = threadIdx.x; b < nblk; b += 256) {
-        const double v2 = bval[b];
-        const long long i2 = bidx[b];
-        if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-    }
-    sv[threadIdx.x] = v;
-    si[threadIdx.x] = i;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) {
-            const double v2 = sv[threadIdx.x + o];
-            const long long i2 = si[threadIdx.x + o];
-            if (v2 > sv[threadIdx.x] || (v2 == sv[threadIdx.x] && i2 < si[threadIdx.x])) {
-                sv[threadIdx.x] = v2;
-                si[threadIdx.x] = i2;
-            }
-        }
-        __syncthreads();
-    }
+    block_argmax<256>(strided_argmax<256>(bval, bidx, nblk), sv, si);
     if (threadIdx.x == 0) { best[0] = sv[0]; besti[0] = si[0]; }
     if (res_host && threadIdx.x == 0) {
         // zero-copy result record (small-problem path): [best value, best index, clamp count];
@@ -832,17 +770,6 @@ static hipError_t presweep_rows_t(Context &c, hipStream_t st, int rows_final, in
 // s^2 / (c + s^2) >= prune_tau * u (u: the contraction's unit roundoff; measured |q - q_f64| / c stays below 122 u,
 // DESIGN §4) keeps every computed variance above 0.99 s^2: no skipped candidate could have clamped, and 0.99 s^2 is a valid
 // lower end of the interval.  More than prune_frac of the batch surviving: the full schedule runs instead.
-__device__ __forceinline__ double acq_at(int acq, double sf, double incumbent, double param, double mu, double sigma) {
-    // finalize_kernel's formulas
-    if (acq == TGP_ACQ_UCB) return sf * mu + param * sigma;
-    if (sigma == 0.0) return 0.0;
-    const double diff = sf * (mu - incumbent) - param;
-    const double Z = diff / sigma;
-    if (acq == TGP_ACQ_PI) return ndtr_dev(Z);
-    const double pdf = exp(-(Z * Z) / 2.0) / 2.5066282746310002;
-    return diff * ndtr_dev(Z) + sigma * pdf;
-}
-
 struct BoundArgs {
     const double *mupart, *abspart; long ldpart; int njs;   // the bound pass's partial sums, njs rows each
     long m;
@@ -863,8 +790,9 @@ __global__ __launch_bounds__(256) void prune_bound_kernel(BoundArgs b) {
     }
     const double e = b.err_scale * s;
     const double mu = b.y_std * (b.sf > 0.0 ? mun + e : mun - e) + b.y_mean;
-    const double a_lo = acq_at(b.acq, b.sf, b.incumbent, b.param, mu, b.sig_lo);
-    const double a_hi = acq_at(b.acq, b.sf, b.incumbent, b.param, mu, b.sig_hi);
+    // (EI / PI / UCB only reach the pruned sweep, so acq_value's other cases are never taken here)
+    const double a_lo = acq_value(b.acq, b.sf, b.incumbent, b.param, mu, b.sig_lo);
+    const double a_hi = acq_value(b.acq, b.sf, b.incumbent, b.param, mu, b.sig_hi);
     double a = a_lo > a_hi ? a_lo : a_hi;
     // margin against the rounding of the formulas themselves (UCB: relative to its terms, which may cancel)
     double scale = fabs(a);
@@ -880,24 +808,13 @@ __global__ __launch_bounds__(256) void prune_pick_kernel(const double *__restric
     __shared__ long long si[256];
     const long g0 = (long)blockIdx.x * gs;
     const long g1 = g0 + gs < m ? g0 + gs : m;
-    double v = -INFINITY;
-    long long i = 0x7fffffffffffffffLL;
+    Best b;   // (not strided_argmax: the values carry no index array, and a thread's own indices only ascend)
     for (long c = g0 + threadIdx.x; c < g1; c += 256) {
         const double u = ub[c];
-        if (u > v) { v = u; i = c; }
+        if (u > b.v) { b.v = u; b.i = c; }
     }
-    sv[threadIdx.x] = v;
-    si[threadIdx.x] = i;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) {
-            const double v2 = sv[threadIdx.x + o];
-            const long long i2 = si[threadIdx.x + o];
-            if (v2 > sv[threadIdx.x] || (v2 == sv[threadIdx.x] && i2 < si[threadIdx.x])) { sv[threadIdx.x] = v2; si[threadIdx.x] = i2; }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) pick[blockIdx.x] = si[0] == 0x7fffffffffffffffLL ? g0 : si[0];   // (all bounds -inf: the group's first)
+    b = block_argmax<256>(b, sv, si);
+    if (threadIdx.x == 0) pick[blockIdx.x] = b.i == IDX_NONE ? g0 : b.i;   // (all bounds -inf: the group's first)
 }
 
 // rows idx[0..n) of the scaled candidates into a dense block of `rows` rows (rows >= n zero)

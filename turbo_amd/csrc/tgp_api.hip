@@ -1682,126 +1682,174 @@ int tgp_acq_grad(tgp_handle h, const double *Xq, int64_t m, int acq, double sf, 
     return TGP_OK;
 } TGP_CATCH
 
-// Greedy batch selection (include/turbogp.h).  The first step IS a sweep (run_sweep) with the posterior kept on the
-// device; every conditioned point then costs its O(N^2) front (w_j = K^-1 k*(z_j)), a one-workgroup small side and --
-// unless it is the last one and no posterior is asked for -- one O(M N D) pass over the candidates with the update and
-// the next selection's arg-max (batch_kernels.hip).  Every step reads the previous winner from device memory: the host
-// issues everything, then waits once.
+// ---- batch selection (include/turbogp.h): what tgp_sweep_batch and tgp_sweep_batch_mc share.  The first step IS a sweep
+// (run_sweep) with the posterior kept on the device; every conditioned point then costs its O(N^2) front
+// (w_j = K^-1 k*(z_j)), a one-workgroup small side and -- unless it is the last one and nothing after it is asked for --
+// one O(M N D) pass over the candidates with the update and the next selection's arg-max (batch_kernels.hip).  Every step
+// reads the previous winner from device memory: the host issues everything, then waits once.
+
+// the checks both entries make, in the order they report; `own`: the failed check particular to the entry, or null
+static int batch_check_args(Context &c, const char *fn, int64_t q, int64_t P, const double *Xp, const char *own, int acq,
+                            double sf, const int64_t *idx_out, const double *val_out) {
+    const std::string f = std::string(fn) + ": ";
+    if (!c.fitted) return fail(c, TGP_NOT_FITTED, f + "no fitted model");
+    if (!c.d_cand || c.M < 1) return fail(c, TGP_BAD_ARG, f + "no candidates set");
+    if (q < 1 || q > c.M) return fail(c, TGP_BAD_ARG, f + "need 1 <= q <= M");
+    if (P < 0 || P + q > BT_MAXP) return fail(c, TGP_BAD_ARG, f + "need P >= 0 and P + q <= 64");
+    if (P > 0 && !Xp) return fail(c, TGP_BAD_ARG, f + "Xp is NULL with P > 0");
+    if (own) return fail(c, TGP_BAD_ARG, f + own);
+    if (acq < TGP_ACQ_UCB || acq > TGP_ACQ_SIGMA) return fail(c, TGP_BAD_ARG, f + "acq must be UCB, PI, EI or SIGMA");
+    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, f + "sf must be +1 or -1");
+    if (!idx_out || !val_out) return fail(c, TGP_BAD_ARG, f + "idx_out and val_out are required");
+    return TGP_OK;
+}
+
+// the call's buffers, carved.  mc: the Monte Carlo tail of d_bt (eps, fant and inc per simulation) in place of the greedy
+// one (fant, e, one incumbent); n_acq: rows of acq_out the steps write (Monte Carlo)
+static int batch_workspace(Context &c, int64_t J, bool mc, int64_t n_acq, BatchWs &ws) {
+    constexpr int64_t NE = (int64_t)BT_MAXP * MC_MAXS;
+    const int64_t D = c.D, Dp = c.Dp, Np = c.Np, M = c.M;
+    ws = BatchWs{};
+    ws.Mpad = ((M + 63) / 64) * 64;
+    ws.nblk = (M + 255) / 256;
+    ws.js = bt_pass_splits(c, M);
+    const size_t n_bt = (size_t)(BT_MAXP * D + BT_MAXP * Dp + BT_MAXP * Np + 3 * Np + BT_MAXP * BT_MAXP + BT_MAXP +
+                                 (mc ? 2 * NE + MC_MAXS : 2 * BT_MAXP + 8));
+    const size_t n_btm = (size_t)(ws.Mpad * Dp + ws.js * ws.Mpad + 2 * M + ws.nblk + J * M + n_acq * M);
+    const size_t n_bti = (size_t)(BT_MAXP + 2 + ws.nblk) * sizeof(long long) + (size_t)M;
+    int rc;
+    if ((rc = grow(c, c.d_bt, c.cap_bt, n_bt * sizeof(double), "hipMalloc batch state")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_btm, c.cap_btm, n_btm * sizeof(double), "hipMalloc batch arrays")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_bti, c.cap_bti, n_bti, "hipMalloc batch indices")) != TGP_OK) return rc;
+    ws.Zraw = c.d_bt; ws.Zs = ws.Zraw + BT_MAXP * D; ws.Kz = ws.Zs + BT_MAXP * Dp; ws.hw = ws.Kz + BT_MAXP * Np;
+    ws.v = ws.hw + Np; ws.w = ws.v + Np; ws.R = ws.w + Np; ws.selv = ws.R + BT_MAXP * BT_MAXP;
+    if (mc) { ws.eps = ws.selv + BT_MAXP; ws.fant = ws.eps + NE; ws.inc = ws.fant + NE; }
+    else { ws.fant = ws.selv + BT_MAXP; ws.e = ws.fant + BT_MAXP; ws.inc = ws.e + BT_MAXP; }
+    ws.Cs = c.d_btm; ws.part = ws.Cs + ws.Mpad * Dp; ws.bmu = ws.part + ws.js * ws.Mpad; ws.bvar = ws.bmu + M;
+    ws.bval = ws.bvar + M; ws.G = ws.bval + ws.nblk; ws.acqd = ws.G + J * M;
+    ws.seli = c.d_bti; ws.clampw = ws.seli + BT_MAXP; ws.flagw = ws.clampw + 1; ws.bidx = ws.flagw + 1;
+    ws.mask = reinterpret_cast<unsigned char *>(ws.bidx + ws.nblk);
+    return TGP_OK;
+}
+
+// the first sweep: means and deviations left in c.d_mu / c.d_sigma (keep_acq: its acquisition vector in c.d_acq), its
+// record in the mapped result buffer (read by the first selection on the device); the winner record of
+// tgp_set_winner_out is not this call's to pack
+static int batch_first_sweep(Context &c, int acq, double sf, double incumbent, double param, bool keep_acq,
+                             size_t pin_in_bytes, size_t pin_out_bytes, CallClock &clk) {
+    SweepCall first;
+    first.acq = acq; first.sf = sf; first.incumbent = incumbent; first.param = param;
+    first.may_use_front = c.pre.front;
+    API_HIP(pre_join(c), "hipStreamWaitEvent");
+    int rc;
+    if ((rc = ensure_outputs(c, true, true, keep_acq)) != TGP_OK) return rc;
+    if ((rc = ensure_pinned(c, pin_in_bytes, pin_out_bytes)) != TGP_OK) return rc;
+    first.mu = c.d_mu; first.sigma = c.d_sigma; first.res = c.d_pin_out;
+    if (keep_acq) first.acqv = c.d_acq;
+    return run_sweep(c, first, clk);
+}
+
+// the J = P + q conditioned points in turn: selection k = j - P read from the first sweep's record or the previous
+// step's arg-max, the strategy's condition(j), then its step(j, last, select, knext) -- skipped for the last point unless
+// run_last (something after it is asked for)
+extern "C++" template <typename Cond, typename Step>
+static int batch_steps(Context &c, const BatchWs &ws, const BtSmall &s, int64_t P, int64_t q, bool run_last, Cond condition,
+                       Step step) {
+    const int64_t J = P + q;
+    hipError_t le;
+    for (int64_t j = 0; j < J; ++j) {
+        if (j >= P) {   // selection k = j - P: the first sweep's winner, or the previous step's
+            const int64_t k = j - P;
+            le = launch_bt_point(c, (P == 0 && k == 0) ? c.d_pin_out : nullptr, s, (int)k, ws.Zraw + j * c.D, ws.mask);
+            if (le != hipSuccess) return hip_fail(c, le, "launch_bt_point");
+        }
+        if ((le = condition((int)j)) != hipSuccess) return hip_fail(c, le, "batch condition");
+        const bool last = j == J - 1;
+        if (last && !run_last) break;
+        const int64_t knext = j + 1 - P;              // the selection this step's update feeds, if any
+        const bool select = !last && knext >= 0 && knext < q;
+        if ((le = step((int)j, last, select, knext)) != hipSuccess) return hip_fail(c, le, "batch step");
+    }
+    return TGP_OK;
+}
+
+// after the wait: hi = [indices (64) | clamp count | flag] as copied back; the not-positive-definite report or idx_out
+static int batch_finish(Context &c, const char *fn, const long long *hi, int64_t P, int64_t q, int64_t *idx_out) {
+    const int flag = (int)(hi[BT_MAXP + 1] & 0xffffffff);
+    if (flag != 0) {
+        char buf[200];
+        snprintf(buf, sizeof buf, "%s: the augmented kernel matrix is not positive definite (%s point %d)", fn,
+                 flag - 1 < P ? "pending" : "selected", flag - 1 < P ? flag - 1 : (int)(flag - 1 - P));
+        return fail(c, TGP_NOT_PD, buf);
+    }
+    for (int64_t k = 0; k < q; ++k) idx_out[k] = (int64_t)hi[k];
+    return TGP_OK;
+}
+
+// Greedy batch selection with Kriging Believer / Constant Liar
 int tgp_sweep_batch(tgp_handle h, int64_t q, int strategy, double lie, const double *Xp, int64_t P, int acq, double sf,
                     double incumbent, double param, int64_t *idx_out, double *val_out, double *x_out,
                     double *fantasy_out, double *mu_out, double *sigma_out, int64_t *n_clamped) try {
     if (!h) return TGP_BAD_ARG;
     HOST_NA("tgp_sweep_batch");
     Context &c = h->c;
-    if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_sweep_batch: no fitted model");
-    if (!c.d_cand || c.M < 1) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: no candidates set");
-    if (q < 1 || q > c.M) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: need 1 <= q <= M");
-    if (P < 0 || P + q > BT_MAXP) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: need P >= 0 and P + q <= 64");
-    if (P > 0 && !Xp) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: Xp is NULL with P > 0");
-    if (strategy != TGP_BATCH_KB && strategy != TGP_BATCH_CL) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: unknown strategy");
-    if (strategy == TGP_BATCH_CL && !std::isfinite(lie)) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: the lie must be finite");
-    if (acq < TGP_ACQ_UCB || acq > TGP_ACQ_SIGMA) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: acq must be UCB, PI, EI or SIGMA");
-    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: sf must be +1 or -1");
-    if (!idx_out || !val_out) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch: idx_out and val_out are required");
-    API_HIP(hipSetDevice(c.device), "hipSetDevice");
-    // ---- the first sweep: means and deviations left in c.d_mu / c.d_sigma, its record in the mapped result buffer (read
-    // by the first selection on the device); the winner record of tgp_set_winner_out is not this call's to pack
-    SweepCall first;
-    first.acq = acq; first.sf = sf; first.incumbent = incumbent; first.param = param;
-    first.may_use_front = c.pre.front;
-    API_HIP(pre_join(c), "hipStreamWaitEvent");
+    const char *own = (strategy != TGP_BATCH_KB && strategy != TGP_BATCH_CL) ? "unknown strategy"
+                      : (strategy == TGP_BATCH_CL && !std::isfinite(lie))    ? "the lie must be finite"
+                                                                             : nullptr;
     int rc;
-    if ((rc = ensure_outputs(c, true, true, false)) != TGP_OK) return rc;
-    const int64_t D = c.D, Dp = c.Dp, Np = c.Np, M = c.M, J = P + q;
-    if ((rc = ensure_pinned(c, (size_t)(P * D + 8) * sizeof(double), 8 * sizeof(double))) != TGP_OK) return rc;
-    first.mu = c.d_mu; first.sigma = c.d_sigma; first.res = c.d_pin_out;
-
-    // ---- the call's buffers
-    const int64_t Mpad = ((M + 63) / 64) * 64;        // rows of the scaled candidates and of the pass partials
-    const int64_t nblk = (M + 255) / 256;             // arg-max partials of the update
-    const int js = bt_pass_splits(c, M);
-    const size_t n_bt = (size_t)(BT_MAXP * D + BT_MAXP * Dp + BT_MAXP * Np + 3 * Np + BT_MAXP * BT_MAXP + 4 * BT_MAXP + 8);
-    const size_t n_btm = (size_t)(Mpad * Dp + js * Mpad + 2 * M + nblk + J * M);
-    const size_t n_bti = (size_t)(BT_MAXP + 2 + nblk) * sizeof(long long) + (size_t)M;
-    if ((rc = grow(c, c.d_bt, c.cap_bt, n_bt * sizeof(double), "hipMalloc batch state")) != TGP_OK) return rc;
-    if ((rc = grow(c, c.d_btm, c.cap_btm, n_btm * sizeof(double), "hipMalloc batch arrays")) != TGP_OK) return rc;
-    if ((rc = grow(c, c.d_bti, c.cap_bti, n_bti, "hipMalloc batch indices")) != TGP_OK) return rc;
-    double *Zraw = c.d_bt, *Zs = Zraw + BT_MAXP * D, *Kz = Zs + BT_MAXP * Dp, *hw = Kz + BT_MAXP * Np, *v = hw + Np,
-           *w = v + Np, *Rb = w + Np, *eb = Rb + BT_MAXP * BT_MAXP, *fant = eb + BT_MAXP, *selv = fant + BT_MAXP,
-           *inc = selv + BT_MAXP;
-    double *Cs = c.d_btm, *part = Cs + Mpad * Dp, *bmu = part + js * Mpad, *bvar = bmu + M, *bval = bvar + M,
-           *G = bval + nblk;
-    long long *seli = c.d_bti, *clampw = seli + BT_MAXP, *flagw = clampw + 1, *bidx = flagw + 1;
-    unsigned char *mask = reinterpret_cast<unsigned char *>(bidx + nblk);
-    const BtSmall s{Rb, eb, fant, inc, selv, seli, reinterpret_cast<int *>(flagw)};
-
+    if ((rc = batch_check_args(c, "tgp_sweep_batch", q, P, Xp, own, acq, sf, idx_out, val_out)) != TGP_OK) return rc;
+    API_HIP(hipSetDevice(c.device), "hipSetDevice");
+    const int64_t D = c.D, M = c.M, J = P + q;
+    BatchWs ws;
+    if ((rc = batch_workspace(c, J, false, 0, ws)) != TGP_OK) return rc;
+    const BtSmall s{ws.R, ws.e, ws.fant, ws.inc, ws.selv, ws.seli, reinterpret_cast<int *>(ws.flagw)};
     CallClock clk;
-    if ((rc = run_sweep(c, first, clk)) != TGP_OK) return rc;
+    rc = batch_first_sweep(c, acq, sf, incumbent, param, false, (size_t)(P * D + 8) * sizeof(double), 8 * sizeof(double), clk);
+    if (rc != TGP_OK) return rc;
     hipError_t le;
 
     // ---- the steps
     double *pin = c.h_pin_in;
     if (P > 0) memcpy(pin, Xp, (size_t)(P * D) * sizeof(double));
     pin[P * D] = incumbent;
-    if (P > 0) API_HIP(hipMemcpyAsync(Zraw, pin, (size_t)(P * D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D pending");
-    API_HIP(hipMemcpyAsync(inc, pin + P * D, sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D incumbent");
-    API_HIP(hipMemsetAsync(w, 0, (size_t)Np * sizeof(double), c.stream), "memset w");
-    API_HIP(hipMemsetAsync(clampw, 0, 2 * sizeof(long long), c.stream), "memset counters");
-    if ((le = launch_bt_prep(c, Cs, Mpad)) != hipSuccess) return hip_fail(c, le, "launch_bt_prep");
-    if ((le = launch_bt_init(c, bmu, bvar, mask)) != hipSuccess) return hip_fail(c, le, "launch_bt_init");
+    if (P > 0) API_HIP(hipMemcpyAsync(ws.Zraw, pin, (size_t)(P * D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D pending");
+    API_HIP(hipMemcpyAsync(ws.inc, pin + P * D, sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D incumbent");
+    API_HIP(hipMemsetAsync(ws.w, 0, (size_t)c.Np * sizeof(double), c.stream), "memset w");
+    API_HIP(hipMemsetAsync(ws.clampw, 0, 2 * sizeof(long long), c.stream), "memset counters");
+    if ((le = launch_bt_prep(c, ws.Cs, ws.Mpad)) != hipSuccess) return hip_fail(c, le, "launch_bt_prep");
+    if ((le = launch_bt_init(c, ws.bmu, ws.bvar, ws.mask)) != hipSuccess) return hip_fail(c, le, "launch_bt_init");
     const int kb = strategy == TGP_BATCH_KB;
-    const bool want_post = mu_out || sigma_out;
-    for (int64_t j = 0; j < J; ++j) {
-        double *zj = Zraw + j * D;
-        if (j >= P) {   // selection k = j - P: the first sweep's winner, or the previous step's
-            const int64_t k = j - P;
-            le = launch_bt_point(c, (P == 0 && k == 0) ? c.d_pin_out : nullptr, s, (int)k, zj, mask);
-            if (le != hipSuccess) return hip_fail(c, le, "launch_bt_point");
-        }
-        if ((le = launch_bt_condition(c, s, (int)j, zj, Kz, Zs, hw, v, w, kb, lie, sf)) != hipSuccess)
-            return hip_fail(c, le, "launch_bt_condition");
-        const bool last = j == J - 1;
-        if (last && !want_post) break;
-        const int64_t knext = j + 1 - P;              // the selection this step's update feeds, if any
-        const bool select = !last && knext >= 0 && knext < q;
-        le = launch_bt_step(c, s, (int)j, Cs, Mpad, Zs, w, part, G, last ? 0 : 1, bmu, bvar, mask,
-                            select ? acq : TGP_ACQ_NONE, sf, param, bval, bidx,
-                            reinterpret_cast<unsigned long long *>(clampw), last ? c.d_mu : nullptr,
-                            last ? c.d_sigma : nullptr, (int)knext);
-        if (le != hipSuccess) return hip_fail(c, le, "launch_bt_step");
-    }
+    rc = batch_steps(c, ws, s, P, q, mu_out || sigma_out,
+                     [&](int j) { return launch_bt_condition(c, ws, s, nullptr, j, kb, lie, sf); },
+                     [&](int j, bool last, bool select, int64_t knext) {
+                         return launch_bt_step(c, ws, s, j, last ? 0 : 1, select ? acq : TGP_ACQ_NONE, sf, param,
+                                               last ? c.d_mu : nullptr, last ? c.d_sigma : nullptr, (int)knext);
+                     });
+    if (rc != TGP_OK) return rc;
     if ((rc = call_stop(c, clk)) != TGP_OK) return rc;
 
     // ---- one wait
-    std::vector<double> hs((size_t)(BT_MAXP * D + 2 * BT_MAXP));
+    std::vector<double> hs((size_t)(BT_MAXP * D + 2 * BT_MAXP));   // [points (64 D) | sel_val (64) | fantasies (64)]
     std::vector<long long> hi((size_t)BT_MAXP + 2);
-    API_HIP(hipMemcpyAsync(hs.data(), Zraw, (size_t)(BT_MAXP * D) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H points");
-    API_HIP(hipMemcpyAsync(hs.data() + BT_MAXP * D, fant, (size_t)(2 * BT_MAXP) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H fantasies");
-    API_HIP(hipMemcpyAsync(hi.data(), seli, (size_t)(BT_MAXP + 2) * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H indices");
+    API_HIP(hipMemcpyAsync(hs.data(), ws.Zraw, (size_t)(BT_MAXP * D) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H points");
+    API_HIP(hipMemcpyAsync(hs.data() + BT_MAXP * D, ws.selv, (size_t)(2 * BT_MAXP) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H fantasies");
+    API_HIP(hipMemcpyAsync(hi.data(), ws.seli, (size_t)(BT_MAXP + 2) * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H indices");
     const size_t bytes = (size_t)M * sizeof(double);
     if (mu_out) API_HIP(hipMemcpyAsync(mu_out, c.d_mu, bytes, hipMemcpyDeviceToHost, c.stream), "D2H mu");
     if (sigma_out) API_HIP(hipMemcpyAsync(sigma_out, c.d_sigma, bytes, hipMemcpyDeviceToHost, c.stream), "D2H sigma");
     if ((rc = call_finish(c, clk, c.last_sweep_ms, "sweep_batch sync")) != TGP_OK) return rc;
-    const int flag = (int)(hi[BT_MAXP + 1] & 0xffffffff);
-    if (flag != 0) {
-        char buf[200];
-        snprintf(buf, sizeof buf, "tgp_sweep_batch: the augmented kernel matrix is not positive definite (%s point %d)",
-                 flag - 1 < P ? "pending" : "selected", flag - 1 < P ? flag - 1 : (int)(flag - 1 - P));
-        return fail(c, TGP_NOT_PD, buf);
-    }
+    if ((rc = batch_finish(c, "tgp_sweep_batch", hi.data(), P, q, idx_out)) != TGP_OK) return rc;
     for (int64_t k = 0; k < q; ++k) {
-        idx_out[k] = (int64_t)hi[k];
-        val_out[k] = hs[BT_MAXP * D + BT_MAXP + k];
+        val_out[k] = hs[BT_MAXP * D + k];
         if (x_out) memcpy(x_out + k * D, hs.data() + (P + k) * D, (size_t)D * sizeof(double));
     }
-    if (fantasy_out) memcpy(fantasy_out, hs.data() + BT_MAXP * D, (size_t)J * sizeof(double));
+    if (fantasy_out) memcpy(fantasy_out, hs.data() + BT_MAXP * D + BT_MAXP, (size_t)J * sizeof(double));
     if (n_clamped) *n_clamped = (int64_t)c.h_pin_out[2] + (int64_t)hi[BT_MAXP];
     return TGP_OK;
 } TGP_CATCH
 
-// The Monte Carlo strategy (include/turbogp.h): tgp_sweep_batch's schedule -- the first sweep, then per conditioned point
-// its front, a one-workgroup small side and one pass with the update and the next arg-max -- with S simulations of
-// every point's outcome carried through the small side and the update (batch_kernels.hip).  One wait.
+// The Monte Carlo strategy: the same schedule with S simulations of every point's outcome carried through the small side
+// and the update (batch_kernels.hip)
 int tgp_sweep_batch_mc(tgp_handle h, int64_t q, int64_t S, uint64_t seed, const double *eps_in, const double *Xp, int64_t P,
                        int acq, double sf, double incumbent, double param, int64_t *idx_out, double *val_out,
                        double *x_out, double *fantasy_out, double *eps_out, double *acq_out, double *sigma_out,
@@ -1809,128 +1857,78 @@ int tgp_sweep_batch_mc(tgp_handle h, int64_t q, int64_t S, uint64_t seed, const 
     if (!h) return TGP_BAD_ARG;
     HOST_NA("tgp_sweep_batch_mc");
     Context &c = h->c;
-    if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_sweep_batch_mc: no fitted model");
-    if (!c.d_cand || c.M < 1) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: no candidates set");
-    if (q < 1 || q > c.M) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: need 1 <= q <= M");
-    if (P < 0 || P + q > BT_MAXP) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: need P >= 0 and P + q <= 64");
-    if (P > 0 && !Xp) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: Xp is NULL with P > 0");
-    if (S < 1 || S > MC_MAXS) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: need 1 <= S <= 64");
-    if (acq < TGP_ACQ_UCB || acq > TGP_ACQ_SIGMA) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: acq must be UCB, PI, EI or SIGMA");
-    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: sf must be +1 or -1");
-    if (!idx_out || !val_out) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: idx_out and val_out are required");
-    const int64_t D = c.D, Dp = c.Dp, Np = c.Np, M = c.M, J = P + q;
+    int rc;
+    if ((rc = batch_check_args(c, "tgp_sweep_batch_mc", q, P, Xp, (S < 1 || S > MC_MAXS) ? "need 1 <= S <= 64" : nullptr, acq,
+                               sf, idx_out, val_out)) != TGP_OK)
+        return rc;
+    const int64_t D = c.D, M = c.M, J = P + q;
     if (eps_in)
         for (int64_t i = 0; i < S * J; ++i)
             if (!std::isfinite(eps_in[i])) return fail(c, TGP_BAD_ARG, "tgp_sweep_batch_mc: eps_in must be finite");
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
-    // ---- the first sweep, as tgp_sweep_batch's (its acquisition vector kept when it is row 0 of acq_out)
-    const bool first_acq = acq_out && P == 0;
-    SweepCall first;
-    first.acq = acq; first.sf = sf; first.incumbent = incumbent; first.param = param;
-    first.may_use_front = c.pre.front;
-    API_HIP(pre_join(c), "hipStreamWaitEvent");
-    int rc;
-    if ((rc = ensure_outputs(c, true, true, first_acq)) != TGP_OK) return rc;
+    const bool first_acq = acq_out && P == 0;                      // the first sweep's vector is row 0 of acq_out
+    const int64_t n_acq = acq_out ? (first_acq ? q - 1 : q) : 0;   // rows of acq_out the steps write
+    BatchWs ws;
+    if ((rc = batch_workspace(c, J, true, n_acq, ws)) != TGP_OK) return rc;
+    McSmall s{};
+    s.b = BtSmall{ws.R, nullptr, nullptr, nullptr, ws.selv, ws.seli, reinterpret_cast<int *>(ws.flagw)};
+    s.eps = ws.eps; s.fant = ws.fant; s.inc = ws.inc; s.S = (int)S;
     constexpr int64_t NE = (int64_t)BT_MAXP * MC_MAXS;
     // result staging (pinned, so the copies back are not staged): [sweep record (8) | x (q D) | sel_val (64) | eps (J 64) |
     // fantasies (J 64) | indices, clamp count, flag (66)]
     const size_t n_pout = (size_t)(8 + q * D + BT_MAXP + 2 * J * MC_MAXS + BT_MAXP + 2);
-    if ((rc = ensure_pinned(c, (size_t)(P * D + NE + 8) * sizeof(double), n_pout * sizeof(double))) != TGP_OK) return rc;
-    first.mu = c.d_mu; first.sigma = c.d_sigma; first.res = c.d_pin_out;
-    if (first_acq) first.acqv = c.d_acq;
-
-    // ---- the call's buffers (tgp_sweep_batch's regions, laid out for this call)
-    const int64_t Mpad = ((M + 63) / 64) * 64;
-    const int64_t nblk = (M + 255) / 256;
-    const int js = bt_pass_splits(c, M);
-    const int64_t n_acq = acq_out ? (first_acq ? q - 1 : q) : 0;   // rows of acq_out the steps write
-    const size_t n_bt = (size_t)(BT_MAXP * D + BT_MAXP * Dp + BT_MAXP * Np + 3 * Np + BT_MAXP * BT_MAXP + BT_MAXP + 2 * NE + MC_MAXS);
-    const size_t n_btm = (size_t)(Mpad * Dp + js * Mpad + 2 * M + nblk + J * M + n_acq * M);
-    const size_t n_bti = (size_t)(BT_MAXP + 2 + nblk) * sizeof(long long) + (size_t)M;
-    if ((rc = grow(c, c.d_bt, c.cap_bt, n_bt * sizeof(double), "hipMalloc batch state")) != TGP_OK) return rc;
-    if ((rc = grow(c, c.d_btm, c.cap_btm, n_btm * sizeof(double), "hipMalloc batch arrays")) != TGP_OK) return rc;
-    if ((rc = grow(c, c.d_bti, c.cap_bti, n_bti, "hipMalloc batch indices")) != TGP_OK) return rc;
-    double *Zraw = c.d_bt, *Zs = Zraw + BT_MAXP * D, *Kz = Zs + BT_MAXP * Dp, *hw = Kz + BT_MAXP * Np, *v = hw + Np,
-           *w = v + Np, *Rb = w + Np, *selv = Rb + BT_MAXP * BT_MAXP, *epsd = selv + BT_MAXP, *fant = epsd + NE,
-           *inc = fant + NE;
-    double *Cs = c.d_btm, *part = Cs + Mpad * Dp, *bmu = part + js * Mpad, *bvar = bmu + M, *bval = bvar + M,
-           *G = bval + nblk, *acqd = G + J * M;
-    long long *seli = c.d_bti, *clampw = seli + BT_MAXP, *flagw = clampw + 1, *bidx = flagw + 1;
-    unsigned char *mask = reinterpret_cast<unsigned char *>(bidx + nblk);
-    McSmall s{};
-    s.b = BtSmall{Rb, nullptr, nullptr, nullptr, selv, seli, reinterpret_cast<int *>(flagw)};
-    s.eps = epsd; s.fant = fant; s.inc = inc; s.S = (int)S;
-
     CallClock clk;
-    if ((rc = run_sweep(c, first, clk)) != TGP_OK) return rc;
+    rc = batch_first_sweep(c, acq, sf, incumbent, param, first_acq, (size_t)(P * D + NE + 8) * sizeof(double),
+                           n_pout * sizeof(double), clk);
+    if (rc != TGP_OK) return rc;
     hipError_t le;
 
     // ---- the steps
     double *pin = c.h_pin_in;
     if (P > 0) {
         memcpy(pin, Xp, (size_t)(P * D) * sizeof(double));
-        API_HIP(hipMemcpyAsync(Zraw, pin, (size_t)(P * D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D pending");
+        API_HIP(hipMemcpyAsync(ws.Zraw, pin, (size_t)(P * D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D pending");
     }
     if (eps_in) {   // (S, J) -> point-major (64, 64), zero elsewhere
         double *pe = pin + P * D;
         memset(pe, 0, (size_t)NE * sizeof(double));
         for (int64_t si = 0; si < S; ++si)
             for (int64_t j = 0; j < J; ++j) pe[j * MC_MAXS + si] = eps_in[si * J + j];
-        API_HIP(hipMemcpyAsync(epsd, pe, (size_t)NE * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D eps");
+        API_HIP(hipMemcpyAsync(ws.eps, pe, (size_t)NE * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D eps");
     }
-    API_HIP(hipMemsetAsync(w, 0, (size_t)Np * sizeof(double), c.stream), "memset w");
-    API_HIP(hipMemsetAsync(clampw, 0, 2 * sizeof(long long), c.stream), "memset counters");
+    API_HIP(hipMemsetAsync(ws.w, 0, (size_t)c.Np * sizeof(double), c.stream), "memset w");
+    API_HIP(hipMemsetAsync(ws.clampw, 0, 2 * sizeof(long long), c.stream), "memset counters");
     if ((le = launch_mc_init(c, s, (int)J, eps_in == nullptr, (unsigned long long)seed, incumbent)) != hipSuccess)
         return hip_fail(c, le, "launch_mc_init");
-    if ((le = launch_bt_prep(c, Cs, Mpad)) != hipSuccess) return hip_fail(c, le, "launch_bt_prep");
-    if ((le = launch_bt_init(c, bmu, bvar, mask)) != hipSuccess) return hip_fail(c, le, "launch_bt_init");
-    for (int64_t j = 0; j < J; ++j) {
-        double *zj = Zraw + j * D;
-        if (j >= P) {   // selection k = j - P: the first sweep's winner, or the previous step's
-            const int64_t k = j - P;
-            le = launch_bt_point(c, (P == 0 && k == 0) ? c.d_pin_out : nullptr, s.b, (int)k, zj, mask);
-            if (le != hipSuccess) return hip_fail(c, le, "launch_bt_point");
-        }
-        if ((le = launch_mc_condition(c, s, (int)j, zj, Kz, Zs, hw, v, w, sf)) != hipSuccess)
-            return hip_fail(c, le, "launch_mc_condition");
-        const bool last = j == J - 1;
-        if (last && !sigma_out) break;
-        const int64_t knext = j + 1 - P;              // the selection this step's update feeds, if any
-        const bool select = !last && knext >= 0 && knext < q;
-        double *arow = (select && acq_out) ? acqd + (knext - (first_acq ? 1 : 0)) * M : nullptr;
-        le = launch_mc_step(c, s, (int)j, Cs, Mpad, Zs, w, part, G, bmu, bvar, mask, select ? acq : TGP_ACQ_NONE, sf,
-                            param, bval, bidx, reinterpret_cast<unsigned long long *>(clampw), arow,
-                            last ? c.d_sigma : nullptr, (int)knext);
-        if (le != hipSuccess) return hip_fail(c, le, "launch_mc_step");
-    }
+    if ((le = launch_bt_prep(c, ws.Cs, ws.Mpad)) != hipSuccess) return hip_fail(c, le, "launch_bt_prep");
+    if ((le = launch_bt_init(c, ws.bmu, ws.bvar, ws.mask)) != hipSuccess) return hip_fail(c, le, "launch_bt_init");
+    rc = batch_steps(c, ws, s.b, P, q, sigma_out != nullptr,
+                     [&](int j) { return launch_bt_condition(c, ws, s.b, &s, j, 0, 0.0, sf); },
+                     [&](int j, bool last, bool select, int64_t knext) {
+                         double *arow = (select && acq_out) ? ws.acqd + (knext - (first_acq ? 1 : 0)) * M : nullptr;
+                         return launch_mc_step(c, ws, s, j, select ? acq : TGP_ACQ_NONE, sf, param, arow,
+                                               last ? c.d_sigma : nullptr, (int)knext);
+                     });
+    if (rc != TGP_OK) return rc;
     if ((rc = call_stop(c, clk)) != TGP_OK) return rc;
 
     // ---- one wait: only what was asked for, and of eps / fantasies only the J rows in use (point-major: contiguous)
     double *h_x = c.h_pin_out + 8, *h_selv = h_x + q * D, *h_eps = h_selv + BT_MAXP, *h_fant = h_eps + J * MC_MAXS;
     long long *hi = reinterpret_cast<long long *>(h_fant + J * MC_MAXS);
     const size_t d8 = sizeof(double);
-    if (x_out) API_HIP(hipMemcpyAsync(h_x, Zraw + P * D, (size_t)(q * D) * d8, hipMemcpyDeviceToHost, c.stream), "D2H points");
-    API_HIP(hipMemcpyAsync(h_selv, selv, (size_t)q * d8, hipMemcpyDeviceToHost, c.stream), "D2H values");
-    if (eps_out) API_HIP(hipMemcpyAsync(h_eps, epsd, (size_t)(J * MC_MAXS) * d8, hipMemcpyDeviceToHost, c.stream), "D2H eps");
-    if (fantasy_out) API_HIP(hipMemcpyAsync(h_fant, fant, (size_t)(J * MC_MAXS) * d8, hipMemcpyDeviceToHost, c.stream), "D2H fantasies");
-    API_HIP(hipMemcpyAsync(hi, seli, (size_t)(BT_MAXP + 2) * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H indices");
+    if (x_out) API_HIP(hipMemcpyAsync(h_x, ws.Zraw + P * D, (size_t)(q * D) * d8, hipMemcpyDeviceToHost, c.stream), "D2H points");
+    API_HIP(hipMemcpyAsync(h_selv, ws.selv, (size_t)q * d8, hipMemcpyDeviceToHost, c.stream), "D2H values");
+    if (eps_out) API_HIP(hipMemcpyAsync(h_eps, ws.eps, (size_t)(J * MC_MAXS) * d8, hipMemcpyDeviceToHost, c.stream), "D2H eps");
+    if (fantasy_out) API_HIP(hipMemcpyAsync(h_fant, ws.fant, (size_t)(J * MC_MAXS) * d8, hipMemcpyDeviceToHost, c.stream), "D2H fantasies");
+    API_HIP(hipMemcpyAsync(hi, ws.seli, (size_t)(BT_MAXP + 2) * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H indices");
     const size_t bytes = (size_t)M * d8;
     if (first_acq) API_HIP(hipMemcpyAsync(acq_out, c.d_acq, bytes, hipMemcpyDeviceToHost, c.stream), "D2H acq");
     if (n_acq > 0)
-        API_HIP(hipMemcpyAsync(acq_out + (first_acq ? M : 0), acqd, (size_t)n_acq * bytes, hipMemcpyDeviceToHost, c.stream), "D2H acq");
+        API_HIP(hipMemcpyAsync(acq_out + (first_acq ? M : 0), ws.acqd, (size_t)n_acq * bytes, hipMemcpyDeviceToHost, c.stream), "D2H acq");
     if (sigma_out) API_HIP(hipMemcpyAsync(sigma_out, c.d_sigma, bytes, hipMemcpyDeviceToHost, c.stream), "D2H sigma");
     if ((rc = call_finish(c, clk, c.last_sweep_ms, "sweep_batch_mc sync")) != TGP_OK) return rc;
-    const int flag = (int)(hi[BT_MAXP + 1] & 0xffffffff);
-    if (flag != 0) {
-        char buf[200];
-        snprintf(buf, sizeof buf, "tgp_sweep_batch_mc: the augmented kernel matrix is not positive definite (%s point %d)",
-                 flag - 1 < P ? "pending" : "selected", flag - 1 < P ? flag - 1 : (int)(flag - 1 - P));
-        return fail(c, TGP_NOT_PD, buf);
-    }
-    for (int64_t k = 0; k < q; ++k) {
-        idx_out[k] = (int64_t)hi[k];
-        val_out[k] = h_selv[k];
-    }
+    if ((rc = batch_finish(c, "tgp_sweep_batch_mc", hi, P, q, idx_out)) != TGP_OK) return rc;
+    for (int64_t k = 0; k < q; ++k) val_out[k] = h_selv[k];
     if (x_out) memcpy(x_out, h_x, (size_t)(q * D) * d8);
     if (first_acq)   // row 0 is the first sweep's vector: NaN -> -inf, the convention of the steps' rows
         for (int64_t x = 0; x < M; ++x)

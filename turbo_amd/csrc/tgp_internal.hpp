@@ -319,18 +319,30 @@ struct BtSmall {                   // the small state of one call (device memory
     long long *sel_idx;            // (64) candidate index of each selection
     int *flag;                     // first point whose pivot failed + 1, or 0
 };
+// one batch call's regions of d_bt / d_btm / d_bti, named once for both strategies (tgp_api.hip carves them)
+struct BatchWs {
+    int64_t Mpad, nblk;            // rows of the scaled candidates and of the pass partials; arg-max partials of the update
+    int js;                        // training-point splits of the pass
+    double *Zraw, *Zs, *Kz, *hw, *v, *w, *R, *selv;   // d_bt: the conditioned points' vectors and the small state ...
+    double *fant, *inc;            // ... greedy: fant (64) right behind selv, inc [1]; Monte Carlo: fant (64, 64), inc (64)
+    double *e, *eps;               // ... greedy only: e (64); Monte Carlo only: eps (64, 64)
+    double *Cs, *part, *bmu, *bvar, *bval, *G, *acqd;  // d_btm (acqd: the Monte Carlo acq_out rows)
+    long long *seli, *clampw, *flagw, *bidx;          // d_bti: clampw and flagw right behind seli (one copy back)
+    unsigned char *mask;           // ... and the selection mask last
+};
 // launch_query's front for one point: uq = x / l, ks = k*(x), v = Linv ks, w = Linv^T v (query_kernels.hip)
 hipError_t launch_query_front(Context &c, const double *d_xq, double *uq, double *ks, double *hw, double *v, double *w);
 int bt_pass_splits(const Context &c, int64_t M);   // training-point splits of the pass = rows of its partials
 hipError_t launch_bt_prep(Context &c, double *Cs, int64_t Mpad);
 hipError_t launch_bt_init(Context &c, double *mu, double *var, unsigned char *mask);   // from c.d_mu / c.d_sigma of the first sweep
 hipError_t launch_bt_point(Context &c, const double *rec, const BtSmall &s, int k, double *zraw, unsigned char *mask);
-hipError_t launch_bt_condition(Context &c, const BtSmall &s, int j, const double *zraw, double *Kz, double *Zs,
-                               double *hw, double *v, double *w, int kb, double lie, double sf);
-hipError_t launch_bt_step(Context &c, const BtSmall &s, int j, const double *Cs, int64_t ldpart, const double *Zs,
-                          const double *w, double *part, double *G, int store, double *mu, double *var,
-                          unsigned char *mask, int acq, double sf, double param, double *bval, long long *bidx,
-                          unsigned long long *clamp, double *mu_out, double *sigma_out, int k);
+struct McSmall;
+// launch_bt_condition: the front of point j and its small side (mc given: mc_small_kernel); launch_bt_step: the pass, the
+// update and (acq != NONE) selection k
+hipError_t launch_bt_condition(Context &c, const BatchWs &ws, const BtSmall &s, const McSmall *mc, int j, int kb,
+                               double lie, double sf);
+hipError_t launch_bt_step(Context &c, const BatchWs &ws, const BtSmall &s, int j, int store, int acq, double sf,
+                          double param, double *mu_out, double *sigma_out, int k);
 // tgp_sweep_batch_mc (batch_kernels.hip): the Monte Carlo strategy, S <= 64 simulations of every conditioned point
 constexpr int MC_MAXS = 64;
 struct McSmall {
@@ -342,12 +354,8 @@ struct McSmall {
 };
 // eps from the Philox stream (draw) or left as the caller copied it; inc[s] = incumbent
 hipError_t launch_mc_init(Context &c, const McSmall &s, int J, bool draw, unsigned long long seed, double incumbent);
-hipError_t launch_mc_condition(Context &c, const McSmall &s, int j, const double *zraw, double *Kz, double *Zs,
-                               double *hw, double *v, double *w, double sf);
-hipError_t launch_mc_step(Context &c, const McSmall &s, int j, const double *Cs, int64_t ldpart, const double *Zs,
-                          const double *w, double *part, double *G, const double *mu0, double *var,
-                          unsigned char *mask, int acq, double sf, double param, double *bval, long long *bidx,
-                          unsigned long long *clamp, double *acq_out, double *sigma_out, int k);
+hipError_t launch_mc_step(Context &c, const BatchWs &ws, const McSmall &s, int j, int acq, double sf, double param,
+                          double *acq_out, double *sigma_out, int k);
 
 // Thompson sampling (ts_kernels.hip): S <= 64 sample paths of the fitted model, F random Fourier features
 struct TsDraw {

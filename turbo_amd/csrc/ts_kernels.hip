@@ -310,24 +310,9 @@ __global__ __launch_bounds__(256) void ts_argmax_part_kernel(const double *__res
     const int tid = threadIdx.x;
     const int s = s0 + (int)blockIdx.y;
     const long x = (long)blockIdx.x * 256 + tid;
-    double best = -INFINITY;
-    long long bi = 0x7fffffffffffffffLL;
-    if (x < M && !mask[x]) {
-        const double a = sf * f[x * S + s];
-        if (!isnan(a)) best = a;
-        bi = x;
-    }
-    sv[tid] = best;
-    si[tid] = bi;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) {
-            const double v2 = sv[tid + o];
-            const long long i2 = si[tid + o];
-            if (v2 > sv[tid] || (v2 == sv[tid] && i2 < si[tid])) { sv[tid] = v2; si[tid] = i2; }
-        }
-        __syncthreads();
-    }
+    Best best;
+    if (x < M && !mask[x]) best = candidate(sf * f[x * S + s], x);
+    block_argmax<256>(best, sv, si);
     if (tid == 0) {
         bval[(long)blockIdx.y * nblk + blockIdx.x] = sv[0];
         bidx[(long)blockIdx.y * nblk + blockIdx.x] = si[0];
@@ -346,27 +331,7 @@ __global__ __launch_bounds__(256) void ts_argmax_final_kernel(const double *__re
     const int j = blockIdx.x, s = s0 + j;
     const double *bv = bval + (long)j * nblk;
     const long long *bx = bidx + (long)j * nblk;
-    double v = -INFINITY;
-    long long i = 0x7fffffffffffffffLL;
-    for (long b = threadIdx.x; b < nblk; b += 256) {
-        const double v2 = bv[b];
-        const long long i2 = bx[b];
-        if (v2 > v || (v2 == v && i2 < i)) { v = v2; i = i2; }
-    }
-    sv[threadIdx.x] = v;
-    si[threadIdx.x] = i;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            const double v2 = sv[threadIdx.x + o];
-            const long long i2 = si[threadIdx.x + o];
-            if (v2 > sv[threadIdx.x] || (v2 == sv[threadIdx.x] && i2 < si[threadIdx.x])) {
-                sv[threadIdx.x] = v2;
-                si[threadIdx.x] = i2;
-            }
-        }
-        __syncthreads();
-    }
+    block_argmax<256>(strided_argmax<256>(bv, bx, nblk), sv, si);
     long long w = si[0];
     if (w < 0 || w >= M) w = M - 1;   // (never: S <= M with distinct leaves an unmasked row, and every one takes part)
     for (int d = threadIdx.x; d < D; d += 256) sel_x[(long)s * D + d] = cand[w * D + d];
