@@ -75,7 +75,7 @@ enum tgp_buffer { TGP_BUF_K = 0, TGP_BUF_L = 1, TGP_BUF_LINV = 2, TGP_BUF_ALPHA 
  * :371, :448, :574-577), which need not own an MI355X.  A host handle serves tgp_fit, tgp_fit_append
  * (as a full fit), tgp_export_state / tgp_import_state (the same blob), tgp_debug_read (L, alpha),
  * tgp_set_candidates, tgp_read_candidates, tgp_get_candidate, tgp_sweep, tgp_evaluate, tgp_predict,
- * tgp_mes_set_maxima and the timing queries, always in float64 (csrc/host_backend.cpp: plain C++, its own arithmetic -- not
+ * tgp_mes_set_maxima, tgp_predict_cov, tgp_sample_joint (eps_in given) and the timing queries, always in float64 (csrc/host_backend.cpp: plain C++, its own arithmetic -- not
  * the HIP kernels, not the test oracle); every other entry returns TGP_BAD_ARG on it. */
 #define TGP_DEVICE_HOST (-1)
 int tgp_create(int device, int dtype, tgp_handle *out);
@@ -370,6 +370,43 @@ int tgp_ts_read(tgp_handle h, double *omega, double *b, double *W, double *eps);
 int tgp_mes_set_maxima(tgp_handle h, const double *ystar, int64_t S);
 int tgp_mes_draw(tgp_handle h, uint64_t seed, int64_t S, int64_t F, double sf, double incumbent, double *ystar_out);
 
+/* The JOINT posterior over m <= 4096 host points Xq (m, D): what the model the reference wraps answers with
+ * predict(return_cov=True) -- sklearn _gpr.py:454-469: V = solve_triangular(L, K*^T), y_cov = kernel_(X) - V^T V, times
+ * y_train_std^2 -- and what its sample_y draws from (:498-535, rng.multivariate_normal(y_mean, y_cov, n_samples)); the
+ * reference's SciKitGPSurrogate.ModelInstance.predict (turbo/modules/surrogates.py:332-338) keeps the diagonal only, and its
+ * roadmap asks the Surrogate for "sampling methods" (docs/source/refactor.md:54-62).  In normalised units (u = x / l, c the
+ * constant, k0 the unit kernel):
+ *   Ks = c k0(Xq, X) (m, N);  V = Linv Ks^T (N, m);  Sigma = c k0(Xq, Xq) + [latent ? 0 : noise] I - V^T V (m, m)
+ *   mu = y_mean + y_std Ks alpha;  raw covariance = y_std^2 Sigma
+ * The noise goes on the diagonal only, duplicated query rows included (sklearn's WhiteKernel(X)); the jitter is not in Sigma
+ * (kernel_(X) does not carry sklearn's alpha).  latent = 0: the diagonal is tgp_predict's sigma^2 before its clamp;
+ * latent = 1: the latent function's covariance, the quantity the Thompson and MES sections above define.  Always float64.
+ * tgp_predict_cov
+ *   mu_out (m) nullable; cov_out (m, m) row-major, raw units, symmetric BIT FOR BIT (the lower triangle is computed, the
+ *   upper one is its copy), the same bits from run to run, and an entry depends on its own two points only: pair (i, j)
+ *   has the same bits whatever other points travel with it.  Negative diagonal entries are NOT clamped (sklearn does not
+ *   clamp y_cov); n_negative_diag (nullable) counts them.
+ * tgp_sample_joint: S exact joint samples,  y_out[s, j] = mu[j] + y_std (Lc eps[s, :])[j],  y_out (S, m)
+ *   Lc         the lower Cholesky factor of Sigma + nugget I (nugget >= 0 and finite), under the fit's pivot rule with the
+ *              row's own diagonal entry as the scale: TGP_NOT_PD when a pivot's square is <= 8 eps (that diagonal entry of
+ *              Sigma + nugget I) or not finite -- exactly duplicated query rows with latent = 1 and nugget = 0 are
+ *              therefore TGP_NOT_PD (sklearn's multivariate_normal falls back to an SVD there; here the nugget is explicit)
+ *   1 <= S <= 4096
+ *   eps_in     NULL: eps[s, j] is a Philox-4x32-10 normal keyed by `seed`, counter (element lo, element hi, 0, tag "COVJ"),
+ *              element s 4096 + j, the 53-bit uniforms and the Box-Muller branch of the Thompson draw (csrc/philox.hpp):
+ *              sample s depends neither on S nor on m.  Else (S, m) finite standard normals used as they are (quasi-random
+ *              or common random numbers)
+ *   eps_out (S, m) the normals used, mu_out (m): nullable
+ * Both: TGP_NOT_FITTED without a model; TGP_BAD_ARG for m or S out of range or non-finite input.  They work on every fitted
+ * GPU handle (all size classes, a factor received with tgp_import_factor_dev included) and touch neither the fit, the
+ * resident candidates, the winner record, a Thompson draw nor the MES maxima.  Host handles serve both in plain C++
+ * (csrc/host_backend.cpp: the Recorder's reload path, turbo/recorder.py:157-163 -- posterior sample paths plotted where no
+ * GPU is visible); tgp_sample_joint needs eps_in there (the Philox draw is device code): NULL is TGP_BAD_ARG. */
+int tgp_predict_cov(tgp_handle h, const double *Xq, int64_t m, int latent,
+                    double *mu_out, double *cov_out, int64_t *n_negative_diag);
+int tgp_sample_joint(tgp_handle h, const double *Xq, int64_t m, int64_t S, int latent, double nugget,
+                     uint64_t seed, const double *eps_in, double *y_out, double *eps_out, double *mu_out);
+
 /* The sweep of tgp_sweep, returning the k <= 64 BEST candidates instead of the single best:
  * vals[0..k) descending, idxs[0..k) their indices (lowest index first among equal values, NaN
  * last, -1 when the batch holds fewer than k candidates).  This is
@@ -614,7 +651,9 @@ int tgp_profile_reset(tgp_handle h);
  * first kernel-matrix tile in LDS, first block factored, fit done, call done (0 when the last fit was not polled).
  * Slots [12..14] (not times): what the last tgp_sweep did about pruning -- -1 not eligible, -2 gated off by the
  * noise, 0 the pruned schedule ran, 1 it fell back to every candidate -- and the candidates of its lb set and its
- * survivors (TGP_SWEEP_PRUNE). */
+ * survivors (TGP_SWEEP_PRUNE).
+ * Slot [15]: device time (ms) of the kernels of the last tgp_predict_cov / tgp_sample_joint, the copies of its inputs and
+ * outputs left out (0 on host handles). */
 int tgp_last_timings(tgp_handle h, double *out, int64_t n);
 /* Candidates per trmm launch (chunk) and padded N used by the sweep, for the roofline maths. */
 int tgp_sweep_geometry(tgp_handle h, int64_t *chunk, int64_t *n_padded);

@@ -41,7 +41,7 @@ SYMBOLS = (
     "tgp_fit_append", "tgp_export_state", "tgp_import_state", "tgp_export_factor_dev", "tgp_import_factor_dev", "tgp_debug_read",
     "tgp_set_candidates", "tgp_set_candidates_dev", "tgp_gen_candidates", "tgp_gen_candidates_lhs", "tgp_lhs_design",
     "tgp_read_candidates", "tgp_get_candidate",
-    "tgp_sweep", "tgp_sweep_batch", "tgp_sweep_batch_mc", "tgp_ts_draw", "tgp_ts_sweep", "tgp_ts_eval", "tgp_ts_read", "tgp_mes_set_maxima", "tgp_mes_draw", "tgp_sweep_topk", "tgp_set_winner_out", "tgp_winner_wait", "tgp_acq_grad", "tgp_acq_refine", "tgp_acq_lbfgsb",
+    "tgp_sweep", "tgp_sweep_batch", "tgp_sweep_batch_mc", "tgp_ts_draw", "tgp_ts_sweep", "tgp_ts_eval", "tgp_ts_read", "tgp_mes_set_maxima", "tgp_mes_draw", "tgp_predict_cov", "tgp_sample_joint", "tgp_sweep_topk", "tgp_set_winner_out", "tgp_winner_wait", "tgp_acq_grad", "tgp_acq_refine", "tgp_acq_lbfgsb",
     "tgp_evaluate", "tgp_predict_batch", "tgp_predict", "tgp_profile_enable", "tgp_profile_read", "tgp_profile_reset",
     "tgp_sweep_geometry", "tgp_last_timings",
     "tgp_multi_create", "tgp_multi_destroy", "tgp_multi_last_error", "tgp_multi_size", "tgp_multi_handle",
@@ -144,6 +144,8 @@ def _argtypes():
         "tgp_ts_read": [_vp, _dp, _dp, _dp, _dp],
         "tgp_mes_set_maxima": [_vp, _dp, c.c_int64],
         "tgp_mes_draw": [_vp, c.c_uint64, c.c_int64, c.c_int64, c.c_double, c.c_double, _dp],
+        "tgp_predict_cov": [_vp, _dp, c.c_int64, c.c_int, _dp, _dp, _i64p],
+        "tgp_sample_joint": [_vp, _dp, c.c_int64, c.c_int64, c.c_int, c.c_double, c.c_uint64, _dp, _dp, _dp, _dp],
         "tgp_acq_refine": [_vp, _dp, c.c_int64, _dp, _dp, c.c_int, c.c_double, c.c_double, c.c_double,
                            c.c_int64, _dp, _dp, _i64p, _i64p],
         "tgp_acq_lbfgsb": [_vp, _dp, c.c_int64, _dp, _dp, c.c_int, c.c_double, c.c_double, c.c_double,
@@ -780,6 +782,34 @@ class NativeGP:
                                           _ptr(out)))
         self.ts_S, self.ts_F = int(S), int(F)
         return out[:int(S)]
+
+    def predict_cov(self, Xq, latent=False):
+        """``tgp_predict_cov``: the joint posterior over m <= 4096 points -- mu (m,), cov (m, m) in raw units (symmetric
+        bit for bit; the noise on the diagonal unless ``latent``) and the number of negative diagonal entries (not
+        clamped, as sklearn's ``predict(return_cov=True)`` does not).  Works on host handles too."""
+        Xq = _f64c(np.atleast_2d(Xq))
+        assert Xq.ndim == 2 and Xq.shape[1] == self.D, "points must be (m, %d)" % self.D
+        m = Xq.shape[0]
+        mu, cov = np.empty(max(m, 1)), np.empty((max(m, 1), max(m, 1)))
+        neg = ctypes.c_int64(0)
+        self._check(self.lib.tgp_predict_cov(self._h, _ptr(Xq), m, 1 if latent else 0, _ptr(mu), _ptr(cov), ctypes.byref(neg)))
+        return mu, cov, neg.value
+
+    def sample_joint(self, Xq, n_samples=1, seed=0, eps=None, latent=False, nugget=1e-10):
+        """``tgp_sample_joint``: ``n_samples`` <= 4096 exact joint samples at m <= 4096 points, y = mu + y_std Lc eps with
+        Lc the Cholesky factor of the joint covariance + ``nugget`` I.  ``eps`` None: the normals come from the Philox
+        stream of ``seed`` (GPU handles only); else (n_samples, m) standard normals used as they are.  Returns a dict:
+        y (n_samples, m), eps (n_samples, m), mu (m,).  ``numpy.linalg.LinAlgError`` when a pivot fails."""
+        Xq = _f64c(np.atleast_2d(Xq))
+        assert Xq.ndim == 2 and Xq.shape[1] == self.D, "points must be (m, %d)" % self.D
+        m, S = Xq.shape[0], int(n_samples)
+        if eps is not None:
+            eps = _f64c(np.asarray(eps, dtype=np.float64))
+            assert eps.shape == (S, m), "eps must be (n_samples, m) = (%d, %d)" % (S, m)
+        y, eo, mu = np.empty((max(S, 1), max(m, 1))), np.empty((max(S, 1), max(m, 1))), np.empty(max(m, 1))
+        self._check(self.lib.tgp_sample_joint(self._h, _ptr(Xq), m, S, 1 if latent else 0, float(nugget), int(seed) % (1 << 64),
+                                              _ptr(eps), _ptr(y), _ptr(eo), _ptr(mu)))
+        return dict(y=y, eps=eo, mu=mu)
 
     def sweep_topk(self, k, acq, sf=1.0, incumbent=0.0, param=0.0):
         """the k best resident candidates: (indices (k,), values (k,)), best first"""

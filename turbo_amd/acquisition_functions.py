@@ -699,3 +699,25 @@ class MES(AcquisitionFunction):
 
         def refine(self, starting_points, bounds, max_iter=200):
             self._refuse('the on-device optimiser (on_device=True, tgp_acq_refine)')
+
+
+def joint_ei(model, Xb, desired_extremum, incumbent, xi=0.01, n_samples=512, seed=None, eps=None, latent=False,
+             nugget=1e-10):
+    """The Monte Carlo q-EI of a batch: the expected improvement of the BEST of the q points of ``Xb`` (q, D), q <= 4096,
+    under their joint posterior,
+
+        mean_s max(0, max_j (sf (y_sj - incumbent) - xi)),   y_s ~ N(mu(Xb), cov(Xb)),   sf = +1 ('max') / -1 ('min')
+
+    with the sign convention of ``EI`` (for q = 1 it converges to ``EI(xi)``'s closed form).  The samples come from
+    ``model.sample_y`` (``tgp_sample_joint``: exact joint samples); the average is host arithmetic on the
+    (n_samples, q) values.  ``seed`` / ``eps`` / ``latent`` / ``nugget`` as ``sample_y``; the same ``eps`` for two batches
+    compares them under common random numbers.  Scores what ``CandidateSweep.select_batch`` or any other batch rule
+    chose.  Native models only."""
+    if not _is_native(model):
+        raise ValueError('joint_ei serves native models only: it needs a model built by HipGPSurrogate (got {!r}) for '
+                         'the joint posterior its samples come from'.format(type(model)))
+    assert desired_extremum in ('min', 'max')
+    sf = 1.0 if desired_extremum == 'max' else -1.0
+    y = model.sample_y(Xb, n_samples=n_samples, seed=seed, eps=eps, latent=latent, nugget=nugget)   # (q, S)
+    best = (sf * (y - float(incumbent)) - float(xi)).max(axis=0)
+    return float(np.maximum(best, 0.0).mean())

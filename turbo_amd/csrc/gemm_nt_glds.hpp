@@ -19,7 +19,8 @@ namespace tgp {
 
 enum KRangeNt { KN_FULL = 0,      // [0, K)
                 KN_LOWER_A = 1,   // A lower-triangular rows: [0, min(K, (tm+1)*128))
-                KN_UPPER_A = 2 }; // A upper-triangular rows: [tm*128, K)
+                KN_UPPER_A = 2,   // A upper-triangular rows: [tm*128, K)
+                KN_LOWER_B = 3 }; // B lower-triangular rows: [0, min(K, (tn+1)*128))
 
 struct GemmNtArgs {
     const void *A; const void *B; void *C;
@@ -71,6 +72,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_glds_kernel(GemmNtArgs g) {
     int kb = 0, ke = g.K;
     if (KR == KN_LOWER_A) { const int lim = (tm + 1) * BM; ke = lim < g.K ? lim : g.K; }
     if (KR == KN_UPPER_A) { kb = tm * BM; }
+    if (KR == KN_LOWER_B) { const int lim = (tn + 1) * BN; ke = lim < g.K ? lim : g.K; }
 
     const T *A = reinterpret_cast<const T *>(g.A) + (long)blockIdx.z * g.strideA;
     const T *B = reinterpret_cast<const T *>(g.B) + (long)blockIdx.z * g.strideB;

@@ -131,6 +131,19 @@ int tgp_predict(tgp_handle h, const double *Xc, int64_t M, double *mu, double *s
     return tgp_evaluate(h, Xc, M, TGP_ACQ_NONE, 1.0, 0.0, 0.0, mu, sigma, nullptr, nullptr, nullptr, nullptr);
 }
 
+int tgp_predict_cov(tgp_handle h, const double *Xq, int64_t m, int latent, double *mu_out, double *cov_out,
+                    int64_t *n_negative_diag) {
+    if (!h) return TGP_BAD_ARG;
+    HOST_TRY(h->g.predict_cov(Xq, m, latent, mu_out, cov_out, n_negative_diag))
+}
+
+int tgp_sample_joint(tgp_handle h, const double *Xq, int64_t m, int64_t S, int latent, double nugget, uint64_t seed,
+                     const double *eps_in, double *y_out, double *eps_out, double *mu_out) {
+    if (!h) return TGP_BAD_ARG;
+    (void)seed;   // (only the device draws: a host handle needs eps_in)
+    HOST_TRY(h->g.sample_joint(Xq, m, S, latent, nugget, eps_in, y_out, eps_out, mu_out))
+}
+
 int tgp_mt19937_uniform_columns(uint32_t *key624, int32_t *pos, int64_t M, int64_t D, const double *lo, const double *hi,
                                 double *out) {
     try {

@@ -429,6 +429,98 @@ int HostGP::sweep(int acq, double sf, double incumbent, double param, double *mu
     return TGP_OK;
 }
 
+// ---- the joint posterior over m query points (include/turbogp.h: tgp_predict_cov, tgp_sample_joint) ----------------
+void HostGP::joint_posterior(const double *Xq, int64_t m, double diag_add, double *mu, double *Sigma) const {
+    const int64_t n = N, d = D;
+    std::vector<double> us((size_t)(m * d)), Vt((size_t)(m * n));
+    for (int64_t i = 0; i < m; ++i)
+        for (int64_t k = 0; k < d; ++k) us[(size_t)(i * d + k)] = Xq[i * d + k] / ls[(size_t)k];   // X / length_scale
+    const double *xs = Xs.data(), *Lp = L.data(), *al = alpha.data(), *up = us.data();
+    double *vt = Vt.data();
+    const double c = constant, ym = y_mean, ys = y_std;
+    const int kern = kernel;
+    // row i of Vt = (L^-1 k*(x_i))^T by forward substitution, and the mean
+    parallel_for(m, threads_for((double)m * (double)n * (double)(n / 2 + d + 8)), [=](int64_t b, int64_t e) {
+        for (int64_t i = b; i < e; ++i) {
+            double *v = vt + i * n;
+            double s = 0.0;
+            for (int64_t j = 0; j < n; ++j) {
+                double d2 = 0.0;
+                for (int64_t k = 0; k < d; ++k) { const double df = up[i * d + k] - xs[j * d + k]; d2 += df * df; }
+                v[j] = kernel_value(kern, d2, c);
+                s += v[j] * al[j];
+            }
+            mu[i] = ym + ys * s;
+            for (int64_t j = 0; j < n; ++j) v[j] = (v[j] - dot(Lp + j * n, v, j)) / Lp[j * n + j];
+        }
+    });
+    // the lower triangle, then its mirror: symmetric bit for bit
+    parallel_for(m, threads_for((double)m * (double)m * (double)(n + d) / 2.0), [=](int64_t b, int64_t e) {
+        for (int64_t i = b; i < e; ++i)
+            for (int64_t j = 0; j <= i; ++j) {
+                double d2 = 0.0;
+                for (int64_t k = 0; k < d; ++k) { const double df = up[i * d + k] - up[j * d + k]; d2 += df * df; }
+                const double v = (kernel_value(kern, d2, c) + (i == j ? diag_add : 0.0)) - dot(vt + i * n, vt + j * n, n);
+                Sigma[i * m + j] = v;
+                Sigma[j * m + i] = v;
+            }
+    });
+}
+
+int HostGP::predict_cov(const double *Xq, int64_t m, int latent, double *mu_out, double *cov_out, int64_t *n_negative_diag) {
+    if (!fitted) { err = "tgp_predict_cov: no fitted model"; return TGP_NOT_FITTED; }
+    if (!Xq || !cov_out || m < 1 || m > 4096) { err = "tgp_predict_cov: need Xq, cov_out and 1 <= m <= 4096"; return TGP_BAD_ARG; }
+    for (int64_t e = 0; e < m * D; ++e)
+        if (!isfinite(Xq[e])) { err = "tgp_predict_cov: Xq must be finite"; return TGP_BAD_ARG; }
+    std::vector<double> mu((size_t)m);
+    joint_posterior(Xq, m, latent ? 0.0 : noise, mu.data(), cov_out);
+    const double s2 = y_std * y_std;
+    int64_t neg = 0;
+    for (int64_t e = 0; e < m * m; ++e) cov_out[e] *= s2;
+    for (int64_t i = 0; i < m; ++i) neg += cov_out[i * m + i] < 0.0 ? 1 : 0;   // not clamped (sklearn does not clamp y_cov), counted
+    if (mu_out) memcpy(mu_out, mu.data(), (size_t)m * 8);
+    if (n_negative_diag) *n_negative_diag = neg;
+    return TGP_OK;
+}
+
+int HostGP::sample_joint(const double *Xq, int64_t m, int64_t S, int latent, double nugget, const double *eps_in,
+                         double *y_out, double *eps_out, double *mu_out) {
+    if (!fitted) { err = "tgp_sample_joint: no fitted model"; return TGP_NOT_FITTED; }
+    if (!Xq || !y_out || m < 1 || m > 4096 || S < 1 || S > 4096) { err = "tgp_sample_joint: need Xq, y_out, 1 <= m <= 4096 and 1 <= S <= 4096"; return TGP_BAD_ARG; }
+    if (!(nugget >= 0.0) || !isfinite(nugget)) { err = "tgp_sample_joint: nugget must be finite and >= 0"; return TGP_BAD_ARG; }
+    if (!eps_in) { err = "tgp_sample_joint: the host backend needs eps_in (the Philox draw is device code)"; return TGP_BAD_ARG; }
+    for (int64_t e = 0; e < m * D; ++e)
+        if (!isfinite(Xq[e])) { err = "tgp_sample_joint: Xq must be finite"; return TGP_BAD_ARG; }
+    for (int64_t e = 0; e < S * m; ++e)
+        if (!isfinite(eps_in[e])) { err = "tgp_sample_joint: eps_in must be finite"; return TGP_BAD_ARG; }
+    std::vector<double> mu((size_t)m), A((size_t)(m * m));
+    joint_posterior(Xq, m, (latent ? 0.0 : noise) + nugget, mu.data(), A.data());
+    // lower Cholesky in place, row by row; the fit's pivot rule with the row's own diagonal entry as the scale
+    double *a = A.data();
+    for (int64_t i = 0; i < m; ++i) {
+        double *ri = a + i * m;
+        const double aii = ri[i];
+        for (int64_t j = 0; j < i; ++j) ri[j] = (ri[j] - dot(ri, a + j * m, j)) / a[j * m + j];
+        const double piv = aii - dot(ri, ri, i);
+        if (!(piv > 8.0 * 2.220446049250313e-16 * aii) || !isfinite(piv)) {
+            char buf[160];
+            snprintf(buf, sizeof buf, "tgp_sample_joint: joint covariance is not positive definite (pivot %lld of %lld): raise the nugget", (long long)i, (long long)m);
+            err = buf;
+            return TGP_NOT_PD;
+        }
+        ri[i] = sqrt(piv);
+    }
+    const double ys = y_std;
+    const double *mup = mu.data();
+    parallel_for(S, threads_for((double)S * (double)m * (double)m / 2.0), [=](int64_t b, int64_t e) {
+        for (int64_t s = b; s < e; ++s)
+            for (int64_t j = 0; j < m; ++j) y_out[s * m + j] = mup[j] + ys * dot(a + j * m, eps_in + s * m, j + 1);
+    });
+    if (eps_out) memcpy(eps_out, eps_in, (size_t)(S * m) * 8);
+    if (mu_out) memcpy(mu_out, mu.data(), (size_t)m * 8);
+    return TGP_OK;
+}
+
 // ---- NumPy's legacy global RNG, continued outside the interpreter (host_backend.hpp) --------------------------------
 namespace {
 

@@ -15,6 +15,8 @@
 //   alpha, LML           _gpr.py:360-364, :584-613 (two triangular substitutions)
 //   predict              _gpr.py:443-494: K*, mu = s_y K* alpha + y_mean, v = L^-1 K*^T by forward
 //                        substitution on tiles of 16 candidates, var = (c + noise) - |v|^2, clamp
+//   joint posterior      _gpr.py:454-462 (y_cov = kernel_(X) - V^T V, lower triangle computed, mirrored) and :497-535
+//                        (sample_y) with the normals handed in: Cholesky of Sigma + nugget I under the fit's pivot rule
 //   acquisition          turbo/modules/acquisition_functions.py UCB :147-158, PI :225-247, EI :336-358;
 //                        max-value entropy search (TGP_ACQ_MES) from the maxima of mes_set_maxima, with an
 //                        erfcx of its own (the standard library has none)
@@ -55,6 +57,14 @@ struct HostGP {
     int mes_set_maxima(const double *ystar, int64_t S);
     int sweep(int acq, double sf, double incumbent, double param, double *mu, double *sigma,
               double *acq_out, double *best_val, int64_t *best_idx, int64_t *n_clamped);
+    // the joint posterior over m <= 4096 points (tgp_predict_cov / tgp_sample_joint; eps_in is required here)
+    int predict_cov(const double *Xq, int64_t m, int latent, double *mu_out, double *cov_out, int64_t *n_negative_diag);
+    int sample_joint(const double *Xq, int64_t m, int64_t S, int latent, double nugget, const double *eps_in,
+                     double *y_out, double *eps_out, double *mu_out);
+
+private:
+    // mu (m) raw and Sigma (m, m) in normalised units, both triangles, diag_add on the diagonal
+    void joint_posterior(const double *Xq, int64_t m, double diag_add, double *mu, double *Sigma) const;
 };
 
 // The candidate batch of the reference's random_selector (turbo/modules/naive_selectors.py:39-46: one

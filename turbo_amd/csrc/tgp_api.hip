@@ -305,6 +305,7 @@ static void free_ws(Context &c) {
     dfree(c.d_bt); dfree(c.d_btm); dfree(c.d_bti); c.cap_bt = c.cap_btm = c.cap_bti = 0;
     dfree(c.d_ts); dfree(c.d_tsm); c.cap_ts = c.cap_tsm = 0; c.ts_gen = -1;
     dfree(c.d_mes); c.mes_S = 0; c.mes_gen = -1;
+    dfree(c.d_cov); c.cap_cov = 0;
     c.cap_Cs = c.cap_Ks[0] = c.cap_Ks[1] = c.cap_part = c.cap_mupart = 0;
     c.ws_Mpad = 0;
 }
@@ -2154,6 +2155,101 @@ int tgp_mes_draw(tgp_handle h, uint64_t seed, int64_t S, int64_t F, double sf, d
     return TGP_OK;
 } TGP_CATCH
 
+// ---- the joint posterior over m query points (include/turbogp.h; cov_kernels.hip) ----
+// what both entries check, in the order they report; host handles are served before this
+static int cov_check(Context &c, const char *fn, const double *Xq, int64_t m, const void *out) {
+    const std::string f = std::string(fn) + ": ";
+    if (!c.fitted) return fail(c, TGP_NOT_FITTED, f + "no fitted model");
+    if (!Xq || !out || m < 1 || m > 4096) return fail(c, TGP_BAD_ARG, f + "need Xq, the output and 1 <= m <= 4096");
+    for (int64_t e = 0; e < m * c.D; ++e)
+        if (!std::isfinite(Xq[e])) return fail(c, TGP_BAD_ARG, f + "Xq must be finite");
+    return TGP_OK;
+}
+
+// the workspace (allocated on first use and kept, as the query workspace is) with Xq copied in
+static int cov_begin(Context &c, const double *Xq, int64_t m, int64_t S, CovWs &w) {
+    API_HIP(hipSetDevice(c.device), "hipSetDevice");
+    API_HIP(pre_join(c), "hipStreamWaitEvent");
+    const int64_t nd = cov_ws_doubles(c, m, S, &w);
+    int rc = grow(c, c.d_cov, c.cap_cov, (size_t)nd * sizeof(double), "hipMalloc joint posterior workspace");
+    if (rc != TGP_OK) return rc;
+    API_HIP(hipMemcpyAsync(c.d_cov + w.o_Xq, Xq, (size_t)(m * c.D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D Xq");
+    return TGP_OK;
+}
+
+// the kernels' device time between the call's two events (the copies are outside): tgp_last_timings slot 15
+static void cov_time(Context &c) {
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, c.ev0, c.ev1);
+    c.last_cov_ms = ms;
+}
+
+int tgp_predict_cov(tgp_handle h, const double *Xq, int64_t m, int latent, double *mu_out, double *cov_out,
+                    int64_t *n_negative_diag) try {
+    if (!h) return TGP_BAD_ARG;
+    if (h->host) return h->host->predict_cov(Xq, m, latent, mu_out, cov_out, n_negative_diag);
+    Context &c = h->c;
+    int rc = cov_check(c, "tgp_predict_cov", Xq, m, cov_out);
+    if (rc != TGP_OK) return rc;
+    CovWs w;
+    if ((rc = cov_begin(c, Xq, m, 0, w)) != TGP_OK) return rc;
+    API_HIP(hipEventRecord(c.ev0, c.stream), "hipEventRecord");
+    hipError_t le = launch_cov_posterior(c, c.d_cov, w, latent, 0.0, false);
+    if (le != hipSuccess) return hip_fail(c, le, "launch_cov_posterior");
+    API_HIP(hipEventRecord(c.ev1, c.stream), "hipEventRecord");
+    const size_t d8 = sizeof(double);
+    long long neg = 0;
+    API_HIP(hipMemcpy2DAsync(cov_out, (size_t)m * d8, c.d_cov + w.o_G, (size_t)w.mpad * d8, (size_t)m * d8, (size_t)m,
+                             hipMemcpyDeviceToHost, c.stream), "D2H cov");
+    if (mu_out) API_HIP(hipMemcpyAsync(mu_out, c.d_cov + w.o_mu, (size_t)m * d8, hipMemcpyDeviceToHost, c.stream), "D2H mu");
+    API_HIP(hipMemcpyAsync(&neg, c.d_cov + w.o_cnt, sizeof neg, hipMemcpyDeviceToHost, c.stream), "D2H count");
+    API_HIP(hipStreamSynchronize(c.stream), "predict_cov sync");
+    cov_time(c);
+    if (n_negative_diag) *n_negative_diag = (int64_t)neg;
+    return TGP_OK;
+} TGP_CATCH
+
+int tgp_sample_joint(tgp_handle h, const double *Xq, int64_t m, int64_t S, int latent, double nugget, uint64_t seed,
+                     const double *eps_in, double *y_out, double *eps_out, double *mu_out) try {
+    if (!h) return TGP_BAD_ARG;
+    if (h->host) return h->host->sample_joint(Xq, m, S, latent, nugget, eps_in, y_out, eps_out, mu_out);
+    Context &c = h->c;
+    int rc = cov_check(c, "tgp_sample_joint", Xq, m, y_out);
+    if (rc != TGP_OK) return rc;
+    if (S < 1 || S > 4096) return fail(c, TGP_BAD_ARG, "tgp_sample_joint: need 1 <= S <= 4096");
+    if (!(nugget >= 0.0) || !std::isfinite(nugget)) return fail(c, TGP_BAD_ARG, "tgp_sample_joint: nugget must be finite and >= 0");
+    if (eps_in)
+        for (int64_t e = 0; e < S * m; ++e)
+            if (!std::isfinite(eps_in[e])) return fail(c, TGP_BAD_ARG, "tgp_sample_joint: eps_in must be finite");
+    CovWs w;
+    if ((rc = cov_begin(c, Xq, m, S, w)) != TGP_OK) return rc;
+    const size_t d8 = sizeof(double);
+    API_HIP(hipEventRecord(c.ev0, c.stream), "hipEventRecord");
+    hipError_t le = launch_cov_posterior(c, c.d_cov, w, latent, nugget, true);
+    if (le != hipSuccess) return hip_fail(c, le, "launch_cov_posterior");
+    // (the given normals land where Ks was: behind the kernels that read it, in stream order)
+    if (eps_in) API_HIP(hipMemcpyAsync(c.d_cov + w.o_Ein, eps_in, (size_t)(S * m) * d8, hipMemcpyHostToDevice, c.stream), "H2D eps");
+    le = launch_cov_sample(c, c.d_cov, w, eps_in == nullptr, (unsigned long long)seed);
+    if (le != hipSuccess) return hip_fail(c, le, "launch_cov_sample");
+    API_HIP(hipEventRecord(c.ev1, c.stream), "hipEventRecord");
+    long long cnt[2] = {0, 0};
+    API_HIP(hipMemcpyAsync(cnt, c.d_cov + w.o_cnt, sizeof cnt, hipMemcpyDeviceToHost, c.stream), "D2H flag");
+    API_HIP(hipMemcpy2DAsync(y_out, (size_t)m * d8, c.d_cov + w.o_Y, (size_t)w.mpad * d8, (size_t)m * d8, (size_t)S,
+                             hipMemcpyDeviceToHost, c.stream), "D2H samples");
+    if (eps_out) API_HIP(hipMemcpy2DAsync(eps_out, (size_t)m * d8, c.d_cov + w.o_E, (size_t)w.mpad * d8, (size_t)m * d8, (size_t)S,
+                                          hipMemcpyDeviceToHost, c.stream), "D2H eps");
+    if (mu_out) API_HIP(hipMemcpyAsync(mu_out, c.d_cov + w.o_mu, (size_t)m * d8, hipMemcpyDeviceToHost, c.stream), "D2H mu");
+    API_HIP(hipStreamSynchronize(c.stream), "sample_joint sync");
+    cov_time(c);
+    const int flag = (int)(cnt[1] & 0xFFFFFFFFll);
+    if (flag != 0) {
+        char buf[200];
+        snprintf(buf, sizeof buf, "tgp_sample_joint: joint covariance is not positive definite (pivot %d of %lld): raise the nugget", flag - 1, (long long)m);
+        return fail(c, TGP_NOT_PD, buf);
+    }
+    return TGP_OK;
+} TGP_CATCH
+
 int tgp_sweep_topk(tgp_handle h, int acq, double sf, double incumbent, double param, int64_t k,
                    double *vals, int64_t *idxs, int64_t *n_clamped) try {
     if (!h) return TGP_BAD_ARG;
@@ -2820,15 +2916,15 @@ int tgp_last_timings(tgp_handle h, double *out, int64_t n) try {
     // inputs staged, first kernel-matrix tile in LDS, first block factored, fit done, call done (0 when the call was not polled)
     // [12..14]: what the last tgp_sweep did about pruning (sweep_pruned): -1 not eligible, -2 gated off, 0 pruned, 1 fell
     // back to every candidate; the candidates of its lb set; its survivors
-    double v[15] = {c.last_fit_ms, c.last_sweep_ms, c.last_grad_ms[0], c.last_grad_ms[1], c.last_grad_ms[2], c.trmm_flops,
+    double v[16] = {c.last_fit_ms, c.last_sweep_ms, c.last_grad_ms[0], c.last_grad_ms[1], c.last_grad_ms[2], c.trmm_flops,
                     (double)c.last_sweep_f64, 0.0, 0.0, 0.0, 0.0, 0.0, (double)c.prune_state, (double)c.prune_lbset,
-                    (double)c.prune_surv};
+                    (double)c.prune_surv, c.last_cov_ms};
     if (c.h_bell && c.h_bell[1]) {
         const unsigned long long t0 = c.h_bell[1];
         const int src[5] = {3, 4, 5, 6, 2};
         for (int k = 0; k < 5; ++k) v[7 + k] = c.h_bell[src[k]] >= t0 ? (double)(c.h_bell[src[k]] - t0) * 1e-2 : 0.0;
     }
-    for (int64_t i = 0; i < n; ++i) out[i] = i < 15 ? v[i] : 0.0;
+    for (int64_t i = 0; i < n; ++i) out[i] = i < 16 ? v[i] : 0.0;
     return TGP_OK;
 } TGP_CATCH
 

@@ -104,6 +104,9 @@ struct Context {
     size_t cap_ts = 0, cap_tsm = 0;   // bytes
     int64_t ts_S = 0, ts_F = 0;    // the resident draw's shape ...
     long ts_gen = -1;              // ... and the fit_gen it belongs to (-1: none)
+    double *d_cov = nullptr;       // tgp_predict_cov / tgp_sample_joint: the joint posterior's workspace (cov_kernels.hip), kept between calls
+    size_t cap_cov = 0;            // bytes
+    double last_cov_ms = 0.0;      // device time of the last joint-posterior call's kernels (the H2D / D2H copies not included)
     double *d_mes = nullptr;       // tgp_mes_set_maxima / tgp_mes_draw: MES_MAXS doubles, the first mes_S are the maxima
     int mes_S = 0;
     long mes_gen = -1;             // the fit_gen the maxima belong to (-1: none)
@@ -382,6 +385,21 @@ hipError_t launch_ts_select(Context &c, const TsDraw &t, const double *f, double
 // tgp_mes_draw: dst[s] = the better of src[s] and incumbent in the direction of sf (a NaN incumbent changes nothing)
 hipError_t launch_mes_take(Context &c, const double *src, int S, double sf, double incumbent, double *dst);
 size_t ts_eval_lds_bytes(const Context &c, int64_t S);
+
+// The joint posterior over m <= 4096 query points (cov_kernels.hip): one workspace, offsets in doubles
+struct CovWs {
+    int64_t m, mpad, S, Spad, NV;  // mpad / Spad: m / S in whole 128-tiles; NV: N in whole 128-tiles, the columns of Vt
+    int64_t o_cnt;                 // [0] (long long) negative entries of the diagonal, [1] (int) first failed pivot + 1
+    int64_t o_Xq, o_Us, o_mu, o_dvec, o_Dinv, o_G;   // raw and scaled points, mu, the unfactored diagonal, a block's inverse, Sigma (mpad, mpad)
+    int64_t o_Ks, o_Vt;            // (mpad, Np), (mpad, NV)
+    int64_t o_Ein, o_E, o_Y;       // (S, m) normals as given; (Spad, mpad) padded normals and samples -- in Ks / Vt's place
+};
+int64_t cov_ws_doubles(const Context &c, int64_t m, int64_t S, CovWs *out);   // S = 0: the covariance alone
+// Xq is in the workspace; leaves mu and G = y_std^2 Sigma mirrored (for_sample = false) or Sigma + nugget I with zeros
+// above the diagonal and its diagonal in dvec (for_sample = true)
+hipError_t launch_cov_posterior(Context &c, double *ws, const CovWs &w, int latent, double nugget, bool for_sample);
+// behind launch_cov_posterior(for_sample = true): G = Lc in place, E = the normals (draw: Philox, else from o_Ein), Y = the samples
+hipError_t launch_cov_sample(Context &c, double *ws, const CovWs &w, bool draw, unsigned long long seed);
 hipError_t launch_ts_eval(Context &c, const TsDraw &t, const double *Xq, int m, double *fout, double *gout);
 
 }  // namespace tgp

@@ -527,6 +527,53 @@ class HipGPSurrogate(Surrogate):
                 return res['mu'], res['sigma']
             return res['mu']
 
+        def _points(self, X):
+            X = np.asarray(X, dtype=np.float64)
+            if X.ndim == 1 and X.size > 0:
+                X = X.reshape(1, -1)
+            assert X.ndim == 2 and X.shape[1] == self.X.shape[1], \
+                'X must have shape (num_points, {})'.format(self.X.shape[1])
+            assert 1 <= X.shape[0] <= 4096, 'the joint posterior serves 1 to 4096 points per call'
+            return X
+
+        def predict_cov(self, X, latent=False):
+            """The JOINT posterior at the rows of X (m <= 4096): ``(mu (m, 1), cov (m, m))``, what the sklearn model the
+            reference wraps returns from ``predict(X, return_cov=True)`` (``tgp_predict_cov``).  ``latent=True`` leaves
+            the WhiteKernel noise off the diagonal: the covariance of the latent function.  ``cov`` is symmetric bit for
+            bit; negative diagonal entries are not clamped (sklearn does not clamp ``y_cov``) but warned about.  Works on
+            a reloaded instance where no GPU is visible (the library's host backend)."""
+            ctx = self._ensure_resident()
+            mu, cov, neg = ctx.predict_cov(self._points(X), latent)
+            if neg > 0:
+                warnings.warn('{} predicted variances on the diagonal of the joint covariance are smaller than 0'.format(neg))
+            return mu.reshape(-1, 1), cov
+
+        def sample_y(self, X, n_samples=1, seed=None, eps=None, latent=False, nugget=1e-10):
+            """``n_samples`` <= 4096 exact joint samples of the posterior at the rows of X (m <= 4096), shape
+            ``(m, n_samples)`` -- sklearn's ``sample_y`` orientation (``tgp_sample_joint``): mu + y_std Lc eps with Lc
+            the Cholesky factor of the joint covariance + ``nugget`` I (the default is the project's default jitter).
+
+            eps:  (n_samples, m) standard normals to use as they are (quasi-random, common random numbers; their row
+                  count then IS n_samples), or None:
+            seed: on the GPU the normals are Philox-4x32-10 draws keyed by ``seed`` (None: one from ``np.random``), and
+                  sample s depends neither on n_samples nor on m.  On a reloaded instance served by the host backend
+                  there is no device draw: ``eps`` is drawn with ``np.random.RandomState(seed)`` instead, so the VALUES
+                  differ from the device's for the same seed (the distribution does not).
+            Raises ``numpy.linalg.LinAlgError`` when the joint covariance is not positive definite at this nugget
+            (exactly duplicated rows with ``latent=True`` and ``nugget=0``)."""
+            ctx = self._ensure_resident()
+            X = self._points(X)
+            n_samples = int(n_samples)
+            if eps is not None:
+                eps = np.atleast_2d(np.asarray(eps, dtype=np.float64))
+                n_samples = eps.shape[0]      # (the normals given say how many samples there are)
+            if eps is None and getattr(ctx, 'host', False):
+                eps = np.random.RandomState(seed).standard_normal((n_samples, X.shape[0]))
+            if eps is None and seed is None:
+                seed = int(np.random.randint(0, 2**63))
+            res = ctx.sample_joint(X, n_samples, 0 if seed is None else seed, eps, latent, nugget)
+            return np.ascontiguousarray(res['y'].T)
+
         def get_hyper_params(self):
             return self.kernel.hyper_params()
 
