@@ -1485,9 +1485,9 @@ void device_streams_release(int device) {
 static hipError_t ensure_lookahead(Context &c, size_t nev) {
     if (!c.stream_bg) TGP_TRY(device_streams(c.device, nullptr, &c.stream_bg, &c.stream_pre));
     while (c.ev_la.size() < nev) {
-        hipEvent_t e;
-        TGP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));   // (hipEventDisableSystemFence on top: 2.49 vs 2.51 ms, not worth the weaker visibility)
-        c.ev_la.push_back(e);
+        Ev e;
+        TGP_TRY(e.create(hipEventDisableTiming));   // (hipEventDisableSystemFence on top: 2.49 vs 2.51 ms, not worth the weaker visibility)
+        c.ev_la.push_back(std::move(e));
     }
     return hipSuccess;
 }
@@ -1543,7 +1543,7 @@ hipError_t launch_fit(Context &c, const double *staged_in, double *res_host, boo
         // 96 us at 8192 when it has to run)
         if (!zero_linv) blocks = std::min<long>(blocks, std::max<long>(1, ((long)Np * Dp + 255) / 256));
         hipLaunchKernelGGL(fit_prologue_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
-                           reinterpret_cast<double2 *>(c.d_Linv), zero_linv ? NN / 2 : 0L, staged_in, c.d_Xs, (long)Np * Dp,
+                           reinterpret_cast<double2 *>(c.d_Linv.get()), zero_linv ? NN / 2 : 0L, staged_in, c.d_Xs, (long)Np * Dp,
                            c.d_yn, (long)Np, c.d_ls, (long)c.D, Dp, c.d_flag, c.d_scal, start_stamp);
         TGP_TRY(hipGetLastError());
     }
@@ -1780,11 +1780,11 @@ hipError_t launch_fit(Context &c, const double *staged_in, double *res_host, boo
     // ticks) and the fit dump them there (tools/stamp_summary.py reads the file); Np <= 8192 only
     constexpr size_t STAMP_STRIDE = FUSED_STAMP_STRIDE;
     const char *stamp_path = tuning().stamp_file.empty() ? nullptr : tuning().stamp_file.c_str();
-    // (debug only.  The buffer belongs to the handle -- free_fit releases it -- so fits on several handles, e.g.
+    // (debug only.  The buffer belongs to the handle -- it goes with the fit's memory -- so fits on several handles, e.g.
     // the threaded hyper-parameter starts, stamp buffers of their own; the FILE is the last finisher's)
     unsigned long long *stamp_dev = nullptr;
     if (stamp_path && Np <= 8192) {
-        if (!c.d_stamp) TGP_TRY(hipMalloc((void **)&c.d_stamp, 2 * 128 * STAMP_STRIDE * sizeof(unsigned long long)));
+        TGP_TRY(c.d_stamp.reserve(2 * 128 * STAMP_STRIDE * sizeof(unsigned long long)));
         TGP_TRY(hipMemsetAsync(c.d_stamp, 0, 2 * 128 * STAMP_STRIDE * sizeof(unsigned long long), s));
         stamp_dev = c.d_stamp;
     }

@@ -658,7 +658,7 @@ template <typename T>
 static hipError_t issue_prep(Context &c, hipStream_t st) {
     const long pe = (long)c.ws_Mpad * c.Dp;
     hipLaunchKernelGGL(prep_candidates_kernel<T>, dim3((unsigned)((pe + 255) / 256 < 8192 ? (pe + 255) / 256 : 8192)),
-                       dim3(256), 0, st, c.d_cand, c.d_ls, reinterpret_cast<T *>(c.d_Cs), (long)c.M, (long)c.ws_Mpad, (int)c.D, (int)c.Dp);
+                       dim3(256), 0, st, c.d_cand, c.d_ls, reinterpret_cast<T *>(c.d_Cs.get()), (long)c.M, (long)c.ws_Mpad, (int)c.D, (int)c.Dp);
     return hipGetLastError();
 }
 
@@ -690,8 +690,8 @@ static hipError_t issue_kstar(Context &c, const SweepPlan<T> &p, int64_t n, int 
     constexpr int KAR = kstar_ar(sizeof(T));
     const dim3 kgrid((unsigned)(r.rows / (16 * KAR)), (unsigned)p.njs);
     const KstarFn<T> kst = kstar_fn<T>(c.kernel, p.h2, p.x3, p.mean_in_trmm, false);
-    hipLaunchKernelGGL(kst, kgrid, dim3(256), 0, st, reinterpret_cast<const T *>(c.d_Cs) + r.off * Dp, Xs, c.d_alpha,
-                       reinterpret_cast<T *>(c.d_Ks[sl]), c.d_mupart + r.off, (int)r.rows, N, Np, Dp, c.constant,
+    hipLaunchKernelGGL(kst, kgrid, dim3(256), 0, st, reinterpret_cast<const T *>(c.d_Cs.get()) + r.off * Dp, Xs, c.d_alpha,
+                       reinterpret_cast<T *>(c.d_Ks[sl].get()), c.d_mupart + r.off, (int)r.rows, N, Np, Dp, c.constant,
                        (long)c.ws_Mpad, (long)Np / 16, p.h2_sb);   // (Np / 16: 16-k blocks per row of the pre-tiled split-operand slabs)
     return hipGetLastError();
 }
@@ -898,14 +898,7 @@ static hipError_t prune_workspace(Context &c, int64_t npick, int64_t rows_cap, P
     const size_t o_pick = al256((size_t)M * 8), o_sidx = o_pick + al256((size_t)npick * 8), o_misc = o_sidx + al256((size_t)M * 8),
                  o_bcnt = o_misc + 256, o_boff = o_bcnt + al256((size_t)nb * 4), o_cs = o_boff + al256((size_t)nb * 4);
     const size_t need = o_cs + (size_t)rows_cap * c.Dp * sizeof(T);
-    if (need > c.cap_prune) {
-        TGP_TRY(hipStreamSynchronize(c.stream));
-        if (c.d_prune) TGP_TRY(hipFree(c.d_prune));
-        c.d_prune = nullptr;
-        c.cap_prune = 0;
-        TGP_TRY(hipMalloc((void **)&c.d_prune, need));
-        c.cap_prune = need;
-    }
+    TGP_TRY(c.d_prune.reserve(need, [&] { return hipStreamSynchronize(c.stream); }));
     char *b = c.d_prune;
     w.ub = reinterpret_cast<double *>(b);
     w.pick = reinterpret_cast<long long *>(b + o_pick);
@@ -946,7 +939,7 @@ static hipError_t contract_rows(Context &c, const SweepPlan<T> &p, const T *cs, 
         const int64_t m = n - off < c.launch_rows ? n - off : c.launch_rows;
         const int64_t rows = ((m + 127) / 128) * 128;
         hipLaunchKernelGGL(kst, dim3((unsigned)(rows / (16 * KAR)), (unsigned)p.njs), dim3(256), 0, st, cs + off * Dp, Xs,
-                           c.d_alpha, reinterpret_cast<T *>(c.d_Ks[0]), c.d_mupart + off, (int)rows, N, Np, Dp, c.constant,
+                           c.d_alpha, reinterpret_cast<T *>(c.d_Ks[0].get()), c.d_mupart + off, (int)rows, N, Np, Dp, c.constant,
                            (long)c.ws_Mpad, (long)Np / 16, 1.f);
         TGP_TRY(hipGetLastError());
         int m2 = prof_mark(c, st);
@@ -988,7 +981,7 @@ static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCal
     PruneWs w;
     TGP_TRY(prune_workspace<T>(c, npick, rows_cap, w));
     TGP_TRY(lds_opt_in(c, p.early.kern, p.early.lds));   // (the request the fit's early row tiles make of the same kernel)
-    const T *Cs = reinterpret_cast<const T *>(c.d_Cs);
+    const T *Cs = reinterpret_cast<const T *>(c.d_Cs.get());
     T *cs = reinterpret_cast<T *>(w.cs);
 
     // 1. the bound of every candidate
@@ -1006,7 +999,7 @@ static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCal
         if (njs_b > p.njs) njs_b = p.njs;
         const T *Xs = reinterpret_cast<const T *>(sizeof(T) == 8 ? (const void *)c.d_Xs : (const void *)c.d_Xs32);
         hipLaunchKernelGGL(kstar_fn<T>(c.kernel, false, false, false, true), dim3((unsigned)xb, (unsigned)njs_b),
-                           dim3(256), 0, st, Cs, Xs, c.d_alpha, reinterpret_cast<T *>(c.d_part), c.d_mupart, (int)Mpad, N,
+                           dim3(256), 0, st, Cs, Xs, c.d_alpha, reinterpret_cast<T *>(c.d_part.get()), c.d_mupart, (int)Mpad, N,
                            (int)c.Np, Dp, c.constant, (long)Mpad, 0L, 1.f);
         TGP_TRY(hipGetLastError());
         const int m2 = prof_mark(c, st);

@@ -146,9 +146,9 @@ namespace tgp {
 int prof_mark(Context &c, hipStream_t s) {
     if (!c.profiling) return -1;
     if (c.ev_used == c.ev_pool.size()) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return -1; }
-        c.ev_pool.push_back(e);
+        Ev e;
+        if (e.create(hipEventDefault) != hipSuccess) { (void)hipGetLastError(); return -1; }
+        c.ev_pool.push_back(std::move(e));
     }
     if (hipEventRecord(c.ev_pool[c.ev_used], s) != hipSuccess) { (void)hipGetLastError(); return -1; }
     return (int)c.ev_used++;
@@ -206,7 +206,7 @@ static hipError_t pre_join(Context &c) {
 // the doorbell of the polled call about to be launched on this handle, or a null one (TGP_POLL_US=0)
 static Bell bell_next(Context &c) {
     Bell b{nullptr, 0, nullptr};
-    if (tuning().poll_us > 0 && c.d_bell) { b.word = c.d_bell; b.seq = ++c.bell_seq; b.ticket = c.d_ticket; }
+    if (tuning().poll_us > 0 && c.h_bell.dev()) { b.word = c.h_bell.dev(); b.seq = ++c.bell_seq; b.ticket = c.d_ticket; }
     return b;
 }
 // wait for that call: spin on the mapped word, after TGP_POLL_US (or without a bell) synchronise the stream
@@ -281,45 +281,18 @@ static int exception_status(tgp_handle h, const char *fn, const char *what, int 
     catch (const std::exception &ex_) { return exception_status(h, __func__, ex_.what(), TGP_HIP_ERROR); }       \
     catch (...) { return exception_status(h, __func__, "unknown C++ exception", TGP_HIP_ERROR); }
 
-template <typename P>
-static void dfree(P *&p) {
-    if (p) (void)hipFree((void *)p);
-    p = nullptr;
+// Growing a buffer of the handle: dev_mem.hpp's reserve() contract, with c.stream drained before the old block goes
+// (sync = false: nothing on the device can be using it -- empty, or its streams known idle)
+template <class B>
+static int grow(Context &c, B &buf, size_t need, const char *what, bool sync = true) {
+    const hipError_t e = buf.reserve(need, [&] {
+        const hipError_t se = sync ? hipStreamSynchronize(c.stream) : hipSuccess;
+        if (se != hipSuccess) what = "hipStreamSynchronize";
+        return se;
+    });
+    return e == hipSuccess ? TGP_OK : hip_fail(c, e, what);
 }
-
-static void free_fit(Context &c) {
-    dfree(c.d_Xs); dfree(c.d_ls); dfree(c.d_K); dfree(c.d_Linv); dfree(c.d_W); dfree(c.d_U); dfree(c.d_Dinv); dfree(c.d_Apan); dfree(c.d_apart);
-    dfree(c.d_yn); dfree(c.d_z); dfree(c.d_alpha); dfree(c.d_Xs32); dfree(c.d_Linv32); dfree(c.d_Linv16); dfree(c.d_x2scal);
-    dfree(c.d_t1); dfree(c.d_t2);
-    dfree(c.d_gpart); dfree(c.d_gout); dfree(c.d_qws); dfree(c.d_rf); dfree(c.d_stamp);
-    c.qws_cap = 0; c.cap_rf = 0;
-    c.cap_Np = c.cap_D = 0;
-    c.cap_full = false;
-    c.g_cap_Np = c.g_cap_Dp = 0;
-}
-static void free_ws(Context &c) {
-    dfree(c.d_Cs); dfree(c.d_Ks[0]); dfree(c.d_Ks[1]); dfree(c.d_part); dfree(c.d_mupart);
-    dfree(c.d_prune); c.cap_prune = 0;
-    dfree(c.d_topv); dfree(c.d_topi); c.cap_topv = c.cap_topi = 0;
-    dfree(c.d_batch); c.cap_batch = 0;
-    dfree(c.d_bt); dfree(c.d_btm); dfree(c.d_bti); c.cap_bt = c.cap_btm = c.cap_bti = 0;
-    dfree(c.d_ts); dfree(c.d_tsm); c.cap_ts = c.cap_tsm = 0; c.ts_gen = -1;
-    dfree(c.d_mes); c.mes_S = 0; c.mes_gen = -1;
-    dfree(c.d_cov); c.cap_cov = 0;
-    c.cap_Cs = c.cap_Ks[0] = c.cap_Ks[1] = c.cap_part = c.cap_mupart = 0;
-    c.ws_Mpad = 0;
-}
-
-template <typename P>
-static int grow(Context &c, P *&buf, size_t &cap, size_t need, const char *what) {
-    if (need <= cap) return TGP_OK;
-    API_HIP(hipStreamSynchronize(c.stream), "hipStreamSynchronize");
-    dfree(buf);
-    cap = 0;
-    API_HIP(hipMalloc((void **)&buf, need), what);
-    cap = need;
-    return TGP_OK;
-}
+#define API_MEM(call) do { const int rc_ = (call); if (rc_ != TGP_OK) return rc_; } while (0)
 
 // y normalisation (sklearn _gpr.py:272-282): mean, population std, exact-zero std -> 1
 static void normalise_targets(const double *y, int64_t N, int normalize_y, std::vector<double> &yn,
@@ -372,33 +345,26 @@ int tgp_create(int device, int dtype, tgp_handle *out) {
     auto bail = [&](hipError_t er, const char *w) {
         g_create_err = std::string(w) + ": " + hipGetErrorString(er);
         (void)hipGetLastError();
-        dfree(c.d_scal); dfree(c.d_flag); dfree(c.d_best); dfree(c.d_besti); dfree(c.d_ticket);
-        if (c.h_bell) (void)hipHostFree(c.h_bell);
-        if (c.ev0) (void)hipEventDestroy(c.ev0);
-        if (c.ev1) (void)hipEventDestroy(c.ev1);
-        if (c.pre.ev) (void)hipEventDestroy(c.pre.ev);
-        if (c.pre.ev_in) (void)hipEventDestroy(c.pre.ev_in);
         const bool had = c.stream != nullptr;
-        delete h;
+        delete h;   // (the owners give back what was created so far)
         if (had) device_streams_release(device);
         return (int)TGP_HIP_ERROR;
     };
     if ((e = hipSetDevice(device)) != hipSuccess) return bail(e, "hipSetDevice");
     if ((e = device_streams(device, &c.stream, nullptr)) != hipSuccess) return bail(e, "hipStreamCreate");
-    if ((e = hipEventCreate(&c.ev0)) != hipSuccess) return bail(e, "hipEventCreate");
-    if ((e = hipEventCreate(&c.ev1)) != hipSuccess) return bail(e, "hipEventCreate");
-    if ((e = hipEventCreateWithFlags(&c.pre.ev, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
-    if ((e = hipEventCreateWithFlags(&c.pre.ev_in, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
-    if ((e = hipMalloc((void **)&c.d_scal, 4 * sizeof(double))) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc((void **)&c.d_flag, sizeof(int))) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc((void **)&c.d_best, sizeof(double))) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc((void **)&c.d_besti, 4 * sizeof(long long))) != hipSuccess) return bail(e, "hipMalloc");
+    if ((e = c.ev0.create(hipEventDefault)) != hipSuccess) return bail(e, "hipEventCreate");
+    if ((e = c.ev1.create(hipEventDefault)) != hipSuccess) return bail(e, "hipEventCreate");
+    if ((e = c.pre.ev.create(hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
+    if ((e = c.pre.ev_in.create(hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
+    if ((e = c.d_scal.reserve(4 * sizeof(double))) != hipSuccess) return bail(e, "hipMalloc");
+    if ((e = c.d_flag.reserve(sizeof(int))) != hipSuccess) return bail(e, "hipMalloc");
+    if ((e = c.d_best.reserve(sizeof(double))) != hipSuccess) return bail(e, "hipMalloc");
+    if ((e = c.d_besti.reserve(4 * sizeof(long long))) != hipSuccess) return bail(e, "hipMalloc");
     if ((e = hipMemset(c.d_besti, 0, 4 * sizeof(long long))) != hipSuccess) return bail(e, "hipMemset");   // [1] = clamp counter, kept at zero between calls
     // the doorbell of the short calls: one cache line of coherent device-mapped host memory + ticket counters
-    if ((e = hipHostMalloc((void **)&c.h_bell, 64, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess) return bail(e, "hipHostMalloc");
+    if ((e = c.h_bell.reserve(64)) != hipSuccess) return bail(e, "hipHostMalloc");
     memset(c.h_bell, 0, 64);
-    if ((e = hipHostGetDevicePointer((void **)&c.d_bell, c.h_bell, 0)) != hipSuccess) return bail(e, "hipHostGetDevicePointer");
-    if ((e = hipMalloc((void **)&c.d_ticket, 64)) != hipSuccess) return bail(e, "hipMalloc");
+    if ((e = c.d_ticket.reserve(64)) != hipSuccess) return bail(e, "hipMalloc");
     if ((e = hipMemset(c.d_ticket, 0, 64)) != hipSuccess) return bail(e, "hipMemset");
     {
         WorkerPool &wp = g_pools[device & 63];
@@ -437,33 +403,10 @@ static int destroy_handle(tgp_handle h) {
     c.pre.pending = false;
     if (c.stream) (void)hipStreamSynchronize(c.stream);
     prof_collect(c);
-    free_fit(c);
-    free_ws(c);
-    if (c.h_pin_in) (void)hipHostFree(c.h_pin_in);
-    if (c.h_pin_out) (void)hipHostFree(c.h_pin_out);
-    if (c.h_pin_cand) (void)hipHostFree(c.h_pin_cand);
-    c.h_pin_in = c.d_pin_in = c.h_pin_out = c.d_pin_out = c.h_pin_cand = c.d_pin_cand = nullptr;
-    if (c.h_mt_words) (void)hipHostFree(c.h_mt_words);
-    c.h_mt_words = nullptr; c.mt_words_cap = 0;
-    for (int b = 0; b < 2; ++b)
-        if (c.ev_mt[b]) { (void)hipEventDestroy(c.ev_mt[b]); c.ev_mt[b] = nullptr; }
-    if (c.h_bell) (void)hipHostFree(c.h_bell);
-    c.h_bell = c.d_bell = nullptr;
-    dfree(c.d_ticket); dfree(c.d_sfg); c.cap_sfg = 0;
-    dfree(c.d_cand_owned); dfree(c.d_mu); dfree(c.d_sigma); dfree(c.d_acq);
-    dfree(c.d_bval); dfree(c.d_bidx); c.cap_bval = c.cap_bidx = 0; dfree(c.d_scal); dfree(c.d_flag); dfree(c.d_best); dfree(c.d_besti);
-    if (c.ev0) (void)hipEventDestroy(c.ev0);
-    if (c.ev1) (void)hipEventDestroy(c.ev1);
-    if (c.pre.ev) (void)hipEventDestroy(c.pre.ev);
-    if (c.pre.ev_in) (void)hipEventDestroy(c.pre.ev_in);
-    if (c.ev_winner) (void)hipEventDestroy(c.ev_winner);
-    for (int i = 0; i < 4; ++i)
-        if (c.evg[i]) (void)hipEventDestroy(c.evg[i]);
-    for (hipEvent_t e : c.ev_la) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c.ev_pool) (void)hipEventDestroy(e);
-    if (c.stream_own) { (void)hipStreamSynchronize(c.stream_own); (void)hipStreamDestroy(c.stream_own); c.stream_own = nullptr; }
     const int dev = c.device;
-    delete h;
+    const hipStream_t own = c.stream_own;
+    delete h;   // every owner frees here: the device is selected and the streams are idle
+    if (own) { (void)hipStreamSynchronize(own); (void)hipStreamDestroy(own); }
     device_streams_release(dev);
     return TGP_OK;
 }
@@ -540,8 +483,8 @@ int tgp_workers_release(tgp_handle h) try {
             (void)hipSetDevice(w->c.device);
             (void)hipStreamSynchronize(w->c.stream);
             w->c.fitted = false;
-            free_fit(w->c);
-            w->c.linv_ld = 0; w->c.linv_extent = 0;
+            static_cast<FitMem &>(w->c) = FitMem{};
+            w->c.linv_extent = 0;
         }
     }
     wp.owner.store(std::thread::id(), std::memory_order_release);
@@ -598,26 +541,13 @@ int64_t tgp_tuning(char *buf, int64_t cap) {
 
 // pinned, device-mapped host memory for the small-problem path: the kernels read their inputs
 // from it and write their scalars / small outputs to it, so a call needs no memcpy at all
+static int ensure_pinned(Context &c, Pin<double> &buf, size_t bytes) {
+    if (bytes <= buf.bytes()) return TGP_OK;
+    return grow(c, buf, std::max<size_t>(bytes, 1u << 20), "hipHostMalloc");
+}
 static int ensure_pinned(Context &c, size_t in_bytes, size_t out_bytes) {
-    if (in_bytes > c.pin_in_cap) {
-        API_HIP(hipStreamSynchronize(c.stream), "hipStreamSynchronize");
-        if (c.h_pin_in) (void)hipHostFree(c.h_pin_in);
-        c.h_pin_in = nullptr; c.d_pin_in = nullptr; c.pin_in_cap = 0;
-        const size_t cap = std::max<size_t>(in_bytes, 1u << 20);
-        API_HIP(hipHostMalloc((void **)&c.h_pin_in, cap, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc");
-        API_HIP(hipHostGetDevicePointer((void **)&c.d_pin_in, c.h_pin_in, 0), "hipHostGetDevicePointer");
-        c.pin_in_cap = cap;
-    }
-    if (out_bytes > c.pin_out_cap) {
-        API_HIP(hipStreamSynchronize(c.stream), "hipStreamSynchronize");
-        if (c.h_pin_out) (void)hipHostFree(c.h_pin_out);
-        c.h_pin_out = nullptr; c.d_pin_out = nullptr; c.pin_out_cap = 0;
-        const size_t cap = std::max<size_t>(out_bytes, 1u << 20);
-        API_HIP(hipHostMalloc((void **)&c.h_pin_out, cap, hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc");
-        API_HIP(hipHostGetDevicePointer((void **)&c.d_pin_out, c.h_pin_out, 0), "hipHostGetDevicePointer");
-        c.pin_out_cap = cap;
-    }
-    return TGP_OK;
+    API_MEM(ensure_pinned(c, c.h_pin_in, in_bytes));
+    return ensure_pinned(c, c.h_pin_out, out_bytes);
 }
 
 static bool small_path_enabled() {
@@ -634,11 +564,10 @@ static int ensure_workspace(Context &c);
 // LML-gradient workspace of the blocked path (allocated on first use, grown with the fit)
 static int ensure_grad_workspace(Context &c) {
     if (c.Np > c.g_cap_Np || c.Dp > c.g_cap_Dp) {
-        API_HIP(hipStreamSynchronize(c.stream), "hipStreamSynchronize");
-        dfree(c.d_gpart); dfree(c.d_gout);
+        c.g_cap_Np = c.g_cap_Dp = 0;   // (until both exist)
         const size_t nt = (size_t)(c.Np / 64);
-        API_HIP(hipMalloc((void **)&c.d_gpart, nt * (nt + 1) / 2 * (size_t)(3 + c.Dp) * sizeof(double)), "hipMalloc gpart");
-        API_HIP(hipMalloc((void **)&c.d_gout, (size_t)(3 + c.Dp) * sizeof(double)), "hipMalloc gout");
+        API_MEM(grow(c, c.d_gpart, nt * (nt + 1) / 2 * (size_t)(3 + c.Dp) * sizeof(double), "hipMalloc gpart"));
+        API_MEM(grow(c, c.d_gout, (size_t)(3 + c.Dp) * sizeof(double), "hipMalloc gout"));
         c.g_cap_Np = c.Np; c.g_cap_Dp = c.Dp;
     }
     return TGP_OK;
@@ -658,37 +587,35 @@ static int ensure_fit_buffers(Context &c, int64_t Np, int64_t D, bool full) {
     if (Np <= c.cap_Np && D <= c.cap_D && (c.cap_full || !full)) return TGP_OK;
     const int64_t Dp = ((D + 3) / 4) * 4;
     API_HIP(hipStreamSynchronize(c.stream), "hipStreamSynchronize");
-    free_fit(c);
+    static_cast<FitMem &>(c) = FitMem{};   // (cap_Np = 0 until the whole set exists; linv_ld = 0: contents unknown)
     const size_t nn = (size_t)Np * Np;
-    API_HIP(hipMalloc((void **)&c.d_Xs, (size_t)Np * Dp * sizeof(double)), "hipMalloc Xs");
-    API_HIP(hipMalloc((void **)&c.d_ls, (size_t)D * sizeof(double)), "hipMalloc ls");
-    API_HIP(hipMalloc((void **)&c.d_Linv, nn * sizeof(double)), "hipMalloc Linv");
+    API_MEM(grow(c, c.d_Xs, (size_t)Np * Dp * sizeof(double), "hipMalloc Xs", false));
+    API_MEM(grow(c, c.d_ls, (size_t)D * sizeof(double), "hipMalloc ls", false));
+    API_MEM(grow(c, c.d_Linv, nn * sizeof(double), "hipMalloc Linv", false));
     if (full) {
-        API_HIP(hipMalloc((void **)&c.d_K, nn * sizeof(double)), "hipMalloc K");
-        API_HIP(hipMalloc((void **)&c.d_W, nn * sizeof(double)), "hipMalloc W");
-        API_HIP(hipMalloc((void **)&c.d_U, nn * sizeof(double)), "hipMalloc U");
-        API_HIP(hipMalloc((void **)&c.d_Dinv, (size_t)2 * (Np / NB) * NB * NB * sizeof(double)), "hipMalloc Dinv");
-        API_HIP(hipMalloc((void **)&c.d_Apan, (size_t)2 * (Np / NB) * NB * NB * sizeof(double)), "hipMalloc Apan");
-        API_HIP(hipMalloc((void **)&c.d_apart, ((size_t)(Np / 128) * Np + Np / 128) * sizeof(double)), "hipMalloc alpha shares");
-        API_HIP(hipMalloc((void **)&c.d_t1, (size_t)Np * sizeof(double)), "hipMalloc t1");
-        API_HIP(hipMalloc((void **)&c.d_t2, (size_t)Np * sizeof(double)), "hipMalloc t2");
+        API_MEM(grow(c, c.d_K, nn * sizeof(double), "hipMalloc K", false));
+        API_MEM(grow(c, c.d_W, nn * sizeof(double), "hipMalloc W", false));
+        API_MEM(grow(c, c.d_U, nn * sizeof(double), "hipMalloc U", false));
+        API_MEM(grow(c, c.d_Dinv, (size_t)2 * (Np / NB) * NB * NB * sizeof(double), "hipMalloc Dinv", false));
+        API_MEM(grow(c, c.d_Apan, (size_t)2 * (Np / NB) * NB * NB * sizeof(double), "hipMalloc Apan", false));
+        API_MEM(grow(c, c.d_apart, ((size_t)(Np / 128) * Np + Np / 128) * sizeof(double), "hipMalloc alpha shares", false));
+        API_MEM(grow(c, c.d_t1, (size_t)Np * sizeof(double), "hipMalloc t1", false));
+        API_MEM(grow(c, c.d_t2, (size_t)Np * sizeof(double), "hipMalloc t2", false));
     }
-    API_HIP(hipMalloc((void **)&c.d_yn, (size_t)Np * sizeof(double)), "hipMalloc yn");
-    API_HIP(hipMalloc((void **)&c.d_z, (size_t)Np * sizeof(double)), "hipMalloc z");
-    API_HIP(hipMalloc((void **)&c.d_alpha, (size_t)Np * sizeof(double)), "hipMalloc alpha");
+    API_MEM(grow(c, c.d_yn, (size_t)Np * sizeof(double), "hipMalloc yn", false));
+    API_MEM(grow(c, c.d_z, (size_t)Np * sizeof(double), "hipMalloc z", false));
+    API_MEM(grow(c, c.d_alpha, (size_t)Np * sizeof(double), "hipMalloc alpha", false));
     if (c.dtype != TGP_F64) {
-        API_HIP(hipMalloc((void **)&c.d_Xs32, (size_t)Np * Dp * sizeof(float)), "hipMalloc Xs32");
-        API_HIP(hipMalloc((void **)&c.d_Linv32, nn * sizeof(float)), "hipMalloc Linv32");
+        API_MEM(grow(c, c.d_Xs32, (size_t)Np * Dp * sizeof(float), "hipMalloc Xs32", false));
+        API_MEM(grow(c, c.d_Linv32, nn * sizeof(float), "hipMalloc Linv32", false));
     }
     if (c.dtype == TGP_F32X3 || c.dtype == TGP_F32H2) {
-        API_HIP(hipMalloc((void **)&c.d_Linv16, (c.dtype == TGP_F32X3 ? 3 : 2) * nn * sizeof(unsigned short)), "hipMalloc Linv16");
-        if (!c.d_x2scal) API_HIP(hipMalloc((void **)&c.d_x2scal, 2 * sizeof(unsigned)), "hipMalloc x2scal");
-        c.linv16_gen = -1;
+        API_MEM(grow(c, c.d_Linv16, (c.dtype == TGP_F32X3 ? 3 : 2) * nn * sizeof(unsigned short), "hipMalloc Linv16", false));
+        API_MEM(grow(c, c.d_x2scal, 2 * sizeof(unsigned), "hipMalloc x2scal", false));
     }
     c.cap_Np = Np;
     c.cap_D = D;
     c.cap_full = full;
-    c.linv_ld = 0;       // fresh allocation: contents unknown
     return TGP_OK;
 }
 
@@ -713,10 +640,7 @@ static int fit_impl(tgp_handle h, const double *X, int64_t N, int64_t D, const d
 
     const int64_t Np = ((N + NPAD - 1) / NPAD) * NPAD;
     const int64_t Dp = ((D + 3) / 4) * 4;
-    {
-        const int arc = ensure_fit_buffers(c, Np, D, true);
-        if (arc != TGP_OK) return arc;
-    }
+    API_MEM(ensure_fit_buffers(c, Np, D, true));
     if (D != c.D) { c.d_cand = nullptr; c.M = 0; c.d_winner = nullptr; }   // resident candidates / winner record belong to the old D
     c.N = N; c.D = D; c.Np = Np; c.Dp = Dp;
     c.imported = false; c.import_rows = 0;
@@ -744,18 +668,15 @@ static int fit_impl(tgp_handle h, const double *X, int64_t N, int64_t D, const d
         // Round 6: ONE launch (the gradient's workgroups run the fit themselves) and a polled completion -- no event
         // record, no stream synchronisation; TGP_SMALL_FUSED=0 / TGP_POLL_US=0 keep round 5's calls (the A/B switches).
         const bool fused = grad_mode && tuning().small_fused != 0;
-        if (fused && !c.d_sfg) {
-            rc = grow(c, c.d_sfg, c.cap_sfg, small_fit_grad_ws_bytes(), "hipMalloc small fit + gradient workspace");
-            if (rc != TGP_OK) return rc;
-        }
+        if (fused) API_MEM(grow(c, c.d_sfg, small_fit_grad_ws_bytes(), "hipMalloc small fit + gradient workspace"));
         const Bell bell = (!grad_mode || fused) ? bell_next(c) : Bell{nullptr, 0, nullptr};
         if (!bell.word) API_HIP(hipEventRecord(c.ev0, c.stream), "hipEventRecord");
-        hipError_t le = fused ? launch_small_fit_grad(c, grad_mode == 2, c.d_pin_out + 8, bell) : launch_small_fit(c, bell);
+        hipError_t le = fused ? launch_small_fit_grad(c, grad_mode == 2, c.h_pin_out.dev() + 8, bell) : launch_small_fit(c, bell);
         c.linv_extent = std::max<int64_t>(c.linv_ld == Np ? c.linv_extent : Np, Nin);   // until the kernel is known to have finished
         c.linv_ld = Np;
         if (le != hipSuccess) return hip_fail(c, le, "launch_small_fit");
         if (grad_mode && !fused) {   // (timed together with the fit: two more event records would cost a third of the call)
-            le = launch_small_grad(c, grad_mode == 2, c.d_pin_out + 8);
+            le = launch_small_grad(c, grad_mode == 2, c.h_pin_out.dev() + 8);
             if (le != hipSuccess) return hip_fail(c, le, "launch_small_grad");
         }
         if (bell.word) {
@@ -860,7 +781,7 @@ static int fit_impl(tgp_handle h, const double *X, int64_t N, int64_t D, const d
         ~PrivateFit() { if (counted) { private_fit_end(c.device, c.bg_lease != nullptr); c.bg_lease = nullptr; } }
     } private_fit{c, c.stream_own != nullptr};
     if (private_fit.counted) c.bg_lease = private_fit_begin(c.device, tuning().bg_lease != 0);
-    hipError_t le = launch_fit(c, staged ? c.d_pin_in : nullptr, staged ? c.d_pin_out : nullptr, !linv_clean,
+    hipError_t le = launch_fit(c, staged ? c.h_pin_in.dev() : nullptr, staged ? c.h_pin_out.dev() : nullptr, !linv_clean,
                                bell.word ? bell.word + 1 : nullptr);
     const bool pre_issued = c.pre.issue != 0;
     c.pre.issue = 0;
@@ -883,7 +804,7 @@ static int fit_impl(tgp_handle h, const double *X, int64_t N, int64_t D, const d
     if (grad_mode) {   // behind the fit, in front of the call's one synchronisation
         c.grad_staged = staged;
         c.grad_timed = !bell.word;
-        le = launch_lml_grad(c, grad_mode == 2, staged ? c.d_pin_out + 8 : c.d_gout, c.grad_timed);
+        le = launch_lml_grad(c, grad_mode == 2, staged ? c.h_pin_out.dev() + 8 : c.d_gout, c.grad_timed);
         if (le != hipSuccess) return hip_fail(c, le, "launch_lml_grad");
     }
     if (bell.word) {
@@ -1190,30 +1111,24 @@ int tgp_debug_read(tgp_handle h, int which, double *out) try {
 static int ensure_outputs(Context &c, bool mu, bool sg, bool aq) {
     if (c.M > c.out_cap) {
         API_HIP(hipStreamSynchronize(c.stream), "hipStreamSynchronize");
-        dfree(c.d_mu); dfree(c.d_sigma); dfree(c.d_acq);
+        static_cast<OutMem &>(c) = OutMem{};
         c.out_cap = c.M;
     }
     // every output buffer is sized for out_cap, whichever call creates it
     const size_t bytes = (size_t)std::max<int64_t>(c.out_cap, 1) * sizeof(double);
-    if (mu && !c.d_mu) API_HIP(hipMalloc((void **)&c.d_mu, bytes), "hipMalloc mu");
-    if (sg && !c.d_sigma) API_HIP(hipMalloc((void **)&c.d_sigma, bytes), "hipMalloc sigma");
-    if (aq && !c.d_acq) API_HIP(hipMalloc((void **)&c.d_acq, bytes), "hipMalloc acq");
+    if (mu) API_MEM(grow(c, c.d_mu, bytes, "hipMalloc mu", false));
+    if (sg) API_MEM(grow(c, c.d_sigma, bytes, "hipMalloc sigma", false));
+    if (aq) API_MEM(grow(c, c.d_acq, bytes, "hipMalloc acq", false));
     return TGP_OK;
 }
 
-// The owned candidate buffer, grown to `need` doubles.  A failing hipMalloc must not leave a stale
-// capacity or a dangling resident batch behind (the next call would copy / launch through a freed
-// pointer): the old batch is forgotten BEFORE the buffer is released and the capacity is only
-// restored once the new allocation exists.
+// The owned candidate buffer, grown to `need` doubles (reserve()'s contract), the resident batch forgotten BEFORE the
+// buffer it points into is released
 static int grow_candidates(Context &c, int64_t need) {
-    if (need <= c.cand_cap) return TGP_OK;
-    API_HIP(hipStreamSynchronize(c.stream), "hipStreamSynchronize");
+    const size_t bytes = (size_t)need * sizeof(double);
+    if (bytes <= c.d_cand_owned.bytes()) return TGP_OK;
     if (c.d_cand == c.d_cand_owned) { c.d_cand = nullptr; c.M = 0; }
-    dfree(c.d_cand_owned);
-    c.cand_cap = 0;
-    API_HIP(hipMalloc((void **)&c.d_cand_owned, (size_t)need * sizeof(double)), "hipMalloc candidates");
-    c.cand_cap = need;
-    return TGP_OK;
+    return grow(c, c.d_cand_owned, bytes, "hipMalloc candidates");
 }
 
 int tgp_set_candidates(tgp_handle h, const double *Xc, int64_t M) try {
@@ -1259,15 +1174,8 @@ int tgp_set_candidates_mt19937(tgp_handle h, uint32_t *key624, int32_t *pos, int
     const int64_t need = 2 * M * D + 2 * D;
     { const int grc = grow_candidates(c, need); if (grc != TGP_OK) return grc; }
     const size_t col_bytes = (size_t)(2 * M) * sizeof(uint32_t);
-    if (2 * col_bytes > c.mt_words_cap) {
-        API_HIP(hipStreamSynchronize(c.stream), "hipStreamSynchronize");
-        if (c.h_mt_words) (void)hipHostFree(c.h_mt_words);
-        c.h_mt_words = nullptr; c.mt_words_cap = 0;
-        API_HIP(hipHostMalloc((void **)&c.h_mt_words, 2 * col_bytes, hipHostMallocDefault), "hipHostMalloc");
-        c.mt_words_cap = 2 * col_bytes;
-    }
-    for (int b = 0; b < 2; ++b)
-        if (!c.ev_mt[b]) API_HIP(hipEventCreateWithFlags(&c.ev_mt[b], hipEventDisableTiming), "hipEventCreate");
+    API_MEM(grow(c, c.h_mt_words, 2 * col_bytes, "hipHostMalloc"));
+    for (int b = 0; b < 2; ++b) API_HIP(c.ev_mt[b].create(hipEventDisableTiming), "hipEventCreate");
     double *d_lo = c.d_cand_owned + M * D, *d_range = d_lo + D;
     uint32_t *d_words = reinterpret_cast<uint32_t *>(d_range + D);
     if (c.d_cand == c.d_cand_owned) { c.d_cand = nullptr; c.M = 0; }     // (the resident batch is being overwritten)
@@ -1475,7 +1383,7 @@ static int ensure_workspace(Context &c) {
     const int64_t mpad = ((c.M + 255) / 256) * 256;   // a multiple of every candidate-tile width in use
     if (mpad <= chunk) chunk = mpad;   // single group
     int rc;
-    if ((rc = grow(c, c.d_Cs, c.cap_Cs, (size_t)mpad * c.Dp * elt, "hipMalloc Cs")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_Cs, (size_t)mpad * c.Dp * elt, "hipMalloc Cs")) != TGP_OK) return rc;
     // The cross-kernel slab.  f64 / f32: one launch pair (cross-kernel, contraction) covers several GROUPS of
     // `chunk` candidates; inside the contraction the tiles walk the slab group by group (sweep_tile()), so the
     // light tail of one group is filled by the heavy head of the next and the cross-kernel runs in fewer,
@@ -1491,26 +1399,23 @@ static int ensure_workspace(Context &c) {
         const int64_t groups = std::max<int64_t>(1, std::min<int64_t>((mpad + chunk - 1) / chunk, cap / chunk));
         launch_rows = groups * chunk;
     }
-    if ((rc = grow(c, c.d_Ks[0], c.cap_Ks[0], (size_t)std::min<int64_t>(launch_rows, std::max<int64_t>(mpad, chunk)) * c.Np * kelt, "hipMalloc Ks")) != TGP_OK) return rc;
-    if (per_group && (rc = grow(c, c.d_Ks[1], c.cap_Ks[1], (size_t)chunk * c.Np * kelt, "hipMalloc Ks")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_Ks[0], (size_t)std::min<int64_t>(launch_rows, std::max<int64_t>(mpad, chunk)) * c.Np * kelt, "hipMalloc Ks")) != TGP_OK) return rc;
+    if (per_group && (rc = grow(c, c.d_Ks[1], (size_t)chunk * c.Np * kelt, "hipMalloc Ks")) != TGP_OK) return rc;
     c.launch_rows = launch_rows;
-    if ((rc = grow(c, c.d_part, c.cap_part, (size_t)(c.Np / SW_BM) * mpad * sizeof(double), "hipMalloc part")) != TGP_OK) return rc;
-    if ((rc = grow(c, c.d_mupart, c.cap_mupart, (size_t)KS_JS * mpad * sizeof(double), "hipMalloc mupart")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_part, (size_t)(c.Np / SW_BM) * mpad * sizeof(double), "hipMalloc part")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_mupart, (size_t)KS_JS * mpad * sizeof(double), "hipMalloc mupart")) != TGP_OK) return rc;
     c.chunk = chunk;
     c.ws_Mpad = mpad;
     const size_t nblk = (size_t)((c.M + NB - 1) / NB + 1);   // the small-problem sweep reduces 64 candidates per block
-    if ((rc = grow(c, c.d_bval, c.cap_bval, nblk * sizeof(double), "hipMalloc bval")) != TGP_OK) return rc;
-    if ((rc = grow(c, c.d_bidx, c.cap_bidx, nblk * sizeof(long long), "hipMalloc bidx")) != TGP_OK) return rc;
-    return TGP_OK;
+    if ((rc = grow(c, c.d_bval, nblk * sizeof(double), "hipMalloc bval")) != TGP_OK) return rc;
+    return grow(c, c.d_bidx, nblk * sizeof(long long), "hipMalloc bidx");
 }
 
 // the small-problem sweep only needs the per-block arg-max partials
 static int ensure_small_workspace(Context &c) {
     const size_t nblk = (size_t)((c.M + 31) / 32 + 1);   // (the one-launch sweep of N <= 512 reduces 32 candidates per workgroup)
-    int rc;
-    if ((rc = grow(c, c.d_bval, c.cap_bval, nblk * sizeof(double), "hipMalloc bval")) != TGP_OK) return rc;
-    if ((rc = grow(c, c.d_bidx, c.cap_bidx, nblk * sizeof(long long), "hipMalloc bidx")) != TGP_OK) return rc;
-    return TGP_OK;
+    API_MEM(grow(c, c.d_bval, nblk * sizeof(double), "hipMalloc bval"));
+    return grow(c, c.d_bidx, nblk * sizeof(long long), "hipMalloc bidx");
 }
 
 // One sweep of the resident candidates with the resident model, for every entry of the family: picks the kernel
@@ -1552,7 +1457,7 @@ static int run_sweep(Context &c, const SweepCall &call, CallClock &clk) {
     if (s.winner && s.acq != TGP_ACQ_NONE) {
         // the winner record is packed: what tgp_winner_wait makes another stream (RCCL's) wait for -- a polled call
         // returns without a stream synchronisation, so the ordering rests on this event
-        if (!c.ev_winner) API_HIP(hipEventCreateWithFlags(&c.ev_winner, hipEventDisableTiming), "hipEventCreate");
+        API_HIP(c.ev_winner.create(hipEventDisableTiming), "hipEventCreate");
         API_HIP(hipEventRecord(c.ev_winner, c.stream), "hipEventRecord");
         c.winner_recorded = true;
     }
@@ -1586,7 +1491,7 @@ int tgp_sweep(tgp_handle h, int acq, double sf, double incumbent, double param, 
     // hands the counters back at zero: no D2H copy, no memset behind it (TGP_SWEEP_ZC=0: the copies, A/B)
     const bool zc = can_ring || tuning().sweep_zc != 0;
     if (zc && (rc = ensure_pinned(c, 0, 8 * sizeof(double))) != TGP_OK) return rc;
-    s.res = zc ? c.d_pin_out : nullptr;
+    s.res = zc ? c.h_pin_out.dev() : nullptr;
     // (round 6) the small-problem sweep that only returns its record -- the arg-max of a trial -- is a polled call: the
     // last kernel rings the doorbell, no event, no stream synchronisation (doorbell.hpp)
     if (can_ring && !mu && !sigma && !acq_out) s.bell = bell_next(c);
@@ -1641,21 +1546,15 @@ int tgp_acq_grad(tgp_handle h, const double *Xq, int64_t m, int acq, double sf, 
         int prc = ensure_pinned(c, zc_in, zc_out);
         if (prc != TGP_OK) return prc;
         memcpy(c.h_pin_in, Xq, zc_in);
-        double *o_val = c.d_pin_out + 8, *o_grad = o_val + m;
+        double *o_val = c.h_pin_out.dev() + 8, *o_grad = o_val + m;
         hipError_t le;
         if (small_q) {
-            le = launch_small_query(c, c.d_pin_in, (int)m, acq, sf, incumbent, param, o_val, o_grad, bell);
+            le = launch_small_query(c, c.h_pin_in.dev(), (int)m, acq, sf, incumbent, param, o_val, o_grad, bell);
         } else {
             const int64_t per = query_ws_doubles(c);   // launch_query's workspace
             const int64_t need = m * (2 * D + 1) + m * per;     // (the layout of the copying path below, so both share d_qws)
-            if (need > c.qws_cap) {
-                API_HIP(hipStreamSynchronize(c.stream), "hipStreamSynchronize");
-                dfree(c.d_qws);
-                c.qws_cap = 0;
-                API_HIP(hipMalloc((void **)&c.d_qws, (size_t)need * sizeof(double)), "hipMalloc query workspace");
-                c.qws_cap = need;
-            }
-            le = launch_query(c, c.d_pin_in, (int)m, acq, sf, incumbent, param, c.d_qws + m * (2 * D + 1), o_val, o_grad, bell);
+            API_MEM(grow(c, c.d_qws, (size_t)need * sizeof(double), "hipMalloc query workspace"));
+            le = launch_query(c, c.h_pin_in.dev(), (int)m, acq, sf, incumbent, param, c.d_qws + m * (2 * D + 1), o_val, o_grad, bell);
         }
         if (le != hipSuccess) return hip_fail(c, le, "launch_query");
         int wrc = bell_wait(c, bell, "query sync");
@@ -1667,12 +1566,7 @@ int tgp_acq_grad(tgp_handle h, const double *Xq, int64_t m, int acq, double sf, 
     // [Xq (m D) | val (m) | grad (m D) | workspace]
     const int64_t per = query_ws_doubles(c);   // launch_query's workspace
     const int64_t need = m * (2 * c.D + 1) + m * per;
-    if (need > c.qws_cap) {
-        API_HIP(hipStreamSynchronize(c.stream), "hipStreamSynchronize");
-        dfree(c.d_qws);
-        API_HIP(hipMalloc((void **)&c.d_qws, (size_t)need * sizeof(double)), "hipMalloc query workspace");
-        c.qws_cap = need;
-    }
+    API_MEM(grow(c, c.d_qws, (size_t)need * sizeof(double), "hipMalloc query workspace"));
     double *d_Xq = c.d_qws, *d_val = d_Xq + m * c.D, *d_grad = d_val + m, *d_ws = d_grad + m * c.D;
     API_HIP(hipMemcpyAsync(d_Xq, Xq, (size_t)(m * c.D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D Xq");
     hipError_t le = launch_query(c, d_Xq, (int)m, acq, sf, incumbent, param, d_ws, d_val, d_grad);
@@ -1719,9 +1613,9 @@ static int batch_workspace(Context &c, int64_t J, bool mc, int64_t n_acq, BatchW
     const size_t n_btm = (size_t)(ws.Mpad * Dp + ws.js * ws.Mpad + 2 * M + ws.nblk + J * M + n_acq * M);
     const size_t n_bti = (size_t)(BT_MAXP + 2 + ws.nblk) * sizeof(long long) + (size_t)M;
     int rc;
-    if ((rc = grow(c, c.d_bt, c.cap_bt, n_bt * sizeof(double), "hipMalloc batch state")) != TGP_OK) return rc;
-    if ((rc = grow(c, c.d_btm, c.cap_btm, n_btm * sizeof(double), "hipMalloc batch arrays")) != TGP_OK) return rc;
-    if ((rc = grow(c, c.d_bti, c.cap_bti, n_bti, "hipMalloc batch indices")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_bt, n_bt * sizeof(double), "hipMalloc batch state")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_btm, n_btm * sizeof(double), "hipMalloc batch arrays")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_bti, n_bti, "hipMalloc batch indices")) != TGP_OK) return rc;
     ws.Zraw = c.d_bt; ws.Zs = ws.Zraw + BT_MAXP * D; ws.Kz = ws.Zs + BT_MAXP * Dp; ws.hw = ws.Kz + BT_MAXP * Np;
     ws.v = ws.hw + Np; ws.w = ws.v + Np; ws.R = ws.w + Np; ws.selv = ws.R + BT_MAXP * BT_MAXP;
     if (mc) { ws.eps = ws.selv + BT_MAXP; ws.fant = ws.eps + NE; ws.inc = ws.fant + NE; }
@@ -1745,7 +1639,7 @@ static int batch_first_sweep(Context &c, int acq, double sf, double incumbent, d
     int rc;
     if ((rc = ensure_outputs(c, true, true, keep_acq)) != TGP_OK) return rc;
     if ((rc = ensure_pinned(c, pin_in_bytes, pin_out_bytes)) != TGP_OK) return rc;
-    first.mu = c.d_mu; first.sigma = c.d_sigma; first.res = c.d_pin_out;
+    first.mu = c.d_mu; first.sigma = c.d_sigma; first.res = c.h_pin_out.dev();
     if (keep_acq) first.acqv = c.d_acq;
     return run_sweep(c, first, clk);
 }
@@ -1761,7 +1655,7 @@ static int batch_steps(Context &c, const BatchWs &ws, const BtSmall &s, int64_t 
     for (int64_t j = 0; j < J; ++j) {
         if (j >= P) {   // selection k = j - P: the first sweep's winner, or the previous step's
             const int64_t k = j - P;
-            le = launch_bt_point(c, (P == 0 && k == 0) ? c.d_pin_out : nullptr, s, (int)k, ws.Zraw + j * c.D, ws.mask);
+            le = launch_bt_point(c, (P == 0 && k == 0) ? c.h_pin_out.dev() : nullptr, s, (int)k, ws.Zraw + j * c.D, ws.mask);
             if (le != hipSuccess) return hip_fail(c, le, "launch_bt_point");
         }
         if ((le = condition((int)j)) != hipSuccess) return hip_fail(c, le, "batch condition");
@@ -2010,7 +1904,7 @@ int tgp_ts_draw(tgp_handle h, uint64_t seed, int64_t S, int64_t F) try {
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
     API_HIP(pre_join(c), "hipStreamWaitEvent");
     c.ts_gen = -1;
-    int rc = grow(c, c.d_ts, c.cap_ts, (size_t)ts_doubles(c, S, F) * sizeof(double), "hipMalloc Thompson draw");
+    int rc = grow(c, c.d_ts, (size_t)ts_doubles(c, S, F) * sizeof(double), "hipMalloc Thompson draw");
     if (rc != TGP_OK) return rc;
     c.ts_S = S; c.ts_F = F;
     double *priorX, *R, *Z;
@@ -2037,7 +1931,7 @@ int tgp_ts_sweep(tgp_handle h, double sf, int distinct, int64_t *idx_out, double
     API_HIP(pre_join(c), "hipStreamWaitEvent");
     const TsDraw t = ts_view(c);
     const int64_t S = t.S, M = c.M, D = c.D;
-    if ((rc = grow(c, c.d_tsm, c.cap_tsm, ts_sweep_ws(c, nullptr, S).bytes, "hipMalloc Thompson sweep")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_tsm, ts_sweep_ws(c, nullptr, S).bytes, "hipMalloc Thompson sweep")) != TGP_OK) return rc;
     const TsSweepWs ws = ts_sweep_ws(c, c.d_tsm, S);
     const int64_t Mpad = ws.Mpad;
     double *Cs = ws.Cs, *f = ws.f, *bval = ws.bval, *selv = ws.selv, *selx = ws.selx;
@@ -2075,7 +1969,7 @@ int tgp_ts_eval(tgp_handle h, const double *Xq, int64_t m, double *f_out, double
     const int64_t S = t.S, D = c.D;
     // [Xq (m D) | f (m S) | grad (m S D)] in the per-call region the sweep uses too
     const int64_t nd = ts_al4(m * D) + ts_al4(m * S) + m * S * D;
-    if ((rc = grow(c, c.d_tsm, c.cap_tsm, (size_t)nd * sizeof(double), "hipMalloc Thompson eval")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_tsm, (size_t)nd * sizeof(double), "hipMalloc Thompson eval")) != TGP_OK) return rc;
     double *dX = c.d_tsm, *df = dX + ts_al4(m * D), *dg = df + ts_al4(m * S);
     API_HIP(hipMemcpyAsync(dX, Xq, (size_t)(m * D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D Xq");
     hipError_t le = launch_ts_eval(c, t, dX, (int)m, df, grad_out ? dg : nullptr);
@@ -2121,7 +2015,7 @@ int tgp_mes_set_maxima(tgp_handle h, const double *ystar, int64_t S) try {
     if (!mes_values_ok(ystar, S)) return fail(c, TGP_BAD_ARG, "tgp_mes_set_maxima: need 1 <= S <= 64 finite values");
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
     c.mes_gen = -1;
-    if (!c.d_mes) API_HIP(hipMalloc((void **)&c.d_mes, MES_MAXS * sizeof(double)), "hipMalloc maxima");
+    API_MEM(grow(c, c.d_mes, MES_MAXS * sizeof(double), "hipMalloc maxima", false));
     API_HIP(hipMemcpyAsync(c.d_mes, ystar, (size_t)S * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D maxima");
     API_HIP(hipStreamSynchronize(c.stream), "mes_set_maxima sync");
     c.mes_S = (int)S;
@@ -2145,7 +2039,7 @@ int tgp_mes_draw(tgp_handle h, uint64_t seed, int64_t S, int64_t F, double sf, d
     for (int64_t s = 0; s < S; ++s)
         if (!std::isfinite(val[s])) return fail(c, TGP_BAD_ARG, "tgp_mes_draw: a sample path has no finite value over the candidates");
     // the sweep's winners are still where it left them on the device: the handle's maxima are formed from there
-    if (!c.d_mes) API_HIP(hipMalloc((void **)&c.d_mes, MES_MAXS * sizeof(double)), "hipMalloc maxima");
+    API_MEM(grow(c, c.d_mes, MES_MAXS * sizeof(double), "hipMalloc maxima", false));
     hipError_t le = launch_mes_take(c, ts_sweep_ws(c, c.d_tsm, S).selv, (int)S, sf, incumbent, c.d_mes);
     if (le != hipSuccess) return hip_fail(c, le, "launch_mes_take");
     if (ystar_out) API_HIP(hipMemcpyAsync(ystar_out, c.d_mes, (size_t)S * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H maxima");
@@ -2171,7 +2065,7 @@ static int cov_begin(Context &c, const double *Xq, int64_t m, int64_t S, CovWs &
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
     API_HIP(pre_join(c), "hipStreamWaitEvent");
     const int64_t nd = cov_ws_doubles(c, m, S, &w);
-    int rc = grow(c, c.d_cov, c.cap_cov, (size_t)nd * sizeof(double), "hipMalloc joint posterior workspace");
+    int rc = grow(c, c.d_cov, (size_t)nd * sizeof(double), "hipMalloc joint posterior workspace");
     if (rc != TGP_OK) return rc;
     API_HIP(hipMemcpyAsync(c.d_cov + w.o_Xq, Xq, (size_t)(m * c.D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D Xq");
     return TGP_OK;
@@ -2267,8 +2161,8 @@ int tgp_sweep_topk(tgp_handle h, int acq, double sf, double incumbent, double pa
     if (rc != TGP_OK) return rc;
     const int64_t nb = (c.M + 4095) / 4096;
     const size_t ents = (size_t)(2 * nb * k);
-    if ((rc = grow(c, c.d_topv, c.cap_topv, ents * sizeof(double), "hipMalloc topk values")) != TGP_OK) return rc;
-    if ((rc = grow(c, c.d_topi, c.cap_topi, ents * sizeof(long long), "hipMalloc topk indices")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_topv, ents * sizeof(double), "hipMalloc topk values")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_topi, ents * sizeof(long long), "hipMalloc topk indices")) != TGP_OK) return rc;
     // (round 6) small and one-launch models: a polled call -- the top-k's final pass leaves values, indices and the clamp
     // count in mapped host memory, hands the counters back at zero and rings; no D2H copy, memset, event or synchronisation.
     // (The one question about the kernel family: that final pass is only wired up behind the two f64 families.)
@@ -2284,7 +2178,7 @@ int tgp_sweep_topk(tgp_handle h, int acq, double sf, double incumbent, double pa
     s.winner = c.d_winner;
     if ((rc = run_sweep(c, s, clk)) != TGP_OK) return rc;
     long off = 0;
-    hipError_t le = launch_topk(c, c.d_acq, (long)c.M, (int)k, c.d_topv, c.d_topi, &off, polled ? c.d_pin_out + 8 : nullptr, clk.bell);
+    hipError_t le = launch_topk(c, c.d_acq, (long)c.M, (int)k, c.d_topv, c.d_topi, &off, polled ? c.h_pin_out.dev() + 8 : nullptr, clk.bell);
     if (le != hipSuccess) return hip_fail(c, le, "launch_topk");
     long long hi[64], bi[2] = {0, 0};
     if (!polled) {
@@ -2332,10 +2226,10 @@ int tgp_acq_refine(tgp_handle h, const double *X0, int64_t R, const double *lo, 
         memcpy(c.h_pin_in, X0, (size_t)(R * D) * sizeof(double));
         memcpy(c.h_pin_in + R * D, lo, (size_t)D * sizeof(double));
         memcpy(c.h_pin_in + R * D + D, hi, (size_t)D * sizeof(double));
-        double *o_x = c.d_pin_out + 8, *o_v = o_x + R * D, *o_info = o_v + R;
+        double *o_x = c.h_pin_out.dev() + 8, *o_v = o_x + R * D, *o_info = o_v + R;
         CallClock clk;
         if ((prc = call_begin(c, clk)) != TGP_OK) return prc;
-        hipError_t le = launch_small_refine(c, c.d_pin_in, c.d_pin_in + R * D, c.d_pin_in + R * D + D, (int)R, acq, sf,
+        hipError_t le = launch_small_refine(c, c.h_pin_in.dev(), c.h_pin_in.dev() + R * D, c.h_pin_in.dev() + R * D + D, (int)R, acq, sf,
                                             incumbent, param, (int)std::min<int64_t>(max_iter, 1 << 30), 1e-5,
                                             2.220446049250313e-09, o_x, o_v, o_info);
         if (le != hipSuccess) return hip_fail(c, le, "launch_small_refine");
@@ -2354,18 +2248,13 @@ int tgp_acq_refine(tgp_handle h, const double *X0, int64_t R, const double *lo, 
     // query workspace as tgp_acq_grad: [Xq (m D) | val (m) | grad (m D) | workspace]
     const int64_t per = query_ws_doubles(c);
     const int64_t need = m * (2 * D + 1) + m * per;
-    if (need > c.qws_cap) {
-        API_HIP(hipStreamSynchronize(c.stream), "hipStreamSynchronize");
-        dfree(c.d_qws);
-        API_HIP(hipMalloc((void **)&c.d_qws, (size_t)need * sizeof(double)), "hipMalloc query workspace");
-        c.qws_cap = need;
-    }
+    API_MEM(grow(c, c.d_qws, (size_t)need * sizeof(double), "hipMalloc query workspace"));
     // optimiser state: [state (R stride) | history of the eight-wave teams (D > 1024) | lo (D) | hi (D) | x_out (R D) |
     //                   v_out (R) | info (2 R) | active (int)]
     const int64_t stride = refine_state_stride((int)D);
     const int64_t hist = refine_hist_doubles((int)D, (int)R);
     const size_t rf_need = (size_t)(R * stride + hist + 2 * D + R * D + R + 2 * R + 2) * sizeof(double);
-    int rc = grow(c, c.d_rf, c.cap_rf, rf_need, "hipMalloc refine state");
+    int rc = grow(c, c.d_rf, rf_need, "hipMalloc refine state");
     if (rc != TGP_OK) return rc;
     double *d_Xq = c.d_qws, *d_val = d_Xq + m * D, *d_grad = d_val + m, *d_ws = d_grad + m * D;
     double *d_state = c.d_rf, *d_lo = d_state + R * stride + hist, *d_hi = d_lo + D, *d_xo = d_hi + D;
@@ -2666,10 +2555,10 @@ int tgp_fit_optimise(tgp_handle h, const double *X, int64_t N, int64_t D, const 
     memcpy(in + N * D + N + S * P, log_lo, (size_t)P * sizeof(double));
     memcpy(in + N * D + N + S * P + P, log_hi, (size_t)P * sizeof(double));
     const size_t ws_need = (size_t)S * (size_t)small_hyper_workspace_doubles((int)N, (int)D, (int)Dp) * sizeof(double);
-    rc = grow(c, c.d_rf, c.cap_rf, ws_need, "hipMalloc hyper workspace");
+    rc = grow(c, c.d_rf, ws_need, "hipMalloc hyper workspace");
     if (rc != TGP_OK) return rc;
-    const double *d_in = c.d_pin_in;
-    double *o_theta = c.d_pin_out + 8, *o_f = o_theta + S * P, *o_info = o_f + S;
+    const double *d_in = c.h_pin_in.dev();
+    double *o_theta = c.h_pin_out.dev() + 8, *o_f = o_theta + S * P, *o_info = o_f + S;
     const double *h_theta = c.h_pin_out + 8, *h_f = h_theta + S * P, *h_info = h_f + S;
     bool timed_out = false;
     // A start whose three workgroups never met (status 3: the barrier's time budget ran out, e.g. CUs taken
@@ -2728,19 +2617,14 @@ int tgp_evaluate(tgp_handle h, const double *Xc, int64_t M, int acq, double sf, 
     // host memory -- two launches, one synchronisation, no memcpy call.
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
     API_HIP(pre_join(c), "hipStreamWaitEvent");
-    if (in_bytes > c.pin_cand_cap) {
-        API_HIP(hipStreamSynchronize(c.stream), "hipStreamSynchronize");
-        if (c.h_pin_cand) (void)hipHostFree(c.h_pin_cand);
-        c.h_pin_cand = nullptr; c.d_pin_cand = nullptr; c.pin_cand_cap = 0;
-        const size_t cap = std::max<size_t>(in_bytes, (size_t)1 << 20);
-        API_HIP(hipHostMalloc((void **)&c.h_pin_cand, cap, hipHostMallocMapped), "hipHostMalloc");
-        API_HIP(hipHostGetDevicePointer((void **)&c.d_pin_cand, c.h_pin_cand, 0), "hipHostGetDevicePointer");
-        c.pin_cand_cap = cap;
+    if (in_bytes > c.h_pin_cand.bytes()) {
+        if (c.d_cand == c.h_pin_cand.dev()) { c.d_cand = nullptr; c.M = 0; }   // (as grow_candidates: forgotten before its buffer goes)
+        API_MEM(ensure_pinned(c, c.h_pin_cand, in_bytes));
     }
     int rc = ensure_pinned(c, 0, (size_t)(8 + 3 * M) * sizeof(double));
     if (rc != TGP_OK) return rc;
     memcpy(c.h_pin_cand, Xc, in_bytes);
-    c.d_cand = c.d_pin_cand;              // resident (in host memory the GPU can read) until replaced
+    c.d_cand = c.h_pin_cand.dev();        // resident (in host memory the GPU can read) until replaced
     c.M = M;
     // (round 6) a polled call.  N <= 128: the record's kernel is a launch of its own behind the sweep, so when it rings every
     // mean / deviation / acquisition value the sweep wrote into mapped host memory is out.  The one-launch sweep of
@@ -2748,9 +2632,9 @@ int tgp_evaluate(tgp_handle h, const double *Xc, int64_t M, int acq, double sf, 
     // fence, and the last workgroup rings
     SweepCall s;
     s.acq = acq; s.sf = sf; s.incumbent = incumbent; s.param = param;
-    double *o_mu = c.d_pin_out + 8, *o_sg = o_mu + M, *o_aq = o_sg + M;
+    double *o_mu = c.h_pin_out.dev() + 8, *o_sg = o_mu + M, *o_aq = o_sg + M;
     s.mu = mu ? o_mu : nullptr; s.sigma = sigma ? o_sg : nullptr; s.acqv = acq_out ? o_aq : nullptr;
-    s.res = c.d_pin_out;
+    s.res = c.h_pin_out.dev();
     s.winner = c.d_winner;
     s.bell = bell_next(c);
     CallClock clk{s.bell};
@@ -2804,13 +2688,13 @@ int tgp_predict_batch(tgp_handle h, int64_t T, const int64_t *Ns, int64_t D, con
     // device: per-model workspaces | counters (4 T long long) | mu (T M) | sigma (T M) | candidates (M D)
     const int64_t wsd = mid ? mid_batch_ws_doubles(D, Dp) : small_batch_ws_doubles(D, Dp);
     const size_t dev_need = (size_t)(T * wsd + 4 * T + 2 * T * M + M * D) * sizeof(double);
-    if ((rc = grow(c, c.d_batch, c.cap_batch, dev_need, "hipMalloc batch workspace")) != TGP_OK) return rc;
+    if ((rc = grow(c, c.d_batch, dev_need, "hipMalloc batch workspace")) != TGP_OK) return rc;
     double *d_ws = c.d_batch;
     long long *d_cnt = reinterpret_cast<long long *>(d_ws + T * wsd);
     double *d_mu = d_ws + T * wsd + 4 * T, *d_sg = d_mu + T * M, *d_xc = d_sg + T * M;
 
-    char *pin = reinterpret_cast<char *>(c.h_pin_in);
-    char *pin_dev = reinterpret_cast<char *>(c.d_pin_in);
+    char *pin = reinterpret_cast<char *>(c.h_pin_in.get());
+    char *pin_dev = reinterpret_cast<char *>(c.h_pin_in.dev());
     void *fit_args = pin + args_off, *sweep_args = pin + args_off + (size_t)T * fa;
     std::vector<double> ymean((size_t)T), ystd((size_t)T), yn((size_t)NPB);
     for (int64_t t = 0; t < T; ++t) {
@@ -2824,7 +2708,7 @@ int tgp_predict_batch(tgp_handle h, int64_t T, const int64_t *Ns, int64_t D, con
         memcpy(in + Nin * Dp, yn.data(), (size_t)N * sizeof(double));
         memcpy(in + Nin * Dp + Nin, ls + t * D, (size_t)D * sizeof(double));
         (mid ? fill_mid_batch_args : fill_small_batch_args)(
-            fit_args, sweep_args, t, c.d_pin_in + t * in_stride, d_ws + t * wsd, c.d_pin_out + 8 + 3 * t, d_cnt + 4 * t,
+            fit_args, sweep_args, t, c.h_pin_in.dev() + t * in_stride, d_ws + t * wsd, c.h_pin_out.dev() + 8 + 3 * t, d_cnt + 4 * t,
             d_xc, d_mu + t * M, sigma ? d_sg + t * M : nullptr, N, D, Dp, M, constants[t], noises[t], jitters[t],
             ymean[(size_t)t], ystd[(size_t)t]);
     }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/turbogp.h"
+#include "dev_mem.hpp"
 #include "doorbell.hpp"
 #include "lds_opt_in.hpp"
 #include "mes_math.hpp"
@@ -36,23 +37,83 @@ struct PreSweep {
     const double *cand = nullptr;
     int64_t M = 0, Mpad = 0, launch_rows = 0, chunk = 0;   // the batch and workspace geometry it was issued for
     bool pending = false;     // work on the device's third stream the main stream has not been told to wait for
-    hipEvent_t ev = nullptr;     // third stream: end of the front
-    hipEvent_t ev_in = nullptr;  // main stream: Xs / length scales staged
+    Ev ev;                    // third stream: end of the front
+    Ev ev_in;                 // main stream: Xs / length scales staged
 };
 
-struct Context {
+// A handle OWNS its Dev / Pin / Ev members (dev_mem.hpp: freed with it); raw pointers and streams are borrowed unless
+// their comment says otherwise.  The fit's memory is released as a whole by `static_cast<FitMem &>(c) = FitMem{}`.
+struct FitMem {
+    Dev<double> d_t1, d_t2;        // (Np,) scratch vectors of the row append
+    Dev<double> d_Xs;              // (Np, Dp) X / ls, rows >= N and columns >= D zero
+    Dev<double> d_ls;              // (D,)
+    Dev<double> d_K;               // (Np, Np) K, then L in the lower triangle
+    Dev<double> d_Linv;            // (Np, Np) L^-1, zeros above the diagonal
+    Dev<double> d_W;               // (Np, Np) workspace of the triangular inverse (T^T above the block diagonal)
+    Dev<double> d_U;               // (Np, Np) Linv^T (upper triangular), so every merge product is NT
+    Dev<double> d_Dinv;            // (2, Np/NB, NB, NB): inverses of the diagonal blocks | the diagonal blocks of L while they wait to be written into K
+    Dev<double> d_Apan;            // (2, Np/NB, NB, NB): the unsolved blocks of the current panel, two slots used in turn (fused_panel_kernel)
+    Dev<double> d_yn;              // (Np,) normalised y
+    Dev<double> d_z;               // (Np,) Linv * yn
+    Dev<double> d_alpha;           // (Np,)
+    Dev<double> d_apart;           // (Np/128, Np) shares of alpha = Linv^T z, one row per 128-row slice of Linv, then (Np/128,) sums of z^2
+    Dev<float> d_Xs32;             // f32 copies for the f32 sweep
+    Dev<float> d_Linv32;
+    Dev<unsigned short> d_Linv16;  // TGP_F32X3: Linv32 as three bf16 planes (3, Np, Np), cut before the first sweep after a fit
+    long linv16_gen = -1;          // which fit (fit_gen) the planes belong to
+    Dev<unsigned> d_x2scal;        // TGP_F32H2: [bits of max|Linv32|, bits of 1 / (s_a s_b)]
+    int64_t cap_Np = 0, cap_D = 0; // the geometry the set above was allocated for
+    bool cap_full = false;         // the buffers include what a FIT needs (K, the inverse's workspaces), not only what a sweep needs
+    int64_t linv_ld = 0;           // d_Linv is zero from row / column linv_extent on for this leading dimension (0: unknown -> clear everything)
+    // LML-gradient workspace (allocated on first tgp_fit_grad)
+    Dev<double> d_gpart;           // (tiles, 3 + Dp) partial sums: [S_c, S_iso, S_diag, gd[0..Dp)] per 64 x 64 tile
+    Dev<double> d_gout;            // [S_c, S_iso, S_diag, gd[Dp]]
+    int64_t g_cap_Np = 0, g_cap_Dp = 0;   // the geometry those two were allocated for
+    Dev<double> d_qws;             // small-batch query workspace (tgp_acq_grad)
+    Dev<double> d_rf;              // on-device optimiser state (tgp_acq_refine)
+    Dev<unsigned long long> d_stamp;   // TGP_STAMP_FILE (debug): in-kernel time stamps of the panel chain
+};
+
+struct WsMem {                     // the sweeps' and the acquisition entries' workspaces: grow-only, each on its own
+    Dev<void> d_Cs;                // (Mpad, Dp) scaled candidates, compute dtype
+    Dev<void> d_Ks[2];             // (chunk, Np) cross-kernel slab, two slots
+    Dev<double> d_part;            // (Np/SW_BM, Mpad) partial ||v||^2
+    Dev<double> d_mupart;          // (KS_JS, Mpad) partial K*.alpha
+    int64_t ws_Mpad = 0;           // leading dimension of Cs / part / mupart for this sweep
+    Dev<char> d_prune;             // the pruned sweep's workspace (sweep_kernels.hip, sweep_pruned)
+    Dev<double> d_topv;            // top-k workspace (tgp_sweep_topk)
+    Dev<long long> d_topi;
+    Dev<double> d_batch;           // tgp_predict_batch: per-model workspaces, outputs, counters
+    Dev<double> d_bt;              // tgp_sweep_batch: the small state and the conditioned points' vectors
+    Dev<double> d_btm;             // ... its per-candidate arrays (scaled candidates, pass partials, G, mean, variance)
+    Dev<long long> d_bti;          // ... its indices, counters and the selection mask
+    Dev<double> d_ts;              // tgp_ts_draw: the draw (omega, b, W, eps, V) and its workspace
+    Dev<double> d_tsm;             // tgp_ts_sweep / tgp_ts_eval: per-call arrays (scaled candidates, f, partials, points)
+    int64_t ts_S = 0, ts_F = 0;    // the resident draw's shape ...
+    long ts_gen = -1;              // ... and the fit_gen it belongs to (-1: none)
+    Dev<double> d_cov;             // tgp_predict_cov / tgp_sample_joint: the joint posterior's workspace (cov_kernels.hip), kept between calls
+    Dev<double> d_mes;             // tgp_mes_set_maxima / tgp_mes_draw: MES_MAXS doubles, the first mes_S are the maxima
+    int mes_S = 0;
+    long mes_gen = -1;             // the fit_gen the maxima belong to (-1: none)
+};
+
+struct OutMem {                    // the sweep's optional (M,) outputs: created lazily at ONE size, released together
+    Dev<double> d_mu, d_sigma, d_acq;
+    int64_t out_cap = 0;           // candidates each of them holds once it exists
+};
+
+struct Context : FitMem, WsMem, OutMem {
     int device = 0;
     int dtype = TGP_F64;
     hipStream_t stream = nullptr;    // everything runs in order on this stream (the device's shared main stream: not owned) ...
-    unsigned long long *d_stamp = nullptr;   // TGP_STAMP_FILE (debug): in-kernel time stamps of the panel chain
     hipStream_t stream_own = nullptr; // tgp_set_private_stream: this handle's own main stream (owned), else null
     hipStream_t bg_lease = nullptr;   // the background stream this fit of a private-stream handle holds on loan (private_fit_begin), else null
     hipStream_t stream_bg = nullptr; // ... except the inverse factor's GEMMs behind the panel chain (the device's shared background stream: not owned)
     hipStream_t stream_pre = nullptr; // ... and the front of the next sweep inside a fit (the device's shared third stream: not owned)
     PreSweep pre;
-    std::vector<hipEvent_t> ev_la;   // the events that order the two (no timing)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // brackets of the last fit / sweep (last_*_ms)
-    hipEvent_t evg[4] = {nullptr, nullptr, nullptr, nullptr};   // stages of the last LML gradient
+    std::vector<Ev> ev_la;           // the events that order the two (no timing)
+    Ev ev0, ev1;                     // brackets of the last fit / sweep (last_*_ms)
+    Ev evg[4];                       // stages of the last LML gradient
     double last_grad_ms[3] = {0.0, 0.0, 0.0};  // K^-1 = U U^T | pairwise weights + traces | ARD products
     std::string err;
 
@@ -68,115 +129,54 @@ struct Context {
     std::vector<double> h_y;       // host copy of the raw targets (N,): tgp_export_state
     int normalize_y = 1;
     double sumlog = 0.0;           // sum(log(diag L)) of the resident factor
-    double *d_t1 = nullptr, *d_t2 = nullptr;   // (Np,) scratch vectors of the row append
-    double *d_Xs = nullptr;        // (Np, Dp) X / ls, rows >= N and columns >= D zero
-    double *d_ls = nullptr;        // (D,)
-    double *d_K = nullptr;         // (Np, Np) K, then L in the lower triangle
-    double *d_Linv = nullptr;      // (Np, Np) L^-1, zeros above the diagonal
-    double *d_W = nullptr;         // (Np, Np) workspace of the triangular inverse (T^T above the block diagonal)
-    double *d_U = nullptr;         // (Np, Np) Linv^T (upper triangular), so every merge product is NT
-    double *d_Dinv = nullptr;      // (2, Np/NB, NB, NB): inverses of the diagonal blocks | the diagonal blocks of L while they wait to be written into K
-    double *d_Apan = nullptr;      // (2, Np/NB, NB, NB): the unsolved blocks of the current panel, two slots used in turn (fused_panel_kernel)
-    double *d_yn = nullptr;        // (Np,) normalised y
-    double *d_z = nullptr;         // (Np,) Linv * yn
-    double *d_alpha = nullptr;     // (Np,)
-    double *d_apart = nullptr;     // (Np/128, Np) shares of alpha = Linv^T z, one row per 128-row slice of Linv, then (Np/128,) sums of z^2
-    double *d_scal = nullptr;      // [0] sum log diag, [1] yn . alpha
-    int *d_flag = nullptr;         // first failing pivot + 1, or 0
-    // LML-gradient workspace (allocated on first tgp_fit_grad)
-    double *d_gpart = nullptr;     // (tiles, 3 + Dp) partial sums: [S_c, S_iso, S_diag, gd[0..Dp)] per 64 x 64 tile
+    Dev<double> d_scal;            // [0] sum log diag, [1] yn . alpha
+    Dev<int> d_flag;               // first failing pivot + 1, or 0
     bool grad_staged = false;      // the last tgp_fit_grad left its sums in the pinned result buffer (+8), not in d_gout
     bool grad_timed = true;        // ... and recorded the events its stage times are read from (false: a polled call)
-    double *d_gout = nullptr;      // [S_c, S_iso, S_diag, gd[Dp]]
-    int64_t g_cap_Np = 0, g_cap_Dp = 0;
-    double *d_qws = nullptr;       // small-batch query workspace (tgp_acq_grad)
-    int64_t qws_cap = 0;
-    double *d_rf = nullptr;        // on-device optimiser state (tgp_acq_refine)
-    size_t cap_rf = 0;
-    double *d_batch = nullptr;     // tgp_predict_batch: per-model workspaces, outputs, counters
-    size_t cap_batch = 0;
-    double *d_bt = nullptr;        // tgp_sweep_batch: the small state and the conditioned points' vectors
-    double *d_btm = nullptr;       // ... its per-candidate arrays (scaled candidates, pass partials, G, mean, variance)
-    long long *d_bti = nullptr;    // ... its indices, counters and the selection mask
-    size_t cap_bt = 0, cap_btm = 0, cap_bti = 0;   // bytes
-    double *d_ts = nullptr;        // tgp_ts_draw: the draw (omega, b, W, eps, V) and its workspace
-    double *d_tsm = nullptr;       // tgp_ts_sweep / tgp_ts_eval: per-call arrays (scaled candidates, f, partials, points)
-    size_t cap_ts = 0, cap_tsm = 0;   // bytes
-    int64_t ts_S = 0, ts_F = 0;    // the resident draw's shape ...
-    long ts_gen = -1;              // ... and the fit_gen it belongs to (-1: none)
-    double *d_cov = nullptr;       // tgp_predict_cov / tgp_sample_joint: the joint posterior's workspace (cov_kernels.hip), kept between calls
-    size_t cap_cov = 0;            // bytes
     double last_cov_ms = 0.0;      // device time of the last joint-posterior call's kernels (the H2D / D2H copies not included)
-    double *d_mes = nullptr;       // tgp_mes_set_maxima / tgp_mes_draw: MES_MAXS doubles, the first mes_S are the maxima
-    int mes_S = 0;
-    long mes_gen = -1;             // the fit_gen the maxima belong to (-1: none)
-    double *d_topv = nullptr;      // top-k workspace (tgp_sweep_topk)
-    long long *d_topi = nullptr;
-    size_t cap_topv = 0, cap_topi = 0;
-    float *d_Xs32 = nullptr;       // f32 copies for the f32 sweep
-    unsigned short *d_Linv16 = nullptr;   // TGP_F32X3: Linv32 as three bf16 planes (3, Np, Np), cut before the first sweep after a fit
-    long fit_gen = 0, linv16_gen = -1;    // which fit the planes belong to
-    float linv16_sb = 0.f;                // TGP_F32H2: the cross-kernel scale the stored 1 / (s_a s_b) was formed with
-    unsigned *d_x2scal = nullptr;         // TGP_F32H2: [bits of max|Linv32|, bits of 1 / (s_a s_b)]
-    float *d_Linv32 = nullptr;
-    int64_t cap_Np = 0, cap_D = 0;
-    bool cap_full = false;         // the buffers include what a FIT needs (K, the inverse's workspaces), not only what a sweep needs
+    long fit_gen = 0;              // counts the fits, appends and imports: what a draw, the maxima and the planes of Linv belong to
+    float linv16_sb = 0.f;         // TGP_F32H2: the cross-kernel scale the stored 1 / (s_a s_b) was formed with
     bool imported = false;         // the resident factor was received (tgp_import_factor_dev), not computed: no training set on the host
     int64_t import_rows = 0;       // rows of Linv received so far of a factor that is arriving block by block
     int64_t fit_gen_src = -1;      // ... and the giver's fit generation they belong to
 
     // ---- small-problem path (N <= 128): pinned, device-mapped staging ----
     bool small = false;            // the resident fit came from small_fit_kernel
-    int64_t linv_extent = 0;       // rows / columns of d_Linv from this on are zero ...
-    int64_t linv_ld = 0;           // ... for this leading dimension (0: unknown -> clear everything)
-    double *h_pin_in = nullptr, *d_pin_in = nullptr;     // host / device view of the input staging
-    double *h_pin_out = nullptr, *d_pin_out = nullptr;   // ... of the result staging
-    size_t pin_in_cap = 0, pin_out_cap = 0;              // bytes
-    double *h_pin_cand = nullptr, *d_pin_cand = nullptr; // candidates handed over by tgp_evaluate on that path
-    size_t pin_cand_cap = 0;
-    uint32_t *h_mt_words = nullptr;                      // tgp_set_candidates_mt19937: two pinned column buffers of the stream's words
-    size_t mt_words_cap = 0;                             // bytes
-    hipEvent_t ev_mt[2] = {nullptr, nullptr};            // ... and "this buffer's copy has left" (no timing)
+    int64_t linv_extent = 0;       // rows / columns of d_Linv from this on are zero (for the leading dimension linv_ld)
+    // each the host pointer, .dev() the device's view of the same block
+    Pin<double> h_pin_in{hipHostMallocMapped | hipHostMallocCoherent};    // the input staging
+    Pin<double> h_pin_out{hipHostMallocMapped | hipHostMallocCoherent};   // the result staging
+    Pin<double> h_pin_cand{hipHostMallocMapped};                          // candidates handed over by tgp_evaluate on that path
+    Pin<uint32_t> h_mt_words{hipHostMallocDefault, false};               // tgp_set_candidates_mt19937: two pinned column buffers of the stream's words (unmapped)
+    Ev ev_mt[2];                                                          // ... and "this buffer's copy has left" (no timing)
     // ---- polled completion (doorbell.hpp): coherent device-mapped [sequence number, start tick, end tick, -] ----
-    unsigned long long *h_bell = nullptr, *d_bell = nullptr;
+    Pin<unsigned long long> h_bell{hipHostMallocMapped | hipHostMallocCoherent};
     unsigned long long bell_seq = 0;   // number of the last polled call issued on this handle
-    unsigned *d_ticket = nullptr;      // ticket counters of the polled multi-workgroup kernels (zero between launches)
-    double *d_sfg = nullptr;           // small fit + gradient in one launch: the workspaces of the two workgroups that only contribute a block pair
-    size_t cap_sfg = 0;
+    Dev<unsigned> d_ticket;            // ticket counters of the polled multi-workgroup kernels (zero between launches)
+    Dev<double> d_sfg;                 // small fit + gradient in one launch: the workspaces of the two workgroups that only contribute a block pair
 
     // ---- candidates ----
-    const double *d_cand = nullptr;   // (M, D) f64 row-major
-    double *d_cand_owned = nullptr;
-    int64_t cand_cap = 0;             // elements owned
+    const double *d_cand = nullptr;   // (M, D) f64 row-major: borrowed -- the caller's, or a view of d_cand_owned / h_pin_cand
+    Dev<double> d_cand_owned;
     int64_t M = 0;
 
     // ---- sweep workspace ----
     int64_t chunk = 0;            // candidates per GROUP of a trmm launch (the slab the caches re-serve: about 256 MiB)
     int64_t launch_rows = 0;      // candidates per trmm launch = rows of the slab (a multiple of chunk; the whole batch when it fits)
-    void *d_Cs = nullptr;                       // (Mpad, Dp) scaled candidates, compute dtype
-    void *d_Ks[2] = {nullptr, nullptr};         // (chunk, Np) cross-kernel slab, two slots
-    double *d_part = nullptr;                   // (Np/SW_BM, Mpad) partial ||v||^2
-    double *d_mupart = nullptr;                 // (KS_JS, Mpad) partial K*.alpha
-    int64_t ws_Mpad = 0;                        // leading dimension of Cs / part / mupart for this sweep
-    size_t cap_Cs = 0, cap_Ks[2] = {0, 0}, cap_part = 0, cap_mupart = 0, cap_bval = 0, cap_bidx = 0;   // bytes
-    double *d_mu = nullptr, *d_sigma = nullptr, *d_acq = nullptr;   // (M,) optional outputs
-    int64_t out_cap = 0;
-    char *d_prune = nullptr;      // the pruned sweep's workspace (sweep_kernels.hip, sweep_pruned)
-    size_t cap_prune = 0;         // bytes
     int prune_state = -1;         // the last sweep: -1 not eligible, -2 gated off, 0 pruned, 1 fell back to every candidate
     int64_t prune_lbset = 0, prune_surv = 0;   // ... candidates in its lb set / survivors
-    double *d_bval = nullptr;     // per finalize block arg-max value
-    long long *d_bidx = nullptr;  // per finalize block arg-max index
+    Dev<double> d_bval;           // per finalize block arg-max value
+    Dev<long long> d_bidx;        // per finalize block arg-max index
     double *d_winner = nullptr;   // borrowed (D + 2) record [value, global index, row] or null (tgp_set_winner_out)
     int64_t winner_offset = 0;    // global index of candidate 0 of the resident batch
-    hipEvent_t ev_winner = nullptr;   // recorded on the stream behind the kernel that packs the record (tgp_winner_wait)
+    Ev ev_winner;                 // recorded on the stream behind the kernel that packs the record (tgp_winner_wait)
     bool winner_recorded = false;
-    double *d_best = nullptr;     // [0] value
-    long long *d_besti = nullptr; // [0] index, [1] clamp count, [2] ticket counter of mid_sweep_kernel (zero between launches), [3] spare
+    Dev<double> d_best;           // [0] value
+    Dev<long long> d_besti;       // [0] index, [1] clamp count, [2] ticket counter of mid_sweep_kernel (zero between launches), [3] spare
 
     // ---- profiling ----
     bool profiling = false;
-    std::vector<hipEvent_t> ev_pool;   // timing events, created once and reused (no create / destroy in the sweep loop)
+    std::vector<Ev> ev_pool;           // timing events, created once and reused (no create / destroy in the sweep loop)
     size_t ev_used = 0;
     std::vector<ProfSeg> segs;
     int64_t trmm_launches = 0, kstar_launches = 0;
