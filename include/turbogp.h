@@ -75,7 +75,7 @@ enum tgp_buffer { TGP_BUF_K = 0, TGP_BUF_L = 1, TGP_BUF_LINV = 2, TGP_BUF_ALPHA 
  * :371, :448, :574-577), which need not own an MI355X.  A host handle serves tgp_fit, tgp_fit_append
  * (as a full fit), tgp_export_state / tgp_import_state (the same blob), tgp_debug_read (L, alpha),
  * tgp_set_candidates, tgp_read_candidates, tgp_get_candidate, tgp_sweep, tgp_evaluate, tgp_predict,
- * tgp_mes_set_maxima, tgp_predict_cov, tgp_sample_joint (eps_in given) and the timing queries, always in float64 (csrc/host_backend.cpp: plain C++, its own arithmetic -- not
+ * tgp_mes_set_maxima, tgp_predict_cov, tgp_sample_joint (eps_in given), tgp_hyper_sample and the timing queries, always in float64 (csrc/host_backend.cpp: plain C++, its own arithmetic -- not
  * the HIP kernels, not the test oracle); every other entry returns TGP_BAD_ARG on it. */
 #define TGP_DEVICE_HOST (-1)
 int tgp_create(int device, int dtype, tgp_handle *out);
@@ -455,6 +455,58 @@ int tgp_fit_optimise(tgp_handle h, const double *X, int64_t N, int64_t D, const 
                      const double *theta0, int64_t S, int64_t n_ls, const double *log_lo, const double *log_hi,
                      double jitter, int normalize_y, int64_t max_iter, double *theta_out, double *f_out,
                      int64_t *status_out, int64_t *evaluations);
+
+/* MARGINALISED hyper-parameters: the second of the two ways the author's older library names for them
+ * (old_library/bayesian_optimiser.py:53-75 -- 'optimise' fits a point estimate, 'marginalise' draws MCMC samples of the
+ * hyper-parameters and averages the acquisition over them, the integrated acquisition of Snoek et al. 2012 -- with the
+ * arguments left #TODO at :153-165).  tgp_fit_optimise / tgp_fit_lbfgsb above are the first; these two are the second.
+ *
+ * tgp_hyper_sample: S samples of theta = log(constant, length scale(s), noise) (layout, units and P = 2 + n_ls of
+ *   tgp_fit_lbfgsb) from the density exp(LML(theta)) on the box [log_lo, log_hi] -- a uniform prior in log space over the
+ *   bounds the optimiser uses.  An entry with log_lo == log_hi is fixed at the bound and not sampled; the noise entry may
+ *   be fixed at -INFINITY.  theta0's free entries must lie inside the box.  The chain is coordinate-wise slice sampling
+ *   with stepping-out and shrinkage (Neal 2003, figs. 3 and 5; csrc/host_slice.hpp): one sweep is one pass over the free
+ *   coordinates in index order; per coordinate the initial interval has width[p] (NULL: 1.0 each) and is placed at random
+ *   around the current value, each side steps out at most 8 times (the left side first) while LML(end) exceeds the slice
+ *   level, an end that leaves the box is clipped to the bound, and proposals are drawn from the interval, which shrinks
+ *   towards the current value, until one exceeds the level.  `burn` sweeps are discarded; sample k is the state after
+ *   sweep burn + (k + 1) thin, thin >= 1, 1 <= S <= 64.
+ *   Every evaluation is this handle's own tgp_fit taken for its LML -- whichever fit path N selects, the host backend on
+ *   a TGP_DEVICE_HOST handle (and in libturbogp_host.so) -- from inside the library: no interpreter between two
+ *   evaluations.  TGP_NOT_PD at a proposal counts as LML = -inf: the proposal is rejected and counted in *not_pd;
+ *   TGP_NOT_PD at theta0 is returned.  The handle is left fitted at the LAST evaluation -- not a model to use.
+ *   Randomness is counter-based, so the walk is a pure function of the arguments: the j-th uniform of the call
+ *   (j = 0, 1, ...) is the 53-bit uniform (csrc/philox.hpp philox_u53) of words 0 and 1 of
+ *   Philox-4x32-10(counter (j lo, j hi, tag "SLIC" = 0x534C4943, 0), key (seed lo, seed hi)).  Consumption order, per
+ *   coordinate update: one uniform u for the slice level (LML(current) + log u), one for the interval's position
+ *   (left end = current - width[p] v), then one per shrinkage proposal (left + t (right - left)); stepping out draws none.
+ *   theta_out (S, P), lml_out (S) the LML at each sample; evaluations (nullable): tgp_fit calls made, theta0's and the
+ *   non-PD ones included; not_pd (nullable).
+ *
+ * tgp_sweep_integrated: the acquisition averaged over S hyper-parameter samples thetas (S, P) (log units, as above) over
+ *   the RESIDENT candidates, and the moments of the equal-weight mixture of the S posteriors.  For k = 0 .. S-1 in order:
+ *   tgp_fit at theta_k, the unpruned predict-only sweep in the handle's dtype (the pruned sweep's bounds belong to a single
+ *   model's arg-max), and -- in float64 whatever the dtype -- the sums of acq(mu_k, sigma_k), mu_k and sigma_k^2 + mu_k^2
+ *   per candidate (csrc/integrate_kernels.hip).  Then
+ *     acq_out = sum_k acq_k / S;   mu = sum_k mu_k / S;   sigma = sqrt(max(0, sum_k (sigma_k^2 + mu_k^2) / S - mu^2))
+ *   and best_val / best_idx the arg-max of acq_out under the library-wide rule (lowest index on ties, NaN never wins; left
+ *   untouched with TGP_ACQ_NONE = moments only).  What replaces S x (acq(random_x) + the argsort of
+ *   turbo/modules/auxiliary_optimisers.py:59-66) and a NumPy mean in a caller's loop.
+ *   acq: TGP_ACQ_UCB / PI / EI / SIGMA / NONE; TGP_ACQ_MES is TGP_BAD_ARG (its maxima belong to one fit).  `incumbent` is
+ *   in raw y units and the same for every sample.  n_clamped is the sum over the samples.  A winner record attached with
+ *   tgp_set_winner_out is packed as by tgp_sweep (and tgp_winner_wait orders another stream behind it).  The candidates
+ *   must be resident for this D (TGP_BAD_ARG otherwise).  TGP_NOT_PD at a sample fails the call with that status and
+ *   names k in tgp_last_error.  The handle ends fitted at theta_{S-1}.  GPU only: TGP_BAD_ARG on host handles. */
+int tgp_hyper_sample(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
+                     const double *theta0, int64_t n_ls, const double *log_lo, const double *log_hi,
+                     double jitter, int normalize_y, int64_t S, int64_t burn, int64_t thin,
+                     const double *width, uint64_t seed, double *theta_out, double *lml_out,
+                     int64_t *evaluations, int64_t *not_pd);
+int tgp_sweep_integrated(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
+                         const double *thetas, int64_t S, int64_t n_ls, double jitter, int normalize_y,
+                         int acq, double sf, double incumbent, double param,
+                         double *mu, double *sigma, double *acq_out,
+                         double *best_val, int64_t *best_idx, int64_t *n_clamped);
 
 /* The gradient stage itself on the device: R <= 4096 restarts X0 (R, D) are refined together by a
  * projected L-BFGS (memory 8; a line search that asks for sufficient decrease 1e-4 and the curvature

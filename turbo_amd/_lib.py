@@ -43,7 +43,7 @@ SYMBOLS = (
     "tgp_read_candidates", "tgp_get_candidate",
     "tgp_sweep", "tgp_sweep_batch", "tgp_sweep_batch_mc", "tgp_ts_draw", "tgp_ts_sweep", "tgp_ts_eval", "tgp_ts_read", "tgp_mes_set_maxima", "tgp_mes_draw", "tgp_predict_cov", "tgp_sample_joint", "tgp_sweep_topk", "tgp_set_winner_out", "tgp_winner_wait", "tgp_acq_grad", "tgp_acq_refine", "tgp_acq_lbfgsb",
     "tgp_evaluate", "tgp_predict_batch", "tgp_predict", "tgp_profile_enable", "tgp_profile_read", "tgp_profile_reset",
-    "tgp_sweep_geometry", "tgp_last_timings",
+    "tgp_sweep_geometry", "tgp_last_timings", "tgp_hyper_sample", "tgp_sweep_integrated",
     "tgp_multi_create", "tgp_multi_destroy", "tgp_multi_last_error", "tgp_multi_size", "tgp_multi_handle",
     "tgp_multi_fit", "tgp_multi_set_candidates", "tgp_multi_gen_candidates", "tgp_multi_sweep",
 )
@@ -120,6 +120,10 @@ def _argtypes():
                              c.c_double, c.c_int, c.c_int64, _dp, _dp, _i64p, _i64p],
         "tgp_fit_lbfgsb": [_vp, _dp, c.c_int64, c.c_int64, _dp, c.c_int, _dp, c.c_int64, c.c_int64, _dp, _dp,
                            c.c_double, c.c_int, c.c_int64, _dp, _dp, _i64p, _i64p],
+        "tgp_hyper_sample": [_vp, _dp, c.c_int64, c.c_int64, _dp, c.c_int, _dp, c.c_int64, _dp, _dp, c.c_double, c.c_int,
+                             c.c_int64, c.c_int64, c.c_int64, _dp, c.c_uint64, _dp, _dp, _i64p, _i64p],
+        "tgp_sweep_integrated": [_vp, _dp, c.c_int64, c.c_int64, _dp, c.c_int, _dp, c.c_int64, c.c_int64, c.c_double, c.c_int,
+                                 c.c_int, c.c_double, c.c_double, c.c_double, _dp, _dp, _dp, _dp, _i64p, _i64p],
         "tgp_export_state": [_vp, _vp, c.c_int64, _i64p],
         "tgp_import_state": [_vp, _vp, c.c_int64, _dp],
         "tgp_export_factor_dev": [_vp, c.POINTER(Factor)],
@@ -527,6 +531,54 @@ class NativeGP:
             _ptr(lo), _ptr(hi), float(jitter), 1 if normalize_y else 0, int(max_iter), _ptr(theta), _ptr(f),
             st.ctypes.data_as(_i64p), ctypes.byref(ev)))
         return theta, f, st, ev.value
+
+    def hyper_sample(self, X, y, kind, theta0, n_ls, log_bounds, jitter, normalize_y, n_samples=8, burn=20, thin=5,
+                     width=None, seed=0):
+        """``tgp_hyper_sample``: S slice-sampling draws of theta = log(constant, length scale(s), noise) from
+        exp(LML) on the box log_bounds (2 + n_ls, 2), started at theta0.  Returns (thetas (S, P), lml (S,),
+        evaluations, not_pd).  The handle is left fitted at the last evaluation -- not a model to use."""
+        X = _f64c(X)
+        y = _f64c(y).reshape(-1)
+        assert X.ndim == 2 and X.shape[0] == y.shape[0], "X must be (N, D) and y (N,)"
+        theta0 = _f64c(theta0).reshape(-1)
+        P = 2 + int(n_ls)
+        assert theta0.shape == (P,), "theta0 must be (2 + n_ls,)"
+        lb = _f64c(np.asarray(log_bounds, dtype=np.float64).reshape(P, 2))
+        lo, hi = _f64c(lb[:, 0]), _f64c(lb[:, 1])
+        w = None if width is None else _f64c(np.broadcast_to(np.asarray(width, dtype=np.float64), (P,)))
+        S = int(n_samples)
+        theta = np.empty((max(S, 0), P))
+        lml = np.empty(max(S, 0))
+        ev, npd = ctypes.c_int64(0), ctypes.c_int64(0)
+        self.fit_gen += 1
+        self._check(self.lib.tgp_hyper_sample(
+            self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(y), KERNELS[kind], _ptr(theta0), int(n_ls), _ptr(lo), _ptr(hi),
+            float(jitter), 1 if normalize_y else 0, S, int(burn), int(thin), _ptr(w), int(seed) & 0xFFFFFFFFFFFFFFFF,
+            _ptr(theta), _ptr(lml), ctypes.byref(ev), ctypes.byref(npd)))
+        self.N, self.D = X.shape
+        return theta, lml, ev.value, npd.value
+
+    def sweep_integrated(self, X, y, kind, thetas, n_ls, jitter, normalize_y, acq=ACQ_NONE, sf=1.0, incumbent=0.0,
+                         param=0.0, want_mu=False, want_sigma=False, want_acq=False):
+        """``tgp_sweep_integrated``: the acquisition averaged over the hyper-parameter samples thetas (S, 2 + n_ls) on
+        the resident candidates, and the mixture's moments; a dict like ``sweep``'s.  The handle ends fitted at the
+        last sample."""
+        X = _f64c(X)
+        y = _f64c(y).reshape(-1)
+        thetas = _f64c(np.atleast_2d(thetas))
+        assert thetas.shape[1] == 2 + int(n_ls), "thetas must be (S, 2 + n_ls)"
+        M = getattr(self, "M", 0)
+        mu = np.empty(M) if want_mu else None
+        sg = np.empty(M) if want_sigma else None
+        aq = np.empty(M) if want_acq else None
+        bv, bi, nc = ctypes.c_double(float("nan")), ctypes.c_int64(-1), ctypes.c_int64(0)
+        self.fit_gen += 1
+        self._check(self.lib.tgp_sweep_integrated(
+            self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(y), KERNELS[kind], _ptr(thetas), thetas.shape[0], int(n_ls),
+            float(jitter), 1 if normalize_y else 0, int(acq), float(sf), float(incumbent), float(param),
+            _ptr(mu), _ptr(sg), _ptr(aq), ctypes.byref(bv), ctypes.byref(bi), ctypes.byref(nc)))
+        self.N, self.D = X.shape
+        return dict(mu=mu, sigma=sg, acq=aq, best_val=bv.value, best_idx=bi.value, n_clamped=nc.value)
 
     def export_state(self):
         """bytes that define the fitted model (theta, X, y) -- see tgp_export_state"""

@@ -25,7 +25,20 @@ def _is_native(model):
     return hasattr(model, '_sweep')
 
 
+def _is_marginalised(model):
+    """a ``MarginalisedModel``: its ``_sweep`` is the integrated sweep (``tgp_sweep_integrated``), so ``__call__`` and
+    ``maximise`` of UCB / PI / EI over it ARE the integrated acquisition; what works on one fitted model refuses it"""
+    return bool(getattr(model, 'is_marginalised', False))
+
+
+def _refuse_marginalised(model, what):
+    if _is_marginalised(model):
+        raise ValueError('{} is not available for a marginalised model (hyper-parameter samples): it works on one '
+                         'fitted model'.format(what))
+
+
 def _require_native(model, what):
+    _refuse_marginalised(model, what)
     if not _is_native(model):
         raise TypeError('{} needs a model built by HipGPSurrogate (got {!r}): it runs on the GPU only'
                         .format(what, type(model)))
@@ -155,6 +168,7 @@ class AcquisitionFunction:
             ``NativeGP.sweep_batch_mc`` (fantasies (n_sim, P + q)) plus n_sim and seed; ``lie`` is not used and
             ``want_posterior`` asks for sigma alone (the S means differ).  The other strategies ignore ``n_sim`` and
             ``seed``."""
+            _refuse_marginalised(self.model, 'maximise_batch')
             if not _is_native(self.model):
                 raise NotImplementedError('maximise_batch runs on the GPU only: it needs a model built by HipGPSurrogate '
                                           '(got {!r})'.format(type(self.model)))
@@ -224,9 +238,12 @@ class AcquisitionFunction:
             later sweep packs [best value, global_offset + best index, candidate row] into it on
             the GPU (``tgp_set_winner_out``).  Returns the torch tensor that owns the memory -- the
             input of the sharded arg-max's all-gather over RCCL."""
-            _require_native(self.model, 'winner_record')
             import torch
-            ctx = self.model._ensure_resident()
+            if _is_marginalised(self.model):     # tgp_sweep_integrated packs the record as a plain sweep does
+                ctx = self.model._resident_context()
+            else:
+                _require_native(self.model, 'winner_record')
+                ctx = self.model._ensure_resident()
             D = self.model.X.shape[1]
             rec = getattr(ctx, '_winner_keepalive', None)
             if rec is None or rec.numel() != D + 2:
@@ -238,8 +255,10 @@ class AcquisitionFunction:
             """acquisition values (m,) and their gradients (m, D) at a small batch of points,
             in closed form on the GPU (the reference differentiates 1-point calls by finite
             differences: turbo/modules/auxiliary_optimisers.py:80-92)"""
-            _require_native(self.model, 'value_and_grad')
             acq, incumbent, param = self._native_args()
+            if _is_marginalised(self.model):      # the mean of the samples' closed forms
+                return self.model.value_and_grad(X, acq, self.scale_factor, incumbent, param)
+            _require_native(self.model, 'value_and_grad')
             ctx = self.model._ensure_resident()
             return ctx.acq_grad(X, acq, self.scale_factor, incumbent, param)
 
@@ -252,7 +271,7 @@ class AcquisitionFunction:
             rows of the batch come from ``ctx.get_candidate``.  ``first`` / ``count``: only rows [first, first + count) of
             the ``num_points``-row batch are kept and swept (a rank's shard; indices are local to it) while ``np.random``
             ends behind the whole batch."""
-            if not _is_native(self.model):
+            if not _is_native(self.model) or _is_marginalised(self.model):
                 return None
             acq, incumbent, param = self._native_args()
             ctx = self.model._ensure_resident()
@@ -279,9 +298,15 @@ class AcquisitionFunction:
             (turbo/optimiser.py:336) starts their sweep inside itself -- candidate scaling, cross-kernel and the first
             row tiles of the contraction beside the Cholesky's panel chain -- and the next call of this method finds
             the batch resident and skips the draw.  Same candidates, same values, same winner as without it."""
-            _require_native(self.model, 'maximise_generated')
             acq, incumbent, param = self._native_args()
-            ctx = self.model._ensure_resident()
+            marginalised = _is_marginalised(self.model)
+            if marginalised:
+                if prefetch_seed is not None:
+                    raise ValueError('prefetch_next is not available for a marginalised model (every sample refits)')
+                ctx = self.model._resident_context()
+            else:
+                _require_native(self.model, 'maximise_generated')
+                ctx = self.model._ensure_resident()
 
             def draw(sd):
                 if lhs_total is not None:
@@ -294,6 +319,9 @@ class AcquisitionFunction:
                    int(lhs_total) if lhs_total is not None else None, lo_b, hi_b)
             if getattr(ctx, 'gen_key', None) != key:      # (resident already when the previous call prefetched it)
                 draw(seed)
+            if marginalised:      # the resident batch under every hyper-parameter sample (tgp_sweep_integrated)
+                res = self.model._integrated(ctx, acq, self.scale_factor, incumbent, param, False, False, False)
+                return ctx.get_candidate(res['best_idx']), res['best_val'], res['best_idx']
             res = ctx.sweep(acq, self.scale_factor, incumbent, param)
             self.last_sweep_ms = res.get('sweep_ms')
             best = ctx.get_candidate(res['best_idx']), res['best_val'], res['best_idx']
@@ -411,6 +439,7 @@ class TS(AcquisitionFunction):
         return 'optimism'
 
     def construct_function(self, trial_num, model, desired_extremum):
+        _refuse_marginalised(model, 'TS (a sample path belongs to one fitted model)')
         if not _is_native(model):
             raise NotImplementedError('TS draws its sample paths on the GPU: it needs a model built by HipGPSurrogate '
                                       '(got {!r})'.format(type(model)))
@@ -582,6 +611,7 @@ class MES(AcquisitionFunction):
         return 'optimism'
 
     def construct_function(self, trial_num, model, desired_extremum):
+        _refuse_marginalised(model, 'MES (its maxima belong to one fitted model)')
         if not _is_native(model):
             raise ValueError('MES serves native models only: it needs a model built by HipGPSurrogate (got {!r}) for the '
                              'noise level and the sample paths its maxima come from'.format(type(model)))

@@ -38,6 +38,12 @@ def _native_acq(acq):
     return model is None or hasattr(model, '_sweep')     # (no .model at all: a duck-typed instance that brings its own methods)
 
 
+def _marginalised(acq):
+    """an acquisition over a ``MarginalisedModel`` (hyper-parameter samples): the sweep is ``tgp_sweep_integrated``, the
+    gradient stage SciPy's over the mean of the samples' closed-form gradients; what needs ONE fitted model is refused"""
+    return bool(getattr(getattr(acq, 'model', None), 'is_marginalised', False))
+
+
 class _Lockstep:
     """Rendezvous of k optimiser threads around one batched evaluator ``fn(X (m, D)) -> (v, g)``."""
 
@@ -162,6 +168,9 @@ class CandidateSweep:
         strategy='thompson' with a ``TS`` acquisition: q distinct rows, row s the best of sample path s of one draw of q
         paths (asynchronous Thompson sampling: ``pending`` is accepted and ignored).  info = {'max_acq' (q,) sf * sampled
         value, 'candidate_indices' (q,), 'sample_values' (q,) raw, 'strategy', 'seed', 'n_features', 'pending_ignored'}."""
+        if _marginalised(acq):
+            raise ValueError('select_batch is not available for a marginalised model: batch strategies over a mixture of '
+                             'hyper-parameter samples are out of scope')
         thompson = bool(getattr(acq, 'is_thompson', False))
         if strategy == 'thompson' and not thompson:
             raise ValueError("strategy='thompson' needs a TS acquisition (got {!r})".format(type(acq)))
@@ -220,6 +229,10 @@ class CandidateSweep:
         """Returns: x (1, num_attribs) within the bounds, {'max_acq': value}"""
         bounds = [(lb[1], lb[2]) for lb in latent_bounds.ordered]
         maximisation_info = {}
+        marginalised = _marginalised(acq)
+        if marginalised and self.on_device:
+            raise ValueError('on_device=True is not available for a marginalised model: the on-device gradient stage '
+                             'refines ONE fitted model (the SciPy path serves the integrated acquisition)')
         rank, world = dist_info() if self.shard else (0, 1)
         # contiguous shards of ONE batch of num_random candidates (SURVEY.md 8e); global index =
         # offset + local index, so the tie rule (lowest index) does not depend on the world size
@@ -295,7 +308,7 @@ class CandidateSweep:
             elif hasattr(acq, 'maximise') and not (self.grad_restarts > 0 and self.start_from_best > 0):
                 random_x = draw_shard()
                 best_i, best_y = acq.maximise(random_x)
-            elif hasattr(acq, 'maximise_topk') and _native_acq(acq) and self.grad_restarts > 0 and self.start_from_best <= 64:
+            elif hasattr(acq, 'maximise_topk') and _native_acq(acq) and not marginalised and self.grad_restarts > 0 and self.start_from_best <= 64:
                 # the best start_from_best candidates come back from the GPU (tgp_sweep_topk, k <= 64);
                 # the (M,) acquisition vector stays there.  More starts than that take the branch below
                 # (the vector comes back and is argsorted here, as the reference does).
@@ -346,7 +359,7 @@ class CandidateSweep:
                 all_warnings.extend(ws)
                 results = [(xs[j], -float(vs[j])) for j in range(len(vs))]
                 maximisation_info['refine_iterations'] = int(its)
-            elif self.lockstep and self.lockstep != 'scipy' and hasattr(acq, 'lbfgsb') and _native_acq(acq):
+            elif self.lockstep and self.lockstep != 'scipy' and hasattr(acq, 'lbfgsb') and _native_acq(acq) and not marginalised:
                 # L-BFGS-B from every start as the reference runs it, walked inside the library (tgp_acq_lbfgsb): the
                 # restarts in lock-step on one thread, one batched gradient evaluation per round, no interpreter
                 # between two rounds -- each restart's walk is the one SciPy would take on the same objective

@@ -10,9 +10,11 @@
 
 #include "../../include/turbogp.h"
 #include "host_backend.hpp"
+#include "host_slice.hpp"
 #include "tuning.hpp"
 #include <string.h>
 #include <algorithm>
+#include <vector>
 
 struct tgp_handle_s {
     tgp_host::HostGP g;
@@ -142,6 +144,37 @@ int tgp_sample_joint(tgp_handle h, const double *Xq, int64_t m, int64_t S, int l
     if (!h) return TGP_BAD_ARG;
     (void)seed;   // (only the device draws: a host handle needs eps_in)
     HOST_TRY(h->g.sample_joint(Xq, m, S, latent, nugget, eps_in, y_out, eps_out, mu_out))
+}
+
+int tgp_hyper_sample(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel, const double *theta0,
+                     int64_t n_ls, const double *log_lo, const double *log_hi, double jitter, int normalize_y, int64_t S,
+                     int64_t burn, int64_t thin, const double *width, uint64_t seed, double *theta_out, double *lml_out,
+                     int64_t *evaluations, int64_t *not_pd) {
+    if (!h) return TGP_BAD_ARG;
+    static_assert(tgp::SLICE_OK == TGP_OK && tgp::SLICE_NOT_PD == TGP_NOT_PD, "host_slice.hpp's statuses are tgp_status values");
+    try {
+        if (const char *msg = tgp::slice_check_args(X, N, D, y, kernel, theta0, n_ls, log_lo, log_hi, jitter, S, burn, thin,
+                                                    width, theta_out, lml_out)) {
+            h->g.err = std::string("tgp_hyper_sample: ") + msg;
+            return TGP_BAD_ARG;
+        }
+        std::vector<double> ls((size_t)n_ls);
+        auto eval = [&](const double *theta, double *lml) {
+            double constant, noise;
+            tgp::slice_unpack(theta, n_ls, constant, ls.data(), noise);
+            return h->g.fit(X, N, D, y, kernel, constant, ls.data(), n_ls, noise, jitter, normalize_y, lml, nullptr, nullptr);
+        };
+        const int rc = tgp::slice_sample(eval, (int)(2 + n_ls), theta0, log_lo, log_hi, width, S, burn, thin, seed, theta_out,
+                                         lml_out, evaluations, not_pd);
+        if (rc != TGP_OK) h->g.err = "tgp_hyper_sample: " + std::string(rc == TGP_NOT_PD ? "at theta0: " : "") + h->g.err;
+        return rc;
+    } catch (const std::bad_alloc &) {
+        h->g.err = "out of host memory";
+        return TGP_NO_MEMORY;
+    } catch (...) {
+        h->g.err = "unexpected C++ exception";
+        return TGP_HIP_ERROR;
+    }
 }
 
 int tgp_mt19937_uniform_columns(uint32_t *key624, int32_t *pos, int64_t M, int64_t D, const double *lo, const double *hi,

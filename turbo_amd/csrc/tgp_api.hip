@@ -19,6 +19,7 @@
 
 #include "host_backend.hpp"
 #include "host_lbfgsb.hpp"
+#include "host_slice.hpp"
 #include "tgp_internal.hpp"
 
 using namespace tgp;
@@ -2586,6 +2587,132 @@ int tgp_fit_optimise(tgp_handle h, const double *X, int64_t N, int64_t D, const 
         ev += (int64_t)h_info[3 * s + 2];
     }
     if (evaluations) *evaluations = ev;
+    return TGP_OK;
+} TGP_CATCH
+
+// ---- marginalised hyper-parameters: the slice sampler and the integrated sweep ------------------------------------
+static_assert(SLICE_OK == TGP_OK && SLICE_NOT_PD == TGP_NOT_PD, "host_slice.hpp's statuses are tgp_status values");
+
+int tgp_hyper_sample(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel, const double *theta0,
+                     int64_t n_ls, const double *log_lo, const double *log_hi, double jitter, int normalize_y, int64_t S,
+                     int64_t burn, int64_t thin, const double *width, uint64_t seed, double *theta_out, double *lml_out,
+                     int64_t *evaluations, int64_t *not_pd) try {
+    if (!h) return TGP_BAD_ARG;
+    std::string &err = h->host ? h->host->err : h->c.err;
+    if (const char *msg = slice_check_args(X, N, D, y, kernel, theta0, n_ls, log_lo, log_hi, jitter, S, burn, thin, width,
+                                           theta_out, lml_out)) {
+        err = std::string("tgp_hyper_sample: ") + msg;
+        return TGP_BAD_ARG;
+    }
+    // every evaluation is the handle's own tgp_fit, taken for its LML: whichever fit path N selects, or the host backend
+    std::vector<double> ls((size_t)n_ls);
+    auto eval = [&](const double *theta, double *lml) {
+        double constant, noise;
+        slice_unpack(theta, n_ls, constant, ls.data(), noise);
+        return tgp_fit(h, X, N, D, y, kernel, constant, ls.data(), n_ls, noise, jitter, normalize_y, lml, nullptr, nullptr);
+    };
+    const int rc = slice_sample(eval, (int)(2 + n_ls), theta0, log_lo, log_hi, width, S, burn, thin, seed, theta_out, lml_out,
+                                evaluations, not_pd);
+    if (rc != TGP_OK) err = "tgp_hyper_sample: " + std::string(rc == TGP_NOT_PD ? "at theta0: " : "") + err;
+    return rc;
+} TGP_CATCH
+
+int tgp_sweep_integrated(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
+                         const double *thetas, int64_t S, int64_t n_ls, double jitter, int normalize_y, int acq, double sf,
+                         double incumbent, double param, double *mu, double *sigma, double *acq_out, double *best_val,
+                         int64_t *best_idx, int64_t *n_clamped) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_sweep_integrated");
+    Context &c = h->c;
+    if (!X || !y || !thetas) return fail(c, TGP_BAD_ARG, "tgp_sweep_integrated: X, y and thetas must not be NULL");
+    if (S < 1 || S > 64) return fail(c, TGP_BAD_ARG, "tgp_sweep_integrated: 1 <= S <= 64 samples");
+    if (D < 1 || (n_ls != 1 && n_ls != D)) return fail(c, TGP_BAD_ARG, "tgp_sweep_integrated: n_ls must be 1 or D");
+    if (acq == TGP_ACQ_MES)
+        return fail(c, TGP_BAD_ARG, "tgp_sweep_integrated: TGP_ACQ_MES is not integrated (its maxima belong to one fit)");
+    if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_SIGMA) return fail(c, TGP_BAD_ARG, "tgp_sweep_integrated: unknown acquisition");
+    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_sweep_integrated: sf must be +1 or -1");
+    if (!c.d_cand || c.M < 1 || c.D != D)
+        return fail(c, TGP_BAD_ARG, "tgp_sweep_integrated: no candidates set for this D (tgp_set_candidates* after a fit with the same D)");
+    API_HIP(hipSetDevice(c.device), "hipSetDevice");
+    SweepCall acc;                        // the acquisition's parameters, for the accumulation and the final kernel
+    acc.acq = acq; acc.sf = sf; acc.incumbent = incumbent; acc.param = param;
+    bool swept = false;
+    // a failure between the first sweep and the final kernel leaves the samples' clamp counts in the counter: hand it
+    // back at zero, as every sweep does
+    auto bail = [&](int rc) {
+        if (swept) {
+            (void)hipMemsetAsync(c.d_besti + 1, 0, sizeof(long long), c.stream);
+            (void)hipStreamSynchronize(c.stream);
+            (void)hipGetLastError();
+        }
+        return rc;
+    };
+    std::vector<double> ls((size_t)n_ls);
+    const int64_t P = 2 + n_ls;
+    for (int64_t k = 0; k < S; ++k) {
+        double constant, noise;
+        slice_unpack(thetas + k * P, n_ls, constant, ls.data(), noise);
+        int rc = fit_impl(h, X, N, D, y, kernel, constant, ls.data(), n_ls, noise, jitter, normalize_y, nullptr, nullptr, nullptr, true);
+        if (rc != TGP_OK) {
+            const std::string why = c.err;
+            return bail(fail(c, rc, "tgp_sweep_integrated: sample " + std::to_string((long long)k) + ": " + why));
+        }
+        if (!c.d_cand || c.M < 1) return bail(fail(c, TGP_BAD_ARG, "tgp_sweep_integrated: the candidates were dropped"));
+        {   // (a front this fit started under tgp_set_overlap is joined and not used: the sweep below wants outputs)
+            const hipError_t e = pre_join(c);
+            if (e != hipSuccess) return bail(hip_fail(c, e, "hipStreamWaitEvent"));
+        }
+        if ((rc = ensure_outputs(c, true, true, acq_out != nullptr)) != TGP_OK) return bail(rc);
+        if (k == 0) {
+            const size_t bytes = (size_t)c.M * sizeof(double);
+            if ((rc = grow(c, c.d_int_a, bytes, "hipMalloc integrated acq")) != TGP_OK) return bail(rc);
+            if ((rc = grow(c, c.d_int_mu, bytes, "hipMalloc integrated mu")) != TGP_OK) return bail(rc);
+            if ((rc = grow(c, c.d_int_m2, bytes, "hipMalloc integrated m2")) != TGP_OK) return bail(rc);
+        }
+        // the unpruned predict-only sweep of this sample, in the handle's arithmetic: no record, no winner, no bell --
+        // the clamp counter keeps adding up over the samples
+        SweepCall s;
+        s.mu = c.d_mu; s.sigma = c.d_sigma;
+        CallClock clk;
+        swept = true;
+        if ((rc = run_sweep(c, s, clk)) != TGP_OK) return bail(rc);
+        const hipError_t le = launch_integrate_accumulate(c, acc, (int)k);
+        if (le != hipSuccess) return bail(hip_fail(c, le, "launch_integrate_accumulate"));
+    }
+    const bool zc = tuning().sweep_zc != 0;
+    int rc;
+    if (zc && (rc = ensure_pinned(c, 0, 8 * sizeof(double))) != TGP_OK) return bail(rc);
+    acc.mu = mu ? c.d_mu.get() : nullptr; acc.sigma = sigma ? c.d_sigma.get() : nullptr; acc.acqv = acq_out ? c.d_acq.get() : nullptr;
+    acc.winner = c.d_winner;
+    acc.res = zc ? c.h_pin_out.dev() : nullptr;
+    {
+        const hipError_t le = launch_integrate_final(c, acc, (int)S);
+        if (le != hipSuccess) return bail(hip_fail(c, le, "launch_integrate_final"));
+    }
+    if (acc.winner && acq != TGP_ACQ_NONE) {   // (as run_sweep: what tgp_winner_wait orders another stream behind)
+        API_HIP(c.ev_winner.create(hipEventDisableTiming), "hipEventCreate");
+        API_HIP(hipEventRecord(c.ev_winner, c.stream), "hipEventRecord");
+        c.winner_recorded = true;
+    }
+    double bv = 0.0;
+    long long bi[2] = {0, 0};
+    if (!zc) {
+        if (acq != TGP_ACQ_NONE) API_HIP(hipMemcpyAsync(&bv, c.d_best, sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H best");
+        API_HIP(hipMemcpyAsync(bi, c.d_besti, 2 * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H besti");
+        API_HIP(hipMemsetAsync(c.d_besti, 0, 4 * sizeof(long long), c.stream), "memset counters");
+    }
+    const size_t bytes = (size_t)c.M * sizeof(double);
+    if (mu) API_HIP(hipMemcpyAsync(mu, c.d_mu, bytes, hipMemcpyDeviceToHost, c.stream), "D2H mu");
+    if (sigma) API_HIP(hipMemcpyAsync(sigma, c.d_sigma, bytes, hipMemcpyDeviceToHost, c.stream), "D2H sigma");
+    if (acq_out) API_HIP(hipMemcpyAsync(acq_out, c.d_acq, bytes, hipMemcpyDeviceToHost, c.stream), "D2H acq");
+    API_HIP(hipStreamSynchronize(c.stream), "integrated sweep sync");
+    if (c.profiling) prof_collect(c);
+    if (zc) { bv = c.h_pin_out[0]; bi[0] = (long long)c.h_pin_out[1]; bi[1] = (long long)c.h_pin_out[2]; }
+    if (acq != TGP_ACQ_NONE) {
+        if (best_val) *best_val = bv;
+        if (best_idx) *best_idx = (bi[0] >= c.M) ? 0 : (int64_t)bi[0];
+    }
+    if (n_clamped) *n_clamped = (int64_t)bi[1];
     return TGP_OK;
 } TGP_CATCH
 

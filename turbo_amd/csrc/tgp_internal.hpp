@@ -95,6 +95,7 @@ struct WsMem {                     // the sweeps' and the acquisition entries' w
     Dev<double> d_mes;             // tgp_mes_set_maxima / tgp_mes_draw: MES_MAXS doubles, the first mes_S are the maxima
     int mes_S = 0;
     long mes_gen = -1;             // the fit_gen the maxima belong to (-1: none)
+    Dev<double> d_int_a, d_int_mu, d_int_m2;   // tgp_sweep_integrated: (M,) sums over the samples of acq, mu, sigma^2 + mu^2
 };
 
 struct OutMem {                    // the sweep's optional (M,) outputs: created lazily at ONE size, released together
@@ -401,5 +402,11 @@ hipError_t launch_cov_posterior(Context &c, double *ws, const CovWs &w, int late
 // behind launch_cov_posterior(for_sample = true): G = Lc in place, E = the normals (draw: Philox, else from o_Ein), Y = the samples
 hipError_t launch_cov_sample(Context &c, double *ws, const CovWs &w, bool draw, unsigned long long seed);
 hipError_t launch_ts_eval(Context &c, const TsDraw &t, const double *Xq, int m, double *fout, double *gout);
+
+// tgp_sweep_integrated (integrate_kernels.hip): behind sample k's predict-only sweep into c.d_mu / c.d_sigma, add its
+// acquisition and moments into c.d_int_* (k == 0 stores); behind the last one, the averages into s.mu / s.sigma / s.acqv
+// (device memory, nullable), their arg-max, the record s.res and the winner record s.winner as a plain sweep leaves them
+hipError_t launch_integrate_accumulate(Context &c, const SweepCall &s, int k);
+hipError_t launch_integrate_final(Context &c, const SweepCall &s, int S);
 
 }  // namespace tgp

@@ -587,3 +587,220 @@ class HipGPSurrogate(Surrogate):
 
         def __getstate__(self):
             return dict(self.__dict__)
+
+
+class MarginalisedHipGPSurrogate(HipGPSurrogate):
+    """``HipGPSurrogate`` with the hyper-parameters MARGINALISED instead of fixed at a point estimate: the second of the
+    two ways the author's older library names (old_library/bayesian_optimiser.py:53-75 'optimise' / 'marginalise', the
+    latter's arguments left #TODO at :153-165; the integrated acquisition of Snoek et al. 2012).  ``construct_model``
+    first does what the parent does -- the optimised (or fixed) point estimate -- then draws ``n_hyper_samples``
+    samples of theta = log(constant, length scale(s), noise) from exp(LML) on the kernel's bounds with the library's slice
+    sampler (``tgp_hyper_sample``: ``burn`` sweeps discarded, samples ``thin`` sweeps apart) and returns a
+    ``MarginalisedModel``: predictions are the moments of the equal-weight mixture of the S posteriors, and UCB / PI / EI
+    over it are the average of the S acquisitions (``tgp_sweep_integrated``).  The chain starts at the point estimate, or
+    -- with ``param_continuity`` -- at the previous trial's last sample.  Hyper-parameters the kernel holds fixed stay
+    fixed.  ``hyper_seed``: trial t samples with ``(hyper_seed + t * 0x9E3779B97F4A7C15) mod 2**64``; None takes one
+    ``np.random.randint(0, 2**63)`` per trial."""
+
+    GOLDEN = 0x9E3779B97F4A7C15
+
+    def __init__(self, *args, n_hyper_samples=8, burn=20, thin=5, hyper_seed=None, **kwargs):
+        super().__init__(*args, **kwargs)
+        n_hyper_samples, burn, thin = int(n_hyper_samples), int(burn), int(thin)
+        if n_hyper_samples < 1 or n_hyper_samples > 64:
+            raise ValueError('n_hyper_samples must be in [1, 64]')
+        if burn < 0 or thin < 1:
+            raise ValueError('burn >= 0 and thin >= 1 required')
+        self.n_hyper_samples, self.burn, self.thin, self.hyper_seed = n_hyper_samples, burn, thin, hyper_seed
+        self._last_sample = None
+        self._grad_handles = []      # the gradient stage's float64 contexts, one per hyper-parameter sample: the FACTORY's,
+        self._grad_owner = None      # ... holding the fits of this model (models are retained per trial; handles are not)
+
+    def _gradient_handles(self, model):
+        """S float64 GPU contexts fitted at ``model``'s samples.  At most ``max S`` of them exist per factory whatever the
+        number of models alive: another model's request refits them, ``close()`` releases them."""
+        handles = self.__dict__.setdefault('_grad_handles', [])
+        if getattr(self._context(), 'host', False):
+            raise ValueError('the gradient of a marginalised model needs the GPU')
+        S = len(model.thetas)
+        if self.__dict__.get('_grad_owner') is not model or len(handles) < S:
+            self._grad_owner = None
+            while len(handles) < S:
+                handles.append(_lib.NativeGP(self.device, 'f64'))
+            for gp, th in zip(handles, model.thetas):
+                c, ls, noise = model._unpack(th)
+                gp.fit(model.X, model.y, model.kernel.kind, c, ls, noise, model.jitter, model.normalize_y)
+            self._grad_owner = model
+        return handles[:S]
+
+    def close(self):
+        for gp in self.__dict__.get('_grad_handles', []):
+            gp.close()
+        self._grad_handles, self._grad_owner = [], None
+        super().close()
+
+    def __getstate__(self):
+        d = super().__getstate__()
+        d['_grad_handles'], d['_grad_owner'] = [], None
+        return d
+
+    def construct_model(self, trial_num, X, y):
+        point, fitting_info = super().construct_model(trial_num, X, y)
+        kernel = point.kernel
+        n_ls = len(kernel.length_scale) if kernel.anisotropic else 1
+        P = 2 + n_ls
+        with np.errstate(divide='ignore'):      # (no noise term: the entry is fixed at log 0)
+            full = np.log(np.concatenate([[kernel.constant], np.atleast_1d(np.asarray(kernel.length_scale, dtype=np.float64)),
+                                          [kernel.noise_level]]))
+        free = np.asarray(kernel.select_gradient(np.arange(P, dtype=np.float64)), dtype=np.int64)
+        bounds = np.stack([full, full], axis=1)
+        if len(free) > 0:
+            tb = np.asarray(kernel.theta_bounds, dtype=np.float64)
+            if not np.isfinite(tb).all():
+                raise ValueError('MarginalisedHipGPSurrogate needs finite bounds on every free hyper-parameter')
+            bounds[free] = tb
+        theta0 = full.copy()
+        if self.param_continuity and self._last_sample is not None and self._last_sample.shape == full.shape:
+            theta0[free] = np.clip(self._last_sample[free], bounds[free, 0], bounds[free, 1])
+        else:
+            theta0[free] = np.clip(theta0[free], bounds[free, 0], bounds[free, 1])
+        base = int(np.random.randint(0, 2**63)) if self.hyper_seed is None else int(self.hyper_seed)
+        seed = (base + int(trial_num) * self.GOLDEN) % (1 << 64)
+        ctx = self._context()
+        self._resident = None        # the context is about to hold other hyper-parameters
+        thetas, lmls, evals, not_pd = ctx.hyper_sample(point.X, point.y, kernel.kind, theta0, n_ls, bounds, point.jitter,
+                                                       point.normalize_y, n_samples=self.n_hyper_samples, burn=self.burn,
+                                                       thin=self.thin, seed=seed)
+        self._last_sample = thetas[-1].copy()
+        model = MarginalisedModel(self, point, thetas, lmls, n_ls)
+        fitting_info.update({'hyper_samples': thetas.copy(), 'evaluations': int(evals), 'not_pd': int(not_pd),
+                             'hyper_seed': seed})
+        return model, fitting_info
+
+
+class MarginalisedModel(Surrogate.ModelInstance):
+    """The equal-weight mixture of S GPs that differ in their hyper-parameters ``thetas`` (S, P) = log(constant, length
+    scale(s), noise); ``point`` is the point-estimate model of the same data.  ``predict`` returns the mixture's moments,
+    mu = mean_k mu_k and sigma = sqrt(mean_k (sigma_k^2 + mu_k^2) - mu^2), from ``tgp_sweep_integrated``; unpickled where no
+    GPU is visible it fits S host handles and averages the same moments in NumPy.  Pickles as X, y, the kernel and
+    ``thetas``: O(N D + S P)."""
+
+    is_marginalised = True
+
+    def __init__(self, factory, point, thetas, lmls, n_ls):
+        self._factory = factory
+        self.point = point
+        self.X, self.y = point.X, point.y
+        self.kernel, self.jitter, self.normalize_y = point.kernel, point.jitter, point.normalize_y
+        self.thetas = np.ascontiguousarray(thetas, dtype=np.float64)
+        self.lmls = np.asarray(lmls, dtype=np.float64)
+        self.n_ls = int(n_ls)
+
+    def _unpack(self, theta):
+        # (the C library's exp, entry by entry, as tgp_sweep_integrated forms them: NumPy's vectorised exp may differ in the
+        # last bit, and the gradient stage's handles must hold the very models the sweep averages)
+        from math import exp
+        ls = np.array([exp(float(t)) for t in theta[1:1 + self.n_ls]])
+        return exp(float(theta[0])), (ls if self.n_ls > 1 else float(ls[0])), exp(float(theta[-1]))
+
+    def _ensure_resident(self):
+        raise ValueError('not available for a marginalised model: this entry works on ONE fitted model '
+                         '(batch strategies, Thompson sampling, MES and the on-device gradient stage over a mixture '
+                         'of hyper-parameter samples are out of scope)')
+
+    def _resident_context(self):
+        """the factory's context with the point estimate's fit -- and so its D -- resident, ready for candidates"""
+        ctx = self.point._ensure_resident()
+        return ctx
+
+    def _integrated(self, ctx, acq, sf, incumbent, param, want_mu, want_sigma, want_acq):
+        """``tgp_sweep_integrated`` over the batch resident in ``ctx``"""
+        self._factory._resident = None          # the context ends fitted at the last sample
+        res = ctx.sweep_integrated(self.X, self.y, self.kernel.kind, self.thetas, self.n_ls, self.jitter, self.normalize_y,
+                                   acq, sf, incumbent, param, want_mu, want_sigma, want_acq)
+        if res['n_clamped'] > 0 and want_sigma:
+            warnings.warn('Predicted variances smaller than 0. Setting those variances to 0.')
+        return res
+
+    def _host_mixture(self, X, acq, sf, incumbent, param, want_mu, want_sigma, want_acq):
+        """no GPU in this process (a reloaded model): S host handles, the same sums in NumPy"""
+        from .acquisition_functions import _from_mu_sigma
+        a = m1 = m2 = None
+        clamped = 0
+        for th in self.thetas:
+            gp = _lib.NativeGP(_lib.DEVICE_HOST, 'f64')
+            try:
+                c, ls, noise = self._unpack(th)
+                gp.fit(self.X, self.y, self.kernel.kind, c, ls, noise, self.jitter, self.normalize_y)
+                r = gp.evaluate(X, _lib.ACQ_NONE, 1.0, 0.0, 0.0, True, True, False)
+            finally:
+                gp.close()
+            mu, sg = r['mu'], r['sigma']
+            clamped += r['n_clamped']
+            ak = _from_mu_sigma(acq, sf, incumbent, param, mu, sg) if acq != _lib.ACQ_NONE else np.zeros_like(mu)
+            if a is None:
+                a, m1, m2 = np.array(ak, dtype=np.float64), mu.copy(), sg * sg + mu * mu
+            else:
+                a, m1, m2 = a + ak, m1 + mu, m2 + (sg * sg + mu * mu)
+        S = len(self.thetas)
+        a, mu = a / S, m1 / S
+        sigma = np.sqrt(np.maximum(0.0, m2 / S - mu * mu))
+        vals = np.where(np.isnan(a), -np.inf, a)
+        bi = int(np.argmax(vals)) if acq != _lib.ACQ_NONE else -1
+        return dict(mu=mu if want_mu else None, sigma=sigma if want_sigma else None, acq=a if want_acq else None,
+                    best_idx=bi, best_val=float(vals[bi]) if bi >= 0 else float('nan'), n_clamped=clamped)
+
+    def _sweep(self, X, acq, sf=1.0, incumbent=0.0, param=0.0, want_mu=False, want_sigma=False, want_acq=False):
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim == 1 and X.size > 0:
+            X = X.reshape(1, -1)
+        assert X.ndim == 2 and X.shape[1] == self.X.shape[1], 'X must have shape (num_points, {})'.format(self.X.shape[1])
+        if X.shape[0] == 0:
+            e = np.empty(0)
+            return dict(mu=e if want_mu else None, sigma=e.copy() if want_sigma else None, acq=e.copy() if want_acq else None,
+                        best_val=float('nan'), best_idx=-1, n_clamped=0)
+        if acq == _lib.ACQ_MES:
+            raise ValueError('MES is not available for a marginalised model (its maxima belong to one fit)')
+        ctx = self._resident_context()
+        if getattr(ctx, 'host', False):
+            return self._host_mixture(X, acq, sf, incumbent, param, want_mu, want_sigma, want_acq)
+        ctx.set_candidates(X)
+        return self._integrated(ctx, acq, sf, incumbent, param, want_mu, want_sigma, want_acq)
+
+    def predict(self, X, return_std_dev=False):
+        res = self._sweep(X, _lib.ACQ_NONE, want_mu=True, want_sigma=return_std_dev)
+        if return_std_dev:
+            return res['mu'], res['sigma']
+        return res['mu']
+
+    def value_and_grad(self, X, acq, sf, incumbent, param):
+        """the integrated acquisition (m,) and its gradient (m, D) at a small batch of points: the mean over the samples
+        of the closed form of ``tgp_acq_grad``, each sample on a float64 context that is fitted once per model.  The
+        contexts belong to the FACTORY (``MarginalisedHipGPSurrogate._gradient_handles``): S of them per factory, refitted
+        when another model asks, released by its ``close()`` -- the device's worker pool holds four, fewer than the samples"""
+        owner = getattr(self._factory, '_gradient_handles', None)
+        if owner is None:
+            raise ValueError('the gradient of a marginalised model needs a MarginalisedHipGPSurrogate factory')
+        handles = owner(self)
+        v = g = None
+        for gp in handles:
+            vk, gk = gp.acq_grad(X, acq, sf, incumbent, param)
+            v, g = (vk.copy(), gk.copy()) if v is None else (v + vk, g + gk)
+        return v / len(handles), g / len(handles)
+
+    def get_hyper_params(self):
+        return self.point.get_hyper_params()
+
+    def get_hyper_param_names(self):
+        return self.point.get_hyper_param_names()
+
+    def get_log_likelihood(self):
+        return self.point.get_log_likelihood()
+
+    def __getstate__(self):
+        return dict(_factory=self._factory, X=self.X, y=self.y, kernel=self.kernel, jitter=self.jitter,
+                    normalize_y=self.normalize_y, thetas=self.thetas, lmls=self.lmls, n_ls=self.n_ls)
+
+    def __setstate__(self, d):
+        self.__dict__.update(d)
+        self.point = HipGPSurrogate.ModelInstance(self._factory, self.X, self.y, self.kernel, self.jitter, self.normalize_y)
