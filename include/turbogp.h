@@ -705,7 +705,11 @@ int tgp_profile_reset(tgp_handle h);
  * noise, 0 the pruned schedule ran, 1 it fell back to every candidate -- and the candidates of its lb set and its
  * survivors (TGP_SWEEP_PRUNE).
  * Slot [15]: device time (ms) of the kernels of the last tgp_predict_cov / tgp_sample_joint, the copies of its inputs and
- * outputs left out (0 on host handles). */
+ * outputs left out (0 on host handles).
+ * Slot [16] (not a time): the candidates that survived the screen in front of the pruned sweep's bound pass (f32 RBF
+ * handles, TGP_PRUNE_SCREEN; `survivors` of slot 14 are those that went on to the exact contraction), -1 when the screen
+ * did not apply.  Slot [17]: profiled time (ms) of the screen's launches since tgp_profile_reset, kept apart from
+ * tgp_profile_read's cross-kernel and contraction times. */
 int tgp_last_timings(tgp_handle h, double *out, int64_t n);
 /* Candidates per trmm launch (chunk) and padded N used by the sweep, for the roofline maths. */
 int tgp_sweep_geometry(tgp_handle h, int64_t *chunk, int64_t *n_padded);

@@ -990,10 +990,11 @@ class NativeGP:
         """what the last ``sweep`` did about pruning (``tgp_last_timings`` slots 12-14): state -1 = not eligible (outputs
         asked for, another acquisition or dtype, N <= 256, TGP_SWEEP_PRUNE=0), -2 = gated off (the noise is too small
         for the contraction's rounding), 0 = the pruned schedule ran, 1 = too many survivors: every candidate was
-        contracted; lb_set / survivors = candidates of its two exact sets"""
-        v = np.zeros(15)
-        self._check(self.lib.tgp_last_timings(self._h, _ptr(v), 15))
-        return dict(state=int(v[12]), lb_set=int(v[13]), survivors=int(v[14]))
+        contracted; lb_set / survivors = candidates of its two exact sets; screen = survivors of the matrix-core screen
+        in front of the bound pass (slot 16), -1 where it does not apply (f64, Matern, TGP_PRUNE_SCREEN=0, not pruned)"""
+        v = np.zeros(17)
+        self._check(self.lib.tgp_last_timings(self._h, _ptr(v), 17))
+        return dict(state=int(v[12]), lb_set=int(v[13]), survivors=int(v[14]), screen=int(v[16]))
 
     def sweep_geometry(self):
         ch, npad = ctypes.c_int64(), ctypes.c_int64()

@@ -18,6 +18,7 @@
 #include "mfma_gemm.hpp"
 #include "pairwise.hpp"
 #include "philox.hpp"
+#include "prune_screen.hpp"
 #include "tgp_internal.hpp"
 #include "trmm_sweep.hpp"
 #include "trmm_bf16x3.hpp"
@@ -774,6 +775,8 @@ struct BoundArgs {
     const double *mupart, *abspart; long ldpart; int njs;   // the bound pass's partial sums, njs rows each
     long m;
     double err_scale;          // |the contraction's K*.alpha - this sum| <= err_scale * sum |k| |alpha| (two orders of the same products)
+    const double *err;         // null (the tight pass: the line above), or (m,) the error of each mean as formed elsewhere (the
+                               // screen's E(c), prune_screen.hpp); abspart is then not read
     double y_mean, y_std;
     double sig_lo, sig_hi;     // every candidate's computed sigma lies in [sig_lo, sig_hi]
     int acq; double sf, incumbent, param, margin;
@@ -786,9 +789,9 @@ __global__ __launch_bounds__(256) void prune_bound_kernel(BoundArgs b) {
     double mun = 0.0, s = 0.0;
     for (int j = 0; j < b.njs; ++j) {
         mun += b.mupart[(long)j * b.ldpart + c];
-        s += b.abspart[(long)j * b.ldpart + c];
+        if (!b.err) s += b.abspart[(long)j * b.ldpart + c];
     }
-    const double e = b.err_scale * s;
+    const double e = b.err ? b.err[c] : b.err_scale * s;
     const double mu = b.y_std * (b.sf > 0.0 ? mun + e : mun - e) + b.y_mean;
     // (EI / PI / UCB only reach the pruned sweep, so acq_value's other cases are never taken here)
     const double a_lo = acq_value(b.acq, b.sf, b.incumbent, b.param, mu, b.sig_lo);
@@ -835,12 +838,13 @@ struct SurvArgs {
     const double *lb; double margin;  // lb: the lb set's best exact value (device)
     int *bcnt; const int *boff;       // survivors per 256-candidate block / exclusive offsets
     long long *sidx;                  // survivors' batch indices, in order
+    const long long *src;             // null, or ub is over a gathered set (already clear of the lb set): src[c] is row c's batch index
 };
 
 __device__ __forceinline__ bool prune_survives(const SurvArgs &s, long c) {
     const double lb = s.lb[0];
     const double bar = isinf(lb) ? lb : lb - s.margin * fabs(lb);
-    return c < s.m && s.ub[c] >= bar && s.pick[c / s.gs] != c;
+    return c < s.m && s.ub[c] >= bar && (s.src || s.pick[c / s.gs] != c);
 }
 
 __global__ __launch_bounds__(256) void prune_count_kernel(SurvArgs s) {
@@ -883,21 +887,26 @@ __global__ __launch_bounds__(256) void prune_scatter_kernel(SurvArgs s) {
     __syncthreads();
     int off = s.boff[blockIdx.x];
     for (int k = 0; k < w; ++k) off += wsum[k];
-    if (keep) s.sidx[off + __popcll(bal & ((1ull << lane) - 1ull))] = c;
+    if (keep) s.sidx[off + __popcll(bal & ((1ull << lane) - 1ull))] = s.src ? s.src[c] : c;
 }
 
-// the pruned sweep's own workspace (grow-only): bounds, lb set, survivors, block counts, the gathered scaled rows
+// the pruned sweep's own workspace (grow-only): bounds, lb set, survivors, block counts, the gathered scaled rows; for the
+// screen: E(c), the gathered set's tight bounds, the second survivor list, |x_i|^2 (misc + 8: its two scalars)
 struct PruneWs {
     double *ub; long long *pick, *sidx, *misc; int *bcnt, *boff; void *cs;
+    double *err, *ub1; long long *sidx1; float *nx;
 };
 static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 template <typename T>
-static hipError_t prune_workspace(Context &c, int64_t npick, int64_t rows_cap, PruneWs &w) {
+static hipError_t prune_workspace(Context &c, int64_t npick, int64_t rows_cap, bool screen, PruneWs &w) {
     const int64_t M = c.M, nb = (M + 255) / 256;
     const size_t o_pick = al256((size_t)M * 8), o_sidx = o_pick + al256((size_t)npick * 8), o_misc = o_sidx + al256((size_t)M * 8),
                  o_bcnt = o_misc + 256, o_boff = o_bcnt + al256((size_t)nb * 4), o_cs = o_boff + al256((size_t)nb * 4);
-    const size_t need = o_cs + (size_t)rows_cap * c.Dp * sizeof(T);
+    const size_t o_err = o_cs + al256((size_t)rows_cap * c.Dp * sizeof(T));
+    const size_t o_ub1 = o_err + (screen ? al256((size_t)c.ws_Mpad * 8) : 0), o_sidx1 = o_ub1 + (screen ? al256((size_t)rows_cap * 8) : 0),
+                 o_nx = o_sidx1 + (screen ? al256((size_t)M * 8) : 0);
+    const size_t need = o_nx + (screen ? al256((size_t)c.Np * 4) : 0);
     TGP_TRY(c.d_prune.reserve(need, [&] { return hipStreamSynchronize(c.stream); }));
     char *b = c.d_prune;
     w.ub = reinterpret_cast<double *>(b);
@@ -907,6 +916,10 @@ static hipError_t prune_workspace(Context &c, int64_t npick, int64_t rows_cap, P
     w.bcnt = reinterpret_cast<int *>(b + o_bcnt);
     w.boff = reinterpret_cast<int *>(b + o_boff);
     w.cs = b + o_cs;
+    w.err = reinterpret_cast<double *>(b + o_err);
+    w.ub1 = reinterpret_cast<double *>(b + o_ub1);
+    w.sidx1 = reinterpret_cast<long long *>(b + o_sidx1);
+    w.nx = reinterpret_cast<float *>(b + o_nx);
     return hipSuccess;
 }
 
@@ -964,6 +977,25 @@ static hipError_t contract_rows(Context &c, const SweepPlan<T> &p, const T *cs, 
 }
 
 // done = false: too many survivors -- the caller runs the full schedule (nothing of this call's results is left behind)
+//
+// With the screen (TGP_PRUNE_SCREEN, f32 + RBF; prune_screen.hpp) the order of work is
+//   1. screen over all M: mu_s and E(c) with |mu_s - mu~| <= E  ->  prune_bound_kernel (the error as its input)  ->  ub0;
+//   2. the lb set picked from ub0 and contracted exactly -> lb (the code below, unchanged);
+//   3. count / scan / scatter on ub0 -> the screen's survivors S0 (one host synchronisation for the count);
+//   4. |S0| <= TGP_PRUNE_DIRECT: S0 is contracted as it is.  |S0| > prune_frac M: the tight bound pass over all M --
+//      the schedule without a screen from its step 1 on, the lb set kept.  Between the two: the tight bound pass
+//      (kstar XP = 4 + prune_bound_kernel, their arithmetic and err_scale unchanged) on the gathered S0 rows, its grid
+//      splitting the training points until the chip is full, and a second filter against lb -> S1 (a second
+//      synchronisation for its count);
+//   5. gather, contract, finalize, ONE arg-max over the lb set and the last survivor set.
+// Why the result is the full sweep's, bit for bit: a candidate's exact value a(c) is formed from the contraction's mean
+// mu~(c) and a variance inside [sig_lo^2, sig_hi^2]; ub0(c) >= a(c) because mu~ lies within E(c) of mu_s(c) and
+// prune_bound_kernel takes the end of that interval, and of the variance's, that raises the acquisition; the tight bound
+// ub1(c) >= a(c) as before.  The winner w of the full sweep has a(w) >= a(any lb-set member) = lb, hence ub0(w) >= lb and
+// ub1(w) >= lb: it is in the lb set or survives every filter, and so does every candidate that ties with it.  Every
+// contracted candidate goes through the full sweep's arithmetic, the one arg-max sees batch indices, and no skipped
+// candidate can clamp (the gate above): value, index and n_clamped are the full sweep's.  The screen's own values and
+// its looseness never reach a result; they only move work between "skipped" and "contracted".
 template <typename T>
 static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCall &call, bool front_usable, bool &done) {
     done = false;
@@ -978,45 +1010,78 @@ static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCal
     const double frac = tuning_prune_frac_now();
     const int64_t keep = frac < 0.0 ? -1 : (frac >= 1.0 ? M : (int64_t)(frac * (double)M));   // most survivors taken
     const int64_t rows_cap = (((npick > keep ? npick : keep) + 127) / 128) * 128;
+    const bool screen = sizeof(T) == 4 && c.kernel == TGP_RBF && c.D <= SCR_MAXD && tuning_prune_screen_now() != 0;
     PruneWs w;
-    TGP_TRY(prune_workspace<T>(c, npick, rows_cap, w));
+    TGP_TRY(prune_workspace<T>(c, npick, rows_cap, screen, w));
     TGP_TRY(lds_opt_in(c, p.early.kern, p.early.lds));   // (the request the fit's early row tiles make of the same kernel)
     const T *Cs = reinterpret_cast<const T *>(c.d_Cs.get());
+    const T *Xs = reinterpret_cast<const T *>(sizeof(T) == 8 ? (const void *)c.d_Xs : (const void *)c.d_Xs32);
     T *cs = reinterpret_cast<T *>(w.cs);
+    constexpr int KAR = kstar_ar(sizeof(T));
+    c.prune_screen = -1;
 
-    // 1. the bound of every candidate
     if (!front_usable) TGP_TRY(issue_prep<T>(c, st));   // (a fit's front has scaled them already)
     int mark = prof_mark(c, st);
-    // Splits of the training points over the bound pass's grid: a big batch fills the chip with its candidate tiles
-    // alone, and every split costs a workgroup its prologue (candidate tile staged, first barrier), 2 x 8 shuffled
-    // partial sums and a row of each partial array for prune_bound_kernel to read.  (Any split is covered by
-    // err_scale: it bounds the distance between two summation orders of the same products.)
-    int njs_b = 1;
-    {
-        constexpr int KAR = kstar_ar(sizeof(T));
-        const int64_t xb = Mpad / (16 * KAR);
-        while (njs_b < p.njs && xb * njs_b < BOUND_MIN_WGS) njs_b *= 2;
-        if (njs_b > p.njs) njs_b = p.njs;
-        const T *Xs = reinterpret_cast<const T *>(sizeof(T) == 8 ? (const void *)c.d_Xs : (const void *)c.d_Xs32);
-        hipLaunchKernelGGL(kstar_fn<T>(c.kernel, false, false, false, true), dim3((unsigned)xb, (unsigned)njs_b),
-                           dim3(256), 0, st, Cs, Xs, c.d_alpha, reinterpret_cast<T *>(c.d_part.get()), c.d_mupart, (int)Mpad, N,
-                           (int)c.Np, Dp, c.constant, (long)Mpad, 0L, 1.f);
-        TGP_TRY(hipGetLastError());
-        const int m2 = prof_mark(c, st);
-        prof_seg(c, mark, m2, 1);
-        mark = m2;
-    }
+
     BoundArgs b{};
-    b.mupart = c.d_mupart; b.abspart = c.d_part; b.ldpart = Mpad; b.njs = njs_b;
-    b.m = M;
+    b.mupart = c.d_mupart; b.abspart = c.d_part; b.ldpart = Mpad;
     b.err_scale = 4.0 * (double)(N + 8) * 0x1p-53;
     b.y_mean = c.y_mean; b.y_std = c.y_std;
     b.sig_lo = sqrt((0.99 * c.noise) * (c.y_std * c.y_std));
     b.sig_hi = sqrt((c.constant + c.noise) * (c.y_std * c.y_std));
     b.acq = acq; b.sf = sf; b.incumbent = incumbent; b.param = param; b.margin = tu.prune_margin;
-    b.ub = w.ub;
-    hipLaunchKernelGGL(prune_bound_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, b);
-    TGP_TRY(hipGetLastError());
+
+    // The tight bound of `rows` scaled candidates (a multiple of 16 KAR; m of them real) into ub.
+    // Splits of the training points over the bound pass's grid: a big batch fills the chip with its candidate tiles
+    // alone, and every split costs a workgroup its prologue (candidate tile staged, first barrier), 2 x 8 shuffled
+    // partial sums and a row of each partial array for prune_bound_kernel to read.  (Any split is covered by
+    // err_scale: it bounds the distance between two summation orders of the same products.)
+    auto tight_bound = [&](const T *rowsrc, int64_t rows, int64_t m, double *ub) -> hipError_t {
+        const int64_t xb = rows / (16 * KAR);
+        int njs_b = 1;
+        while (njs_b < p.njs && xb * njs_b < BOUND_MIN_WGS) njs_b *= 2;
+        if (njs_b > p.njs) njs_b = p.njs;
+        hipLaunchKernelGGL(kstar_fn<T>(c.kernel, false, false, false, true), dim3((unsigned)xb, (unsigned)njs_b),
+                           dim3(256), 0, st, rowsrc, Xs, c.d_alpha, reinterpret_cast<T *>(c.d_part.get()), c.d_mupart, (int)rows, N,
+                           (int)c.Np, Dp, c.constant, (long)Mpad, 0L, 1.f);
+        TGP_TRY(hipGetLastError());
+        const int m2 = prof_mark(c, st);
+        prof_seg(c, mark, m2, 1);
+        mark = m2;
+        b.njs = njs_b; b.m = m; b.err = nullptr; b.ub = ub;
+        hipLaunchKernelGGL(prune_bound_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, b);
+        return hipGetLastError();
+    };
+
+    // 1. the bound of every candidate: the screen's where it applies, else the tight one
+    if (screen) {
+        if constexpr (sizeof(T) == 4) {
+            const ScreenTerms et = screen_error_terms(c.constant, (int)c.D, N);
+            double *scal = reinterpret_cast<double *>(w.misc + 8);
+            hipLaunchKernelGGL(screen_stats_kernel, dim3(1), dim3(1024), 0, st, Xs, c.d_alpha, N, (int)c.Np, Dp, et.P, et.Q, w.nx, scal);
+            TGP_TRY(hipGetLastError());
+            const int m1 = prof_mark(c, st);
+            const int64_t xb = Mpad / SCR_T;
+            const int njt = (N + SCR_T - 1) / SCR_T;
+            int njs_s = 1;
+            while (njs_s < p.njs && njs_s < njt && xb * njs_s < SCREEN_MIN_WGS) njs_s *= 2;
+            if (njs_s > p.njs) njs_s = p.njs;
+            ScreenArgs g{};
+            g.Cs = Cs; g.Xs = Xs; g.alpha = c.d_alpha; g.nx = w.nx; g.scal = scal;
+            g.mupart = c.d_mupart; g.err = w.err; g.ldpart = Mpad;
+            g.N = N; g.Np = (int)c.Np; g.Dp = Dp; g.constant = c.constant;
+            hipLaunchKernelGGL(prune_screen_kernel, dim3((unsigned)xb, (unsigned)njs_s), dim3(256), 0, st, g);
+            TGP_TRY(hipGetLastError());
+            const int m2 = prof_mark(c, st);
+            prof_seg(c, m1, m2, 2);
+            mark = m2;
+            b.njs = njs_s; b.m = M; b.err = w.err; b.ub = w.ub;
+            hipLaunchKernelGGL(prune_bound_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, b);
+            TGP_TRY(hipGetLastError());
+        }
+    } else {
+        TGP_TRY(tight_bound(Cs, Mpad, M, w.ub));
+    }
     hipLaunchKernelGGL(prune_pick_kernel, dim3((unsigned)npick), dim3(256), 0, st, w.ub, (long)M, (long)gs, w.pick);
     TGP_TRY(hipGetLastError());
 
@@ -1042,6 +1107,20 @@ static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCal
         hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n + FIN_BLOCK - 1) / FIN_BLOCK)), dim3(FIN_BLOCK), 0, st, f);
         return hipGetLastError();
     };
+    // the candidates of ub[0, m) that reach the bar, compacted in order into out; their number comes back to the host
+    // (the launches behind it are sized by the count)
+    auto survivors = [&](const double *ub, int64_t m, const long long *src, long long *out, long long &n) -> hipError_t {
+        const int64_t nb = (m + 255) / 256;
+        SurvArgs s{ub, (long)m, w.pick, (long)gs, c.d_best, tu.prune_margin, w.bcnt, w.boff, out, src};
+        hipLaunchKernelGGL(prune_count_kernel, dim3((unsigned)nb), dim3(256), 0, st, s);
+        TGP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(1024), 0, st, w.bcnt, (int)nb, w.boff, w.misc);
+        TGP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(prune_scatter_kernel, dim3((unsigned)nb), dim3(256), 0, st, s);
+        TGP_TRY(hipGetLastError());
+        TGP_TRY(hipMemcpyAsync(&n, w.misc, sizeof(long long), hipMemcpyDeviceToHost, st));
+        return hipStreamSynchronize(st);
+    };
 
     // 2. the lb set, exactly; its best value is the bar (d_best)
     TGP_TRY(gather(w.pick, npick));
@@ -1053,18 +1132,28 @@ static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCal
     TGP_TRY(hipGetLastError());
 
     // 3. the survivors, in index order
-    const int64_t nb = (M + 255) / 256;
-    SurvArgs s{w.ub, (long)M, w.pick, (long)gs, c.d_best, tu.prune_margin, w.bcnt, w.boff, w.sidx};
-    hipLaunchKernelGGL(prune_count_kernel, dim3((unsigned)nb), dim3(256), 0, st, s);
-    TGP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(1024), 0, st, w.bcnt, (int)nb, w.boff, w.misc);
-    TGP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(prune_scatter_kernel, dim3((unsigned)nb), dim3(256), 0, st, s);
-    TGP_TRY(hipGetLastError());
     long long nsurv = 0;
-    TGP_TRY(hipMemcpyAsync(&nsurv, w.misc, sizeof(long long), hipMemcpyDeviceToHost, st));
-    TGP_TRY(hipStreamSynchronize(st));   // (the launches below are sized by the count)
+    const long long *sidx = w.sidx;
+    TGP_TRY(survivors(w.ub, M, nullptr, w.sidx, nsurv));
     c.prune_lbset = npick;
+    if (screen) {
+        c.prune_screen = nsurv;
+        if (nsurv > keep) {
+            // the screen was too loose for this batch: the tight bound of every candidate, against the same lb
+            mark = prof_mark(c, st);
+            TGP_TRY(tight_bound(Cs, Mpad, M, w.ub));
+            TGP_TRY(survivors(w.ub, M, nullptr, w.sidx, nsurv));
+        } else if (nsurv > tuning_prune_direct_now()) {
+            const int64_t rows = ((nsurv + 127) / 128) * 128;
+            TGP_TRY(gather(w.sidx, nsurv));
+            mark = prof_mark(c, st);
+            TGP_TRY(tight_bound(cs, rows, nsurv, w.ub1));
+            const long long n0 = nsurv;
+            TGP_TRY(survivors(w.ub1, n0, w.sidx, w.sidx1, nsurv));
+            sidx = w.sidx1;
+        }
+        mark = prof_mark(c, st);
+    }
     c.prune_surv = nsurv;
     if (nsurv > keep) {
         // the full schedule instead: it counts the lb set's clamps again (the counter was zero when this sweep began)
@@ -1073,9 +1162,9 @@ static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCal
     }
     int64_t nblk_b = 0;
     if (nsurv > 0) {
-        TGP_TRY(gather(w.sidx, nsurv));
+        TGP_TRY(gather(sidx, nsurv));
         TGP_TRY(contract_rows<T>(c, p, cs, nsurv, st, mark));
-        TGP_TRY(finalize(w.sidx, nsurv, nblk_a));
+        TGP_TRY(finalize(sidx, nsurv, nblk_a));
         nblk_b = (nsurv + FIN_BLOCK - 1) / FIN_BLOCK;
     }
     hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, st, c.d_bval, c.d_bidx, (long)(nblk_a + nblk_b), c.d_best,

@@ -165,6 +165,7 @@ static void prof_collect(Context &c) {
         if (hipEventSynchronize(c.ev_pool[g.b]) == hipSuccess &&
             hipEventElapsedTime(&ms, c.ev_pool[g.a], c.ev_pool[g.b]) == hipSuccess) {
             if (g.kind == 0) { c.trmm_ms += ms; c.trmm_launches++; c.trmm_flops += g.flops; }
+            else if (g.kind == 2) { c.screen_ms += ms; }
             else { c.kstar_ms += ms; c.kstar_launches++; }
         } else {
             (void)hipGetLastError();
@@ -1444,6 +1445,7 @@ static int run_sweep(Context &c, const SweepCall &call, CallClock &clk) {
     c.last_sweep_f64 = path != SweepPath::General || c.dtype == TGP_F64;   // (the one-workgroup / one-launch kernels only exist in f64)
     c.prune_state = -1;
     c.prune_lbset = c.prune_surv = 0;
+    c.prune_screen = -1;
     if ((rc = call_begin(c, clk)) != TGP_OK) return rc;
     hipError_t le;
     if (path == SweepPath::OneLaunch) {
@@ -2884,7 +2886,7 @@ int tgp_profile_reset(tgp_handle h) try {
     Context &c = h->c;
     prof_collect(c);
     c.trmm_launches = c.kstar_launches = 0;
-    c.trmm_ms = c.kstar_ms = 0.0;
+    c.trmm_ms = c.kstar_ms = c.screen_ms = 0.0;
     c.trmm_flops = 0.0;
     return TGP_OK;
 } TGP_CATCH
@@ -2916,7 +2918,7 @@ int tgp_last_timings(tgp_handle h, double *out, int64_t n) try {
     if (!h) return TGP_BAD_ARG;
     if (h->host) {
         if (!out || n < 1) { h->host->err = "tgp_last_timings: need out and n >= 1"; return TGP_BAD_ARG; }
-        for (int64_t i = 0; i < n; ++i) out[i] = i == 0 ? h->host->last_fit_ms : (i == 1 ? h->host->last_sweep_ms : (i == 6 ? 1.0 : (i == 12 ? -1.0 : 0.0)));   // [6]: the host backend is float64 throughout; [12]: it never prunes
+        for (int64_t i = 0; i < n; ++i) out[i] = i == 0 ? h->host->last_fit_ms : (i == 1 ? h->host->last_sweep_ms : (i == 6 ? 1.0 : (i == 12 || i == 16 ? -1.0 : 0.0)));   // [6]: the host backend is float64 throughout; [12], [16]: it never prunes
         return TGP_OK;
     }
     Context &c = h->c;
@@ -2927,15 +2929,17 @@ int tgp_last_timings(tgp_handle h, double *out, int64_t n) try {
     // inputs staged, first kernel-matrix tile in LDS, first block factored, fit done, call done (0 when the call was not polled)
     // [12..14]: what the last tgp_sweep did about pruning (sweep_pruned): -1 not eligible, -2 gated off, 0 pruned, 1 fell
     // back to every candidate; the candidates of its lb set; its survivors
-    double v[16] = {c.last_fit_ms, c.last_sweep_ms, c.last_grad_ms[0], c.last_grad_ms[1], c.last_grad_ms[2], c.trmm_flops,
+    // [16]: the survivors of that sweep's screen (prune_screen.hpp), -1 when the screen did not apply; [17]: profiled time of
+    // the screen's launches since tgp_profile_reset (ms; apart from the cross-kernel's and the contraction's)
+    double v[18] = {c.last_fit_ms, c.last_sweep_ms, c.last_grad_ms[0], c.last_grad_ms[1], c.last_grad_ms[2], c.trmm_flops,
                     (double)c.last_sweep_f64, 0.0, 0.0, 0.0, 0.0, 0.0, (double)c.prune_state, (double)c.prune_lbset,
-                    (double)c.prune_surv, c.last_cov_ms};
+                    (double)c.prune_surv, c.last_cov_ms, (double)c.prune_screen, c.screen_ms};
     if (c.h_bell && c.h_bell[1]) {
         const unsigned long long t0 = c.h_bell[1];
         const int src[5] = {3, 4, 5, 6, 2};
         for (int k = 0; k < 5; ++k) v[7 + k] = c.h_bell[src[k]] >= t0 ? (double)(c.h_bell[src[k]] - t0) * 1e-2 : 0.0;
     }
-    for (int64_t i = 0; i < n; ++i) out[i] = i < 16 ? v[i] : 0.0;
+    for (int64_t i = 0; i < n; ++i) out[i] = i < 18 ? v[i] : 0.0;
     return TGP_OK;
 } TGP_CATCH
 

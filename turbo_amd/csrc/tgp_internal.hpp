@@ -23,9 +23,10 @@ constexpr int SW_BN = 128;      // sweep tile: candidates
 constexpr int KS_JS = 8;        // most training-point splits of the cross-kernel grid (rows of mupart)
 constexpr int FIN_BLOCK = 256;  // finalize block = candidates per arg-max partial
 constexpr int CONTRACT_MIN_WGS = 512;   // a gathered set's contraction takes the widest candidate tile that still gives this many workgroups (two per CU)
+constexpr int SCREEN_MIN_WGS = 1024;    // ... and the screen in front of it (prune_screen.hpp; 128 candidates per workgroup, two workgroups per CU)
 constexpr int BOUND_MIN_WGS = 2048;     // the bound pass splits the training points only as far as its grid needs to reach this many workgroups
 
-struct ProfSeg { int a, b, kind; double flops; };   // pooled events a -> b bracket one launch; kind: 0 trmm, 1 kstar; flops: the contraction's algorithmic flops of that launch (a launch a fit took row tiles of has fewer)
+struct ProfSeg { int a, b, kind; double flops; };   // pooled events a -> b bracket one launch; kind: 0 trmm, 1 kstar, 2 the pruned sweep's screen (counted apart: screen_ms); flops: the contraction's algorithmic flops of that launch (a launch a fit took row tiles of has fewer)
 
 // The front of the resident batch's sweep, started INSIDE a fit (tgp_set_overlap; sweep_kernels.hip presweep_*)
 struct PreSweep {
@@ -166,6 +167,8 @@ struct Context : FitMem, WsMem, OutMem {
     int64_t launch_rows = 0;      // candidates per trmm launch = rows of the slab (a multiple of chunk; the whole batch when it fits)
     int prune_state = -1;         // the last sweep: -1 not eligible, -2 gated off, 0 pruned, 1 fell back to every candidate
     int64_t prune_lbset = 0, prune_surv = 0;   // ... candidates in its lb set / survivors
+    int64_t prune_screen = -1;    // ... survivors of its screen (prune_screen.hpp); -1: the screen did not apply (f64, Matern, TGP_PRUNE_SCREEN=0, not pruned)
+    double screen_ms = 0.0;       // profiling: the screen's launches since tgp_profile_reset
     Dev<double> d_bval;           // per finalize block arg-max value
     Dev<long long> d_bidx;        // per finalize block arg-max index
     double *d_winner = nullptr;   // borrowed (D + 2) record [value, global index, row] or null (tgp_set_winner_out)
