@@ -236,16 +236,18 @@ static double bell_ms(const Context &c) {
 }
 
 // ---- one call's clock and its one wait ----
-// A polled call (live bell) is timed on the host clock, launch to doorbell, and records no event; any other call is
-// bracketed by ev0 / ev1 on its stream and ends in a stream synchronisation.
+// A polled call (live bell) records no event and is timed on the host clock, launch to doorbell -- a sweep -- or by the
+// kernels' own stamps (device_ticks) -- a fit; any other call is bracketed by ev0 / ev1 on its stream and ends in a
+// stream synchronisation.
 struct CallClock {
     Bell bell{nullptr, 0, nullptr};
     std::chrono::steady_clock::time_point t0{};
     bool stopped = false;      // ev1 is out
+    bool device_ticks = false; // a polled call reports bell_ms(): what last_fit_ms has always meant
 };
 static int call_begin(Context &c, CallClock &k) {
-    k.t0 = std::chrono::steady_clock::now();
     if (!k.bell.word) API_HIP(hipEventRecord(c.ev0, c.stream), "hipEventRecord");
+    else if (!k.device_ticks) k.t0 = std::chrono::steady_clock::now();
     return TGP_OK;
 }
 // optional: ev1 HERE, so that what the entry queues behind it (copies back to the caller) is not timed
@@ -258,7 +260,8 @@ static int call_stop(Context &c, CallClock &k) {
 static int call_finish(Context &c, CallClock &k, double &last_ms, const char *where) {
     if (k.bell.word) {
         const int rc = bell_wait(c, k.bell, where);
-        if (rc == TGP_OK) last_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - k.t0).count();
+        if (rc == TGP_OK)
+            last_ms = k.device_ticks ? bell_ms(c) : std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - k.t0).count();
         return rc;
     }
     const int rc = call_stop(c, k);
@@ -278,10 +281,11 @@ static int exception_status(tgp_handle h, const char *fn, const char *what, int 
     }
     return code;
 }
-#define TGP_CATCH                                                                               \
-    catch (const std::bad_alloc &) { return exception_status(h, __func__, "out of host memory", TGP_NO_MEMORY); } \
-    catch (const std::exception &ex_) { return exception_status(h, __func__, ex_.what(), TGP_HIP_ERROR); }       \
-    catch (...) { return exception_status(h, __func__, "unknown C++ exception", TGP_HIP_ERROR); }
+#define TGP_CATCH_AS(fn)                                                                        \
+    catch (const std::bad_alloc &) { return exception_status(h, fn, "out of host memory", TGP_NO_MEMORY); } \
+    catch (const std::exception &ex_) { return exception_status(h, fn, ex_.what(), TGP_HIP_ERROR); }       \
+    catch (...) { return exception_status(h, fn, "unknown C++ exception", TGP_HIP_ERROR); }
+#define TGP_CATCH TGP_CATCH_AS(__func__)
 
 // Growing a buffer of the handle: dev_mem.hpp's reserve() contract, with c.stream drained before the old block goes
 // (sync = false: nothing on the device can be using it -- empty, or its streams known idle)
@@ -556,11 +560,6 @@ static bool small_path_enabled() {
     return tuning().small != 0;   // A/B switch
 }
 
-static int fit_impl(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
-                    double constant, const double *ls, int64_t n_ls, double noise, double jitter,
-                    int normalize_y, double *lml, double *y_mean, double *y_std, bool allow_small,
-                    int grad_mode = 0);   // grad_mode: 1 / 2 = the LML gradient (iso / ARD) is launched behind the fit, before the one synchronisation
-
 static int ensure_workspace(Context &c);
 
 // LML-gradient workspace of the blocked path (allocated on first use, grown with the fit)
@@ -573,14 +572,7 @@ static int ensure_grad_workspace(Context &c) {
         c.g_cap_Np = c.Np; c.g_cap_Dp = c.Dp;
     }
     return TGP_OK;
-}   // small_grad: 1 / 2 = also launch the one-workgroup LML gradient (iso / ARD) when the small path is taken
-
-int tgp_fit(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
-            double constant, const double *ls, int64_t n_ls, double noise, double jitter,
-            int normalize_y, double *lml, double *y_mean, double *y_std) try {
-    if (h && h->host) return h->host->fit(X, N, D, y, kernel, constant, ls, n_ls, noise, jitter, normalize_y, lml, y_mean, y_std);
-    return fit_impl(h, X, N, D, y, kernel, constant, ls, n_ls, noise, jitter, normalize_y, lml, y_mean, y_std, true);
-} TGP_CATCH
+}
 
 // the fit state's device buffers for Np padded rows and D dimensions.  full: everything a fit needs; otherwise only what
 // a handle that RECEIVES a factor needs to sweep with it (tgp_import_factor_dev: no K, no inverse workspaces -- 4 N^2
@@ -621,163 +613,185 @@ static int ensure_fit_buffers(Context &c, int64_t Np, int64_t D, bool full) {
     return TGP_OK;
 }
 
-static int fit_impl(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
-                    double constant, const double *ls, int64_t n_ls, double noise, double jitter,
-                    int normalize_y, double *lml, double *y_mean, double *y_std, bool allow_small,
-                    int grad_mode) {
-    if (!h) return TGP_BAD_ARG;
-    Context &c = h->c;
-    c.fitted = false;
-    if (!X || !y || !ls) return fail(c, TGP_BAD_ARG, "tgp_fit: X, y and ls must not be NULL");
-    if (N < 1 || D < 1) return fail(c, TGP_BAD_ARG, "tgp_fit: need N >= 1 and D >= 1");
-    if (N > 65536 || D > 4096) return fail(c, TGP_BAD_ARG, "tgp_fit: N <= 65536 and D <= 4096 supported");
-    if (n_ls != 1 && n_ls != D) return fail(c, TGP_BAD_ARG, "tgp_fit: n_ls must be 1 or D");
-    if (kernel < TGP_RBF || kernel > TGP_MATERN52) return fail(c, TGP_BAD_ARG, "tgp_fit: unknown kernel");
-    if (!(constant > 0.0) || !(noise >= 0.0) || !(jitter >= 0.0)) return fail(c, TGP_BAD_ARG, "tgp_fit: constant > 0, noise >= 0, jitter >= 0 required");
-    for (int64_t d = 0; d < n_ls; ++d)
-        if (!(ls[d] > 0.0)) return fail(c, TGP_BAD_ARG, "tgp_fit: length scales must be > 0");
+// ---- the fit entries: one argument list, one argument check, one completion (CallClock), one commit ----
+struct FitArgs {
+    const double *X; int64_t N, D; const double *y;
+    int kernel; double constant; const double *ls; int64_t n_ls; double noise, jitter;
+    int normalize_y;
+};
+struct FitOut { double *lml = nullptr, *y_mean = nullptr, *y_std = nullptr; };
+// ... and what a fit's kernels hand back: sum(log(diag L)), yn . alpha, first failing pivot + 1 (0: none)
+struct FitResult { double sumlog = 0.0, y_alpha = 0.0; int flag = 0; };
+
+static int host_fit(tgp_handle h, const FitArgs &a, const FitOut &out) {
+    return h->host->fit(a.X, a.N, a.D, a.y, a.kernel, a.constant, a.ls, a.n_ls, a.noise, a.jitter, a.normalize_y, out.lml, out.y_mean, out.y_std);
+}
+static int check_fit_args(Context &c, const FitArgs &a) {
+    if (!a.X || !a.y || !a.ls) return fail(c, TGP_BAD_ARG, "tgp_fit: X, y and ls must not be NULL");
+    if (a.N < 1 || a.D < 1) return fail(c, TGP_BAD_ARG, "tgp_fit: need N >= 1 and D >= 1");
+    if (a.N > 65536 || a.D > 4096) return fail(c, TGP_BAD_ARG, "tgp_fit: N <= 65536 and D <= 4096 supported");
+    if (a.n_ls != 1 && a.n_ls != a.D) return fail(c, TGP_BAD_ARG, "tgp_fit: n_ls must be 1 or D");
+    if (a.kernel < TGP_RBF || a.kernel > TGP_MATERN52) return fail(c, TGP_BAD_ARG, "tgp_fit: unknown kernel");
+    if (!(a.constant > 0.0) || !(a.noise >= 0.0) || !(a.jitter >= 0.0)) return fail(c, TGP_BAD_ARG, "tgp_fit: constant > 0, noise >= 0, jitter >= 0 required");
+    for (int64_t d = 0; d < a.n_ls; ++d)
+        if (!(a.ls[d] > 0.0)) return fail(c, TGP_BAD_ARG, "tgp_fit: length scales must be > 0");
+    return TGP_OK;
+}
+
+// TGP_NOT_PD with the pivot's number (who: "" or "model t of the batch: ")
+static int not_pd(Context &c, int pivot, int64_t N, const std::string &who = std::string()) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "kernel matrix is not positive definite (pivot %d of %lld <= 0)", pivot, (long long)N);
+    return fail(c, TGP_NOT_PD, who + buf);
+}
+// _gpr.py:609-611: -0.5 y.alpha - sum(log(diag L)) - n/2 log(2 pi)
+static double lml_from(double sumlog, double y_alpha, int64_t N) {
+    return -0.5 * y_alpha - sumlog - (double)N / 2.0 * log(2.0 * M_PI);
+}
+
+// the one-workgroup kernels' packed input: Nin = N rounded up to NB rows of X / length_scale (stride Dp), Nin targets, D length scales
+static void pack_small_inputs(double *in, const double *X, int64_t N, int64_t D, int64_t Dp, const double *ls, const double *yn) {
+    const int64_t Nin = ((N + NB - 1) / NB) * NB;
+    memset(in, 0, (size_t)(Nin * Dp + Nin) * sizeof(double));
+    for (int64_t i = 0; i < N; ++i)
+        for (int64_t d = 0; d < D; ++d) in[(size_t)i * Dp + d] = X[(size_t)i * D + d] / ls[d];   // X / length_scale
+    memcpy(in + Nin * Dp, yn, (size_t)N * sizeof(double));
+    memcpy(in + Nin * Dp + Nin, ls, (size_t)D * sizeof(double));
+}
+
+// a fit's clock: polled (where the path can ring and TGP_POLL_US allows) it reports the kernels' own ticks
+static CallClock fit_clock(Context &c, bool may_poll) {
+    CallClock k;
+    k.device_ticks = true;
+    if (may_poll) k.bell = bell_next(c);
+    return k;
+}
+
+// the host's copies of the inputs (tgp_fit_append's prefix test, tgp_export_state); nobody reads them while c.fitted is false
+static void keep_training_set(Context &c, const FitArgs &a) {
+    c.h_X.assign(a.X, a.X + (size_t)a.N * a.D);
+    c.h_y.assign(a.y, a.y + (size_t)a.N);
+}
+
+// the handle ready for this fit: third stream joined, buffers, theta and geometry recorded, targets normalised into yn (Np, zero beyond N)
+static int fit_begin(Context &c, const FitArgs &a, std::vector<double> &yn) {
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
     API_HIP(pre_join(c), "hipStreamWaitEvent");
     c.pre.front = false;   // whatever an earlier fit started early belongs to a factor this one replaces
-
-    const int64_t Np = ((N + NPAD - 1) / NPAD) * NPAD;
-    const int64_t Dp = ((D + 3) / 4) * 4;
-    API_MEM(ensure_fit_buffers(c, Np, D, true));
-    if (D != c.D) { c.d_cand = nullptr; c.M = 0; c.d_winner = nullptr; }   // resident candidates / winner record belong to the old D
-    c.N = N; c.D = D; c.Np = Np; c.Dp = Dp;
+    const int64_t Np = ((a.N + NPAD - 1) / NPAD) * NPAD;
+    const int64_t Dp = ((a.D + 3) / 4) * 4;
+    API_MEM(ensure_fit_buffers(c, Np, a.D, true));
+    if (a.D != c.D) { c.d_cand = nullptr; c.M = 0; c.d_winner = nullptr; }   // resident candidates / winner record belong to the old D
+    c.N = a.N; c.D = a.D; c.Np = Np; c.Dp = Dp;
     c.imported = false; c.import_rows = 0;
-    c.kernel = kernel; c.constant = constant; c.noise = noise; c.jitter = jitter;
-    c.ls.assign((size_t)D, 0.0);
-    for (int64_t d = 0; d < D; ++d) c.ls[d] = ls[n_ls == 1 ? 0 : d];
+    c.kernel = a.kernel; c.constant = a.constant; c.noise = a.noise; c.jitter = a.jitter;
+    c.ls.assign((size_t)a.D, 0.0);
+    for (int64_t d = 0; d < a.D; ++d) c.ls[d] = a.ls[a.n_ls == 1 ? 0 : d];
+    yn.assign((size_t)Np, 0.0);
+    normalise_targets(a.y, a.N, a.normalize_y, yn, c.y_mean, c.y_std);
+    return TGP_OK;
+}
 
-    double mean = 0.0, sd = 1.0;
-    std::vector<double> yn((size_t)Np, 0.0);
-    normalise_targets(y, N, normalize_y, yn, mean, sd);
-    c.y_mean = mean; c.y_std = sd;
-
-    // ---- small problems (N <= 128): one workgroup, one launch, no memcpy (small_kernels.hip) ----
-    c.small = allow_small && N <= 2 * NB && small_path_enabled();
-    if (c.small) {
-        const int64_t Nin = ((N + NB - 1) / NB) * NB;
-        int rc = ensure_pinned(c, (size_t)(Nin * Dp + Nin + D) * sizeof(double), (size_t)(8 + 3 * SMALL_GRAD_OUT_STRIDE) * sizeof(double));
-        if (rc != TGP_OK) return rc;
-        double *in = c.h_pin_in;
-        memset(in, 0, (size_t)(Nin * Dp + Nin) * sizeof(double));
-        for (int64_t i = 0; i < N; ++i)
-            for (int64_t d = 0; d < D; ++d) in[(size_t)i * Dp + d] = X[(size_t)i * D + d] / c.ls[d];   // X / length_scale
-        memcpy(in + Nin * Dp, yn.data(), (size_t)N * sizeof(double));
-        memcpy(in + Nin * Dp + Nin, c.ls.data(), (size_t)D * sizeof(double));
-        // Round 6: ONE launch (the gradient's workgroups run the fit themselves) and a polled completion -- no event
-        // record, no stream synchronisation; TGP_SMALL_FUSED=0 / TGP_POLL_US=0 keep round 5's calls (the A/B switches).
-        const bool fused = grad_mode && tuning().small_fused != 0;
-        if (fused) API_MEM(grow(c, c.d_sfg, small_fit_grad_ws_bytes(), "hipMalloc small fit + gradient workspace"));
-        const Bell bell = (!grad_mode || fused) ? bell_next(c) : Bell{nullptr, 0, nullptr};
-        if (!bell.word) API_HIP(hipEventRecord(c.ev0, c.stream), "hipEventRecord");
-        hipError_t le = fused ? launch_small_fit_grad(c, grad_mode == 2, c.h_pin_out.dev() + 8, bell) : launch_small_fit(c, bell);
-        c.linv_extent = std::max<int64_t>(c.linv_ld == Np ? c.linv_extent : Np, Nin);   // until the kernel is known to have finished
-        c.linv_ld = Np;
-        if (le != hipSuccess) return hip_fail(c, le, "launch_small_fit");
-        if (grad_mode && !fused) {   // (timed together with the fit: two more event records would cost a third of the call)
-            le = launch_small_grad(c, grad_mode == 2, c.h_pin_out.dev() + 8);
-            if (le != hipSuccess) return hip_fail(c, le, "launch_small_grad");
-        }
-        if (bell.word) {
-            rc = bell_wait(c, bell, "fit sync");
-            if (rc != TGP_OK) return rc;
-            c.last_fit_ms = bell_ms(c);
-        } else {
-            API_HIP(hipEventRecord(c.ev1, c.stream), "hipEventRecord");
-            API_HIP(hipStreamSynchronize(c.stream), "fit sync");
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, c.ev0, c.ev1);
-            c.last_fit_ms = ms;
-        }
-        const double *res = c.h_pin_out;
-        if (res[2] != 0.0) {
-            char buf[160];
-            snprintf(buf, sizeof buf, "kernel matrix is not positive definite (pivot %d of %lld <= 0)", (int)res[2] - 1, (long long)N);
-            return fail(c, TGP_NOT_PD, buf);
-        }
-        c.linv_extent = Nin; c.linv_ld = Np;
-        c.sumlog = res[0];
-        c.lml = -0.5 * res[1] - res[0] - (double)N / 2.0 * log(2.0 * M_PI);
-        c.normalize_y = normalize_y ? 1 : 0;
-        c.h_X.assign(X, X + (size_t)N * D);
-        c.h_y.assign(y, y + (size_t)N);
-        if (lml) *lml = c.lml;
-        if (y_mean) *y_mean = c.y_mean;
-        if (y_std) *y_std = c.y_std;
-        c.fitted = true; ++c.fit_gen; ++c.fit_gen;
-        return TGP_OK;
+// ---- small problems (N <= 128): one workgroup, one launch, no memcpy (small_kernels.hip) ----
+// grad_mode: 1 / 2 = the LML gradient (iso / ARD) too
+static int fit_small(Context &c, const FitArgs &a, const std::vector<double> &yn, int grad_mode, FitResult &r) {
+    const int64_t N = a.N, Np = c.Np, Nin = ((N + NB - 1) / NB) * NB;
+    API_MEM(ensure_pinned(c, (size_t)(Nin * c.Dp + Nin + a.D) * sizeof(double), (size_t)(8 + 3 * SMALL_GRAD_OUT_STRIDE) * sizeof(double)));
+    pack_small_inputs(c.h_pin_in, a.X, N, a.D, c.Dp, c.ls.data(), yn.data());
+    // Round 6: ONE launch (the gradient's workgroups run the fit themselves) and a polled completion -- no event
+    // record, no stream synchronisation; TGP_SMALL_FUSED=0 / TGP_POLL_US=0 keep round 5's calls (the A/B switches).
+    const bool fused = grad_mode && tuning().small_fused != 0;
+    if (fused) API_MEM(grow(c, c.d_sfg, small_fit_grad_ws_bytes(), "hipMalloc small fit + gradient workspace"));
+    CallClock clk = fit_clock(c, !grad_mode || fused);
+    API_MEM(call_begin(c, clk));
+    hipError_t le = fused ? launch_small_fit_grad(c, grad_mode == 2, c.h_pin_out.dev() + 8, clk.bell) : launch_small_fit(c, clk.bell);
+    c.linv_extent = std::max<int64_t>(c.linv_ld == Np ? c.linv_extent : Np, Nin);   // until the kernel is known to have finished
+    c.linv_ld = Np;
+    if (le != hipSuccess) return hip_fail(c, le, "launch_small_fit");
+    if (grad_mode && !fused) {   // (timed together with the fit: two more event records would cost a third of the call)
+        le = launch_small_grad(c, grad_mode == 2, c.h_pin_out.dev() + 8);
+        if (le != hipSuccess) return hip_fail(c, le, "launch_small_grad");
     }
+    API_MEM(call_finish(c, clk, c.last_fit_ms, "fit sync"));
+    r = FitResult{c.h_pin_out[0], c.h_pin_out[1], (int)c.h_pin_out[2]};
+    if (r.flag == 0) {
+        c.linv_extent = Nin;
+        keep_training_set(c, a);
+    }
+    return TGP_OK;
+}
 
-    // X / length_scale (kernels.py:1556 / 1711), padded rows zero.  Up to 64 MiB of inputs are
-    // staged in device-mapped host memory and fetched by the fit's first kernel; the scalars come
-    // back the same way: no memcpy, no memset in the call.
+// ---- the blocked fit (fit_kernels.hip) ----
+// X / length_scale (kernels.py:1556 / 1711), padded rows zero.  Up to 64 MiB of inputs are
+// staged in device-mapped host memory and fetched by the fit's first kernel; the scalars come
+// back the same way: no memcpy, no memset in the call.  Beyond: xs_heap, for the H2D copies
+static int stage_blocked_inputs(Context &c, const FitArgs &a, const std::vector<double> &yn, bool &staged, std::vector<double> &xs_heap) {
+    const double *X = a.X;
+    const int64_t N = a.N, D = a.D, Np = c.Np, Dp = c.Dp;
     const size_t n_in = (size_t)Np * Dp + (size_t)Np + (size_t)D;
-    const bool staged = n_in * sizeof(double) <= ((size_t)64 << 20);
-    std::vector<double> xs_heap;
-    double *xs;
+    staged = n_in * sizeof(double) <= ((size_t)64 << 20);
     if (staged) {
-        int rc = ensure_pinned(c, n_in * sizeof(double), (size_t)(8 + 3 + Dp) * sizeof(double));
-        if (rc != TGP_OK) return rc;
-        xs = c.h_pin_in;
+        API_MEM(ensure_pinned(c, n_in * sizeof(double), (size_t)(8 + 3 + Dp) * sizeof(double)));
+        double *xs = c.h_pin_in;
         if (D == Dp) memset(xs + (size_t)N * Dp, 0, (size_t)(Np - N) * Dp * sizeof(double));   // (the rows are about to be overwritten whole)
         else memset(xs, 0, (size_t)Np * Dp * sizeof(double));
         memcpy(xs + (size_t)Np * Dp, yn.data(), (size_t)Np * sizeof(double));
         memcpy(xs + (size_t)Np * Dp + Np, c.ls.data(), (size_t)D * sizeof(double));
-    } else {
-        xs_heap.assign((size_t)Np * Dp, 0.0);
-        xs = xs_heap.data();
-    }
-    if (staged) {
         // raw rows: the fit's first kernel divides by the length scales (same IEEE division, off the host's critical path)
         if (D == Dp) memcpy(xs, X, (size_t)N * D * sizeof(double));
         else
             for (int64_t i = 0; i < N; ++i) memcpy(xs + (size_t)i * Dp, X + (size_t)i * D, (size_t)D * sizeof(double));
     } else {
+        xs_heap.assign((size_t)Np * Dp, 0.0);
         for (int64_t i = 0; i < N; ++i)
-            for (int64_t d = 0; d < D; ++d) xs[(size_t)i * Dp + d] = X[(size_t)i * D + d] / c.ls[d];
+            for (int64_t d = 0; d < D; ++d) xs_heap[(size_t)i * Dp + d] = X[(size_t)i * D + d] / c.ls[d];
     }
+    return TGP_OK;
+}
 
-    const hipEvent_t e0 = c.ev0, e1 = c.ev1;
+// tgp_set_overlap: the front of the resident batch's sweep goes out with this fit (the general sweep's f64 / f32
+// kernels on the shared streams only; the geometry it is issued for is recorded and checked again by tgp_sweep)
+static int decide_overlap_front(Context &c, int grad_mode) {
+    c.pre.issue = 0; c.pre.front = false;
+    // (never for tgp_fit_grad: an evaluation of the hyper-parameter objective is followed by another evaluation,
+    // not by a sweep)
+    const int mode = grad_mode ? 0 : std::min(c.pre.mode, tuning().overlap);
+    if (mode > 0 && c.d_cand && c.M > 0 && !c.stream_own && (c.dtype == TGP_F64 || c.dtype == TGP_F32) &&
+        sweep_path(c, c.M) == SweepPath::General) {
+        API_MEM(ensure_workspace(c));
+        c.pre.issue = mode;
+        c.pre.gen = c.fit_gen + 1;
+        c.pre.cand = c.d_cand; c.pre.M = c.M; c.pre.Mpad = c.ws_Mpad; c.pre.launch_rows = c.launch_rows; c.pre.chunk = c.chunk;
+    }
+    return TGP_OK;
+}
+
+// grad_mode: 1 / 2 = the LML gradient (iso / ARD) is launched behind the fit, before the one synchronisation
+static int fit_blocked(Context &c, const FitArgs &a, const std::vector<double> &yn, int grad_mode, FitResult &r) {
+    const int64_t N = a.N, D = a.D, Np = c.Np, Dp = c.Dp;
+    bool staged;
+    std::vector<double> xs_heap;
+    API_MEM(stage_blocked_inputs(c, a, yn, staged, xs_heap));
     // (round 6) a fit whose inputs and scalars travel through the mapped staging buffers is a POLLED call up to Np = 4096:
     // no event record, no stream synchronisation -- a one-wave kernel behind the chain rings the doorbell (launch_ring) and
     // the chain's first kernel leaves the start tick.  Not while the per-launch profiling of tgp_profile_enable is on
     // (bench.py's headline runs: they keep round 5's events), nor with TGP_POLL_US=0.
-    const Bell bell = (staged && !c.profiling && Np <= 4096) ? bell_next(c) : Bell{nullptr, 0, nullptr};
-    if (!bell.word) API_HIP(hipEventRecord(e0, c.stream), "hipEventRecord");
+    CallClock clk = fit_clock(c, staged && !c.profiling && Np <= 4096);
+    const Bell &bell = clk.bell;
+    API_MEM(call_begin(c, clk));
     if (!staged) {
-        API_HIP(hipMemcpyAsync(c.d_Xs, xs, (size_t)Np * Dp * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D Xs");
+        API_HIP(hipMemcpyAsync(c.d_Xs, xs_heap.data(), (size_t)Np * Dp * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D Xs");
         API_HIP(hipMemcpyAsync(c.d_ls, c.ls.data(), (size_t)D * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D ls");
         API_HIP(hipMemcpyAsync(c.d_yn, yn.data(), (size_t)Np * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D yn");
     }
-    if (grad_mode) {
-        int rc = ensure_grad_workspace(c);
-        if (rc != TGP_OK) return rc;
-    }
+    if (grad_mode) API_MEM(ensure_grad_workspace(c));
     // Linv is zero above the diagonal whenever its leading dimension is known (nothing ever writes there) and
     // zero from row linv_extent on; this fit writes everything on and below the diagonal of its Nr rows and
     // skips the panels of pure padding: the zero fill is only needed when an older fit reached further down
     const int64_t Nr = ((N + NB - 1) / NB) * NB;
     const bool always_zero = tuning().linv_zero != 0;   // A/B
     const bool linv_clean = !always_zero && c.linv_ld == Np && c.linv_extent <= Nr;
-    // tgp_set_overlap: the front of the resident batch's sweep goes out with this fit (the general sweep's f64 / f32
-    // kernels on the shared streams only; the geometry it is issued for is recorded and checked again by tgp_sweep)
-    c.pre.issue = 0; c.pre.front = false;
-    {
-        // (never for tgp_fit_grad: an evaluation of the hyper-parameter objective is followed by another evaluation,
-        // not by a sweep)
-        const int mode = grad_mode ? 0 : std::min(c.pre.mode, tuning().overlap);
-        if (mode > 0 && c.d_cand && c.M > 0 && !c.stream_own && (c.dtype == TGP_F64 || c.dtype == TGP_F32) &&
-            sweep_path(c, c.M) == SweepPath::General) {
-            int rc = ensure_workspace(c);
-            if (rc != TGP_OK) return rc;
-            c.pre.issue = mode;
-            c.pre.gen = c.fit_gen + 1;
-            c.pre.cand = c.d_cand; c.pre.M = c.M; c.pre.Mpad = c.ws_Mpad; c.pre.launch_rows = c.launch_rows; c.pre.chunk = c.chunk;
-        }
-    }
+    API_MEM(decide_overlap_front(c, grad_mode));
     struct PrivateFit {                // (ended on every way out of this function, i.e. after the fit's synchronisation)
         Context &c; bool counted;
         ~PrivateFit() { if (counted) { private_fit_end(c.device, c.bg_lease != nullptr); c.bg_lease = nullptr; } }
@@ -802,7 +816,7 @@ static int fit_impl(tgp_handle h, const double *X, int64_t N, int64_t D, const d
         API_HIP(hipMemcpyAsync(&flag, c.d_flag, sizeof(int), hipMemcpyDeviceToHost, c.stream), "D2H flag");
         API_HIP(hipMemcpyAsync(scal, c.d_scal, 2 * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H scal");
     }
-    if (!bell.word) API_HIP(hipEventRecord(e1, c.stream), "hipEventRecord");
+    API_MEM(call_stop(c, clk));   // (an event-timed call's ev1: behind the scalars' copies, in front of the gradient)
     if (grad_mode) {   // behind the fit, in front of the call's one synchronisation
         c.grad_staged = staged;
         c.grad_timed = !bell.word;
@@ -813,70 +827,69 @@ static int fit_impl(tgp_handle h, const double *X, int64_t N, int64_t D, const d
         le = launch_ring(c, bell);
         if (le != hipSuccess) return hip_fail(c, le, "launch_ring");
     }
-    // the host's copies of the inputs (tgp_fit_append's prefix test, tgp_export_state) while the GPU works: c.fitted is
-    // false until the fit has succeeded, so nobody reads them if it does not
-    c.h_X.assign(X, X + (size_t)N * D);
-    c.h_y.assign(y, y + (size_t)N);
-    if (bell.word) {
-        const int wrc = bell_wait(c, bell, "fit sync");
-        if (wrc != TGP_OK) return wrc;
-        c.last_fit_ms = bell_ms(c);      // (the whole call: the LML gradient of tgp_fit_grad included)
-    } else {
-        API_HIP(hipStreamSynchronize(c.stream), "fit sync");
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        c.last_fit_ms = ms;
-    }
-    if (staged) {
-        scal[0] = c.h_pin_out[0];
-        scal[1] = c.h_pin_out[1];
-        flag = (int)c.h_pin_out[2];
-    }
-    if (flag != 0) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "kernel matrix is not positive definite (pivot %d of %lld <= 0)", flag - 1, (long long)N);
-        return fail(c, TGP_NOT_PD, buf);
-    }
-    // _gpr.py:609-611: -0.5 y.alpha - sum(log(diag L)) - n/2 log(2 pi)
-    c.lml = -0.5 * scal[1] - scal[0] - (double)N / 2.0 * log(2.0 * M_PI);
-    c.sumlog = scal[0];
-    c.normalize_y = normalize_y ? 1 : 0;
-    if (lml) *lml = c.lml;
-    if (y_mean) *y_mean = c.y_mean;
-    if (y_std) *y_std = c.y_std;
+    keep_training_set(c, a);   // while the GPU works
+    API_MEM(call_finish(c, clk, c.last_fit_ms, "fit sync"));   // (a polled call's time is the whole call: the LML gradient of tgp_fit_grad included)
+    r = staged ? FitResult{c.h_pin_out[0], c.h_pin_out[1], (int)c.h_pin_out[2]} : FitResult{scal[0], scal[1], flag};
+    return TGP_OK;
+}
+
+// The one place a fit or an append becomes the handle's model: TGP_NOT_PD for a failed pivot, else the LML, the optional
+// outputs, the fitted flag and the next fit generation.  (ONE step of fit_gen, where the small path took two: every reader
+// -- linv16_gen, ts_gen, mes_gen, pre.gen, an exported factor's fit_gen against fit_gen_src -- asks only whether a stored
+// generation EQUALS the current one, and pre.gen, formed ahead as fit_gen + 1, is set by the blocked path alone.)
+static int fit_commit(Context &c, const FitArgs &a, double sumlog, double y_alpha, int flag, const FitOut &out) {
+    if (flag != 0) return not_pd(c, flag - 1, a.N);
+    c.sumlog = sumlog;
+    c.lml = lml_from(sumlog, y_alpha, a.N);
+    c.normalize_y = a.normalize_y ? 1 : 0;
+    if (out.lml) *out.lml = c.lml;
+    if (out.y_mean) *out.y_mean = c.y_mean;
+    if (out.y_std) *out.y_std = c.y_std;
     c.fitted = true; ++c.fit_gen;
     return TGP_OK;
 }
 
-int tgp_fit_append(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
-                   double constant, const double *ls, int64_t n_ls, double noise, double jitter,
-                   int normalize_y, double *lml, double *y_mean, double *y_std, int *appended) try {
+static int fit_impl(tgp_handle h, const FitArgs &a, const FitOut &out, bool allow_small, int grad_mode = 0) {
     if (!h) return TGP_BAD_ARG;
-    if (h->host) { if (appended) *appended = 0; return h->host->fit(X, N, D, y, kernel, constant, ls, n_ls, noise, jitter, normalize_y, lml, y_mean, y_std); }
     Context &c = h->c;
-    if (appended) *appended = 0;
-    bool ok = c.fitted && X && y && ls && D == c.D && N == c.N + 1 && N <= c.Np &&
-              kernel == c.kernel && constant == c.constant && noise == c.noise && jitter == c.jitter &&
-              (normalize_y ? 1 : 0) == c.normalize_y && (n_ls == 1 || n_ls == D) &&
-              (int64_t)c.h_X.size() == c.N * c.D;
-    if (ok)
-        for (int64_t d = 0; d < D && ok; ++d) ok = (c.ls[d] == ls[n_ls == 1 ? 0 : d]);
-    if (ok) ok = memcmp(c.h_X.data(), X, (size_t)c.N * D * sizeof(double)) == 0;
-    if (!ok) return tgp_fit(h, X, N, D, y, kernel, constant, ls, n_ls, noise, jitter, normalize_y, lml, y_mean, y_std);
+    c.fitted = false;   // (before the checks: a rejected call leaves the handle un-fitted)
+    API_MEM(check_fit_args(c, a));
+    std::vector<double> yn;
+    API_MEM(fit_begin(c, a, yn));
+    c.small = allow_small && a.N <= 2 * NB && small_path_enabled();
+    FitResult r;
+    API_MEM(c.small ? fit_small(c, a, yn, grad_mode, r) : fit_blocked(c, a, yn, grad_mode, r));
+    return fit_commit(c, a, r.sumlog, r.y_alpha, r.flag, out);
+}
 
+// tgp_fit for the entries that end in one (tgp_fit_append, tgp_import_state, tgp_hyper_sample): either backend
+static int fit_entry(tgp_handle h, const FitArgs &a, const FitOut &out) try {
+    if (h && h->host) return host_fit(h, a, out);
+    return fit_impl(h, a, out, true);
+} TGP_CATCH_AS("tgp_fit")
+
+int tgp_fit(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
+            double constant, const double *ls, int64_t n_ls, double noise, double jitter,
+            int normalize_y, double *lml, double *y_mean, double *y_std) {
+    return fit_entry(h, FitArgs{X, N, D, y, kernel, constant, ls, n_ls, noise, jitter, normalize_y}, FitOut{lml, y_mean, y_std});
+}
+
+// the append's body: the resident fit is this one less its last row (tgp_fit_append has checked)
+static int fit_append(Context &c, const FitArgs &a, const FitOut &out) {
+    const double *X = a.X;
+    const int64_t N = a.N, D = a.D;
     c.fitted = false;
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
     API_HIP(pre_join(c), "hipStreamWaitEvent");
     const int64_t n_old = c.N, Np = c.Np, Dp = c.Dp;
     double mean = 0.0, sd = 1.0;
     std::vector<double> yn((size_t)Np, 0.0);
-    normalise_targets(y, N, normalize_y, yn, mean, sd);
+    normalise_targets(a.y, N, a.normalize_y, yn, mean, sd);
     std::vector<double> xrow((size_t)Dp, 0.0);
     for (int64_t d = 0; d < D; ++d) xrow[d] = X[(size_t)n_old * D + d] / c.ls[d];
 
     CallClock clk;
-    int rc = call_begin(c, clk);
-    if (rc != TGP_OK) return rc;
+    API_MEM(call_begin(c, clk));
     API_HIP(hipMemcpyAsync(c.d_Xs + n_old * Dp, xrow.data(), (size_t)Dp * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D x row");
     API_HIP(hipMemcpyAsync(c.d_yn, yn.data(), (size_t)Np * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D yn");
     c.linv_extent = std::max<int64_t>(c.linv_extent, ((N + NB - 1) / NB) * NB);   // the appended row of Linv
@@ -886,85 +899,97 @@ int tgp_fit_append(tgp_handle h, const double *X, int64_t N, int64_t D, const do
     double scal[4] = {0.0, 0.0, 0.0, 0.0};
     API_HIP(hipMemcpyAsync(&flag, c.d_flag, sizeof(int), hipMemcpyDeviceToHost, c.stream), "D2H flag");
     API_HIP(hipMemcpyAsync(scal, c.d_scal, 4 * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H scal");
-    if ((rc = call_finish(c, clk, c.last_fit_ms, "append sync")) != TGP_OK) return rc;
-    if (flag != 0) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "kernel matrix is not positive definite (pivot %d of %lld <= 0)", flag - 1, (long long)N);
-        return fail(c, TGP_NOT_PD, buf);
+    API_MEM(call_finish(c, clk, c.last_fit_ms, "append sync"));
+    if (flag == 0) {
+        c.N = N;
+        if (N > 2 * NB) c.small = false;      // grown out of the small-problem kernels' range
+        c.y_mean = mean; c.y_std = sd;
+        c.h_X.insert(c.h_X.end(), X + (size_t)n_old * D, X + (size_t)N * D);
+        c.h_y.assign(a.y, a.y + (size_t)N);
     }
-    c.N = N;
-    if (N > 2 * NB) c.small = false;      // grown out of the small-problem kernels' range
-    c.y_mean = mean; c.y_std = sd;
-    c.sumlog += scal[3];
-    c.lml = -0.5 * scal[1] - c.sumlog - (double)N / 2.0 * log(2.0 * M_PI);
-    c.h_X.insert(c.h_X.end(), X + (size_t)n_old * D, X + (size_t)N * D);
-    c.h_y.assign(y, y + (size_t)N);
-    if (lml) *lml = c.lml;
-    if (y_mean) *y_mean = c.y_mean;
-    if (y_std) *y_std = c.y_std;
-    if (appended) *appended = 1;
-    c.fitted = true; ++c.fit_gen;
-    return TGP_OK;
+    return fit_commit(c, a, c.sumlog + scal[3], scal[1], flag, out);   // (scal[3]: log of the new pivot)
+}
+
+int tgp_fit_append(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
+                   double constant, const double *ls, int64_t n_ls, double noise, double jitter,
+                   int normalize_y, double *lml, double *y_mean, double *y_std, int *appended) try {
+    if (!h) return TGP_BAD_ARG;
+    const FitArgs a{X, N, D, y, kernel, constant, ls, n_ls, noise, jitter, normalize_y};
+    const FitOut out{lml, y_mean, y_std};
+    if (appended) *appended = 0;
+    if (h->host) return fit_entry(h, a, out);
+    Context &c = h->c;
+    bool ok = c.fitted && X && y && ls && D == c.D && N == c.N + 1 && N <= c.Np &&
+              kernel == c.kernel && constant == c.constant && noise == c.noise && jitter == c.jitter &&
+              (normalize_y ? 1 : 0) == c.normalize_y && (n_ls == 1 || n_ls == D) &&
+              (int64_t)c.h_X.size() == c.N * c.D;
+    if (ok)
+        for (int64_t d = 0; d < D && ok; ++d) ok = (c.ls[d] == ls[n_ls == 1 ? 0 : d]);
+    if (ok) ok = memcmp(c.h_X.data(), X, (size_t)c.N * D * sizeof(double)) == 0;
+    if (!ok) return fit_entry(h, a, out);
+    const int rc = fit_append(c, a, out);
+    if (rc == TGP_OK && appended) *appended = 1;
+    return rc;
 } TGP_CATCH
 
-int tgp_fit_grad(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
-                 double constant, const double *ls, int64_t n_ls, double noise, double jitter,
-                 int normalize_y, double *lml, double *y_mean, double *y_std, double *grad) try {
+// 0.5 * trace((alpha alpha^T - K^-1) dK/dtheta) from the gradient kernels' sums [S_c, S_iso, S_diag, gd[0..D)]: _gpr.py:643-647
+static void lml_grad_from_sums(const FitArgs &a, const double *sums, double *grad) {
+    grad[0] = 0.5 * a.constant * sums[0];
+    if (a.n_ls > 1) {
+        for (int64_t d = 0; d < a.D; ++d) grad[1 + d] = a.constant * sums[3 + (size_t)d];
+    } else {
+        grad[1] = 0.5 * a.constant * sums[1];
+    }
+    grad[1 + a.n_ls] = 0.5 * a.noise * sums[2];
+}
+
+static int fit_grad_entry(tgp_handle h, const FitArgs &a, const FitOut &out, double *grad) try {
     if (!h) return TGP_BAD_ARG;
     HOST_NA("tgp_fit_grad");
     Context &c = h->c;
     if (!grad) return fail(c, TGP_BAD_ARG, "tgp_fit_grad: grad is NULL");
-    const bool ard = n_ls > 1;
+    const bool ard = a.n_ls > 1;
     // small problems: fit and gradient as two one-workgroup launches, one synchronisation, no memcpy
-    const bool small = N <= 2 * NB && ((D + 3) / 4) * 4 <= 64 && small_path_enabled();
+    const bool small = a.N <= 2 * NB && ((a.D + 3) / 4) * 4 <= 64 && small_path_enabled();
     // (otherwise the gradient needs U = Linv^T and the N^2 workspaces of the blocked path; there too it is
     // launched behind the fit, in front of the call's one synchronisation)
-    int rc = fit_impl(h, X, N, D, y, kernel, constant, ls, n_ls, noise, jitter, normalize_y, lml, y_mean, y_std, small,
-                      ard ? 2 : 1);
+    const int rc = fit_impl(h, a, out, small, ard ? 2 : 1);
     if (rc != TGP_OK) return rc;
+    const int nout = ard ? 3 + (int)c.Dp : 3;
     if (small && c.small) {
-        double out[3 + 64];
-        {
-            const double *sh = c.h_pin_out + 8;   // the shares of the block pairs, added in a fixed order
-            const int nsh = N > NB ? 3 : 1, nout = ard ? 3 + (int)c.Dp : 3;
-            for (int i = 0; i < nout; ++i) {
-                double s = sh[i];
-                for (int g = 1; g < nsh; ++g) s += sh[g * SMALL_GRAD_OUT_STRIDE + i];
-                out[i] = s;
-            }
+        double sums[3 + 64];
+        const double *sh = c.h_pin_out + 8;   // the shares of the block pairs, added in a fixed order
+        const int nsh = a.N > NB ? 3 : 1;
+        for (int i = 0; i < nout; ++i) {
+            double s = sh[i];
+            for (int g = 1; g < nsh; ++g) s += sh[g * SMALL_GRAD_OUT_STRIDE + i];
+            sums[i] = s;
         }
         c.last_grad_ms[0] = c.last_grad_ms[1] = c.last_grad_ms[2] = 0.0;   // (inside last_fit_ms)
-        grad[0] = 0.5 * constant * out[0];
-        if (ard) {
-            for (int64_t d = 0; d < D; ++d) grad[1 + d] = constant * out[3 + (size_t)d];
-        } else {
-            grad[1] = 0.5 * constant * out[1];
-        }
-        grad[1 + n_ls] = 0.5 * noise * out[2];
+        lml_grad_from_sums(a, sums, grad);
         return TGP_OK;
     }
-    std::vector<double> out((size_t)(3 + c.Dp), 0.0);
+    std::vector<double> sums((size_t)(3 + c.Dp), 0.0);
     if (c.grad_staged) {
-        memcpy(out.data(), c.h_pin_out + 8, (size_t)(ard ? 3 + c.Dp : 3) * sizeof(double));
+        memcpy(sums.data(), c.h_pin_out + 8, (size_t)nout * sizeof(double));
     } else {
         API_HIP(hipSetDevice(c.device), "hipSetDevice");
-        API_HIP(hipMemcpy(out.data(), c.d_gout, (size_t)(ard ? 3 + c.Dp : 3) * sizeof(double), hipMemcpyDeviceToHost), "D2H grad");
+        API_HIP(hipMemcpy(sums.data(), c.d_gout, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost), "D2H grad");
     }
     for (int i = 0; i < 3; ++i) {
         float gms = 0.f;
         if (c.grad_timed) (void)hipEventElapsedTime(&gms, c.evg[i], c.evg[i + 1]);   // (a polled call records no stage events: its time is all in last_fit_ms)
         c.last_grad_ms[i] = gms;
     }
-    // 0.5 * trace((alpha alpha^T - K^-1) dK/dtheta): _gpr.py:643-647
-    grad[0] = 0.5 * constant * out[0];
-    if (ard) {
-        for (int64_t d = 0; d < D; ++d) grad[1 + d] = constant * out[3 + (size_t)d];
-    } else {
-        grad[1] = 0.5 * constant * out[1];
-    }
-    grad[1 + n_ls] = 0.5 * noise * out[2];
+    lml_grad_from_sums(a, sums.data(), grad);
     return TGP_OK;
-} TGP_CATCH
+} TGP_CATCH_AS("tgp_fit_grad")
+
+int tgp_fit_grad(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
+                 double constant, const double *ls, int64_t n_ls, double noise, double jitter,
+                 int normalize_y, double *lml, double *y_mean, double *y_std, double *grad) {
+    return fit_grad_entry(h, FitArgs{X, N, D, y, kernel, constant, ls, n_ls, noise, jitter, normalize_y}, FitOut{lml, y_mean, y_std}, grad);
+}
 
 // State blob: what defines the fitted model, not the factor (the factor is N^2 and is rebuilt in
 // milliseconds; X, y and theta are N*(D+1) + D + 3 doubles).  Layout, all little-endian 8-byte
@@ -1015,8 +1040,8 @@ int tgp_import_state(tgp_handle h, const void *buf, int64_t size, double *lml) t
     memcpy(ls.data(), p, (size_t)D * 8); p += D * 8;
     memcpy(X.data(), p, (size_t)N * D * 8); p += N * D * 8;
     memcpy(y.data(), p, (size_t)N * 8);
-    return tgp_fit(h, X.data(), N, D, y.data(), (int)ints[2], reals[0], ls.data(), D, reals[1], reals[2],
-                   (int)ints[3], lml, nullptr, nullptr);
+    return fit_entry(h, FitArgs{X.data(), N, D, y.data(), (int)ints[2], reals[0], ls.data(), D, reals[1], reals[2], (int)ints[3]},
+                     FitOut{lml, nullptr, nullptr});
 } TGP_CATCH
 
 // ---- handing a FACTOR over instead of recomputing it (round 6; SURVEY 8e's alternative: "fit on GPU0 + broadcast of L, alpha") ----
@@ -1432,6 +1457,16 @@ static int mes_check(Context &c, int acq, const char *fn) {
     return TGP_OK;
 }
 
+// the winner record is packed: what tgp_winner_wait makes another stream (RCCL's) wait for -- a polled call
+// returns without a stream synchronisation, so the ordering rests on this event
+static int winner_mark(Context &c, const SweepCall &s) {
+    if (!s.winner || s.acq == TGP_ACQ_NONE) return TGP_OK;
+    API_HIP(c.ev_winner.create(hipEventDisableTiming), "hipEventCreate");
+    API_HIP(hipEventRecord(c.ev_winner, c.stream), "hipEventRecord");
+    c.winner_recorded = true;
+    return TGP_OK;
+}
+
 static int run_sweep(Context &c, const SweepCall &call, CallClock &clk) {
     SweepCall s = call;
     if (s.acq == TGP_ACQ_MES) s.mes = MesArgs{c.d_mes, c.mes_S, c.noise * (c.y_std * c.y_std)};
@@ -1457,14 +1492,35 @@ static int run_sweep(Context &c, const SweepCall &call, CallClock &clk) {
         le = launch_sweep(c, s, front);
     }
     if (le != hipSuccess) return hip_fail(c, le, "launch_sweep");
-    if (s.winner && s.acq != TGP_ACQ_NONE) {
-        // the winner record is packed: what tgp_winner_wait makes another stream (RCCL's) wait for -- a polled call
-        // returns without a stream synchronisation, so the ordering rests on this event
-        API_HIP(c.ev_winner.create(hipEventDisableTiming), "hipEventCreate");
-        API_HIP(hipEventRecord(c.ev_winner, c.stream), "hipEventRecord");
-        c.winner_recorded = true;
+    return winner_mark(c, s);
+}
+
+// ---- the record [best value, best index, clamp count] of tgp_sweep and tgp_sweep_integrated ----
+struct SweepRecord { double bv = 0.0; long long bi[2] = {0, 0}; };   // (the D2H copies' target: alive until the call's wait)
+// behind the last kernel: nothing when it left the record in mapped host memory (zc), else two D2H copies and the counters'
+// memset; ev1 of a clocked call (last_sweep_ms leaves the copies of the (M,) outputs out); those copies
+static int sweep_queue_return(Context &c, bool zc, int acq, SweepRecord &r, CallClock *clk, double *mu, double *sigma, double *acq_out) {
+    if (!zc) {
+        if (acq != TGP_ACQ_NONE) API_HIP(hipMemcpyAsync(&r.bv, c.d_best, sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H best");
+        API_HIP(hipMemcpyAsync(r.bi, c.d_besti, 2 * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H besti");
+        API_HIP(hipMemsetAsync(c.d_besti, 0, 4 * sizeof(long long), c.stream), "memset counters");   // zero between calls
     }
+    if (clk) API_MEM(call_stop(c, *clk));
+    const size_t bytes = (size_t)c.M * sizeof(double);
+    if (mu) API_HIP(hipMemcpyAsync(mu, c.d_mu, bytes, hipMemcpyDeviceToHost, c.stream), "D2H mu");
+    if (sigma) API_HIP(hipMemcpyAsync(sigma, c.d_sigma, bytes, hipMemcpyDeviceToHost, c.stream), "D2H sigma");
+    if (acq_out) API_HIP(hipMemcpyAsync(acq_out, c.d_acq, bytes, hipMemcpyDeviceToHost, c.stream), "D2H acq");
     return TGP_OK;
+}
+// after the call's wait: the record into the caller's optional outputs
+static void sweep_read_record(Context &c, bool zc, int acq, SweepRecord &r, double *best_val, int64_t *best_idx, int64_t *n_clamped) {
+    if (c.profiling) prof_collect(c);
+    if (zc) { r.bv = c.h_pin_out[0]; r.bi[0] = (long long)c.h_pin_out[1]; r.bi[1] = (long long)c.h_pin_out[2]; }
+    if (acq != TGP_ACQ_NONE) {
+        if (best_val) *best_val = r.bv;
+        if (best_idx) *best_idx = (r.bi[0] >= c.M) ? 0 : (int64_t)r.bi[0];
+    }
+    if (n_clamped) *n_clamped = (int64_t)r.bi[1];
 }
 
 int tgp_sweep(tgp_handle h, int acq, double sf, double incumbent, double param, double *mu,
@@ -1500,26 +1556,10 @@ int tgp_sweep(tgp_handle h, int acq, double sf, double incumbent, double param, 
     if (can_ring && !mu && !sigma && !acq_out) s.bell = bell_next(c);
     CallClock clk{s.bell};
     if ((rc = run_sweep(c, s, clk)) != TGP_OK) return rc;
-    double bv = 0.0;
-    long long bi[2] = {0, 0};
-    if (!zc) {
-        if (acq != TGP_ACQ_NONE) API_HIP(hipMemcpyAsync(&bv, c.d_best, sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H best");
-        API_HIP(hipMemcpyAsync(bi, c.d_besti, 2 * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H besti");
-        API_HIP(hipMemsetAsync(c.d_besti, 0, 4 * sizeof(long long), c.stream), "memset counters");   // zero between calls
-    }
-    if ((rc = call_stop(c, clk)) != TGP_OK) return rc;   // (last_sweep_ms leaves the copies of the (M,) outputs out)
-    const size_t bytes = (size_t)c.M * sizeof(double);
-    if (mu) API_HIP(hipMemcpyAsync(mu, c.d_mu, bytes, hipMemcpyDeviceToHost, c.stream), "D2H mu");
-    if (sigma) API_HIP(hipMemcpyAsync(sigma, c.d_sigma, bytes, hipMemcpyDeviceToHost, c.stream), "D2H sigma");
-    if (acq_out) API_HIP(hipMemcpyAsync(acq_out, c.d_acq, bytes, hipMemcpyDeviceToHost, c.stream), "D2H acq");
+    SweepRecord rec;
+    if ((rc = sweep_queue_return(c, zc, acq, rec, &clk, mu, sigma, acq_out)) != TGP_OK) return rc;
     if ((rc = call_finish(c, clk, c.last_sweep_ms, "sweep sync")) != TGP_OK) return rc;
-    if (c.profiling) prof_collect(c);
-    if (zc) { bv = c.h_pin_out[0]; bi[0] = (long long)c.h_pin_out[1]; bi[1] = (long long)c.h_pin_out[2]; }
-    if (acq != TGP_ACQ_NONE) {
-        if (best_val) *best_val = bv;
-        if (best_idx) *best_idx = (bi[0] >= c.M) ? 0 : (int64_t)bi[0];
-    }
-    if (n_clamped) *n_clamped = (int64_t)bi[1];
+    sweep_read_record(c, zc, acq, rec, best_val, best_idx, n_clamped);
     return TGP_OK;
 } TGP_CATCH
 
@@ -2450,8 +2490,8 @@ static int fit_optimise_streams(tgp_handle h, const double *X, int64_t N, int64_
                 const double constant = exp(th[0]), noise = exp(th[(size_t)(P - 1)]);
                 for (int64_t d = 0; d < n_ls; ++d) ls[(size_t)d] = exp(th[(size_t)(1 + d)]);
                 double lml = 0.0, phit;
-                const int rc = tgp_fit_grad(hw, X, N, D, y, kernel, constant, ls.data(), n_ls, noise, jitter, normalize_y,
-                                            &lml, nullptr, nullptr, grad.data());
+                const int rc = fit_grad_entry(hw, FitArgs{X, N, D, y, kernel, constant, ls.data(), n_ls, noise, jitter, normalize_y},
+                                              FitOut{&lml, nullptr, nullptr}, grad.data());
                 if (rc == TGP_NOT_PD) {            // -inf likelihood, zero gradient (_gpr.py:586-589)
                     phit = INFINITY;
                     for (int k = 0; k < Pf; ++k) gt[(size_t)k] = 0.0;
@@ -2611,7 +2651,7 @@ int tgp_hyper_sample(tgp_handle h, const double *X, int64_t N, int64_t D, const 
     auto eval = [&](const double *theta, double *lml) {
         double constant, noise;
         slice_unpack(theta, n_ls, constant, ls.data(), noise);
-        return tgp_fit(h, X, N, D, y, kernel, constant, ls.data(), n_ls, noise, jitter, normalize_y, lml, nullptr, nullptr);
+        return fit_entry(h, FitArgs{X, N, D, y, kernel, constant, ls.data(), n_ls, noise, jitter, normalize_y}, FitOut{lml, nullptr, nullptr});
     };
     const int rc = slice_sample(eval, (int)(2 + n_ls), theta0, log_lo, log_hi, width, S, burn, thin, seed, theta_out, lml_out,
                                 evaluations, not_pd);
@@ -2654,7 +2694,7 @@ int tgp_sweep_integrated(tgp_handle h, const double *X, int64_t N, int64_t D, co
     for (int64_t k = 0; k < S; ++k) {
         double constant, noise;
         slice_unpack(thetas + k * P, n_ls, constant, ls.data(), noise);
-        int rc = fit_impl(h, X, N, D, y, kernel, constant, ls.data(), n_ls, noise, jitter, normalize_y, nullptr, nullptr, nullptr, true);
+        int rc = fit_impl(h, FitArgs{X, N, D, y, kernel, constant, ls.data(), n_ls, noise, jitter, normalize_y}, FitOut{}, true);
         if (rc != TGP_OK) {
             const std::string why = c.err;
             return bail(fail(c, rc, "tgp_sweep_integrated: sample " + std::to_string((long long)k) + ": " + why));
@@ -2691,30 +2731,12 @@ int tgp_sweep_integrated(tgp_handle h, const double *X, int64_t N, int64_t D, co
         const hipError_t le = launch_integrate_final(c, acc, (int)S);
         if (le != hipSuccess) return bail(hip_fail(c, le, "launch_integrate_final"));
     }
-    if (acc.winner && acq != TGP_ACQ_NONE) {   // (as run_sweep: what tgp_winner_wait orders another stream behind)
-        API_HIP(c.ev_winner.create(hipEventDisableTiming), "hipEventCreate");
-        API_HIP(hipEventRecord(c.ev_winner, c.stream), "hipEventRecord");
-        c.winner_recorded = true;
-    }
-    double bv = 0.0;
-    long long bi[2] = {0, 0};
-    if (!zc) {
-        if (acq != TGP_ACQ_NONE) API_HIP(hipMemcpyAsync(&bv, c.d_best, sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H best");
-        API_HIP(hipMemcpyAsync(bi, c.d_besti, 2 * sizeof(long long), hipMemcpyDeviceToHost, c.stream), "D2H besti");
-        API_HIP(hipMemsetAsync(c.d_besti, 0, 4 * sizeof(long long), c.stream), "memset counters");
-    }
-    const size_t bytes = (size_t)c.M * sizeof(double);
-    if (mu) API_HIP(hipMemcpyAsync(mu, c.d_mu, bytes, hipMemcpyDeviceToHost, c.stream), "D2H mu");
-    if (sigma) API_HIP(hipMemcpyAsync(sigma, c.d_sigma, bytes, hipMemcpyDeviceToHost, c.stream), "D2H sigma");
-    if (acq_out) API_HIP(hipMemcpyAsync(acq_out, c.d_acq, bytes, hipMemcpyDeviceToHost, c.stream), "D2H acq");
+    if ((rc = winner_mark(c, acc)) != TGP_OK) return rc;
+    // (the call keeps no clock: no ev1, one plain synchronisation)
+    SweepRecord rec;
+    if ((rc = sweep_queue_return(c, zc, acq, rec, nullptr, mu, sigma, acq_out)) != TGP_OK) return rc;
     API_HIP(hipStreamSynchronize(c.stream), "integrated sweep sync");
-    if (c.profiling) prof_collect(c);
-    if (zc) { bv = c.h_pin_out[0]; bi[0] = (long long)c.h_pin_out[1]; bi[1] = (long long)c.h_pin_out[2]; }
-    if (acq != TGP_ACQ_NONE) {
-        if (best_val) *best_val = bv;
-        if (best_idx) *best_idx = (bi[0] >= c.M) ? 0 : (int64_t)bi[0];
-    }
-    if (n_clamped) *n_clamped = (int64_t)bi[1];
+    sweep_read_record(c, zc, acq, rec, best_val, best_idx, n_clamped);
     return TGP_OK;
 } TGP_CATCH
 
@@ -2827,15 +2849,10 @@ int tgp_predict_batch(tgp_handle h, int64_t T, const int64_t *Ns, int64_t D, con
     void *fit_args = pin + args_off, *sweep_args = pin + args_off + (size_t)T * fa;
     std::vector<double> ymean((size_t)T), ystd((size_t)T), yn((size_t)NPB);
     for (int64_t t = 0; t < T; ++t) {
-        const int64_t N = Ns[t], Nin = ((N + NB - 1) / NB) * NB;
-        double *in = c.h_pin_in + t * in_stride;
-        memset(in, 0, (size_t)(Nin * Dp + Nin) * sizeof(double));
-        for (int64_t i = 0; i < N; ++i)
-            for (int64_t d = 0; d < D; ++d) in[(size_t)i * Dp + d] = Xs[t][(size_t)i * D + d] / ls[t * D + d];
+        const int64_t N = Ns[t];
         std::fill(yn.begin(), yn.end(), 0.0);
         normalise_targets(ys[t], N, normalize_y, yn, ymean[(size_t)t], ystd[(size_t)t]);
-        memcpy(in + Nin * Dp, yn.data(), (size_t)N * sizeof(double));
-        memcpy(in + Nin * Dp + Nin, ls + t * D, (size_t)D * sizeof(double));
+        pack_small_inputs(c.h_pin_in + t * in_stride, Xs[t], N, D, Dp, ls + t * D, yn.data());
         (mid ? fill_mid_batch_args : fill_small_batch_args)(
             fit_args, sweep_args, t, c.h_pin_in.dev() + t * in_stride, d_ws + t * wsd, c.h_pin_out.dev() + 8 + 3 * t, d_cnt + 4 * t,
             d_xc, d_mu + t * M, sigma ? d_sg + t * M : nullptr, N, D, Dp, M, constants[t], noises[t], jitters[t],
@@ -2856,13 +2873,8 @@ int tgp_predict_batch(tgp_handle h, int64_t T, const int64_t *Ns, int64_t D, con
     int64_t clamped = 0;
     for (int64_t t = 0; t < T; ++t) {
         const double *res = c.h_pin_out + 8 + 3 * t;
-        if (res[2] != 0.0) {
-            char buf[200];
-            snprintf(buf, sizeof buf, "model %lld of the batch: kernel matrix is not positive definite (pivot %d of %lld <= 0)",
-                     (long long)t, (int)res[2] - 1, (long long)Ns[t]);
-            return fail(c, TGP_NOT_PD, buf);
-        }
-        if (lml) lml[t] = -0.5 * res[1] - res[0] - (double)Ns[t] / 2.0 * log(2.0 * M_PI);
+        if (res[2] != 0.0) return not_pd(c, (int)res[2] - 1, Ns[t], "model " + std::to_string((long long)t) + " of the batch: ");
+        if (lml) lml[t] = lml_from(res[0], res[1], Ns[t]);
         clamped += (int64_t)cnt[(size_t)(4 * t + 1)];
     }
     if (n_clamped) *n_clamped = clamped;
