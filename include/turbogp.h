@@ -709,7 +709,8 @@ int tgp_profile_reset(tgp_handle h);
  * Slot [16] (not a time): the candidates that survived the screen in front of the pruned sweep's bound pass (f32 RBF
  * handles, TGP_PRUNE_SCREEN; `survivors` of slot 14 are those that went on to the exact contraction), -1 when the screen
  * did not apply.  Slot [17]: profiled time (ms) of the screen's launches since tgp_profile_reset, kept apart from
- * tgp_profile_read's cross-kernel and contraction times. */
+ * tgp_profile_read's cross-kernel and contraction times.  Slot [18] (not a time): that screen's arithmetic, 0 none,
+ * 1 the f32 matrix pipe, 2 fp16 planes with the k-weighted error (TGP_SCREEN_ARITH). */
 int tgp_last_timings(tgp_handle h, double *out, int64_t n);
 /* Candidates per trmm launch (chunk) and padded N used by the sweep, for the roofline maths. */
 int tgp_sweep_geometry(tgp_handle h, int64_t *chunk, int64_t *n_padded);

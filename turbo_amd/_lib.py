@@ -991,10 +991,11 @@ class NativeGP:
         asked for, another acquisition or dtype, N <= 256, TGP_SWEEP_PRUNE=0), -2 = gated off (the noise is too small
         for the contraction's rounding), 0 = the pruned schedule ran, 1 = too many survivors: every candidate was
         contracted; lb_set / survivors = candidates of its two exact sets; screen = survivors of the matrix-core screen
-        in front of the bound pass (slot 16), -1 where it does not apply (f64, Matern, TGP_PRUNE_SCREEN=0, not pruned)"""
-        v = np.zeros(17)
-        self._check(self.lib.tgp_last_timings(self._h, _ptr(v), 17))
-        return dict(state=int(v[12]), lb_set=int(v[13]), survivors=int(v[14]), screen=int(v[16]))
+        in front of the bound pass (slot 16), -1 where it does not apply (f64, Matern, TGP_PRUNE_SCREEN=0, not pruned);
+        screen_arith = that screen's arithmetic (slot 18): 0 none, 1 f32, 2 fp16 planes (TGP_SCREEN_ARITH)"""
+        v = np.zeros(19)
+        self._check(self.lib.tgp_last_timings(self._h, _ptr(v), 19))
+        return dict(state=int(v[12]), lb_set=int(v[13]), survivors=int(v[14]), screen=int(v[16]), screen_arith=int(v[18]))
 
     def sweep_geometry(self):
         ch, npad = ctypes.c_int64(), ctypes.c_int64()

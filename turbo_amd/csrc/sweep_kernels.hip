@@ -19,6 +19,7 @@
 #include "pairwise.hpp"
 #include "philox.hpp"
 #include "prune_screen.hpp"
+#include "prune_screen_h2.hpp"
 #include "tgp_internal.hpp"
 #include "trmm_sweep.hpp"
 #include "trmm_bf16x3.hpp"
@@ -776,7 +777,9 @@ struct BoundArgs {
     long m;
     double err_scale;          // |the contraction's K*.alpha - this sum| <= err_scale * sum |k| |alpha| (two orders of the same products)
     const double *err;         // null (the tight pass: the line above), or (m,) the error of each mean as formed elsewhere (the
-                               // screen's E(c), prune_screen.hpp); abspart is then not read
+                               // screen's E(c), prune_screen.hpp); abspart is then not read ...
+    const double *wcoef;       // ... unless this is given too (the fp16 screen, prune_screen_h2.hpp): abspart then holds the shares of
+    const double *wadd;        // W = sum k_s |alpha|, and the error is the smaller of err and wcoef[c] * W + wadd[0]
     double y_mean, y_std;
     double sig_lo, sig_hi;     // every candidate's computed sigma lies in [sig_lo, sig_hi]
     int acq; double sf, incumbent, param, margin;
@@ -789,9 +792,10 @@ __global__ __launch_bounds__(256) void prune_bound_kernel(BoundArgs b) {
     double mun = 0.0, s = 0.0;
     for (int j = 0; j < b.njs; ++j) {
         mun += b.mupart[(long)j * b.ldpart + c];
-        if (!b.err) s += b.abspart[(long)j * b.ldpart + c];
+        if (!b.err || b.wcoef) s += b.abspart[(long)j * b.ldpart + c];
     }
-    const double e = b.err ? b.err[c] : b.err_scale * s;
+    double e = b.err ? b.err[c] : b.err_scale * s;
+    if (b.wcoef) e = screen_h2_error(e, b.wcoef[c], s, b.wadd[0]);
     const double mu = b.y_std * (b.sf > 0.0 ? mun + e : mun - e) + b.y_mean;
     // (EI / PI / UCB only reach the pruned sweep, so acq_value's other cases are never taken here)
     const double a_lo = acq_value(b.acq, b.sf, b.incumbent, b.param, mu, b.sig_lo);
@@ -891,22 +895,27 @@ __global__ __launch_bounds__(256) void prune_scatter_kernel(SurvArgs s) {
 }
 
 // the pruned sweep's own workspace (grow-only): bounds, lb set, survivors, block counts, the gathered scaled rows; for the
-// screen: E(c), the gathered set's tight bounds, the second survivor list, |x_i|^2 (misc + 8: its two scalars)
+// screen: E(c), the gathered set's tight bounds, the second survivor list, |x_i|^2 (misc + 8: its scalars); for the fp16
+// screen also the weighted form's factors and the sign-partitioned copy of the training points (planes, |x|^2, |alpha|)
 struct PruneWs {
     double *ub; long long *pick, *sidx, *misc; int *bcnt, *boff; void *cs;
     double *err, *ub1; long long *sidx1; float *nx;
+    double *wcoef; unsigned char *xh; float *nxp, *absa; long ncap;
 };
 static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 template <typename T>
-static hipError_t prune_workspace(Context &c, int64_t npick, int64_t rows_cap, bool screen, PruneWs &w) {
+static hipError_t prune_workspace(Context &c, int64_t npick, int64_t rows_cap, bool screen, bool h2, PruneWs &w) {
     const int64_t M = c.M, nb = (M + 255) / 256;
     const size_t o_pick = al256((size_t)M * 8), o_sidx = o_pick + al256((size_t)npick * 8), o_misc = o_sidx + al256((size_t)M * 8),
                  o_bcnt = o_misc + 256, o_boff = o_bcnt + al256((size_t)nb * 4), o_cs = o_boff + al256((size_t)nb * 4);
     const size_t o_err = o_cs + al256((size_t)rows_cap * c.Dp * sizeof(T));
     const size_t o_ub1 = o_err + (screen ? al256((size_t)c.ws_Mpad * 8) : 0), o_sidx1 = o_ub1 + (screen ? al256((size_t)rows_cap * 8) : 0),
                  o_nx = o_sidx1 + (screen ? al256((size_t)M * 8) : 0);
-    const size_t need = o_nx + (screen ? al256((size_t)c.Np * 4) : 0);
+    const long ncap = (long)((c.N + SCR_T - 1) / SCR_T + 1) * SCR_T, nch = (long)((c.Dp + SCR_DC - 1) / SCR_DC);
+    const size_t o_wc = o_nx + (screen ? al256((size_t)c.Np * 4) : 0), o_xh = o_wc + (h2 ? al256((size_t)c.ws_Mpad * 8) : 0),
+                 o_nxp = o_xh + (h2 ? al256((size_t)nch * ncap * 128) : 0), o_absa = o_nxp + (h2 ? al256((size_t)ncap * 4) : 0);
+    const size_t need = o_absa + (h2 ? al256((size_t)ncap * 4) : 0);
     TGP_TRY(c.d_prune.reserve(need, [&] { return hipStreamSynchronize(c.stream); }));
     char *b = c.d_prune;
     w.ub = reinterpret_cast<double *>(b);
@@ -920,6 +929,11 @@ static hipError_t prune_workspace(Context &c, int64_t npick, int64_t rows_cap, b
     w.ub1 = reinterpret_cast<double *>(b + o_ub1);
     w.sidx1 = reinterpret_cast<long long *>(b + o_sidx1);
     w.nx = reinterpret_cast<float *>(b + o_nx);
+    w.wcoef = reinterpret_cast<double *>(b + o_wc);
+    w.xh = reinterpret_cast<unsigned char *>(b + o_xh);
+    w.nxp = reinterpret_cast<float *>(b + o_nxp);
+    w.absa = reinterpret_cast<float *>(b + o_absa);
+    w.ncap = ncap;
     return hipSuccess;
 }
 
@@ -979,7 +993,8 @@ static hipError_t contract_rows(Context &c, const SweepPlan<T> &p, const T *cs, 
 // done = false: too many survivors -- the caller runs the full schedule (nothing of this call's results is left behind)
 //
 // With the screen (TGP_PRUNE_SCREEN, f32 + RBF; prune_screen.hpp) the order of work is
-//   1. screen over all M: mu_s and E(c) with |mu_s - mu~| <= E  ->  prune_bound_kernel (the error as its input)  ->  ub0;
+//   1. screen over all M: mu_s and E(c) with |mu_s - mu~| <= E  ->  prune_bound_kernel (the error as its input)  ->  ub0
+//      (TGP_SCREEN_ARITH: on the fp16 matrix pipe with the k-weighted E of prune_screen_h2.hpp, or the f32 kernel);
 //   2. the lb set picked from ub0 and contracted exactly -> lb (the code below, unchanged);
 //   3. count / scan / scatter on ub0 -> the screen's survivors S0 (one host synchronisation for the count);
 //   4. |S0| <= TGP_PRUNE_DIRECT: S0 is contracted as it is.  |S0| > prune_frac M: the tight bound pass over all M --
@@ -1011,14 +1026,17 @@ static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCal
     const int64_t keep = frac < 0.0 ? -1 : (frac >= 1.0 ? M : (int64_t)(frac * (double)M));   // most survivors taken
     const int64_t rows_cap = (((npick > keep ? npick : keep) + 127) / 128) * 128;
     const bool screen = sizeof(T) == 4 && c.kernel == TGP_RBF && c.D <= SCR_MAXD && tuning_prune_screen_now() != 0;
+    // the screen's arithmetic: fp16 planes and the weighted error where its closed form is no looser than the f32 screen's
+    const bool h2 = screen && tuning_screen_arith_now() == 2 && c.D >= SCRH_MIN_D;
     PruneWs w;
-    TGP_TRY(prune_workspace<T>(c, npick, rows_cap, screen, w));
+    TGP_TRY(prune_workspace<T>(c, npick, rows_cap, screen, h2, w));
     TGP_TRY(lds_opt_in(c, p.early.kern, p.early.lds));   // (the request the fit's early row tiles make of the same kernel)
     const T *Cs = reinterpret_cast<const T *>(c.d_Cs.get());
     const T *Xs = reinterpret_cast<const T *>(sizeof(T) == 8 ? (const void *)c.d_Xs : (const void *)c.d_Xs32);
     T *cs = reinterpret_cast<T *>(w.cs);
     constexpr int KAR = kstar_ar(sizeof(T));
     c.prune_screen = -1;
+    c.prune_arith = 0;
 
     if (!front_usable) TGP_TRY(issue_prep<T>(c, st));   // (a fit's front has scaled them already)
     int mark = prof_mark(c, st);
@@ -1048,7 +1066,7 @@ static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCal
         const int m2 = prof_mark(c, st);
         prof_seg(c, mark, m2, 1);
         mark = m2;
-        b.njs = njs_b; b.m = m; b.err = nullptr; b.ub = ub;
+        b.njs = njs_b; b.m = m; b.err = nullptr; b.wcoef = nullptr; b.ub = ub;
         hipLaunchKernelGGL(prune_bound_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, b);
         return hipGetLastError();
     };
@@ -1056,25 +1074,53 @@ static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCal
     // 1. the bound of every candidate: the screen's where it applies, else the tight one
     if (screen) {
         if constexpr (sizeof(T) == 4) {
-            const ScreenTerms et = screen_error_terms(c.constant, (int)c.D, N);
-            double *scal = reinterpret_cast<double *>(w.misc + 8);
-            hipLaunchKernelGGL(screen_stats_kernel, dim3(1), dim3(1024), 0, st, Xs, c.d_alpha, N, (int)c.Np, Dp, et.P, et.Q, w.nx, scal);
-            TGP_TRY(hipGetLastError());
-            const int m1 = prof_mark(c, st);
             const int64_t xb = Mpad / SCR_T;
             const int njt = (N + SCR_T - 1) / SCR_T;
             int njs_s = 1;
             while (njs_s < p.njs && njs_s < njt && xb * njs_s < SCREEN_MIN_WGS) njs_s *= 2;
             if (njs_s > p.njs) njs_s = p.njs;
-            ScreenArgs g{};
-            g.Cs = Cs; g.Xs = Xs; g.alpha = c.d_alpha; g.nx = w.nx; g.scal = scal;
-            g.mupart = c.d_mupart; g.err = w.err; g.ldpart = Mpad;
-            g.N = N; g.Np = (int)c.Np; g.Dp = Dp; g.constant = c.constant;
-            hipLaunchKernelGGL(prune_screen_kernel, dim3((unsigned)xb, (unsigned)njs_s), dim3(256), 0, st, g);
-            TGP_TRY(hipGetLastError());
-            const int m2 = prof_mark(c, st);
-            prof_seg(c, m1, m2, 2);
-            mark = m2;
+            if (h2) {
+                // one prep launch (sign partition, fp16 planes, the scalars of E), the screen, then prune_bound_kernel sums the
+                // splits' weights (in d_part, which the screened bound does not otherwise read) and takes the smaller form
+                const ScreenH2Terms et = screen_h2_error_terms(c.constant, (int)c.D, N);
+                ScreenH2Scal *scal = reinterpret_cast<ScreenH2Scal *>(w.misc + 8);
+                static_assert(sizeof(ScreenH2Scal) <= 256 - 64, "the scalars live behind misc's first eight words");
+                ScreenH2PrepArgs a{};
+                a.Xs = Xs; a.alpha = c.d_alpha; a.N = N; a.Dp = Dp; a.nch = (Dp + SCR_DC - 1) / SCR_DC; a.ncap = w.ncap;
+                a.P = et.P; a.Qc = et.Qc; a.Qw = et.Qw;
+                a.Xh = w.xh; a.nxp = w.nxp; a.absa = w.absa; a.scal = scal;
+                hipLaunchKernelGGL(screen_h2_prep_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, a);
+                TGP_TRY(hipGetLastError());
+                const int m1 = prof_mark(c, st);
+                ScreenH2Args g{};
+                g.Cs = Cs; g.Xh = w.xh; g.nxp = w.nxp; g.absa = w.absa; g.scal = scal;
+                g.mupart = c.d_mupart; g.wpart = c.d_part; g.err = w.err; g.wcoef = w.wcoef; g.ldpart = Mpad; g.ncap = w.ncap;
+                g.Dp = Dp; g.constant = c.constant; g.dcoef = et.dcoef;
+                hipLaunchKernelGGL(prune_screen_h2_kernel, dim3((unsigned)xb, (unsigned)njs_s), dim3(256), 0, st, g);
+                TGP_TRY(hipGetLastError());
+                const int m2 = prof_mark(c, st);
+                prof_seg(c, m1, m2, 2);
+                mark = m2;
+                c.prune_arith = 2;
+                b.wcoef = w.wcoef; b.wadd = &scal->wadd;
+            } else {
+                const ScreenTerms et = screen_error_terms(c.constant, (int)c.D, N);
+                double *scal = reinterpret_cast<double *>(w.misc + 8);
+                hipLaunchKernelGGL(screen_stats_kernel, dim3(1), dim3(1024), 0, st, Xs, c.d_alpha, N, (int)c.Np, Dp, et.P, et.Q, w.nx, scal);
+                TGP_TRY(hipGetLastError());
+                const int m1 = prof_mark(c, st);
+                ScreenArgs g{};
+                g.Cs = Cs; g.Xs = Xs; g.alpha = c.d_alpha; g.nx = w.nx; g.scal = scal;
+                g.mupart = c.d_mupart; g.err = w.err; g.ldpart = Mpad;
+                g.N = N; g.Np = (int)c.Np; g.Dp = Dp; g.constant = c.constant;
+                hipLaunchKernelGGL(prune_screen_kernel, dim3((unsigned)xb, (unsigned)njs_s), dim3(256), 0, st, g);
+                TGP_TRY(hipGetLastError());
+                const int m2 = prof_mark(c, st);
+                prof_seg(c, m1, m2, 2);
+                mark = m2;
+                c.prune_arith = 1;
+                b.wcoef = nullptr;
+            }
             b.njs = njs_s; b.m = M; b.err = w.err; b.ub = w.ub;
             hipLaunchKernelGGL(prune_bound_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, b);
             TGP_TRY(hipGetLastError());

@@ -1481,6 +1481,7 @@ static int run_sweep(Context &c, const SweepCall &call, CallClock &clk) {
     c.prune_state = -1;
     c.prune_lbset = c.prune_surv = 0;
     c.prune_screen = -1;
+    c.prune_arith = 0;
     if ((rc = call_begin(c, clk)) != TGP_OK) return rc;
     hipError_t le;
     if (path == SweepPath::OneLaunch) {
@@ -2942,16 +2943,17 @@ int tgp_last_timings(tgp_handle h, double *out, int64_t n) try {
     // [12..14]: what the last tgp_sweep did about pruning (sweep_pruned): -1 not eligible, -2 gated off, 0 pruned, 1 fell
     // back to every candidate; the candidates of its lb set; its survivors
     // [16]: the survivors of that sweep's screen (prune_screen.hpp), -1 when the screen did not apply; [17]: profiled time of
-    // the screen's launches since tgp_profile_reset (ms; apart from the cross-kernel's and the contraction's)
-    double v[18] = {c.last_fit_ms, c.last_sweep_ms, c.last_grad_ms[0], c.last_grad_ms[1], c.last_grad_ms[2], c.trmm_flops,
+    // the screen's launches since tgp_profile_reset (ms; apart from the cross-kernel's and the contraction's); [18]: that
+    // screen's arithmetic, 0 none, 1 f32, 2 fp16 planes (TGP_SCREEN_ARITH)
+    double v[19] = {c.last_fit_ms, c.last_sweep_ms, c.last_grad_ms[0], c.last_grad_ms[1], c.last_grad_ms[2], c.trmm_flops,
                     (double)c.last_sweep_f64, 0.0, 0.0, 0.0, 0.0, 0.0, (double)c.prune_state, (double)c.prune_lbset,
-                    (double)c.prune_surv, c.last_cov_ms, (double)c.prune_screen, c.screen_ms};
+                    (double)c.prune_surv, c.last_cov_ms, (double)c.prune_screen, c.screen_ms, (double)c.prune_arith};
     if (c.h_bell && c.h_bell[1]) {
         const unsigned long long t0 = c.h_bell[1];
         const int src[5] = {3, 4, 5, 6, 2};
         for (int k = 0; k < 5; ++k) v[7 + k] = c.h_bell[src[k]] >= t0 ? (double)(c.h_bell[src[k]] - t0) * 1e-2 : 0.0;
     }
-    for (int64_t i = 0; i < n; ++i) out[i] = i < 18 ? v[i] : 0.0;
+    for (int64_t i = 0; i < n; ++i) out[i] = i < 19 ? v[i] : 0.0;
     return TGP_OK;
 } TGP_CATCH
 

@@ -168,6 +168,7 @@ struct Context : FitMem, WsMem, OutMem {
     int prune_state = -1;         // the last sweep: -1 not eligible, -2 gated off, 0 pruned, 1 fell back to every candidate
     int64_t prune_lbset = 0, prune_surv = 0;   // ... candidates in its lb set / survivors
     int64_t prune_screen = -1;    // ... survivors of its screen (prune_screen.hpp); -1: the screen did not apply (f64, Matern, TGP_PRUNE_SCREEN=0, not pruned)
+    int prune_arith = 0;          // ... and the screen's arithmetic: 0 no screen, 1 f32 (prune_screen.hpp), 2 fp16 planes (prune_screen_h2.hpp)
     double screen_ms = 0.0;       // profiling: the screen's launches since tgp_profile_reset
     Dev<double> d_bval;           // per finalize block arg-max value
     Dev<long long> d_bidx;        // per finalize block arg-max index

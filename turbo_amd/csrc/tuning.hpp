@@ -41,6 +41,7 @@ namespace tgp {
     X(DBL, prune_min_work, "TGP_PRUNE_MIN_WORK", 1e11, "the pruned sweep runs only when M * N^2 (the full contraction's multiply-adds) reaches this: below, its fixed cost is more than it saves [per call]") \
     X(DBL, prune_tau, "TGP_PRUNE_TAU", 2e4, "the pruned sweep needs s^2 / (c + s^2) >= this * the contraction's unit roundoff (no skipped candidate can clamp)") \
     X(INT, prune_screen, "TGP_PRUNE_SCREEN", 1, "1 = the pruned sweep of an f32 RBF handle screens every candidate on the matrix cores first (prune_screen.hpp) and runs its tight bound pass only on the screen's survivors; 0 = the tight bound pass over all candidates [per call]") \
+    X(STR, screen_arith, "TGP_SCREEN_ARITH", "h2", "arithmetic of that screen: h2 = two fp16 planes per operand on v_mfma_f32_32x32x16_f16 and a k-weighted error (prune_screen_h2.hpp; D >= 15, else f32), f32 = prune_screen.hpp's kernel and closed form; the A/B switch [per call]") \
     X(INT, prune_direct, "TGP_PRUNE_DIRECT", 1024, "screen survivors up to this many are contracted as they are; more (up to TGP_PRUNE_FRAC of the batch) go through the tight bound pass first [per call]") \
     X(DBL, prune_margin, "TGP_PRUNE_MARGIN", 1e-6, "relative slack of the pruned sweep's bounds against the bar (rounding of the acquisition formulas)") \
     X(INT, mid, "TGP_MID", 1, "0 = 128 < N <= 256 down the general sweep instead of the one-launch kernel")                      \
@@ -143,6 +144,7 @@ inline int tuning_mid_maxm_now() { const char *v = getenv("TGP_MID_MAXM"); retur
 inline int tuning_sweep_prune_now() { const char *v = getenv("TGP_SWEEP_PRUNE"); return v ? atoi(v) : 1; }
 inline double tuning_prune_frac_now() { const char *v = getenv("TGP_PRUNE_FRAC"); return v ? atof(v) : 0.25; }
 inline int tuning_prune_screen_now() { const char *v = getenv("TGP_PRUNE_SCREEN"); return v ? atoi(v) : 1; }
+inline int tuning_screen_arith_now() { const char *v = getenv("TGP_SCREEN_ARITH"); return v && !strcmp(v, "f32") ? 1 : 2; }   // 1 = f32, 2 = h2
 inline int tuning_prune_direct_now() { const char *v = getenv("TGP_PRUNE_DIRECT"); return v ? atoi(v) : 1024; }
 inline double tuning_prune_min_work_now() { const char *v = getenv("TGP_PRUNE_MIN_WORK"); return v ? atof(v) : 1e11; }
 
