@@ -1,4 +1,4 @@
-"""NumPy restatement of the pruned sweep's bound and margin logic (csrc/sweep_kernels.hip, sweep_pruned).
+"""NumPy restatement of the pruned sweep's bound and margin logic (csrc/sweep_pruned.hpp, sweep_pruned).
 
 An arg-max-only sweep needs a candidate's variance only when the candidate can still win.  With q = k^T K^-1 k in [0, c]
 the variance c + s^2 - q lies in [s^2, c + s^2], and EI / PI / UCB are monotone in sigma for a fixed mean, so the mean

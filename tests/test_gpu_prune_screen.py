@@ -1,4 +1,4 @@
-"""The matrix-core screen in front of the pruned sweep's bound pass (turbo_amd/csrc/prune_screen.hpp, sweep_kernels.hip
+"""The matrix-core screen in front of the pruned sweep's bound pass (turbo_amd/csrc/prune_screen.hpp, sweep_pruned.hpp
 sweep_pruned).
 
 * Winner value, index and n_clamped byte-identical between TGP_PRUNE_SCREEN=1, TGP_PRUNE_SCREEN=0 and TGP_SWEEP_PRUNE=0

@@ -1,4 +1,4 @@
-"""The fp16 screen in front of the pruned sweep's bound pass (turbo_amd/csrc/prune_screen_h2.hpp, sweep_kernels.hip
+"""The fp16 screen in front of the pruned sweep's bound pass (turbo_amd/csrc/prune_screen_h2.hpp, sweep_pruned.hpp
 sweep_pruned).
 
 * Candidate by candidate (tests/prune_screen_h2_driver.hip on the adversarial inputs of tests/prune_screen_reference.py and

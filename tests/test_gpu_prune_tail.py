@@ -1,4 +1,4 @@
-"""The pruned sweep's shortened tail (csrc/trmm_sweep.hpp trmm_sumsq_glds_narrow_kernel, csrc/sweep_kernels.hip
+"""The pruned sweep's shortened tail (csrc/trmm_sweep.hpp trmm_sumsq_glds_narrow_kernel, csrc/sweep_pruned.hpp
 contract_variant / sweep_pruned).
 
 * The narrow contraction (128 rows x 32 / 64 candidates, the four waves splitting the rows) against the 128 x 128 kernel

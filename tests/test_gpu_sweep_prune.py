@@ -1,4 +1,4 @@
-"""The pruned arg-max-only sweep (csrc/sweep_kernels.hip, sweep_pruned) against the full sweep on the same
+"""The pruned arg-max-only sweep (csrc/sweep_pruned.hpp, sweep_pruned) against the full sweep on the same
 handle: the winner's value and index bit for bit, and the same clamp count, with and without TGP_SWEEP_PRUNE; the
 schedule that actually ran is read back (NativeGP.last_prune), so a case cannot pass by never pruning."""
 import numpy as np

@@ -1,4 +1,4 @@
-// prune_screen.hpp -- the loose screen in front of the pruned sweep's bound pass (sweep_kernels.hip, sweep_pruned).
+// prune_screen.hpp -- the loose screen in front of the pruned sweep's bound pass (sweep_pruned.hpp, sweep_pruned).
 //
 // f32 handles with the RBF kernel only.  For every candidate c the screen forms
 //     mu_s(c) = sum_i k_s(c, i) alpha_i,     k_s = exp2(fma(s, -log2(e) / 2, log2(constant))),

@@ -210,7 +210,7 @@ hipError_t launch_mt19937_columns(Context &c, const void *d_words, double *dst, 
 // MU: also accumulate the partial means Ks . alpha (the split-operand dtypes and the register-staged A/B contraction;
 // round 5: the f64 / f32 contraction does it itself -- MeanAcc in mfma_gemm.hpp -- so that this kernel needs nothing
 // of a fit but Xs and can run inside it)
-// XP == 4: the BOUND pass of the pruned sweep (sweep_pruned): no slab at all; the partial means Ks . alpha and the partial
+// XP == 4: the BOUND pass of the pruned sweep (sweep_pruned.hpp): no slab at all; the partial means Ks . alpha and the partial
 // sums |Ks| . |alpha| (the scale of their rounding error) go to mupart and to `Ks` read as (splits, ldpart) doubles --
 // from the very k values the slab-writing instantiations produce
 template <typename T, int KIND, int AR, int XP = 0, bool MU = true>
@@ -436,7 +436,7 @@ struct FinArgs {
     int acq; double sf, incumbent, param;
     double *mu, *sigma, *acqv; // nullable (M,) outputs
     double *bval; long long *bidx; long long *counters;   // counters[1] += clamped
-    const long long *gidx;     // null, or the batch index of each of the m rows (a gathered subset, sweep_pruned); `off` then only
+    const long long *gidx;     // null, or the batch index of each of the m rows (a gathered subset, sweep_pruned.hpp); `off` then only
                                // places the block partials
 };
 
@@ -656,6 +656,29 @@ static PairRows pair_rows(const Context &c, int64_t n, int tile_n) {
     return r;
 }
 
+// what every finalize of a sweep shares; the caller adds its rows (off, m, gidx, njs), which units are pairs of 128-row tiles
+// (base_pairs, pre_m / pre_pairs) and the output vectors
+template <typename T>
+static FinArgs fin_args(Context &c, const SweepPlan<T> &p, const SweepCall &call) {
+    FinArgs f{};
+    f.part = c.d_part; f.ldpart = c.ws_Mpad;
+    f.nunits = p.nunits; f.n128 = p.n128;
+    f.mupart = c.d_mupart;
+    f.kss = c.constant + c.noise;
+    f.y_mean = c.y_mean; f.y_std = c.y_std;
+    f.acq = call.acq; f.sf = call.sf; f.incumbent = call.incumbent; f.param = call.param;
+    f.bval = c.d_bval; f.bidx = c.d_bidx; f.counters = c.d_besti;
+    return f;
+}
+
+// THE launch of the final arg-max over nblk block partials into d_best / d_besti; winner, res and bell as argmax_final_kernel
+// takes them (null: not asked for)
+static hipError_t launch_argmax(Context &c, hipStream_t st, long nblk, double *winner, double *res, Bell bell) {
+    hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, st, c.d_bval, c.d_bidx, nblk, c.d_best, c.d_besti, winner,
+                       c.d_cand, (int)c.D, (long)c.M, (long long)c.winner_offset, res, bell);
+    return hipGetLastError();
+}
+
 template <typename T>
 static hipError_t issue_prep(Context &c, hipStream_t st) {
     const long pe = (long)c.ws_Mpad * c.Dp;
@@ -664,60 +687,121 @@ static hipError_t issue_prep(Context &c, hipStream_t st) {
     return hipGetLastError();
 }
 
-// the cross-kernel slab of launch pair n (rows padded to `tile_n`, the widest candidate tile any contraction of this
-// pair uses)
+constexpr int64_t pad128(int64_t n) { return ((n + 127) / 128) * 128; }
+
+// Splits of the training points over a grid of xb candidate tiles: doubled while the grid has fewer than min_wgs workgroups
+// and the count is below `stop`, then at most `cap`.  (stop < cap for the screen, whose doubling also ends at its tile
+// count: the last doubling may pass `stop`, and only `cap` cuts it back.)
+static int grid_splits(int64_t xb, int min_wgs, int cap, int stop) {
+    int s = 1;
+    while (s < stop && xb * s < min_wgs) s *= 2;
+    return s < cap ? s : cap;
+}
+
+// The profiling cursor of one schedule: the event that closed the previous launch opens the next (tgp_internal.hpp,
+// prof_mark / prof_seg).  Nothing is recorded while profiling is off.
+struct ProfCursor {
+    Context &c;
+    hipStream_t st;
+    int mark;
+    void restart() { mark = prof_mark(c, st); }          // (after a host synchronisation, or behind a launch that is not timed)
+    void seg(int kind, double flops = 0.0) {              // the launches since the mark are one segment of `kind`
+        const int m2 = prof_mark(c, st);
+        prof_seg(c, mark, m2, kind, flops);
+        mark = m2;
+    }
+};
+
+template <typename T>
+static const T *train_points(const Context &c) {
+    return reinterpret_cast<const T *>(sizeof(T) == 8 ? (const void *)c.d_Xs : (const void *)c.d_Xs32);
+}
+
 template <typename T>
 using KstarFn = void (*)(const T *, const T *, const double *, T *, double *, int, int, int, int, double, long, long, float);
 constexpr int kstar_ar(size_t bytes) { return bytes == 4 ? 8 : 4; }   // candidate rows per thread: tiles of 128 (f32) / 64 (f64)
 
-// the cross-kernel instantiation for the handle's kernel: split-operand slab (h2 / x3), slab without / with the partial
-// means (nomu), or the pruned sweep's bound pass (bound)
+// the cross-kernel's instantiations: the slab with / without the partial means, the split-operand slabs (h2 / x3), or the
+// pruned sweep's bound pass
+enum class Kstar { Slab, SlabNoMean, H2, X3, Bound };
 template <typename T>
-static KstarFn<T> kstar_fn(int kernel, bool h2, bool x3, bool nomu, bool bound) {
+static Kstar plan_kstar(const SweepPlan<T> &p) {
+    return p.h2 ? Kstar::H2 : p.x3 ? Kstar::X3 : p.mean_in_trmm ? Kstar::SlabNoMean : Kstar::Slab;
+}
+template <typename T, int KIND>
+static KstarFn<T> kstar_of_kind(Kstar which) {
     constexpr int KAR = kstar_ar(sizeof(T));
     constexpr int P3 = sizeof(T) == 4 ? 3 : 0, P2 = sizeof(T) == 4 ? 2 : 0;
+    switch (which) {
+        case Kstar::Bound: return kstar_kernel<T, KIND, KAR, 4>;
+        case Kstar::H2: return kstar_kernel<T, KIND, KAR, P2>;
+        case Kstar::X3: return kstar_kernel<T, KIND, KAR, P3>;
+        case Kstar::SlabNoMean: return kstar_kernel<T, KIND, KAR, 0, false>;
+        default: return kstar_kernel<T, KIND, KAR>;
+    }
+}
+template <typename T>
+static KstarFn<T> kstar_fn(int kernel, Kstar which) {
     switch (kernel) {
-        case TGP_RBF: return bound ? kstar_kernel<T, TGP_RBF, KAR, 4> : h2 ? kstar_kernel<T, TGP_RBF, KAR, P2> : x3 ? kstar_kernel<T, TGP_RBF, KAR, P3> : nomu ? kstar_kernel<T, TGP_RBF, KAR, 0, false> : kstar_kernel<T, TGP_RBF, KAR>;
-        case TGP_MATERN12: return bound ? kstar_kernel<T, TGP_MATERN12, KAR, 4> : h2 ? kstar_kernel<T, TGP_MATERN12, KAR, P2> : x3 ? kstar_kernel<T, TGP_MATERN12, KAR, P3> : nomu ? kstar_kernel<T, TGP_MATERN12, KAR, 0, false> : kstar_kernel<T, TGP_MATERN12, KAR>;
-        case TGP_MATERN32: return bound ? kstar_kernel<T, TGP_MATERN32, KAR, 4> : h2 ? kstar_kernel<T, TGP_MATERN32, KAR, P2> : x3 ? kstar_kernel<T, TGP_MATERN32, KAR, P3> : nomu ? kstar_kernel<T, TGP_MATERN32, KAR, 0, false> : kstar_kernel<T, TGP_MATERN32, KAR>;
-        default: return bound ? kstar_kernel<T, TGP_MATERN52, KAR, 4> : h2 ? kstar_kernel<T, TGP_MATERN52, KAR, P2> : x3 ? kstar_kernel<T, TGP_MATERN52, KAR, P3> : nomu ? kstar_kernel<T, TGP_MATERN52, KAR, 0, false> : kstar_kernel<T, TGP_MATERN52, KAR>;
+        case TGP_RBF: return kstar_of_kind<T, TGP_RBF>(which);
+        case TGP_MATERN12: return kstar_of_kind<T, TGP_MATERN12>(which);
+        case TGP_MATERN32: return kstar_of_kind<T, TGP_MATERN32>(which);
+        default: return kstar_of_kind<T, TGP_MATERN52>(which);
     }
 }
 
+// THE launch of the cross-kernel: `rows` scaled candidates at `src` (a multiple of its candidate tile) against the training
+// points in `splits` splits.  out: the slab -- for Kstar::Bound the (splits, Mpad) partial sums |Ks|.|alpha|; mupart: row 0 of
+// the partial means; pstride: 16-k blocks per row of a pre-tiled split-operand slab.
 template <typename T>
-static hipError_t issue_kstar(Context &c, const SweepPlan<T> &p, int64_t n, int sl, int tile_n, hipStream_t st) {
-    const int N = (int)c.N, Np = (int)c.Np, Dp = (int)c.Dp;
-    const T *Xs = reinterpret_cast<const T *>(sizeof(T) == 8 ? (const void *)c.d_Xs : (const void *)c.d_Xs32);
-    const PairRows r = pair_rows(c, n, tile_n);
+static hipError_t launch_kstar(Context &c, Kstar which, const T *src, int64_t rows, int splits, void *out, double *mupart,
+                               long pstride, float xscale, hipStream_t st) {
     constexpr int KAR = kstar_ar(sizeof(T));
-    const dim3 kgrid((unsigned)(r.rows / (16 * KAR)), (unsigned)p.njs);
-    const KstarFn<T> kst = kstar_fn<T>(c.kernel, p.h2, p.x3, p.mean_in_trmm, false);
-    hipLaunchKernelGGL(kst, kgrid, dim3(256), 0, st, reinterpret_cast<const T *>(c.d_Cs.get()) + r.off * Dp, Xs, c.d_alpha,
-                       reinterpret_cast<T *>(c.d_Ks[sl].get()), c.d_mupart + r.off, (int)r.rows, N, Np, Dp, c.constant,
-                       (long)c.ws_Mpad, (long)Np / 16, p.h2_sb);   // (Np / 16: 16-k blocks per row of the pre-tiled split-operand slabs)
+    hipLaunchKernelGGL(kstar_fn<T>(c.kernel, which), dim3((unsigned)(rows / (16 * KAR)), (unsigned)splits), dim3(256), 0, st, src,
+                       train_points<T>(c), c.d_alpha, reinterpret_cast<T *>(out), mupart, (int)rows, (int)c.N, (int)c.Np, (int)c.Dp,
+                       c.constant, (long)c.ws_Mpad, pstride, xscale);
     return hipGetLastError();
 }
 
-// the contraction of launch pair n over the row tiles [tm0, tm0 + ntm) of variant v
+// the cross-kernel slab of launch pair n (rows padded to `tile_n`, the widest candidate tile any contraction of this
+// pair uses)
 template <typename T>
-static hipError_t issue_trmm(Context &c, const SweepPlan<T> &p, const TrmmVariant &v, int64_t n, int sl, int tile_n_rows,
-                             int tm0, int ntm, hipStream_t st) {
-    if (ntm <= 0) return hipSuccess;
+static hipError_t issue_kstar(Context &c, const SweepPlan<T> &p, int64_t n, int sl, int tile_n, hipStream_t st) {
+    const PairRows r = pair_rows(c, n, tile_n);
+    return launch_kstar<T>(c, plan_kstar(p), reinterpret_cast<const T *>(c.d_Cs.get()) + r.off * c.Dp, r.rows, p.njs, c.d_Ks[sl].get(),
+                           c.d_mupart + r.off, (long)c.Np / 16, p.h2_sb, st);
+}
+
+// THE launch of the contraction: variant v over the row tiles [tm0, tm0 + ntm) of Linv (or its planes) and `rows` slab rows
+// of slot sl, whose partial sums start at column `off` of part / mupart.  prm and K follow from the variant's row tile (the
+// 128-row variants: prm = 1, K = n128 * 128).
+template <typename T>
+static hipError_t launch_trmm(Context &c, const SweepPlan<T> &p, const TrmmVariant &v, int sl, int64_t off, int64_t rows, int tm0,
+                              int ntm, int ntn_group, bool mean, hipStream_t st) {
     const int N = (int)c.N, Np = (int)c.Np;
-    const PairRows r = pair_rows(c, n, tile_n_rows);
     GemmArgs g{};
     g.A = sizeof(T) == 8 ? (const void *)c.d_Linv : (const void *)c.d_Linv32; g.lda = Np;
     g.B = c.d_Ks[sl]; g.ldb = Np;
     if (p.h2) { g.A = c.d_Linv16; g.K_blocks = (long)Np / 16; g.Ct = c.d_x2scal + 1; }
     if (p.x3) { g.A = c.d_Linv16; g.K_blocks = (long)Np / 16; }
-    g.part = c.d_part + r.off; g.ldpart = c.ws_Mpad;
+    g.part = c.d_part + off; g.ldpart = c.ws_Mpad;
     g.prm = v.tile_m / 128;
-    g.tm0 = tm0; g.ntm = ntm; g.ntn = (int)(r.rows / v.tile_n);
-    g.ntn_group = (c.chunk % v.tile_n == 0 && c.chunk < r.rows) ? (int)(c.chunk / v.tile_n) : 0;
+    g.tm0 = tm0; g.ntm = ntm; g.ntn = (int)(rows / v.tile_n); g.ntn_group = ntn_group;
     g.K = ((N + v.tile_m - 1) / v.tile_m) * v.tile_m;
-    if (p.mean_in_trmm) { g.mu_alpha = c.d_alpha; g.mu = c.d_mupart + r.off; }
+    if (mean) { g.mu_alpha = c.d_alpha; g.mu = c.d_mupart + off; }
     hipLaunchKernelGGL(v.kern, dim3((unsigned)(g.ntm * g.ntn)), dim3(v.threads), v.lds, st, g);
     return hipGetLastError();
+}
+
+// the contraction of launch pair n over the row tiles [tm0, tm0 + ntm) of variant v; its tiles walk the slab in groups of
+// c.chunk candidates
+template <typename T>
+static hipError_t issue_trmm(Context &c, const SweepPlan<T> &p, const TrmmVariant &v, int64_t n, int sl, int tile_n_rows,
+                             int tm0, int ntm, hipStream_t st) {
+    if (ntm <= 0) return hipSuccess;
+    const PairRows r = pair_rows(c, n, tile_n_rows);
+    const int ntn_group = (c.chunk % v.tile_n == 0 && c.chunk < r.rows) ? (int)(c.chunk / v.tile_n) : 0;
+    return launch_trmm<T>(c, p, v, sl, r.off, r.rows, tm0, ntm, ntn_group, p.mean_in_trmm, st);
 }
 
 // ---- the front of a sweep INSIDE the fit (tgp_set_overlap; north_star's step is fit -> sweep over a batch that is
@@ -756,475 +840,16 @@ static hipError_t presweep_rows_t(Context &c, hipStream_t st, int rows_final, in
     return hipSuccess;
 }
 
-// ---- the pruned sweep: contract only the candidates that can still win ----------------------------------
-// An arg-max-only sweep (no mean, deviation or acquisition vector asked for) needs a candidate's variance only if its
-// acquisition could still be the largest.  c + s^2 - q lies in [s^2, c + s^2] (q = k^T K^-1 k in [0, c]), and for a fixed
-// mean EI and UCB (param >= 0) increase with sigma, PI increases or decreases with it by the sign of its argument -- so
-// the mean alone bounds each candidate's acquisition from above, at the larger of its values at the interval's ends:
-//   1. bound pass: kstar (XP = 4) over all M without a slab -> Ks.alpha and |Ks|.|alpha| -> prune_bound_kernel: the mean
-//      moved by its rounding-error bound the way that raises the acquisition, then a relative margin on top;
-//   2. lb set: the largest bound of each of prune_top groups of consecutive candidates, contracted exactly (kstar, the
-//      128 x 128 contraction, finalize on the gathered rows); its best value is the bar lb;
-//   3. survivors: every other candidate whose bound reaches lb (less the margin), compacted in index order and contracted
-//      the same way; ONE arg-max over both sets with the batch indices, so the lowest index still wins a tie.
-// A contracted candidate goes through the full sweep's arithmetic (same Ks bits, MeanAcc's one summation order, the same
-// units in finalize whichever tiling ran): the winner's value and index are the full sweep's, bit for bit.  The clamp gate
-// s^2 / (c + s^2) >= prune_tau * u (u: the contraction's unit roundoff; measured |q - q_f64| / c stays below 122 u,
-// DESIGN §4) keeps every computed variance above 0.99 s^2: no skipped candidate could have clamped, and 0.99 s^2 is a valid
-// lower end of the interval.  More than prune_frac of the batch surviving: the full schedule runs instead.
-struct BoundArgs {
-    const double *mupart, *abspart; long ldpart; int njs;   // the bound pass's partial sums, njs rows each
-    long m;
-    double err_scale;          // |the contraction's K*.alpha - this sum| <= err_scale * sum |k| |alpha| (two orders of the same products)
-    const double *err;         // null (the tight pass: the line above), or (m,) the error of each mean as formed elsewhere (the
-                               // screen's E(c), prune_screen.hpp); abspart is then not read ...
-    const double *wcoef;       // ... unless this is given too (the fp16 screen, prune_screen_h2.hpp): abspart then holds the shares of
-    const double *wadd;        // W = sum k_s |alpha|, and the error is the smaller of err and wcoef[c] * W + wadd[0]
-    double y_mean, y_std;
-    double sig_lo, sig_hi;     // every candidate's computed sigma lies in [sig_lo, sig_hi]
-    int acq; double sf, incumbent, param, margin;
-    double *ub;                // (m,) the bound; NaN -> +inf (always contracted)
-};
+}  // namespace tgp
 
-__global__ __launch_bounds__(256) void prune_bound_kernel(BoundArgs b) {
-    const long c = (long)blockIdx.x * 256 + threadIdx.x;
-    if (c >= b.m) return;
-    double mun = 0.0, s = 0.0;
-    for (int j = 0; j < b.njs; ++j) {
-        mun += b.mupart[(long)j * b.ldpart + c];
-        if (!b.err || b.wcoef) s += b.abspart[(long)j * b.ldpart + c];
-    }
-    double e = b.err ? b.err[c] : b.err_scale * s;
-    if (b.wcoef) e = screen_h2_error(e, b.wcoef[c], s, b.wadd[0]);
-    const double mu = b.y_std * (b.sf > 0.0 ? mun + e : mun - e) + b.y_mean;
-    // (EI / PI / UCB only reach the pruned sweep, so acq_value's other cases are never taken here)
-    const double a_lo = acq_value(b.acq, b.sf, b.incumbent, b.param, mu, b.sig_lo);
-    const double a_hi = acq_value(b.acq, b.sf, b.incumbent, b.param, mu, b.sig_hi);
-    double a = a_lo > a_hi ? a_lo : a_hi;
-    // margin against the rounding of the formulas themselves (UCB: relative to its terms, which may cancel)
-    double scale = fabs(a);
-    if (b.acq == TGP_ACQ_UCB) scale += fabs(mu) + fabs(b.param) * b.sig_hi;
-    a += b.margin * scale;
-    b.ub[c] = (isnan(a_lo) || isnan(a_hi) || isnan(a)) ? INFINITY : a;
-}
+// the pruned schedule (prune_eligible, sweep_pruned): part of this translation unit -- the same flags, the same code object
+#include "sweep_pruned.hpp"
 
-// the lb set: per group of gs consecutive candidates the one with the largest bound (lowest index on ties)
-__global__ __launch_bounds__(256) void prune_pick_kernel(const double *__restrict__ ub, long m, long gs,
-                                                         long long *__restrict__ pick) {
-    __shared__ double sv[256];
-    __shared__ long long si[256];
-    const long g0 = (long)blockIdx.x * gs;
-    const long g1 = g0 + gs < m ? g0 + gs : m;
-    Best b;   // (not strided_argmax: the values carry no index array, and a thread's own indices only ascend)
-    for (long c = g0 + threadIdx.x; c < g1; c += 256) {
-        const double u = ub[c];
-        if (u > b.v) { b.v = u; b.i = c; }
-    }
-    b = block_argmax<256>(b, sv, si);
-    if (threadIdx.x == 0) pick[blockIdx.x] = b.i == IDX_NONE ? g0 : b.i;   // (all bounds -inf: the group's first)
-}
-
-// rows idx[0..n) of the scaled candidates into a dense block of `rows` rows (rows >= n zero)
-template <typename T>
-__global__ __launch_bounds__(256) void prune_gather_kernel(const T *__restrict__ Cs, int Dp, const long long *__restrict__ idx,
-                                                           long n, long rows, T *__restrict__ out) {
-    const long total = rows * Dp;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const long r = i / Dp;
-        const int d = (int)(i - r * Dp);
-        out[i] = r < n ? Cs[idx[r] * Dp + d] : (T)0;
-    }
-}
-
-struct SurvArgs {
-    const double *ub; long m;
-    const long long *pick; long gs;   // the lb set (already contracted: not a survivor)
-    const double *lb; double margin;  // lb: the lb set's best exact value (device)
-    int *bcnt; const int *boff;       // survivors per 256-candidate block / exclusive offsets
-    long long *sidx;                  // survivors' batch indices, in order
-    const long long *src;             // null, or ub is over a gathered set (already clear of the lb set): src[c] is row c's batch index
-};
-
-__device__ __forceinline__ bool prune_survives(const SurvArgs &s, long c) {
-    const double lb = s.lb[0];
-    const double bar = isinf(lb) ? lb : lb - s.margin * fabs(lb);
-    return c < s.m && s.ub[c] >= bar && (s.src || s.pick[c / s.gs] != c);
-}
-
-__global__ __launch_bounds__(256) void prune_count_kernel(SurvArgs s) {
-    __shared__ int wsum[4];
-    const long c = (long)blockIdx.x * 256 + threadIdx.x;
-    const unsigned long long bal = __ballot(prune_survives(s, c));
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) s.bcnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-}
-
-__global__ __launch_bounds__(1024) void prune_scan_kernel(const int *__restrict__ bcnt, int nb, int *__restrict__ boff,
-                                                          long long *__restrict__ total) {
-    __shared__ int part[1024];
-    const int per = (nb + 1023) / 1024;
-    const int b0 = (int)threadIdx.x * per;
-    const int b1 = b0 + per < nb ? b0 + per : nb;
-    int s = 0;
-    for (int b = b0; b < b1; ++b) s += bcnt[b];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int v = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int run = part[threadIdx.x] - s;
-    for (int b = b0; b < b1; ++b) { boff[b] = run; run += bcnt[b]; }
-    if (threadIdx.x == 1023) total[0] = part[1023];
-}
-
-__global__ __launch_bounds__(256) void prune_scatter_kernel(SurvArgs s) {
-    __shared__ int wsum[4];
-    const long c = (long)blockIdx.x * 256 + threadIdx.x;
-    const bool keep = prune_survives(s, c);
-    const unsigned long long bal = __ballot(keep);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) wsum[w] = __popcll(bal);
-    __syncthreads();
-    int off = s.boff[blockIdx.x];
-    for (int k = 0; k < w; ++k) off += wsum[k];
-    if (keep) s.sidx[off + __popcll(bal & ((1ull << lane) - 1ull))] = s.src ? s.src[c] : c;
-}
-
-// the pruned sweep's own workspace (grow-only): bounds, lb set, survivors, block counts, the gathered scaled rows; for the
-// screen: E(c), the gathered set's tight bounds, the second survivor list, |x_i|^2 (misc + 8: its scalars); for the fp16
-// screen also the weighted form's factors and the sign-partitioned copy of the training points (planes, |x|^2, |alpha|)
-struct PruneWs {
-    double *ub; long long *pick, *sidx, *misc; int *bcnt, *boff; void *cs;
-    double *err, *ub1; long long *sidx1; float *nx;
-    double *wcoef; unsigned char *xh; float *nxp, *absa; long ncap;
-};
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-template <typename T>
-static hipError_t prune_workspace(Context &c, int64_t npick, int64_t rows_cap, bool screen, bool h2, PruneWs &w) {
-    const int64_t M = c.M, nb = (M + 255) / 256;
-    const size_t o_pick = al256((size_t)M * 8), o_sidx = o_pick + al256((size_t)npick * 8), o_misc = o_sidx + al256((size_t)M * 8),
-                 o_bcnt = o_misc + 256, o_boff = o_bcnt + al256((size_t)nb * 4), o_cs = o_boff + al256((size_t)nb * 4);
-    const size_t o_err = o_cs + al256((size_t)rows_cap * c.Dp * sizeof(T));
-    const size_t o_ub1 = o_err + (screen ? al256((size_t)c.ws_Mpad * 8) : 0), o_sidx1 = o_ub1 + (screen ? al256((size_t)rows_cap * 8) : 0),
-                 o_nx = o_sidx1 + (screen ? al256((size_t)M * 8) : 0);
-    const long ncap = (long)((c.N + SCR_T - 1) / SCR_T + 1) * SCR_T, nch = (long)((c.Dp + SCR_DC - 1) / SCR_DC);
-    const size_t o_wc = o_nx + (screen ? al256((size_t)c.Np * 4) : 0), o_xh = o_wc + (h2 ? al256((size_t)c.ws_Mpad * 8) : 0),
-                 o_nxp = o_xh + (h2 ? al256((size_t)nch * ncap * 128) : 0), o_absa = o_nxp + (h2 ? al256((size_t)ncap * 4) : 0);
-    const size_t need = o_absa + (h2 ? al256((size_t)ncap * 4) : 0);
-    TGP_TRY(c.d_prune.reserve(need, [&] { return hipStreamSynchronize(c.stream); }));
-    char *b = c.d_prune;
-    w.ub = reinterpret_cast<double *>(b);
-    w.pick = reinterpret_cast<long long *>(b + o_pick);
-    w.sidx = reinterpret_cast<long long *>(b + o_sidx);
-    w.misc = reinterpret_cast<long long *>(b + o_misc);
-    w.bcnt = reinterpret_cast<int *>(b + o_bcnt);
-    w.boff = reinterpret_cast<int *>(b + o_boff);
-    w.cs = b + o_cs;
-    w.err = reinterpret_cast<double *>(b + o_err);
-    w.ub1 = reinterpret_cast<double *>(b + o_ub1);
-    w.sidx1 = reinterpret_cast<long long *>(b + o_sidx1);
-    w.nx = reinterpret_cast<float *>(b + o_nx);
-    w.wcoef = reinterpret_cast<double *>(b + o_wc);
-    w.xh = reinterpret_cast<unsigned char *>(b + o_xh);
-    w.nxp = reinterpret_cast<float *>(b + o_nxp);
-    w.absa = reinterpret_cast<float *>(b + o_absa);
-    w.ncap = ncap;
-    return hipSuccess;
-}
-
-// The contraction of `rows` gathered candidates (a multiple of 128) over ntm 128-row tiles: the widest candidate tile of
-// 128 / 64 / 32 that still gives CONTRACT_MIN_WGS workgroups, else the narrowest.  A launch with fewer workgroups than
-// CUs lasts as long as its heaviest wave, and the narrow variants (trmm_sweep.hpp) cut that wave's share of a row tile
-// from 128 x 32 to 32 x 64 / 32 x 32; they write the 128 x 128 kernel's bits, so the choice never shows in a result.
-template <typename T>
-static TrmmVariant contract_variant(const SweepPlan<T> &p, int64_t rows, int ntm) {
-    TrmmVariant v;
-    v.kern = p.early.kern; v.lds = trmm_glds_lds_bytes(); v.tile_m = 128; v.tile_n = 128; v.threads = 256;
-    if ((rows / 128) * ntm >= CONTRACT_MIN_WGS) return v;
-    if ((rows / 64) * ntm >= CONTRACT_MIN_WGS) {
-        v.kern = trmm_sumsq_glds_narrow_kernel<T, 64>; v.lds = trmm_narrow_lds_bytes<64>(); v.tile_n = 64;
-    } else {
-        v.kern = trmm_sumsq_glds_narrow_kernel<T, 32>; v.lds = trmm_narrow_lds_bytes<32>(); v.tile_n = 32;
-    }
-    return v;
-}
-
-// n gathered rows: per launch_rows of them the cross-kernel into slot 0, then the 128-row contraction over every row
-// tile with the mean inside (part / mupart rows [0, n))
-template <typename T>
-static hipError_t contract_rows(Context &c, const SweepPlan<T> &p, const T *cs, int64_t n, hipStream_t st, int &mark) {
-    const int N = (int)c.N, Np = (int)c.Np, Dp = (int)c.Dp;
-    constexpr int KAR = kstar_ar(sizeof(T));
-    const T *Xs = reinterpret_cast<const T *>(sizeof(T) == 8 ? (const void *)c.d_Xs : (const void *)c.d_Xs32);
-    const KstarFn<T> kst = kstar_fn<T>(c.kernel, false, false, true, false);
-    for (int64_t off = 0; off < n; off += c.launch_rows) {
-        const int64_t m = n - off < c.launch_rows ? n - off : c.launch_rows;
-        const int64_t rows = ((m + 127) / 128) * 128;
-        hipLaunchKernelGGL(kst, dim3((unsigned)(rows / (16 * KAR)), (unsigned)p.njs), dim3(256), 0, st, cs + off * Dp, Xs,
-                           c.d_alpha, reinterpret_cast<T *>(c.d_Ks[0].get()), c.d_mupart + off, (int)rows, N, Np, Dp, c.constant,
-                           (long)c.ws_Mpad, (long)Np / 16, 1.f);
-        TGP_TRY(hipGetLastError());
-        int m2 = prof_mark(c, st);
-        prof_seg(c, mark, m2, 1);
-        mark = m2;
-        GemmArgs g{};
-        g.A = sizeof(T) == 8 ? (const void *)c.d_Linv : (const void *)c.d_Linv32; g.lda = Np;
-        g.B = c.d_Ks[0]; g.ldb = Np;
-        g.part = c.d_part + off; g.ldpart = c.ws_Mpad;
-        g.prm = 1;
-        const TrmmVariant v = contract_variant<T>(p, rows, p.n128);
-        g.tm0 = 0; g.ntm = p.n128; g.ntn = (int)(rows / v.tile_n); g.ntn_group = 0;
-        g.K = p.n128 * 128;
-        g.mu_alpha = c.d_alpha; g.mu = c.d_mupart + off;
-        hipLaunchKernelGGL(v.kern, dim3((unsigned)(g.ntm * g.ntn)), dim3(v.threads), v.lds, st, g);
-        TGP_TRY(hipGetLastError());
-        m2 = prof_mark(c, st);
-        prof_seg(c, mark, m2, 0, (double)m * (double)N * (double)N);
-        mark = m2;
-    }
-    return hipSuccess;
-}
-
-// done = false: too many survivors -- the caller runs the full schedule (nothing of this call's results is left behind)
-//
-// With the screen (TGP_PRUNE_SCREEN, f32 + RBF; prune_screen.hpp) the order of work is
-//   1. screen over all M: mu_s and E(c) with |mu_s - mu~| <= E  ->  prune_bound_kernel (the error as its input)  ->  ub0
-//      (TGP_SCREEN_ARITH: on the fp16 matrix pipe with the k-weighted E of prune_screen_h2.hpp, or the f32 kernel);
-//   2. the lb set picked from ub0 and contracted exactly -> lb (the code below, unchanged);
-//   3. count / scan / scatter on ub0 -> the screen's survivors S0 (one host synchronisation for the count);
-//   4. |S0| <= TGP_PRUNE_DIRECT: S0 is contracted as it is.  |S0| > prune_frac M: the tight bound pass over all M --
-//      the schedule without a screen from its step 1 on, the lb set kept.  Between the two: the tight bound pass
-//      (kstar XP = 4 + prune_bound_kernel, their arithmetic and err_scale unchanged) on the gathered S0 rows, its grid
-//      splitting the training points until the chip is full, and a second filter against lb -> S1 (a second
-//      synchronisation for its count);
-//   5. gather, contract, finalize, ONE arg-max over the lb set and the last survivor set.
-// Why the result is the full sweep's, bit for bit: a candidate's exact value a(c) is formed from the contraction's mean
-// mu~(c) and a variance inside [sig_lo^2, sig_hi^2]; ub0(c) >= a(c) because mu~ lies within E(c) of mu_s(c) and
-// prune_bound_kernel takes the end of that interval, and of the variance's, that raises the acquisition; the tight bound
-// ub1(c) >= a(c) as before.  The winner w of the full sweep has a(w) >= a(any lb-set member) = lb, hence ub0(w) >= lb and
-// ub1(w) >= lb: it is in the lb set or survives every filter, and so does every candidate that ties with it.  Every
-// contracted candidate goes through the full sweep's arithmetic, the one arg-max sees batch indices, and no skipped
-// candidate can clamp (the gate above): value, index and n_clamped are the full sweep's.  The screen's own values and
-// its looseness never reach a result; they only move work between "skipped" and "contracted".
-template <typename T>
-static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCall &call, bool front_usable, bool &done) {
-    done = false;
-    const int acq = call.acq;
-    const double sf = call.sf, incumbent = call.incumbent, param = call.param;
-    const Tuning &tu = tuning();
-    const int64_t M = c.M, Mpad = c.ws_Mpad;
-    const int N = (int)c.N, Dp = (int)c.Dp;
-    hipStream_t st = c.stream;
-    const int64_t top = tu.prune_top < 1 ? 1 : tu.prune_top;
-    const int64_t gs = (M + top - 1) / top, npick = (M + gs - 1) / gs;
-    const double frac = tuning_prune_frac_now();
-    const int64_t keep = frac < 0.0 ? -1 : (frac >= 1.0 ? M : (int64_t)(frac * (double)M));   // most survivors taken
-    const int64_t rows_cap = (((npick > keep ? npick : keep) + 127) / 128) * 128;
-    const bool screen = sizeof(T) == 4 && c.kernel == TGP_RBF && c.D <= SCR_MAXD && tuning_prune_screen_now() != 0;
-    // the screen's arithmetic: fp16 planes and the weighted error where its closed form is no looser than the f32 screen's
-    const bool h2 = screen && tuning_screen_arith_now() == 2 && c.D >= SCRH_MIN_D;
-    PruneWs w;
-    TGP_TRY(prune_workspace<T>(c, npick, rows_cap, screen, h2, w));
-    TGP_TRY(lds_opt_in(c, p.early.kern, p.early.lds));   // (the request the fit's early row tiles make of the same kernel)
-    const T *Cs = reinterpret_cast<const T *>(c.d_Cs.get());
-    const T *Xs = reinterpret_cast<const T *>(sizeof(T) == 8 ? (const void *)c.d_Xs : (const void *)c.d_Xs32);
-    T *cs = reinterpret_cast<T *>(w.cs);
-    constexpr int KAR = kstar_ar(sizeof(T));
-    c.prune_screen = -1;
-    c.prune_arith = 0;
-
-    if (!front_usable) TGP_TRY(issue_prep<T>(c, st));   // (a fit's front has scaled them already)
-    int mark = prof_mark(c, st);
-
-    BoundArgs b{};
-    b.mupart = c.d_mupart; b.abspart = c.d_part; b.ldpart = Mpad;
-    b.err_scale = 4.0 * (double)(N + 8) * 0x1p-53;
-    b.y_mean = c.y_mean; b.y_std = c.y_std;
-    b.sig_lo = sqrt((0.99 * c.noise) * (c.y_std * c.y_std));
-    b.sig_hi = sqrt((c.constant + c.noise) * (c.y_std * c.y_std));
-    b.acq = acq; b.sf = sf; b.incumbent = incumbent; b.param = param; b.margin = tu.prune_margin;
-
-    // The tight bound of `rows` scaled candidates (a multiple of 16 KAR; m of them real) into ub.
-    // Splits of the training points over the bound pass's grid: a big batch fills the chip with its candidate tiles
-    // alone, and every split costs a workgroup its prologue (candidate tile staged, first barrier), 2 x 8 shuffled
-    // partial sums and a row of each partial array for prune_bound_kernel to read.  (Any split is covered by
-    // err_scale: it bounds the distance between two summation orders of the same products.)
-    auto tight_bound = [&](const T *rowsrc, int64_t rows, int64_t m, double *ub) -> hipError_t {
-        const int64_t xb = rows / (16 * KAR);
-        int njs_b = 1;
-        while (njs_b < p.njs && xb * njs_b < BOUND_MIN_WGS) njs_b *= 2;
-        if (njs_b > p.njs) njs_b = p.njs;
-        hipLaunchKernelGGL(kstar_fn<T>(c.kernel, false, false, false, true), dim3((unsigned)xb, (unsigned)njs_b),
-                           dim3(256), 0, st, rowsrc, Xs, c.d_alpha, reinterpret_cast<T *>(c.d_part.get()), c.d_mupart, (int)rows, N,
-                           (int)c.Np, Dp, c.constant, (long)Mpad, 0L, 1.f);
-        TGP_TRY(hipGetLastError());
-        const int m2 = prof_mark(c, st);
-        prof_seg(c, mark, m2, 1);
-        mark = m2;
-        b.njs = njs_b; b.m = m; b.err = nullptr; b.wcoef = nullptr; b.ub = ub;
-        hipLaunchKernelGGL(prune_bound_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, b);
-        return hipGetLastError();
-    };
-
-    // 1. the bound of every candidate: the screen's where it applies, else the tight one
-    if (screen) {
-        if constexpr (sizeof(T) == 4) {
-            const int64_t xb = Mpad / SCR_T;
-            const int njt = (N + SCR_T - 1) / SCR_T;
-            int njs_s = 1;
-            while (njs_s < p.njs && njs_s < njt && xb * njs_s < SCREEN_MIN_WGS) njs_s *= 2;
-            if (njs_s > p.njs) njs_s = p.njs;
-            if (h2) {
-                // one prep launch (sign partition, fp16 planes, the scalars of E), the screen, then prune_bound_kernel sums the
-                // splits' weights (in d_part, which the screened bound does not otherwise read) and takes the smaller form
-                const ScreenH2Terms et = screen_h2_error_terms(c.constant, (int)c.D, N);
-                ScreenH2Scal *scal = reinterpret_cast<ScreenH2Scal *>(w.misc + 8);
-                static_assert(sizeof(ScreenH2Scal) <= 256 - 64, "the scalars live behind misc's first eight words");
-                ScreenH2PrepArgs a{};
-                a.Xs = Xs; a.alpha = c.d_alpha; a.N = N; a.Dp = Dp; a.nch = (Dp + SCR_DC - 1) / SCR_DC; a.ncap = w.ncap;
-                a.P = et.P; a.Qc = et.Qc; a.Qw = et.Qw;
-                a.Xh = w.xh; a.nxp = w.nxp; a.absa = w.absa; a.scal = scal;
-                hipLaunchKernelGGL(screen_h2_prep_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, a);
-                TGP_TRY(hipGetLastError());
-                const int m1 = prof_mark(c, st);
-                ScreenH2Args g{};
-                g.Cs = Cs; g.Xh = w.xh; g.nxp = w.nxp; g.absa = w.absa; g.scal = scal;
-                g.mupart = c.d_mupart; g.wpart = c.d_part; g.err = w.err; g.wcoef = w.wcoef; g.ldpart = Mpad; g.ncap = w.ncap;
-                g.Dp = Dp; g.constant = c.constant; g.dcoef = et.dcoef;
-                hipLaunchKernelGGL(prune_screen_h2_kernel, dim3((unsigned)xb, (unsigned)njs_s), dim3(256), 0, st, g);
-                TGP_TRY(hipGetLastError());
-                const int m2 = prof_mark(c, st);
-                prof_seg(c, m1, m2, 2);
-                mark = m2;
-                c.prune_arith = 2;
-                b.wcoef = w.wcoef; b.wadd = &scal->wadd;
-            } else {
-                const ScreenTerms et = screen_error_terms(c.constant, (int)c.D, N);
-                double *scal = reinterpret_cast<double *>(w.misc + 8);
-                hipLaunchKernelGGL(screen_stats_kernel, dim3(1), dim3(1024), 0, st, Xs, c.d_alpha, N, (int)c.Np, Dp, et.P, et.Q, w.nx, scal);
-                TGP_TRY(hipGetLastError());
-                const int m1 = prof_mark(c, st);
-                ScreenArgs g{};
-                g.Cs = Cs; g.Xs = Xs; g.alpha = c.d_alpha; g.nx = w.nx; g.scal = scal;
-                g.mupart = c.d_mupart; g.err = w.err; g.ldpart = Mpad;
-                g.N = N; g.Np = (int)c.Np; g.Dp = Dp; g.constant = c.constant;
-                hipLaunchKernelGGL(prune_screen_kernel, dim3((unsigned)xb, (unsigned)njs_s), dim3(256), 0, st, g);
-                TGP_TRY(hipGetLastError());
-                const int m2 = prof_mark(c, st);
-                prof_seg(c, m1, m2, 2);
-                mark = m2;
-                c.prune_arith = 1;
-                b.wcoef = nullptr;
-            }
-            b.njs = njs_s; b.m = M; b.err = w.err; b.ub = w.ub;
-            hipLaunchKernelGGL(prune_bound_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, b);
-            TGP_TRY(hipGetLastError());
-        }
-    } else {
-        TGP_TRY(tight_bound(Cs, Mpad, M, w.ub));
-    }
-    hipLaunchKernelGGL(prune_pick_kernel, dim3((unsigned)npick), dim3(256), 0, st, w.ub, (long)M, (long)gs, w.pick);
-    TGP_TRY(hipGetLastError());
-
-    auto gather = [&](const long long *idx, int64_t n) -> hipError_t {
-        const long total = (long)(((n + 127) / 128) * 128) * Dp;
-        const long blocks = (total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192;
-        hipLaunchKernelGGL(prune_gather_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, Cs, Dp, idx, (long)n,
-                           (long)(((n + 127) / 128) * 128), cs);
-        return hipGetLastError();
-    };
-    auto finalize = [&](const long long *idx, int64_t n, int64_t blk0) -> hipError_t {
-        FinArgs f{};
-        f.part = c.d_part; f.ldpart = Mpad;
-        f.nunits = p.nunits; f.n128 = p.n128;
-        f.base_pairs = p.nunits;   // 128-row tiles throughout
-        f.mupart = c.d_mupart; f.njs = 1;
-        f.off = blk0 * FIN_BLOCK; f.m = n;
-        f.kss = c.constant + c.noise;
-        f.y_mean = c.y_mean; f.y_std = c.y_std;
-        f.acq = acq; f.sf = sf; f.incumbent = incumbent; f.param = param;
-        f.bval = c.d_bval; f.bidx = c.d_bidx; f.counters = c.d_besti;
-        f.gidx = idx;
-        hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n + FIN_BLOCK - 1) / FIN_BLOCK)), dim3(FIN_BLOCK), 0, st, f);
-        return hipGetLastError();
-    };
-    // the candidates of ub[0, m) that reach the bar, compacted in order into out; their number comes back to the host
-    // (the launches behind it are sized by the count)
-    auto survivors = [&](const double *ub, int64_t m, const long long *src, long long *out, long long &n) -> hipError_t {
-        const int64_t nb = (m + 255) / 256;
-        SurvArgs s{ub, (long)m, w.pick, (long)gs, c.d_best, tu.prune_margin, w.bcnt, w.boff, out, src};
-        hipLaunchKernelGGL(prune_count_kernel, dim3((unsigned)nb), dim3(256), 0, st, s);
-        TGP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(1024), 0, st, w.bcnt, (int)nb, w.boff, w.misc);
-        TGP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(prune_scatter_kernel, dim3((unsigned)nb), dim3(256), 0, st, s);
-        TGP_TRY(hipGetLastError());
-        TGP_TRY(hipMemcpyAsync(&n, w.misc, sizeof(long long), hipMemcpyDeviceToHost, st));
-        return hipStreamSynchronize(st);
-    };
-
-    // 2. the lb set, exactly; its best value is the bar (d_best)
-    TGP_TRY(gather(w.pick, npick));
-    TGP_TRY(contract_rows<T>(c, p, cs, npick, st, mark));
-    TGP_TRY(finalize(w.pick, npick, 0));
-    const int64_t nblk_a = (npick + FIN_BLOCK - 1) / FIN_BLOCK;
-    hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, st, c.d_bval, c.d_bidx, (long)nblk_a, c.d_best, c.d_besti,
-                       nullptr, c.d_cand, (int)c.D, (long)M, 0LL, nullptr, Bell{nullptr, 0, nullptr});
-    TGP_TRY(hipGetLastError());
-
-    // 3. the survivors, in index order
-    long long nsurv = 0;
-    const long long *sidx = w.sidx;
-    TGP_TRY(survivors(w.ub, M, nullptr, w.sidx, nsurv));
-    c.prune_lbset = npick;
-    if (screen) {
-        c.prune_screen = nsurv;
-        if (nsurv > keep) {
-            // the screen was too loose for this batch: the tight bound of every candidate, against the same lb
-            mark = prof_mark(c, st);
-            TGP_TRY(tight_bound(Cs, Mpad, M, w.ub));
-            TGP_TRY(survivors(w.ub, M, nullptr, w.sidx, nsurv));
-        } else if (nsurv > tuning_prune_direct_now()) {
-            const int64_t rows = ((nsurv + 127) / 128) * 128;
-            TGP_TRY(gather(w.sidx, nsurv));
-            mark = prof_mark(c, st);
-            TGP_TRY(tight_bound(cs, rows, nsurv, w.ub1));
-            const long long n0 = nsurv;
-            TGP_TRY(survivors(w.ub1, n0, w.sidx, w.sidx1, nsurv));
-            sidx = w.sidx1;
-        }
-        mark = prof_mark(c, st);
-    }
-    c.prune_surv = nsurv;
-    if (nsurv > keep) {
-        // the full schedule instead: it counts the lb set's clamps again (the counter was zero when this sweep began)
-        c.prune_state = 1;
-        return hipMemsetAsync(c.d_besti + 1, 0, sizeof(long long), st);
-    }
-    int64_t nblk_b = 0;
-    if (nsurv > 0) {
-        TGP_TRY(gather(sidx, nsurv));
-        TGP_TRY(contract_rows<T>(c, p, cs, nsurv, st, mark));
-        TGP_TRY(finalize(sidx, nsurv, nblk_a));
-        nblk_b = (nsurv + FIN_BLOCK - 1) / FIN_BLOCK;
-    }
-    hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, st, c.d_bval, c.d_bidx, (long)(nblk_a + nblk_b), c.d_best,
-                       c.d_besti, call.winner, c.d_cand, (int)c.D, (long)M, (long long)c.winner_offset, call.res,
-                       Bell{nullptr, 0, nullptr});
-    TGP_TRY(hipGetLastError());
-    c.prune_state = 0;
-    done = true;
-    return hipSuccess;
-}
+namespace tgp {
 
 template <typename T, int BK>
 static hipError_t sweep_chunks(Context &c, const SweepCall &call, bool front_usable) {
-    const int Np = (int)c.Np, D = (int)c.D;
+    const int Np = (int)c.Np;
     const int acq = call.acq;
     SweepPlan<T> p;
     TGP_TRY((make_plan<T, BK>(c, p)));
@@ -1233,18 +858,16 @@ static hipError_t sweep_chunks(Context &c, const SweepCall &call, bool front_usa
     // an arg-max-only EI / PI / UCB sweep in f32 / f64 first tries the pruned schedule (TGP_SWEEP_PRUNE); its bounds are
     // proved for those three only, so TGP_ACQ_MES always takes the schedule below (prune_state stays "not eligible")
     bool fell_back = false;
-    if (!call.mu && !call.sigma && !call.acqv && (acq == TGP_ACQ_EI || acq == TGP_ACQ_PI || acq == TGP_ACQ_UCB) &&
-        (c.dtype == TGP_F32 || c.dtype == TGP_F64) && p.mean_in_trmm && tuning_sweep_prune_now() != 0 &&
-        c.M > tuning().prune_top && (double)c.M * (double)c.N * (double)c.N >= tuning_prune_min_work_now()) {
-        const double u = sizeof(T) == 4 ? 0x1p-24 : 0x1p-53;
-        if (c.noise > 0.0 && c.noise / (c.constant + c.noise) >= tuning().prune_tau * u) {
+    switch (prune_eligible<T>(c, p, call)) {
+        case PruneGo::Go: {
             bool done = false;
             TGP_TRY(sweep_pruned<T>(c, p, call, front_usable, done));
             if (done) return hipSuccess;
             fell_back = true;
-        } else {
-            c.prune_state = -2;
+            break;
         }
+        case PruneGo::GatedOff: c.prune_state = -2; break;
+        case PruneGo::NotEligible: break;
     }
 
     // One pass over the batch: scale all candidates once, then per chunk the cross-kernel slab and
@@ -1253,7 +876,6 @@ static hipError_t sweep_chunks(Context &c, const SweepCall &call, bool front_usa
     // (Running kstar / finalize on a second stream beside the contraction was measured slower twice
     // -- their workgroups take CUs from the MFMA kernel instead of sharing them -- and was removed.)
     hipStream_t sa = c.stream;
-    const int64_t Mpad = c.ws_Mpad;
     // what the last fit already started for this very batch (tgp_set_overlap): the scaling, launch pair 0's
     // cross-kernel and the first pre128 row tiles of its contraction
     // (after a fall-back from the pruned schedule the slab and the partial sums hold its rows: the front is spent)
@@ -1279,43 +901,31 @@ static hipError_t sweep_chunks(Context &c, const SweepCall &call, bool front_usa
     const bool two_slots = c.d_Ks[1] != nullptr && c.launch_rows == c.chunk && (x3 || h2);
     const int64_t nchunks = (c.M + c.launch_rows - 1) / c.launch_rows;
     const int tn_rows = v.tile_n > 128 ? v.tile_n : 128;   // (the early contraction's tiles are 128 candidates wide: pad to the wider of the two, always)
-    int mark = -1;   // profiling: the event that closed the previous launch opens the next
+    ProfCursor cur{c, sa, -1};   // profiling: the event that closed the previous launch opens the next
     for (int64_t n = 0; n < nchunks; ++n) {
         const int sl = two_slots ? (int)(n & 1) : 0;
-        if (mark < 0) mark = prof_mark(c, sa);
+        if (cur.mark < 0) cur.restart();
         if (!(pre && n == 0)) {
             TGP_TRY(issue_kstar<T>(c, p, n, sl, p.mean_in_trmm ? tn_rows : v.tile_n, sa));
-            const int m2 = prof_mark(c, sa);
-            prof_seg(c, mark, m2, 1);
-            mark = m2;
+            cur.seg(1);
         }
         // row tiles of this variant from the first one the fit has not contracted already
         const int tm_first = (pre && n == 0) ? pre128 * 128 / v.tile_m : 0;
         const int ntm_all = ((int)c.N + v.tile_m - 1) / v.tile_m;
         TGP_TRY(issue_trmm<T>(c, p, v, n, sl, p.mean_in_trmm ? tn_rows : v.tile_n, tm_first, ntm_all - tm_first, sa));
-        {
-            const int m2 = prof_mark(c, sa);
-            // algorithmic flops of this launch: rows^2 per candidate over the rows it covers (the solve's
-            // N (N + 1) / 2 FMAs) -- a launch the fit took row tiles of has N^2 - r0^2
-            const double r0 = (double)tm_first * v.tile_m;
-            prof_seg(c, mark, m2, 0, (double)pair_rows(c, n, v.tile_n).m * ((double)c.N * (double)c.N - r0 * r0));
-            mark = m2;
-        }
+        // algorithmic flops of this launch: rows^2 per candidate over the rows it covers (the solve's
+        // N (N + 1) / 2 FMAs) -- a launch the fit took row tiles of has N^2 - r0^2
+        const double r0 = (double)tm_first * v.tile_m;
+        cur.seg(0, (double)pair_rows(c, n, v.tile_n).m * ((double)c.N * (double)c.N - r0 * r0));
     }
     {
-        FinArgs f{};
-        f.part = c.d_part; f.ldpart = Mpad;
-        f.nunits = p.nunits; f.n128 = p.n128;
+        FinArgs f = fin_args<T>(c, p, call);
         f.base_pairs = (v.tile_m == 128) ? p.nunits : 0;
         f.pre_m = pre ? pair_rows(c, 0, tn_rows).m : 0;
         f.pre_pairs = pre128 / 2;
-        f.mupart = c.d_mupart; f.njs = p.mean_in_trmm ? 1 : p.njs;
+        f.njs = p.mean_in_trmm ? 1 : p.njs;
         f.off = 0; f.m = c.M;
-        f.kss = c.constant + c.noise;
-        f.y_mean = c.y_mean; f.y_std = c.y_std;
-        f.acq = acq; f.sf = call.sf; f.incumbent = call.incumbent; f.param = call.param;
         f.mu = call.mu; f.sigma = call.sigma; f.acqv = call.acqv;
-        f.bval = c.d_bval; f.bidx = c.d_bidx; f.counters = c.d_besti;
         const dim3 fgrid((unsigned)((c.M + FIN_BLOCK - 1) / FIN_BLOCK));
         if (acq == TGP_ACQ_MES) hipLaunchKernelGGL(finalize_mes_kernel, fgrid, dim3(FIN_BLOCK), 0, sa, f, call.mes);
         else hipLaunchKernelGGL(finalize_kernel, fgrid, dim3(FIN_BLOCK), 0, sa, f);
@@ -1324,10 +934,7 @@ static hipError_t sweep_chunks(Context &c, const SweepCall &call, bool front_usa
     if (acq != TGP_ACQ_NONE || call.res) {
         // (without an acquisition the launch only hands the clamp count over and zeroes the counter)
         const long nblk = acq != TGP_ACQ_NONE ? (long)((c.M + FIN_BLOCK - 1) / FIN_BLOCK) : 0L;
-        hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, sa, c.d_bval, c.d_bidx, nblk,
-                           c.d_best, c.d_besti, acq != TGP_ACQ_NONE ? call.winner : nullptr, c.d_cand, D, (long)c.M,
-                           (long long)c.winner_offset, call.res, Bell{nullptr, 0, nullptr});
-        TGP_TRY(hipGetLastError());
+        TGP_TRY(launch_argmax(c, sa, nblk, acq != TGP_ACQ_NONE ? call.winner : nullptr, call.res, Bell{nullptr, 0, nullptr}));
     }
     return hipSuccess;
 }
@@ -1335,10 +942,7 @@ static hipError_t sweep_chunks(Context &c, const SweepCall &call, bool front_usa
 // behind launch_small_sweep (64 candidates per arg-max partial; without an acquisition only the clamp count is handed over)
 hipError_t launch_argmax_final(Context &c, const SweepCall &call) {
     const long nblk = call.acq != TGP_ACQ_NONE ? (long)((c.M + NB - 1) / NB) : 0L;
-    hipLaunchKernelGGL(argmax_final_kernel, dim3(1), dim3(256), 0, c.stream, c.d_bval, c.d_bidx, nblk,
-                       c.d_best, c.d_besti, call.winner, c.d_cand, (int)c.D, (long)c.M,
-                       (long long)c.winner_offset, call.res, call.bell);
-    return hipGetLastError();
+    return launch_argmax(c, c.stream, nblk, call.winner, call.res, call.bell);
 }
 
 // dispatch on (dtype, TGP_BK)

@@ -1,0 +1,527 @@
+// sweep_pruned.hpp -- the pruned arg-max sweep: its kernels, its workspace, and the schedule as a driver over
+// named steps.
+//
+// NOT a header of its own: sweep_kernels.hip includes it once, after SweepPlan, make_plan and the launch helpers both
+// schedules share (launch_kstar, launch_trmm, fin_args, launch_argmax, ProfCursor, grid_splits, pad128), so that the pruned
+// sweep stays in that translation unit -- the same compile flags, the same kernel symbols, the same code object.
+#pragma once
+
+namespace tgp {
+
+// ---- the pruned sweep: contract only the candidates that can still win ----------------------------------
+// An arg-max-only sweep (no mean, deviation or acquisition vector asked for) needs a candidate's variance only if its
+// acquisition could still be the largest.  c + s^2 - q lies in [s^2, c + s^2] (q = k^T K^-1 k in [0, c]), and for a fixed
+// mean EI and UCB (param >= 0) increase with sigma, PI increases or decreases with it by the sign of its argument -- so
+// the mean alone bounds each candidate's acquisition from above, at the larger of its values at the interval's ends:
+//   1. bound pass: kstar (XP = 4) over all M without a slab -> Ks.alpha and |Ks|.|alpha| -> prune_bound_kernel: the mean
+//      moved by its rounding-error bound the way that raises the acquisition, then a relative margin on top;
+//   2. lb set: the largest bound of each of prune_top groups of consecutive candidates, contracted exactly (kstar, the
+//      128 x 128 contraction, finalize on the gathered rows); its best value is the bar lb;
+//   3. survivors: every other candidate whose bound reaches lb (less the margin), compacted in index order and contracted
+//      the same way; ONE arg-max over both sets with the batch indices, so the lowest index still wins a tie.
+// A contracted candidate goes through the full sweep's arithmetic (same Ks bits, MeanAcc's one summation order, the same
+// units in finalize whichever tiling ran): the winner's value and index are the full sweep's, bit for bit.  The clamp gate
+// s^2 / (c + s^2) >= prune_tau * u (u: the contraction's unit roundoff; measured |q - q_f64| / c stays below 122 u,
+// DESIGN §4) keeps every computed variance above 0.99 s^2: no skipped candidate could have clamped, and 0.99 s^2 is a valid
+// lower end of the interval.  More than prune_frac of the batch surviving: the full schedule runs instead.
+struct BoundArgs {
+    const double *mupart, *abspart; long ldpart; int njs;   // the bound pass's partial sums, njs rows each
+    long m;
+    double err_scale;          // |the contraction's K*.alpha - this sum| <= err_scale * sum |k| |alpha| (two orders of the same products)
+    const double *err;         // null (the tight pass: the line above), or (m,) the error of each mean as formed elsewhere (the
+                               // screen's E(c), prune_screen.hpp); abspart is then not read ...
+    const double *wcoef;       // ... unless this is given too (the fp16 screen, prune_screen_h2.hpp): abspart then holds the shares of
+    const double *wadd;        // W = sum k_s |alpha|, and the error is the smaller of err and wcoef[c] * W + wadd[0]
+    double y_mean, y_std;
+    double sig_lo, sig_hi;     // every candidate's computed sigma lies in [sig_lo, sig_hi]
+    int acq; double sf, incumbent, param, margin;
+    double *ub;                // (m,) the bound; NaN -> +inf (always contracted)
+};
+
+__global__ __launch_bounds__(256) void prune_bound_kernel(BoundArgs b) {
+    const long c = (long)blockIdx.x * 256 + threadIdx.x;
+    if (c >= b.m) return;
+    double mun = 0.0, s = 0.0;
+    for (int j = 0; j < b.njs; ++j) {
+        mun += b.mupart[(long)j * b.ldpart + c];
+        if (!b.err || b.wcoef) s += b.abspart[(long)j * b.ldpart + c];
+    }
+    double e = b.err ? b.err[c] : b.err_scale * s;
+    if (b.wcoef) e = screen_h2_error(e, b.wcoef[c], s, b.wadd[0]);
+    const double mu = b.y_std * (b.sf > 0.0 ? mun + e : mun - e) + b.y_mean;
+    // (EI / PI / UCB only reach the pruned sweep, so acq_value's other cases are never taken here)
+    const double a_lo = acq_value(b.acq, b.sf, b.incumbent, b.param, mu, b.sig_lo);
+    const double a_hi = acq_value(b.acq, b.sf, b.incumbent, b.param, mu, b.sig_hi);
+    double a = a_lo > a_hi ? a_lo : a_hi;
+    // margin against the rounding of the formulas themselves (UCB: relative to its terms, which may cancel)
+    double scale = fabs(a);
+    if (b.acq == TGP_ACQ_UCB) scale += fabs(mu) + fabs(b.param) * b.sig_hi;
+    a += b.margin * scale;
+    b.ub[c] = (isnan(a_lo) || isnan(a_hi) || isnan(a)) ? INFINITY : a;
+}
+
+// the lb set: per group of gs consecutive candidates the one with the largest bound (lowest index on ties)
+__global__ __launch_bounds__(256) void prune_pick_kernel(const double *__restrict__ ub, long m, long gs,
+                                                         long long *__restrict__ pick) {
+    __shared__ double sv[256];
+    __shared__ long long si[256];
+    const long g0 = (long)blockIdx.x * gs;
+    const long g1 = g0 + gs < m ? g0 + gs : m;
+    Best b;   // (not strided_argmax: the values carry no index array, and a thread's own indices only ascend)
+    for (long c = g0 + threadIdx.x; c < g1; c += 256) {
+        const double u = ub[c];
+        if (u > b.v) { b.v = u; b.i = c; }
+    }
+    b = block_argmax<256>(b, sv, si);
+    if (threadIdx.x == 0) pick[blockIdx.x] = b.i == IDX_NONE ? g0 : b.i;   // (all bounds -inf: the group's first)
+}
+
+// rows idx[0..n) of the scaled candidates into a dense block of `rows` rows (rows >= n zero)
+template <typename T>
+__global__ __launch_bounds__(256) void prune_gather_kernel(const T *__restrict__ Cs, int Dp, const long long *__restrict__ idx,
+                                                           long n, long rows, T *__restrict__ out) {
+    const long total = rows * Dp;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const long r = i / Dp;
+        const int d = (int)(i - r * Dp);
+        out[i] = r < n ? Cs[idx[r] * Dp + d] : (T)0;
+    }
+}
+
+struct SurvArgs {
+    const double *ub; long m;
+    const long long *pick; long gs;   // the lb set (already contracted: not a survivor)
+    const double *lb; double margin;  // lb: the lb set's best exact value (device)
+    int *bcnt; const int *boff;       // survivors per 256-candidate block / exclusive offsets
+    long long *sidx;                  // survivors' batch indices, in order
+    const long long *src;             // null, or ub is over a gathered set (already clear of the lb set): src[c] is row c's batch index
+};
+
+__device__ __forceinline__ bool prune_survives(const SurvArgs &s, long c) {
+    const double lb = s.lb[0];
+    const double bar = isinf(lb) ? lb : lb - s.margin * fabs(lb);
+    return c < s.m && s.ub[c] >= bar && (s.src || s.pick[c / s.gs] != c);
+}
+
+__global__ __launch_bounds__(256) void prune_count_kernel(SurvArgs s) {
+    __shared__ int wsum[4];
+    const long c = (long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long bal = __ballot(prune_survives(s, c));
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __popcll(bal);
+    __syncthreads();
+    if (threadIdx.x == 0) s.bcnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+__global__ __launch_bounds__(1024) void prune_scan_kernel(const int *__restrict__ bcnt, int nb, int *__restrict__ boff,
+                                                          long long *__restrict__ total) {
+    __shared__ int part[1024];
+    const int per = (nb + 1023) / 1024;
+    const int b0 = (int)threadIdx.x * per;
+    const int b1 = b0 + per < nb ? b0 + per : nb;
+    int s = 0;
+    for (int b = b0; b < b1; ++b) s += bcnt[b];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const int v = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int run = part[threadIdx.x] - s;
+    for (int b = b0; b < b1; ++b) { boff[b] = run; run += bcnt[b]; }
+    if (threadIdx.x == 1023) total[0] = part[1023];
+}
+
+__global__ __launch_bounds__(256) void prune_scatter_kernel(SurvArgs s) {
+    __shared__ int wsum[4];
+    const long c = (long)blockIdx.x * 256 + threadIdx.x;
+    const bool keep = prune_survives(s, c);
+    const unsigned long long bal = __ballot(keep);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) wsum[w] = __popcll(bal);
+    __syncthreads();
+    int off = s.boff[blockIdx.x];
+    for (int k = 0; k < w; ++k) off += wsum[k];
+    if (keep) s.sidx[off + __popcll(bal & ((1ull << lane) - 1ull))] = s.src ? s.src[c] : c;
+}
+
+// the pruned sweep's own workspace (grow-only): bounds, lb set, survivors, block counts, the gathered scaled rows; for the
+// screen: E(c), the gathered set's tight bounds, the second survivor list, |x_i|^2 (misc + 8: its scalars); for the fp16
+// screen also the weighted form's factors and the sign-partitioned copy of the training points (planes, |x|^2, |alpha|)
+struct PruneWs {
+    double *ub; long long *pick, *sidx, *misc; int *bcnt, *boff; void *cs;
+    double *err, *ub1; long long *sidx1; float *nx;
+    double *wcoef; unsigned char *xh; float *nxp, *absa; long ncap;
+};
+static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// sub-buffers of one allocation in the order they are taken, each on a 256-byte boundary; one that is not wanted takes no
+// room (its pointer is the next one's).  Without a base only the bytes are counted.
+struct Carver {
+    char *base = nullptr;
+    size_t off = 0;
+    template <typename U>
+    U *take(size_t count, bool wanted = true) {
+        U *ptr = base ? reinterpret_cast<U *>(base + off) : nullptr;
+        if (wanted) off += al256(count * sizeof(U));
+        return ptr;
+    }
+};
+
+template <typename T>
+static void prune_carve(const Context &c, int64_t npick, int64_t rows_cap, bool screen, bool h2, Carver &k, PruneWs &w) {
+    const size_t M = (size_t)c.M, nb = (size_t)((c.M + 255) / 256), Mpad = (size_t)c.ws_Mpad;
+    w.ncap = (long)((c.N + SCR_T - 1) / SCR_T + 1) * SCR_T;
+    const size_t ncap = (size_t)w.ncap, nch = (size_t)((c.Dp + SCR_DC - 1) / SCR_DC);
+    w.ub = k.take<double>(M);
+    w.pick = k.take<long long>((size_t)npick);
+    w.sidx = k.take<long long>(M);
+    w.misc = k.take<long long>(32);   // 256 bytes: [0] a survivor count; from word 8 on the screen's scalars
+    w.bcnt = k.take<int>(nb);
+    w.boff = k.take<int>(nb);
+    w.cs = k.take<T>((size_t)rows_cap * c.Dp);
+    w.err = k.take<double>(Mpad, screen);
+    w.ub1 = k.take<double>((size_t)rows_cap, screen);
+    w.sidx1 = k.take<long long>(M, screen);
+    w.nx = k.take<float>((size_t)c.Np, screen);
+    w.wcoef = k.take<double>(Mpad, h2);
+    w.xh = k.take<unsigned char>(nch * ncap * 128, h2);
+    w.nxp = k.take<float>(ncap, h2);
+    w.absa = k.take<float>(ncap, h2);
+}
+
+template <typename T>
+static hipError_t prune_workspace(Context &c, int64_t npick, int64_t rows_cap, bool screen, bool h2, PruneWs &w) {
+    Carver count;
+    prune_carve<T>(c, npick, rows_cap, screen, h2, count, w);
+    TGP_TRY(c.d_prune.reserve(count.off, [&] { return hipStreamSynchronize(c.stream); }));
+    Carver k{c.d_prune};
+    prune_carve<T>(c, npick, rows_cap, screen, h2, k, w);
+    return hipSuccess;
+}
+
+// The contraction of `rows` gathered candidates (a multiple of 128) over ntm 128-row tiles: the widest candidate tile of
+// 128 / 64 / 32 that still gives CONTRACT_MIN_WGS workgroups, else the narrowest.  A launch with fewer workgroups than
+// CUs lasts as long as its heaviest wave, and the narrow variants (trmm_sweep.hpp) cut that wave's share of a row tile
+// from 128 x 32 to 32 x 64 / 32 x 32; they write the 128 x 128 kernel's bits, so the choice never shows in a result.
+template <typename T>
+static TrmmVariant contract_variant(const SweepPlan<T> &p, int64_t rows, int ntm) {
+    TrmmVariant v;
+    v.kern = p.early.kern; v.lds = trmm_glds_lds_bytes(); v.tile_m = 128; v.tile_n = 128; v.threads = 256;
+    if ((rows / 128) * ntm >= CONTRACT_MIN_WGS) return v;
+    if ((rows / 64) * ntm >= CONTRACT_MIN_WGS) {
+        v.kern = trmm_sumsq_glds_narrow_kernel<T, 64>; v.lds = trmm_narrow_lds_bytes<64>(); v.tile_n = 64;
+    } else {
+        v.kern = trmm_sumsq_glds_narrow_kernel<T, 32>; v.lds = trmm_narrow_lds_bytes<32>(); v.tile_n = 32;
+    }
+    return v;
+}
+
+// n gathered rows: per launch_rows of them the cross-kernel into slot 0, then the 128-row contraction over every row
+// tile with the mean inside (part / mupart rows [0, n))
+template <typename T>
+static hipError_t contract_rows(Context &c, const SweepPlan<T> &p, const T *cs, int64_t n, ProfCursor &cur) {
+    for (int64_t off = 0; off < n; off += c.launch_rows) {
+        const int64_t m = n - off < c.launch_rows ? n - off : c.launch_rows;
+        const int64_t rows = pad128(m);
+        TGP_TRY(launch_kstar<T>(c, Kstar::SlabNoMean, cs + off * c.Dp, rows, p.njs, c.d_Ks[0].get(), c.d_mupart + off,
+                                (long)c.Np / 16, 1.f, cur.st));
+        cur.seg(1);
+        TGP_TRY(launch_trmm<T>(c, p, contract_variant<T>(p, rows, p.n128), 0, off, rows, 0, p.n128, 0, true, cur.st));
+        cur.seg(0, (double)m * (double)c.N * (double)c.N);
+    }
+    return hipSuccess;
+}
+
+// May this sweep take the pruned schedule?  NotEligible: not an arg-max-only EI / PI / UCB sweep in f32 / f64 with the mean
+// inside the contraction, switched off, or too small to pay (prune_state stays -1).  GatedOff: the noise is too small for
+// the clamp gate above (-2).
+enum class PruneGo { NotEligible, GatedOff, Go };
+template <typename T>
+static PruneGo prune_eligible(const Context &c, const SweepPlan<T> &p, const SweepCall &call) {
+    const int acq = call.acq;
+    if (call.mu || call.sigma || call.acqv) return PruneGo::NotEligible;
+    if (acq != TGP_ACQ_EI && acq != TGP_ACQ_PI && acq != TGP_ACQ_UCB) return PruneGo::NotEligible;
+    if (c.dtype != TGP_F32 && c.dtype != TGP_F64) return PruneGo::NotEligible;
+    if (!p.mean_in_trmm || tuning_sweep_prune_now() == 0) return PruneGo::NotEligible;
+    if (!(c.M > tuning().prune_top)) return PruneGo::NotEligible;
+    if (!((double)c.M * (double)c.N * (double)c.N >= tuning_prune_min_work_now())) return PruneGo::NotEligible;
+    const double u = sizeof(T) == 4 ? 0x1p-24 : 0x1p-53;
+    const bool gate = c.noise > 0.0 && c.noise / (c.constant + c.noise) >= tuning().prune_tau * u;
+    return gate ? PruneGo::Go : PruneGo::GatedOff;
+}
+
+// what the steps of one pruned sweep share
+template <typename T>
+struct PruneRun {
+    Context &c;
+    const SweepPlan<T> &p;
+    const SweepCall &call;
+    PruneWs w;
+    BoundArgs b;               // a bound pass's arguments; each pass sets its rows (njs, m, err, wcoef, ub)
+    const T *Cs, *Xs;          // every scaled candidate; the scaled training points
+    T *cs;                     // the gathered rows (w.cs)
+    int64_t gs, npick, keep;   // candidates per group of the lb set; its size; the most survivors taken (-1: none)
+    bool screen, h2;           // the screen runs; on the fp16 matrix pipe
+    ProfCursor cur;
+};
+
+// The tight bound of `rows` scaled candidates (a multiple of 16 KAR; m of them real) into ub.
+// Splits of the training points over the bound pass's grid: a big batch fills the chip with its candidate tiles
+// alone, and every split costs a workgroup its prologue (candidate tile staged, first barrier), 2 x 8 shuffled
+// partial sums and a row of each partial array for prune_bound_kernel to read.  (Any split is covered by
+// err_scale: it bounds the distance between two summation orders of the same products.)
+template <typename T>
+static hipError_t tight_bound(PruneRun<T> &r, const T *rowsrc, int64_t rows, int64_t m, double *ub) {
+    Context &c = r.c;
+    const int njs_b = grid_splits(rows / (16 * kstar_ar(sizeof(T))), BOUND_MIN_WGS, r.p.njs, r.p.njs);
+    TGP_TRY(launch_kstar<T>(c, Kstar::Bound, rowsrc, rows, njs_b, c.d_part.get(), c.d_mupart, 0L, 1.f, c.stream));
+    r.cur.seg(1);
+    r.b.njs = njs_b; r.b.m = m; r.b.err = nullptr; r.b.wcoef = nullptr; r.b.ub = ub;
+    hipLaunchKernelGGL(prune_bound_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, c.stream, r.b);
+    return hipGetLastError();
+}
+
+// The screen on the fp16 matrix pipe (prune_screen_h2.hpp) over all M on a grid of (xb, njs_s): one prep launch (sign
+// partition, fp16 planes, the scalars of E), the screen; prune_bound_kernel then sums the splits' weights (in d_part, which
+// the screened bound does not otherwise read) and takes the smaller form
+static hipError_t screen_h2_bound(PruneRun<float> &r, int64_t xb, int njs_s) {
+    Context &c = r.c;
+    const PruneWs &w = r.w;
+    const int N = (int)c.N, Dp = (int)c.Dp;
+    const ScreenH2Terms et = screen_h2_error_terms(c.constant, (int)c.D, N);
+    ScreenH2Scal *scal = reinterpret_cast<ScreenH2Scal *>(w.misc + 8);
+    static_assert(sizeof(ScreenH2Scal) <= 256 - 64, "the scalars live behind misc's first eight words");
+    ScreenH2PrepArgs a{};
+    a.Xs = r.Xs; a.alpha = c.d_alpha; a.N = N; a.Dp = Dp; a.nch = (Dp + SCR_DC - 1) / SCR_DC; a.ncap = w.ncap;
+    a.P = et.P; a.Qc = et.Qc; a.Qw = et.Qw;
+    a.Xh = w.xh; a.nxp = w.nxp; a.absa = w.absa; a.scal = scal;
+    hipLaunchKernelGGL(screen_h2_prep_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c.stream, a);
+    TGP_TRY(hipGetLastError());
+    r.cur.restart();
+    ScreenH2Args g{};
+    g.Cs = r.Cs; g.Xh = w.xh; g.nxp = w.nxp; g.absa = w.absa; g.scal = scal;
+    g.mupart = c.d_mupart; g.wpart = c.d_part; g.err = w.err; g.wcoef = w.wcoef; g.ldpart = c.ws_Mpad; g.ncap = w.ncap;
+    g.Dp = Dp; g.constant = c.constant; g.dcoef = et.dcoef;
+    hipLaunchKernelGGL(prune_screen_h2_kernel, dim3((unsigned)xb, (unsigned)njs_s), dim3(256), 0, c.stream, g);
+    TGP_TRY(hipGetLastError());
+    r.cur.seg(2);
+    c.prune_arith = 2;
+    r.b.wcoef = w.wcoef; r.b.wadd = &scal->wadd;
+    return hipSuccess;
+}
+
+// The screen in f32 (prune_screen.hpp) on the same grid: |x_i|^2 and the scalars of E, then the screen
+static hipError_t screen_f32_bound(PruneRun<float> &r, int64_t xb, int njs_s) {
+    Context &c = r.c;
+    const PruneWs &w = r.w;
+    const int N = (int)c.N, Dp = (int)c.Dp;
+    const ScreenTerms et = screen_error_terms(c.constant, (int)c.D, N);
+    double *scal = reinterpret_cast<double *>(w.misc + 8);
+    hipLaunchKernelGGL(screen_stats_kernel, dim3(1), dim3(1024), 0, c.stream, r.Xs, c.d_alpha, N, (int)c.Np, Dp, et.P, et.Q, w.nx, scal);
+    TGP_TRY(hipGetLastError());
+    r.cur.restart();
+    ScreenArgs g{};
+    g.Cs = r.Cs; g.Xs = r.Xs; g.alpha = c.d_alpha; g.nx = w.nx; g.scal = scal;
+    g.mupart = c.d_mupart; g.err = w.err; g.ldpart = c.ws_Mpad;
+    g.N = N; g.Np = (int)c.Np; g.Dp = Dp; g.constant = c.constant;
+    hipLaunchKernelGGL(prune_screen_kernel, dim3((unsigned)xb, (unsigned)njs_s), dim3(256), 0, c.stream, g);
+    TGP_TRY(hipGetLastError());
+    r.cur.seg(2);
+    c.prune_arith = 1;
+    r.b.wcoef = nullptr;
+    return hipSuccess;
+}
+
+// 1. the bound of every candidate into w.ub: the screen's where it applies (its error the input of prune_bound_kernel), else
+// the tight one
+template <typename T>
+static hipError_t bound_all(PruneRun<T> &r) {
+    Context &c = r.c;
+    if (!r.screen) return tight_bound<T>(r, r.Cs, c.ws_Mpad, c.M, r.w.ub);
+    if constexpr (sizeof(T) == 4) {
+        const int64_t xb = c.ws_Mpad / SCR_T;
+        const int njt = ((int)c.N + SCR_T - 1) / SCR_T;
+        const int njs_s = grid_splits(xb, SCREEN_MIN_WGS, r.p.njs, njt < r.p.njs ? njt : r.p.njs);
+        TGP_TRY(r.h2 ? screen_h2_bound(r, xb, njs_s) : screen_f32_bound(r, xb, njs_s));
+        r.b.njs = njs_s; r.b.m = c.M; r.b.err = r.w.err; r.b.ub = r.w.ub;
+        hipLaunchKernelGGL(prune_bound_kernel, dim3((unsigned)((c.M + 255) / 256)), dim3(256), 0, c.stream, r.b);
+        return hipGetLastError();
+    }
+    return hipSuccess;
+}
+
+// rows idx[0, n) of the scaled candidates into the dense block cs (zero rows up to a multiple of 128)
+template <typename T>
+static hipError_t gather_rows(PruneRun<T> &r, const long long *idx, int64_t n) {
+    const int Dp = (int)r.c.Dp;
+    const long total = (long)pad128(n) * Dp;
+    const long blocks = (total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192;
+    hipLaunchKernelGGL(prune_gather_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, r.c.stream, r.Cs, Dp, idx, (long)n,
+                       (long)pad128(n), r.cs);
+    return hipGetLastError();
+}
+
+// value and block arg-max of the n contracted rows idx[0, n), their partials from block blk0 on
+template <typename T>
+static hipError_t finalize_rows(PruneRun<T> &r, const long long *idx, int64_t n, int64_t blk0) {
+    FinArgs f = fin_args<T>(r.c, r.p, r.call);
+    f.base_pairs = r.p.nunits;   // 128-row tiles throughout
+    f.njs = 1;
+    f.off = blk0 * FIN_BLOCK; f.m = n;
+    f.gidx = idx;
+    hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)((n + FIN_BLOCK - 1) / FIN_BLOCK)), dim3(FIN_BLOCK), 0, r.c.stream, f);
+    return hipGetLastError();
+}
+
+// 2. the lb set, picked from w.ub and contracted exactly; its best value is the bar (d_best); nblk: its blocks of partials
+template <typename T>
+static hipError_t lb_set(PruneRun<T> &r, int64_t &nblk) {
+    Context &c = r.c;
+    hipLaunchKernelGGL(prune_pick_kernel, dim3((unsigned)r.npick), dim3(256), 0, c.stream, r.w.ub, (long)c.M, (long)r.gs, r.w.pick);
+    TGP_TRY(hipGetLastError());
+    TGP_TRY(gather_rows(r, r.w.pick, r.npick));
+    TGP_TRY(contract_rows<T>(c, r.p, r.cs, r.npick, r.cur));
+    TGP_TRY(finalize_rows(r, r.w.pick, r.npick, 0));
+    nblk = (r.npick + FIN_BLOCK - 1) / FIN_BLOCK;
+    return launch_argmax(c, c.stream, (long)nblk, nullptr, nullptr, Bell{nullptr, 0, nullptr});
+}
+
+// 3. the candidates of ub[0, m) that reach the bar, compacted in order into out; their number comes back to the host
+// (the launches behind it are sized by the count)
+template <typename T>
+static hipError_t survivors(PruneRun<T> &r, const double *ub, int64_t m, const long long *src, long long *out, long long &n) {
+    Context &c = r.c;
+    const PruneWs &w = r.w;
+    hipStream_t st = c.stream;
+    const int64_t nb = (m + 255) / 256;
+    SurvArgs s{ub, (long)m, w.pick, (long)r.gs, c.d_best, r.b.margin, w.bcnt, w.boff, out, src};
+    hipLaunchKernelGGL(prune_count_kernel, dim3((unsigned)nb), dim3(256), 0, st, s);
+    TGP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(1024), 0, st, w.bcnt, (int)nb, w.boff, w.misc);
+    TGP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(prune_scatter_kernel, dim3((unsigned)nb), dim3(256), 0, st, s);
+    TGP_TRY(hipGetLastError());
+    TGP_TRY(hipMemcpyAsync(&n, w.misc, sizeof(long long), hipMemcpyDeviceToHost, st));
+    return hipStreamSynchronize(st);
+}
+
+// 4. behind the screen, by the number of its survivors S0 (in w.sidx): more than `keep` -- the screen was too loose for this
+// batch: the tight bound of every candidate, against the same lb; more than TGP_PRUNE_DIRECT -- the tight bound on the
+// gathered S0 rows and a second filter (S1, in w.sidx1); else S0 as it is.  nsurv / sidx: the set to contract
+template <typename T>
+static hipError_t narrow_after_screen(PruneRun<T> &r, long long &nsurv, const long long *&sidx) {
+    Context &c = r.c;
+    const PruneWs &w = r.w;
+    if (nsurv > r.keep) {
+        r.cur.restart();
+        TGP_TRY(tight_bound<T>(r, r.Cs, c.ws_Mpad, c.M, w.ub));
+        TGP_TRY(survivors(r, w.ub, c.M, nullptr, w.sidx, nsurv));
+    } else if (nsurv > tuning_prune_direct_now()) {
+        TGP_TRY(gather_rows(r, w.sidx, nsurv));
+        r.cur.restart();
+        TGP_TRY(tight_bound<T>(r, r.cs, pad128(nsurv), nsurv, w.ub1));
+        const long long n0 = nsurv;
+        TGP_TRY(survivors(r, w.ub1, n0, w.sidx, w.sidx1, nsurv));
+        sidx = w.sidx1;
+    }
+    r.cur.restart();
+    return hipSuccess;
+}
+
+// 5. the survivors contracted like the lb set, then ONE arg-max over both sets' partials with the batch indices
+template <typename T>
+static hipError_t contract_survivors_and_pick(PruneRun<T> &r, const long long *sidx, int64_t nsurv, int64_t nblk_lb) {
+    int64_t nblk = 0;
+    if (nsurv > 0) {
+        TGP_TRY(gather_rows(r, sidx, nsurv));
+        TGP_TRY(contract_rows<T>(r.c, r.p, r.cs, nsurv, r.cur));
+        TGP_TRY(finalize_rows(r, sidx, nsurv, nblk_lb));
+        nblk = (nsurv + FIN_BLOCK - 1) / FIN_BLOCK;
+    }
+    return launch_argmax(r.c, r.c.stream, (long)(nblk_lb + nblk), r.call.winner, r.call.res, Bell{nullptr, 0, nullptr});
+}
+
+// what every bound pass of this sweep shares: the partial sums' home, the error scale of the tight pass, the interval of
+// sigma, the acquisition and the margin
+static BoundArgs bound_args(const Context &c, const SweepCall &call, double margin) {
+    BoundArgs b{};
+    b.mupart = c.d_mupart; b.abspart = c.d_part; b.ldpart = c.ws_Mpad;
+    b.err_scale = 4.0 * (double)((int)c.N + 8) * 0x1p-53;
+    b.y_mean = c.y_mean; b.y_std = c.y_std;
+    b.sig_lo = sqrt((0.99 * c.noise) * (c.y_std * c.y_std));
+    b.sig_hi = sqrt((c.constant + c.noise) * (c.y_std * c.y_std));
+    b.acq = call.acq; b.sf = call.sf; b.incumbent = call.incumbent; b.param = call.param; b.margin = margin;
+    return b;
+}
+
+// done = false: too many survivors -- the caller runs the full schedule (nothing of this call's results is left behind)
+//
+// With the screen (TGP_PRUNE_SCREEN, f32 + RBF; prune_screen.hpp) the order of work is
+//   1. screen over all M: mu_s and E(c) with |mu_s - mu~| <= E  ->  prune_bound_kernel (the error as its input)  ->  ub0
+//      (TGP_SCREEN_ARITH: on the fp16 matrix pipe with the k-weighted E of prune_screen_h2.hpp, or the f32 kernel);
+//   2. the lb set picked from ub0 and contracted exactly -> lb (the code below, unchanged);
+//   3. count / scan / scatter on ub0 -> the screen's survivors S0 (one host synchronisation for the count);
+//   4. |S0| <= TGP_PRUNE_DIRECT: S0 is contracted as it is.  |S0| > prune_frac M: the tight bound pass over all M --
+//      the schedule without a screen from its step 1 on, the lb set kept.  Between the two: the tight bound pass
+//      (kstar XP = 4 + prune_bound_kernel, their arithmetic and err_scale unchanged) on the gathered S0 rows, its grid
+//      splitting the training points until the chip is full, and a second filter against lb -> S1 (a second
+//      synchronisation for its count);
+//   5. gather, contract, finalize, ONE arg-max over the lb set and the last survivor set.
+// Why the result is the full sweep's, bit for bit: a candidate's exact value a(c) is formed from the contraction's mean
+// mu~(c) and a variance inside [sig_lo^2, sig_hi^2]; ub0(c) >= a(c) because mu~ lies within E(c) of mu_s(c) and
+// prune_bound_kernel takes the end of that interval, and of the variance's, that raises the acquisition; the tight bound
+// ub1(c) >= a(c) as before.  The winner w of the full sweep has a(w) >= a(any lb-set member) = lb, hence ub0(w) >= lb and
+// ub1(w) >= lb: it is in the lb set or survives every filter, and so does every candidate that ties with it.  Every
+// contracted candidate goes through the full sweep's arithmetic, the one arg-max sees batch indices, and no skipped
+// candidate can clamp (the gate above): value, index and n_clamped are the full sweep's.  The screen's own values and
+// its looseness never reach a result; they only move work between "skipped" and "contracted".
+template <typename T>
+static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCall &call, bool front_usable, bool &done) {
+    done = false;
+    const Tuning &tu = tuning();
+    const int64_t M = c.M;
+    const int64_t top = tu.prune_top < 1 ? 1 : tu.prune_top;
+    const int64_t gs = (M + top - 1) / top, npick = (M + gs - 1) / gs;
+    const double frac = tuning_prune_frac_now();
+    const int64_t keep = frac < 0.0 ? -1 : (frac >= 1.0 ? M : (int64_t)(frac * (double)M));   // most survivors taken
+    const int64_t rows_cap = pad128(npick > keep ? npick : keep);
+    const bool screen = sizeof(T) == 4 && c.kernel == TGP_RBF && c.D <= SCR_MAXD && tuning_prune_screen_now() != 0;
+    // the screen's arithmetic: fp16 planes and the weighted error where its closed form is no looser than the f32 screen's
+    const bool h2 = screen && tuning_screen_arith_now() == 2 && c.D >= SCRH_MIN_D;
+    PruneRun<T> r{c, p, call, PruneWs{}, BoundArgs{}, reinterpret_cast<const T *>(c.d_Cs.get()), train_points<T>(c), nullptr,
+                  gs, npick, keep, screen, h2, ProfCursor{c, c.stream, -1}};
+    TGP_TRY(prune_workspace<T>(c, npick, rows_cap, screen, h2, r.w));
+    TGP_TRY(lds_opt_in(c, p.early.kern, p.early.lds));   // (the request the fit's early row tiles make of the same kernel)
+    r.cs = reinterpret_cast<T *>(r.w.cs);
+    c.prune_screen = -1;
+    c.prune_arith = 0;
+    if (!front_usable) TGP_TRY(issue_prep<T>(c, c.stream));   // (a fit's front has scaled them already)
+    r.cur.restart();
+    r.b = bound_args(c, call, tu.prune_margin);
+
+    TGP_TRY(bound_all(r));                                                   // 1. the bound of every candidate
+    int64_t nblk_lb = 0;
+    TGP_TRY(lb_set(r, nblk_lb));                                             // 2. the lb set, exactly: the bar
+    long long nsurv = 0;
+    const long long *sidx = r.w.sidx;
+    TGP_TRY(survivors(r, r.w.ub, M, nullptr, r.w.sidx, nsurv));              // 3. the survivors, in index order
+    c.prune_lbset = npick;
+    if (screen) {
+        c.prune_screen = nsurv;
+        TGP_TRY(narrow_after_screen(r, nsurv, sidx));                        // 4. the screen's survivors, narrowed
+    }
+    c.prune_surv = nsurv;
+    if (nsurv > keep) {
+        // the full schedule instead: it counts the lb set's clamps again (the counter was zero when this sweep began)
+        c.prune_state = 1;
+        return hipMemsetAsync(c.d_besti + 1, 0, sizeof(long long), c.stream);
+    }
+    TGP_TRY(contract_survivors_and_pick(r, sidx, nsurv, nblk_lb));           // 5. contract them; one arg-max over both sets
+    c.prune_state = 0;
+    done = true;
+    return hipSuccess;
+}
+
+}  // namespace tgp

@@ -81,7 +81,7 @@ struct WsMem {                     // the sweeps' and the acquisition entries' w
     Dev<double> d_part;            // (Np/SW_BM, Mpad) partial ||v||^2
     Dev<double> d_mupart;          // (KS_JS, Mpad) partial K*.alpha
     int64_t ws_Mpad = 0;           // leading dimension of Cs / part / mupart for this sweep
-    Dev<char> d_prune;             // the pruned sweep's workspace (sweep_kernels.hip, sweep_pruned)
+    Dev<char> d_prune;             // the pruned sweep's workspace (sweep_pruned.hpp, prune_workspace)
     Dev<double> d_topv;            // top-k workspace (tgp_sweep_topk)
     Dev<long long> d_topi;
     Dev<double> d_batch;           // tgp_predict_batch: per-model workspaces, outputs, counters

@@ -3,7 +3,7 @@
 // The defaults are the fastest measured settings; the switches exist for A/B measurements and so that the tests
 // can run kernel variants the size-based defaults would only pick at sizes the suite never uses
 // (tests/test_gpu_parity.py::test_alternate_kernel_paths).  The table is read ONCE, at the first use in the
-// process (two rows are marked "per call": they are looked up again at every call because tests flip them inside
+// process (the rows marked "per call" are looked up again at every call because tests flip them inside
 // one process).  tgp_tuning() (include/turbogp.h) prints the table with the values in force, so documentation
 // cannot drift from the code: DESIGN.md section 5 is generated from that print.
 //
@@ -19,7 +19,7 @@ namespace tgp {
 
 // X(kind, field, "ENV_NAME", default, "what it selects")      kind: INT | DBL | STR
 #define TGP_TUNING_TABLE(X)                                                                                                      \
-    /* ---- sweep (sweep_kernels.hip, tgp_api.hip) ---- */                                                                      \
+    /* ---- sweep (sweep_kernels.hip, sweep_pruned.hpp, tgp_api.hip) ---- */                                                    \
     X(INT, chunk, "TGP_CHUNK", 0, "candidates per slab group (multiple of 1024; 0 = about 256 MiB of slab) [per call]")          \
     X(DBL, slab_gb, "TGP_SLAB_GB", 1.0, "GiB of cross-kernel slab per launch pair (groups of TGP_CHUNK inside it)")              \
     X(STR, tile, "TGP_TILE", "", "contraction tile: 128 | 256x128 | 256x256 (default: by launch size)")                         \
@@ -91,16 +91,19 @@ struct Tuning {
     // derived
     bool trmm_reg = false, gemm64_reg = false, inner_generic = false;
 
-    Tuning() {
+    // from_env = false: the table's defaults alone (tuning_defaults())
+    explicit Tuning(bool from_env = true) {
+        if (from_env) {
 #define TGP_TP_INT(f, env) if (const char *v = getenv(env)) f = atoi(v);
 #define TGP_TP_DBL(f, env) if (const char *v = getenv(env)) f = atof(v);
 #define TGP_TP_STR(f, env) if (const char *v = getenv(env)) f = v;
 #define TGP_TP(kind, f, env, d, doc) TGP_TP_##kind(f, env)
-        TGP_TUNING_TABLE(TGP_TP)
+            TGP_TUNING_TABLE(TGP_TP)
 #undef TGP_TP
 #undef TGP_TP_INT
 #undef TGP_TP_DBL
 #undef TGP_TP_STR
+        }
         trmm_reg = trmm == "reg";
         gemm64_reg = gemm64 == "reg";
         inner_generic = inner == "gemm64";
@@ -138,14 +141,30 @@ inline const Tuning &tuning() {
 // NOT a switch of this library: the HIP runtime's own variable, reported by tgp_stream_status (0 = unset)
 inline int runtime_hw_queues_env() { const char *v = getenv("GPU_MAX_HW_QUEUES"); return v ? atoi(v) : 0; }
 
-// the rows tests flip inside one process: looked up at every call
-inline int tuning_chunk_now() { const char *v = getenv("TGP_CHUNK"); return v ? atoi(v) : 0; }
-inline int tuning_mid_maxm_now() { const char *v = getenv("TGP_MID_MAXM"); return v ? atoi(v) : 0; }
-inline int tuning_sweep_prune_now() { const char *v = getenv("TGP_SWEEP_PRUNE"); return v ? atoi(v) : 1; }
-inline double tuning_prune_frac_now() { const char *v = getenv("TGP_PRUNE_FRAC"); return v ? atof(v) : 0.25; }
-inline int tuning_prune_screen_now() { const char *v = getenv("TGP_PRUNE_SCREEN"); return v ? atoi(v) : 1; }
-inline int tuning_screen_arith_now() { const char *v = getenv("TGP_SCREEN_ARITH"); return v && !strcmp(v, "f32") ? 1 : 2; }   // 1 = f32, 2 = h2
-inline int tuning_prune_direct_now() { const char *v = getenv("TGP_PRUNE_DIRECT"); return v ? atoi(v) : 1024; }
-inline double tuning_prune_min_work_now() { const char *v = getenv("TGP_PRUNE_MIN_WORK"); return v ? atof(v) : 1e11; }
+// The rows tests flip inside one process ("[per call]" in the table): looked up at every call, and an unset variable means
+// the table's DEFAULT -- not tuning().field, which holds whatever the environment said when the table was first read.
+// Name and default both come from the table's row.
+inline const Tuning &tuning_defaults() {
+    static const Tuning t(false);
+    return t;
+}
+namespace tuning_env {
+#define TGP_TE(kind, f, env, d, doc) constexpr const char *f = env;
+TGP_TUNING_TABLE(TGP_TE)
+#undef TGP_TE
+}  // namespace tuning_env
+inline int now_int(const char *env, int dflt) { const char *v = getenv(env); return v ? atoi(v) : dflt; }
+inline double now_dbl(const char *env, double dflt) { const char *v = getenv(env); return v ? atof(v) : dflt; }
+inline std::string now_str(const char *env, const std::string &dflt) { const char *v = getenv(env); return v ? v : dflt; }
+#define TGP_NOW(kind, f) now_##kind(tuning_env::f, tuning_defaults().f)
+inline int tuning_chunk_now() { return TGP_NOW(int, chunk); }
+inline int tuning_mid_maxm_now() { return TGP_NOW(int, mid_maxm); }
+inline int tuning_sweep_prune_now() { return TGP_NOW(int, sweep_prune); }
+inline double tuning_prune_frac_now() { return TGP_NOW(dbl, prune_frac); }
+inline int tuning_prune_screen_now() { return TGP_NOW(int, prune_screen); }
+inline int tuning_screen_arith_now() { return TGP_NOW(str, screen_arith) == "f32" ? 1 : 2; }   // 1 = f32, 2 = h2
+inline int tuning_prune_direct_now() { return TGP_NOW(int, prune_direct); }
+inline double tuning_prune_min_work_now() { return TGP_NOW(dbl, prune_min_work); }
+#undef TGP_NOW
 
 }  // namespace tgp
