@@ -33,6 +33,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include <type_traits>
+
 #include "prune_screen.hpp"
 #include "trmm_f16x2.hpp"
 
@@ -103,23 +105,40 @@ __global__ __launch_bounds__(256) void screen_h2_prep_kernel(ScreenH2PrepArgs a)
     double a1 = 0.0;
     float mxx = 0.f, mxn = 0.f;
     int npos = 0, before = 0, bad = 0;
-    for (int i = tid; i < N; i += 256) {
-        const float *row = a.Xs + (long)i * Dp;
-        double s = 0.0;
-        float m = 0.f;
-        for (int d = 0; d < Dp; d += 4) {
-            const f4_t x = *reinterpret_cast<const f4_t *>(row + d);
+    // four of this thread's rows at a time: their f64 chains are independent (each in its own dimension order, as one row
+    // alone would run it), so the loads and the fmas of four rows overlap; the per-thread sums then take the rows in order
+    for (int i0 = tid; i0 < N; i0 += 4 * 256) {
+        double s[4] = {0.0, 0.0, 0.0, 0.0}, al[4];
+        float m[4] = {0.f, 0.f, 0.f, 0.f};
+        const float *row[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { s = fma((double)x[e], (double)x[e], s); m = fmaxf(m, fabsf(x[e])); }
+        for (int q = 0; q < 4; ++q) {
+            const int i = i0 + 256 * q;
+            row[q] = a.Xs + (long)(i < N ? i : i0) * Dp;      // (a row past the end: the first one again, not used)
+            al[q] = a.alpha[i < N ? i : i0];
         }
-        if (!(s < (double)INFINITY)) bad = 1;      // (an inf or a NaN coordinate)
-        mxn = fmaxf(mxn, (float)s);
-        mxx = fmaxf(mxx, m);
-        const double al = a.alpha[i];
-        a1 += fabs(al);
-        const int p = al >= 0.0;
-        npos += p;
-        if (i < base) before += p;
+        for (int d = 0; d < Dp; d += 4) {
+            f4_t x[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) x[q] = *reinterpret_cast<const f4_t *>(row[q] + d);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) { s[q] = fma((double)x[q][e], (double)x[q][e], s[q]); m[q] = fmaxf(m[q], fabsf(x[q][e])); }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int i = i0 + 256 * q;
+            if (i < N) {
+                if (!(s[q] < (double)INFINITY)) bad = 1;      // (an inf or a NaN coordinate)
+                mxn = fmaxf(mxn, (float)s[q]);
+                mxx = fmaxf(mxx, m[q]);
+                a1 += fabs(al[q]);
+                const int p = al[q] >= 0.0;
+                npos += p;
+                if (i < base) before += p;
+            }
+        }
     }
     sa[tid] = a1; smx[tid] = mxx; smn[tid] = mxn; spos[tid] = npos; sbef[tid] = before; sbad[tid] = bad;
     __syncthreads();
@@ -213,7 +232,7 @@ __global__ __launch_bounds__(256, 2) void prune_screen_h2_kernel(ScreenH2Args g)
     __shared__ __attribute__((aligned(16))) f4_t rowc[SCR_T];      // per candidate: S, kappa / S, L_r, -S |c|^2
     __shared__ float srow[SCR_T];                                   // S_r
     __shared__ double mpos[SCR_T];                                  // mu+ while the negative tiles run
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, lh = lane >> 5;
     const long c0 = (long)blockIdx.x * SCR_T;
     const int Dp = g.Dp;
@@ -291,6 +310,26 @@ __global__ __launch_bounds__(256, 2) void prune_screen_h2_kernel(ScreenH2Args g)
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
     };
     f16_t hi[4], mid[4];
+    auto kstep = [&](int kb, auto first_tag) {
+        constexpr bool FIRST = decltype(first_tag)::value;
+        const int off = 32 * kb + 16 * lh;
+        const unsigned char *ap = Ct + (32 * w + li) * SCRH_ROW + off;
+        const u4_t a1 = *reinterpret_cast<const u4_t *>(ap), a2 = *reinterpret_cast<const u4_t *>(ap + 64);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const unsigned char *bp = Xt + (32 * b + li) * SCRH_ROW + off;
+            const u4_t b1 = *reinterpret_cast<const u4_t *>(bp), b2 = *reinterpret_cast<const u4_t *>(bp + 64);
+            if constexpr (FIRST) {
+                const f16_t zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                hi[b] = mma(a1, b1, zero);
+                mid[b] = mma(a1, b2, zero);
+            } else {
+                hi[b] = mma(a1, b1, hi[b]);
+                mid[b] = mma(a1, b2, mid[b]);
+            }
+            mid[b] = mma(a2, b1, mid[b]);
+        }
+    };
     for (int st = 0; st < nsteps; ++st) {
         const int jt = jt0 + st / nch, ch = st - (st / nch) * nch;
         const int j0 = jt * SCR_T;
@@ -307,41 +346,26 @@ __global__ __launch_bounds__(256, 2) void prune_screen_h2_kernel(ScreenH2Args g)
                 al[b] = g.absa[j0 + 32 * b + li];
             }
         }
-        if (ch == 0) {
-            if (jt == ntp && jt > jt0) {
-                // the sign boundary: the f64 sums so far are mu+; close them once and start mu-
+        if (ch == 0 && jt == ntp && jt > jt0) {
+            // the sign boundary: the f64 sums so far are mu+; close them once and start mu-
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    double s = sum[r];
+            for (int r = 0; r < 16; ++r) {
+                double s = sum[r];
 #pragma unroll
-                    for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-                    if (li == 0) mpos[32 * w + Mfma<float>::c_row(lane, r)] = s;
-                    sum[r] = 0.0;
-                }
+                for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+                if (li == 0) mpos[32 * w + Mfma<float>::c_row(lane, r)] = s;
+                sum[r] = 0.0;
             }
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { hi[b][r] = 0.f; mid[b][r] = 0.f; }
         }
         int dn = Dp - ch * SCR_DC;
         if (dn > SCR_DC) dn = SCR_DC;
-        const int nkb = (dn + 15) >> 4;               // (the staged block is zero beyond Dp)
-        // k-values 16 kb .. 16 kb + 15: lane half h takes 16 kb + 8 h + j for element j, both operands alike
-#pragma unroll 1
-        for (int kb = 0; kb < nkb; ++kb) {
-            const int off = 32 * kb + 16 * lh;
-            const unsigned char *ap = Ct + (32 * w + li) * SCRH_ROW + off;
-            const u4_t a1 = *reinterpret_cast<const u4_t *>(ap), a2 = *reinterpret_cast<const u4_t *>(ap + 64);
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const unsigned char *bp = Xt + (32 * b + li) * SCRH_ROW + off;
-                const u4_t b1 = *reinterpret_cast<const u4_t *>(bp), b2 = *reinterpret_cast<const u4_t *>(bp + 64);
-                hi[b] = mma(a1, b1, hi[b]);
-                mid[b] = mma(a1, b2, mid[b]);
-                mid[b] = mma(a2, b1, mid[b]);
-            }
-        }
+        const int nkb = (dn + 15) >> 4;               // 1 or 2 (the staged block is zero beyond Dp)
+        // k-values 16 kb .. 16 kb + 15: lane half h takes 16 kb + 8 h + j for element j, both operands alike.  The first
+        // step of a tile's first chunk hands the MFMAs a zero constant for C (the instruction's inline 0, the same
+        // product as on a zeroed accumulator): no accumulator is zeroed in front of a tile.
+        if (ch == 0) kstep(0, std::true_type{});
+        else kstep(0, std::false_type{});
+        if (nkb == 2) kstep(1, std::false_type{});
         if (ch == nch - 1) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -368,13 +392,15 @@ __global__ __launch_bounds__(256, 2) void prune_screen_h2_kernel(ScreenH2Args g)
         }
     }
     const bool has_pos = nsteps > 0 && jt0 < ntp, has_neg = nsteps > 0 && jt1 > ntp;
+    // (the lane index read again, not kept in a register across the tile loop: the loop has none to spare)
+    const int elane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         double s = sum[r];
 #pragma unroll
         for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        if (li == 0) {
-            const int row = 32 * w + Mfma<float>::c_row(lane, r);
+        if ((elane & 31) == 0) {
+            const int row = 32 * w + Mfma<float>::c_row(elane, r);
             const double mp = has_neg ? (has_pos ? mpos[row] : 0.0) : s, mn = has_neg ? s : 0.0;
             const long o = (long)blockIdx.y * g.ldpart + c0 + row;
             g.mupart[o] = mp - mn;

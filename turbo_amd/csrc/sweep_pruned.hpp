@@ -225,7 +225,13 @@ static hipError_t contract_rows(Context &c, const SweepPlan<T> &p, const T *cs, 
     for (int64_t off = 0; off < n; off += c.launch_rows) {
         const int64_t m = n - off < c.launch_rows ? n - off : c.launch_rows;
         const int64_t rows = pad128(m);
-        TGP_TRY(launch_kstar<T>(c, Kstar::SlabNoMean, cs + off * c.Dp, rows, p.njs, c.d_Ks[0].get(), c.d_mupart + off,
+        // (SlabNoMean writes no row of mupart, so KS_JS does not bind its splits: every Ks entry is formed the same way
+        // whatever the split count, and a small gathered set has one or two candidate tiles to fill the chip with.  A
+        // set with candidate tiles enough keeps the plan's splits.)
+        const int ntile = (int)c.Np / 128;
+        const int njs_s = grid_splits(rows / (16 * kstar_ar(sizeof(T))), GATHER_KS_MIN_WGS, ntile, ntile);
+        const int njs_g = njs_s > p.njs ? njs_s : p.njs;
+        TGP_TRY(launch_kstar<T>(c, Kstar::SlabNoMean, cs + off * c.Dp, rows, njs_g, c.d_Ks[0].get(), c.d_mupart + off,
                                 (long)c.Np / 16, 1.f, cur.st));
         cur.seg(1);
         TGP_TRY(launch_trmm<T>(c, p, contract_variant<T>(p, rows, p.n128), 0, off, rows, 0, p.n128, 0, true, cur.st));

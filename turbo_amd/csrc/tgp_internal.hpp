@@ -23,6 +23,7 @@ constexpr int SW_BN = 128;      // sweep tile: candidates
 constexpr int KS_JS = 8;        // most training-point splits of the cross-kernel grid (rows of mupart)
 constexpr int FIN_BLOCK = 256;  // finalize block = candidates per arg-max partial
 constexpr int CONTRACT_MIN_WGS = 512;   // a gathered set's contraction takes the widest candidate tile that still gives this many workgroups (two per CU)
+constexpr int GATHER_KS_MIN_WGS = 256;   // ... and its cross-kernel splits the training points until its grid has one workgroup per CU (it writes no mupart row: KS_JS does not bind it)
 constexpr int SCREEN_MIN_WGS = 1024;    // ... and the screen in front of it (prune_screen.hpp; 128 candidates per workgroup, two workgroups per CU)
 constexpr int BOUND_MIN_WGS = 2048;     // the bound pass splits the training points only as far as its grid needs to reach this many workgroups
 
