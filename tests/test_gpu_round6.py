@@ -333,7 +333,8 @@ def test_the_matrix_core_products_of_tgp_acq_grad_against_the_earlier_kernels_an
     """tgp_acq_grad above N = 128: z = Linv k and w = Linv^T z on v_mfma_f64_16x16x4 (default) against the wave-per-row /
     split-column kernels (TGP_QUERY_MFMA=0, a child process: csrc/tuning.hpp is read once) -- the same values and
     gradients to rounding at three size classes (4 / 8 / 16 waves per block), 1 ... 40 points (three groups of sixteen),
-    and a point's result bit for bit the same alone and inside a batch"""
+    and a point's result bit for bit the same alone and inside a batch (m = 1 and m = 3 among them: the odd counts at
+    which the workspace behind the points once started off a 32-byte boundary)"""
     code = r'''
 import sys, json
 import numpy as np
@@ -352,6 +353,10 @@ for N, D in ((300, 3), (1000, 6), (1500, 5)):
         assert v1[0] == v[17] and np.array_equal(g1[0], g[17])
         v9, g9 = gp.acq_grad(P[:9], acq, -1.0, float(y.min()), par)
         assert np.array_equal(v9, v[:9]) and np.array_equal(g9, g[:9])
+        if N <= 1000:      # odd m: the [Xq | val | grad] prefix of the query workspace is no multiple of 4 doubles
+            for m in (1, 3):
+                vm, gm = gp.acq_grad(P[:m], acq, -1.0, float(y.min()), par)
+                assert np.array_equal(vm, v[:m]) and np.array_equal(gm, g[:m])
         out.append([v.tolist(), g.tolist()])
 print("RESULT" + json.dumps(out))
 ''' % ROOT

@@ -9,7 +9,12 @@ per process) must print the same lines where the switch promises the same bytes:
     TGP_POLL_US=0 TGP_SMALL_FUSED=0 TGP_SMALL_LIVE=0 python tools/short_calls_digest.py > b.txt && diff a.txt b.txt
 
 `--skip` leaves out groups a switch is NOT expected to keep bit-identical (TGP_SMALL_QUERY changes the kernels of
-tgp_acq_grad at N <= 128: same values to rounding, other bytes): names of groups, comma separated."""
+tgp_acq_grad at N <= 128: same values to rounding, other bytes): names of groups, comma separated.
+
+`--all-kinds` appends, behind the lines above (which it leaves as they are), the calls whose launchers choose a kernel
+instance by the covariance kind -- fit, fit + gradient, acquisition gradient, sweep, batch selection, Thompson draw and
+sweep, joint posterior -- at N = 300, D = 3 for each of the four kinds: two BUILDS of the same arithmetic must print the
+same lines."""
 import argparse
 import hashlib
 import os
@@ -30,6 +35,7 @@ def digest(*arrays):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip", default="")
+    ap.add_argument("--all-kinds", action="store_true")
     args = ap.parse_args()
     skip = set(filter(None, args.skip.split(",")))
     import turbo_amd as ta
@@ -105,7 +111,44 @@ def main():
                 v1, g1 = gp.acq_grad(P[5:6], acq, -1.0, float(y.min()), par)
                 assert v1[0] == v[5] and np.array_equal(g1[0], g[5])
                 print("acq_grad N=%3d general  acq=%d %s v=%s" % (N, acq, digest(v, g), np.array2string(v[:3], precision=15)))
+    if args.all_kinds:
+        all_kinds(gp, L)
     print("digest done")
+
+
+def all_kinds(gp, L):
+    N, D = 300, 3
+    rng = np.random.RandomState(N + D)
+    X = rng.uniform(0, 1, (N, D))
+    y = np.sin(3 * X.sum(1)) + 0.3 * ((X - 0.4) ** 2).sum(1) + 0.02 * rng.normal(size=N)
+    P = rng.uniform(0, 1, (7, D))
+    P[0] = X[0]
+    C = rng.uniform(0, 1, (1500, D))
+    C[7] = X[1]
+    inc = float(y.min())
+    ard = 0.7 * (0.6 + 0.8 * np.arange(D) / (D - 1))
+    for kind in ("rbf", "matern12", "matern32", "matern52"):
+        tag = "N=%3d %-8s" % (N, kind)
+        lml, g = gp.fit_grad(X, y, kind, 0.7, ard, 5e-3, 1e-10, True)
+        print("fit_grad %s %s lml=%.15g g1=%.15g" % (tag, digest([lml], g), lml, g[1]))
+        lml, ym, ys = gp.fit(X, y, kind, 1.3, 0.7, 2e-2, 1e-10, True)
+        print("fit      %s %s lml=%.15g L=%s Linv=%s alpha=%s" % (
+            tag, digest([lml, ym, ys]), lml, digest(np.tril(gp.debug_read(L.BUF_L))), digest(gp.debug_read(L.BUF_LINV)),
+            digest(gp.debug_read(L.BUF_ALPHA))))
+        v, g = gp.acq_grad(P, L.ACQ_EI, -1.0, inc, 0.01)
+        v1, g1 = gp.acq_grad(P[:1], L.ACQ_EI, -1.0, inc, 0.01)
+        print("acq_grad %s m=7 %s m=1 %s v=%s" % (tag, digest(v, g), digest(v1, g1), np.array2string(v[:3], precision=15)))
+        gp.set_candidates(C)
+        r = gp.sweep(L.ACQ_EI, -1.0, inc, 0.01, want_mu=True, want_sigma=True, want_acq=True)
+        print("sweep    %s %s best=%d/%.15g" % (tag, digest(r["mu"], r["sigma"], r["acq"], [r["best_val"], r["best_idx"], r["n_clamped"]]),
+                                             r["best_idx"], r["best_val"]))
+        b = gp.sweep_batch(3, acq=L.ACQ_EI, sf=-1.0, incumbent=inc, param=0.01)
+        print("sweep_batch %s %s idx=%s" % (tag, digest(b["idx"], b["val"], b["x"], b["fantasies"]), list(map(int, b["idx"]))))
+        gp.ts_draw(12345, S=4)
+        t = gp.ts_sweep(-1.0)
+        print("ts_sweep %s %s idx=%s" % (tag, digest(t["idx"], t["val"], t["x"]), list(map(int, t["idx"]))))
+        mu, cov, neg = gp.predict_cov(P[:5])
+        print("predict_cov %s %s neg=%d mu0=%.15g" % (tag, digest(mu, cov), neg, mu[0]))
 
 
 if __name__ == "__main__":

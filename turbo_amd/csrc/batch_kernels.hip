@@ -501,16 +501,6 @@ __global__ __launch_bounds__(BT_BLOCK) void mc_update_kernel(McUpd u) {
 }
 
 // ---- launchers ----
-#define BT_KIND_DISPATCH(kernel_tmpl, grid, block, ...)                                                          \
-    do {                                                                                                         \
-        switch (c.kernel) {                                                                                      \
-            case TGP_RBF: hipLaunchKernelGGL(kernel_tmpl<TGP_RBF>, grid, block, 0, c.stream, __VA_ARGS__); break; \
-            case TGP_MATERN12: hipLaunchKernelGGL(kernel_tmpl<TGP_MATERN12>, grid, block, 0, c.stream, __VA_ARGS__); break; \
-            case TGP_MATERN32: hipLaunchKernelGGL(kernel_tmpl<TGP_MATERN32>, grid, block, 0, c.stream, __VA_ARGS__); break; \
-            default: hipLaunchKernelGGL(kernel_tmpl<TGP_MATERN52>, grid, block, 0, c.stream, __VA_ARGS__); break; \
-        }                                                                                                        \
-    } while (0)
-
 int bt_pass_splits(const Context &c, int64_t M) {
     const int64_t tiles = (M + BT_CT - 1) / BT_CT;
     const int live = (int)((c.N + 127) / 128);
@@ -542,19 +532,19 @@ hipError_t launch_bt_condition(Context &c, const BatchWs &ws, const BtSmall &s, 
                                double lie, double sf) {
     TGP_TRY(launch_query_front(c, ws.Zraw + (long)j * c.D, ws.Zs + (long)j * c.Dp, ws.Kz + (long)j * c.Np, ws.hw, ws.v, ws.w));
     if (mc)
-        BT_KIND_DISPATCH(mc_small_kernel, dim3(1), dim3(256), ws.Kz, ws.w, c.d_alpha, ws.Zs, *mc, j, (int)c.N, (int)c.Np,
-                         (int)c.Dp, c.constant, c.noise, c.jitter, c.y_mean, c.y_std, sf);
+        hipLaunchKernelGGL(by_kind(c.kernel, [](auto K) { return mc_small_kernel<K()>; }), dim3(1), dim3(256), 0, c.stream, ws.Kz, ws.w,
+                           c.d_alpha, ws.Zs, *mc, j, (int)c.N, (int)c.Np, (int)c.Dp, c.constant, c.noise, c.jitter, c.y_mean, c.y_std, sf);
     else
-        BT_KIND_DISPATCH(bt_small_kernel, dim3(1), dim3(256), ws.Kz, ws.w, c.d_alpha, ws.Zs, s, j, (int)c.N, (int)c.Np,
-                         (int)c.Dp, c.constant, c.noise, c.jitter, c.y_mean, c.y_std, kb, lie, sf);
+        hipLaunchKernelGGL(by_kind(c.kernel, [](auto K) { return bt_small_kernel<K()>; }), dim3(1), dim3(256), 0, c.stream, ws.Kz, ws.w,
+                           c.d_alpha, ws.Zs, s, j, (int)c.N, (int)c.Np, (int)c.Dp, c.constant, c.noise, c.jitter, c.y_mean, c.y_std, kb, lie, sf);
     return hipGetLastError();
 }
 
 // the pass over every candidate for the point whose w is in ws.w
 static hipError_t launch_bt_pass(Context &c, const BatchWs &ws) {
     const dim3 gp((unsigned)((c.M + BT_CT - 1) / BT_CT), (unsigned)ws.js);
-    BT_KIND_DISPATCH(bt_pass_kernel, gp, dim3(256), ws.Cs, c.d_Xs, ws.w, ws.part, (int)c.M, (int)c.N, (int)c.Np, (int)c.Dp,
-                     c.constant, (long)ws.Mpad);
+    hipLaunchKernelGGL(by_kind(c.kernel, [](auto K) { return bt_pass_kernel<K()>; }), gp, dim3(256), 0, c.stream, ws.Cs, c.d_Xs, ws.w,
+                       ws.part, (int)c.M, (int)c.N, (int)c.Np, (int)c.Dp, c.constant, (long)ws.Mpad);
     return hipGetLastError();
 }
 
@@ -586,7 +576,7 @@ hipError_t launch_bt_step(Context &c, const BatchWs &ws, const BtSmall &s, int j
     BtUpd u{};
     u.b = bt_upd_base(c, ws, j, acq, sf, param, sigma_out);
     u.s = s; u.store = store; u.mu = ws.bmu; u.mu_out = mu_out;
-    BT_KIND_DISPATCH(bt_update_kernel, dim3((unsigned)ws.nblk), dim3(BT_BLOCK), u);
+    hipLaunchKernelGGL(by_kind(c.kernel, [](auto K) { return bt_update_kernel<K()>; }), dim3((unsigned)ws.nblk), dim3(BT_BLOCK), 0, c.stream, u);
     TGP_TRY(hipGetLastError());
     return acq != TGP_ACQ_NONE ? launch_bt_select(c, ws, s, k) : hipSuccess;
 }
@@ -604,7 +594,7 @@ hipError_t launch_mc_step(Context &c, const BatchWs &ws, const McSmall &s, int j
     McUpd u{};
     u.b = bt_upd_base(c, ws, j, acq, sf, param, sigma_out);
     u.s = s; u.mu0 = ws.bmu; u.acq_out = acq_out;
-    BT_KIND_DISPATCH(mc_update_kernel, dim3((unsigned)ws.nblk), dim3(BT_BLOCK), u);
+    hipLaunchKernelGGL(by_kind(c.kernel, [](auto K) { return mc_update_kernel<K()>; }), dim3((unsigned)ws.nblk), dim3(BT_BLOCK), 0, c.stream, u);
     TGP_TRY(hipGetLastError());
     return acq != TGP_ACQ_NONE ? launch_bt_select(c, ws, s.b, k) : hipSuccess;
 }

@@ -339,13 +339,7 @@ hipError_t launch_cov_posterior(Context &c, double *ws, const CovWs &w, int late
     hipLaunchKernelGGL(cov_scale_kernel, dim3((unsigned)(((long)mpad * Dp + 255) / 256)), dim3(256), 0, s, ws + w.o_Xq, c.d_ls, Us, m, mpad, D, Dp, cnt);
     TGP_TRY(hipGetLastError());
     {
-        void (*k)(const double *, const double *, double *, int, int, int, int, double);
-        switch (c.kernel) {
-            case TGP_RBF: k = cov_ks_kernel<TGP_RBF>; break;
-            case TGP_MATERN12: k = cov_ks_kernel<TGP_MATERN12>; break;
-            case TGP_MATERN32: k = cov_ks_kernel<TGP_MATERN32>; break;
-            default: k = cov_ks_kernel<TGP_MATERN52>; break;
-        }
+        auto k = by_kind(c.kernel, [](auto K) { return cov_ks_kernel<K()>; });
         hipLaunchKernelGGL(k, dim3(Np / PW_T, mpad / PW_T), dim3(256), 0, s, Us, c.d_Xs, Ks, m, N, Np, Dp, c.constant);
         TGP_TRY(hipGetLastError());
     }
@@ -366,13 +360,7 @@ hipError_t launch_cov_posterior(Context &c, double *ws, const CovWs &w, int late
         a.constant = c.constant; a.diag_add = (latent ? 0.0 : c.noise) + (for_sample ? nugget : 0.0);
         a.scale = for_sample ? 1.0 : c.y_std * c.y_std;
         a.mirror = for_sample ? 0 : 1;
-        void (*k)(CovSyrkArgs);
-        switch (c.kernel) {
-            case TGP_RBF: k = cov_syrk_kernel<TGP_RBF>; break;
-            case TGP_MATERN12: k = cov_syrk_kernel<TGP_MATERN12>; break;
-            case TGP_MATERN32: k = cov_syrk_kernel<TGP_MATERN32>; break;
-            default: k = cov_syrk_kernel<TGP_MATERN52>; break;
-        }
+        auto k = by_kind(c.kernel, [](auto K) { return cov_syrk_kernel<K()>; });
         constexpr size_t lds = trmm_glds_lds_bytes();
         static LdsOptIn opt_in[4];
         TGP_TRY(opt_in[c.kernel & 3].ensure(reinterpret_cast<const void *>(k), c.device, lds));

@@ -691,12 +691,7 @@ hipError_t launch_fit_append(Context &c, int n_old) {
     const int Np = (int)c.Np, Dp = (int)c.Dp;
     TGP_TRY(hipMemsetAsync(c.d_flag, 0, sizeof(int), s));
     const dim3 kg((Np + 255) / 256);
-    switch (c.kernel) {
-        case TGP_RBF: hipLaunchKernelGGL(kvec_kernel<TGP_RBF>, kg, dim3(256), 0, s, c.d_Xs, c.d_t1, n_old, Np, Dp, c.constant); break;
-        case TGP_MATERN12: hipLaunchKernelGGL(kvec_kernel<TGP_MATERN12>, kg, dim3(256), 0, s, c.d_Xs, c.d_t1, n_old, Np, Dp, c.constant); break;
-        case TGP_MATERN32: hipLaunchKernelGGL(kvec_kernel<TGP_MATERN32>, kg, dim3(256), 0, s, c.d_Xs, c.d_t1, n_old, Np, Dp, c.constant); break;
-        default: hipLaunchKernelGGL(kvec_kernel<TGP_MATERN52>, kg, dim3(256), 0, s, c.d_Xs, c.d_t1, n_old, Np, Dp, c.constant); break;
-    }
+    hipLaunchKernelGGL(by_kind(c.kernel, [](auto K) { return kvec_kernel<K()>; }), kg, dim3(256), 0, s, c.d_Xs, c.d_t1, n_old, Np, Dp, c.constant);
     TGP_TRY(hipGetLastError());
     // l = Linv k  (the new row of L), then its pivot
     hipLaunchKernelGGL(gemv_lower_rows_kernel, dim3((Np + 3) / 4), dim3(256), 0, s, c.d_Linv, c.d_t1, c.d_t2, Np);
@@ -1577,12 +1572,7 @@ hipError_t launch_fit(Context &c, const double *staged_in, double *res_host, boo
     {
         const int nt = Np / PW_T;
         const dim3 grid(nt * (nt + 1) / 2);
-        switch (c.kernel) {
-            case TGP_RBF: hipLaunchKernelGGL(kernel_matrix_kernel<TGP_RBF>, grid, dim3(256), 0, s, c.d_Xs, c.d_K, N, Np, Dp, c.constant, c.noise, c.jitter); break;
-            case TGP_MATERN12: hipLaunchKernelGGL(kernel_matrix_kernel<TGP_MATERN12>, grid, dim3(256), 0, s, c.d_Xs, c.d_K, N, Np, Dp, c.constant, c.noise, c.jitter); break;
-            case TGP_MATERN32: hipLaunchKernelGGL(kernel_matrix_kernel<TGP_MATERN32>, grid, dim3(256), 0, s, c.d_Xs, c.d_K, N, Np, Dp, c.constant, c.noise, c.jitter); break;
-            default: hipLaunchKernelGGL(kernel_matrix_kernel<TGP_MATERN52>, grid, dim3(256), 0, s, c.d_Xs, c.d_K, N, Np, Dp, c.constant, c.noise, c.jitter); break;
-        }
+        hipLaunchKernelGGL(by_kind(c.kernel, [](auto K) { return kernel_matrix_kernel<K()>; }), grid, dim3(256), 0, s, c.d_Xs, c.d_K, N, Np, Dp, c.constant, c.noise, c.jitter);
         TGP_TRY(hipGetLastError());
     }
     // ---- blocked Cholesky, two levels ----

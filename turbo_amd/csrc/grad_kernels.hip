@@ -141,13 +141,7 @@ hipError_t launch_small_grad(Context &c, bool ard, double *out) {
     SmallGradArgs a{};
     a.Xs = c.d_Xs; a.alpha = c.d_alpha; a.Linv = c.d_Linv; a.out = out;
     a.N = (int)c.N; a.Np = (int)c.Np; a.Dp = (int)c.Dp; a.ard = ard ? 1 : 0;
-    void (*k)(SmallGradArgs);
-    switch (c.kernel) {
-        case TGP_RBF: k = small_grad_kernel<TGP_RBF>; break;
-        case TGP_MATERN12: k = small_grad_kernel<TGP_MATERN12>; break;
-        case TGP_MATERN32: k = small_grad_kernel<TGP_MATERN32>; break;
-        default: k = small_grad_kernel<TGP_MATERN52>; break;
-    }
+    auto k = by_kind(c.kernel, [](auto K) { return small_grad_kernel<K()>; });
     static LdsOptIn opt_in[4];
     TGP_TRY(opt_in[c.kernel & 3].ensure(reinterpret_cast<const void *>(k), c.device, SMALL_GRAD_LDS));
     hipLaunchKernelGGL(k, dim3(c.N > NB ? 3 : 1), dim3(256), SMALL_GRAD_LDS, c.stream, a);
@@ -204,12 +198,7 @@ hipError_t launch_lml_grad(Context &c, bool ard, double *gout, bool timed) {
     const int nblk = nt * (nt + 1) / 2;
     const dim3 grid(nblk);
     const int wr = ard ? 1 : 0;
-    switch (c.kernel) {
-        case TGP_RBF: hipLaunchKernelGGL(lml_weights_kernel<TGP_RBF>, grid, dim3(256), 0, s, c.d_Xs, c.d_alpha, c.d_W, c.d_gpart, N, Np, Dp, wr); break;
-        case TGP_MATERN12: hipLaunchKernelGGL(lml_weights_kernel<TGP_MATERN12>, grid, dim3(256), 0, s, c.d_Xs, c.d_alpha, c.d_W, c.d_gpart, N, Np, Dp, wr); break;
-        case TGP_MATERN32: hipLaunchKernelGGL(lml_weights_kernel<TGP_MATERN32>, grid, dim3(256), 0, s, c.d_Xs, c.d_alpha, c.d_W, c.d_gpart, N, Np, Dp, wr); break;
-        default: hipLaunchKernelGGL(lml_weights_kernel<TGP_MATERN52>, grid, dim3(256), 0, s, c.d_Xs, c.d_alpha, c.d_W, c.d_gpart, N, Np, Dp, wr); break;
-    }
+    hipLaunchKernelGGL(by_kind(c.kernel, [](auto K) { return lml_weights_kernel<K()>; }), grid, dim3(256), 0, s, c.d_Xs, c.d_alpha, c.d_W, c.d_gpart, N, Np, Dp, wr);
     TGP_TRY(hipGetLastError());
     if (timed) TGP_TRY(hipEventRecord(c.evg[2], s));
     const int ncols = ard ? 3 + Dp : 3;

@@ -18,6 +18,11 @@
 
 namespace tgp {
 
+// SciPy's defaults of L-BFGS-B: what every optimiser of the library stops by, the ones on the device included
+constexpr double LBFGSB_PGTOL = 1e-5;                    // pgtol: largest entry of the projected gradient
+constexpr double LBFGSB_FTOL = 2.220446049250313e-09;    // factr x eps = 1e7 x 2.22e-16: relative reduction of f
+constexpr int LBFGSB_MAXFUN = 15000;                     // maxfun: evaluations of one start, a line search's trials included
+
 struct HostLbfgsb {
     static constexpr int M = 10;           // pairs kept (SciPy's maxcor)
     static constexpr int MAXLS = 20;       // evaluations per line search (SciPy's maxls)
@@ -51,6 +56,14 @@ struct HostLbfgsb {
     std::vector<double> x_eval, g_eval;
     double f_eval = 0;
     bool evaluated(const std::vector<double> &xt) const { return !x_eval.empty() && xt == x_eval; }
+    // ... in one place: when xt is that point, take the step from the stored evaluation and say so (false: xt is a new
+    // point, or the first one, and wants evaluating)
+    bool step_from_cache(std::vector<double> &xt) {
+        if (!evaluated(xt)) return false;
+        const std::vector<double> gt = g_eval;      // (step() stores its arguments over the cache)
+        step(xt, gt, f_eval, false);
+        return true;
+    }
 
     HostLbfgsb(const double *lo_, const double *hi_, int P_)
         : P(P_), lo(lo_, lo_ + P_), hi(hi_, hi_ + P_), x(P_), g(P_), z(P_), d(P_), gt_prev(P_), where(P_) {
@@ -476,7 +489,8 @@ struct HostLbfgsb {
 
     // (phit, gt) = the objective and its gradient at xt; leaves the next point to evaluate in xt (the iterate itself
     // once the start has finished).  pgtol and ftol are SciPy's gtol and ftol (= factr x machine epsilon).
-    void step(std::vector<double> &xt, const std::vector<double> &gt, double phit, bool first, double pgtol, double ftol) {
+    void step(std::vector<double> &xt, const std::vector<double> &gt, double phit, bool first, double pgtol = LBFGSB_PGTOL,
+              double ftol = LBFGSB_FTOL) {
         x_eval = xt; g_eval = gt; f_eval = phit;
         if (first) {
             cnstnd = false; boxed = true;

@@ -450,16 +450,53 @@ __global__ void q_finalize_kernel(const double *__restrict__ red, QFinal fin) {
     q_finalize_point<MES>(fin, red + (long)q * (2 + 2 * fin.D), q, [](const double *a) { return *a; });
 }
 
-// doubles of launch_query's workspace per query point
-int64_t query_ws_doubles(const Context &c) { return c.Dp + (int64_t)(3 + QCOLS_SPLIT) * c.Np + 2 + 2 * c.D; }
-
 // where launch_query leaves, per query point q, [k.alpha, v.v, gm[0..D), gv[0..D)] (stride 2 + 2 D)
-double *query_red(const Context &c, double *d_ws, int m) {
+static double *query_red(const Context &c, double *d_ws, int m) {
     return d_ws + (long)m * c.Dp + (long)(3 + QCOLS_SPLIT) * m * c.Np;
 }
 
-// workspace per query point: uq (Dp) | ks, hw, v (3 Np) | w's QCOLS_SPLIT shares (16 Np) | red (2 + 2 D)  [query_ws_doubles].
-// d_val == nullptr: stop after the sums (the caller turns query_red() into value + gradient itself).
+// c.d_qws for m points: the entry's [Xq | val | grad], rounded up to whole groups of 4 doubles (hipMalloc aligns the
+// buffer itself) so that every vector of launch_query's workspace behind it starts on 32 bytes for odd m too (Dp and Np
+// are multiples of 4), then that workspace: the doubles per point listed at launch_query
+QueryWs query_ws(const Context &c, int m) {
+    const int64_t front = (m * (2 * c.D + 1) + 3) / 4 * 4;
+    const int64_t per = c.Dp + (int64_t)(3 + QCOLS_SPLIT) * c.Np + 2 + 2 * c.D;
+    QueryWs q;
+    q.bytes = (size_t)(front + m * per) * sizeof(double);
+    q.Xq = c.d_qws; q.val = q.Xq + m * c.D; q.grad = q.val + m; q.ws = c.d_qws + front;
+    q.red = query_red(c, q.ws, m);
+    return q;
+}
+
+// the cross-kernel of m points: uq = x / l (Dp each), ks = c k0(x, X) (Np each, zero from N on) and hw beside it
+static hipError_t launch_q_kvec(Context &c, const double *d_Xq, int m, double *uq, double *ks, double *hw, unsigned long long *stamp) {
+    const int Np = (int)c.Np, Dp = (int)c.Dp;
+    hipLaunchKernelGGL(by_kind(c.kernel, [](auto K) { return q_kvec_kernel<K()>; }), dim3((Np + 255) / 256, m), dim3(256),
+                       (size_t)Dp * sizeof(double), c.stream, d_Xq, c.d_ls, c.d_Xs, uq, ks, hw, (int)c.N, Np, (int)c.D, Dp, c.constant, stamp);
+    return hipGetLastError();
+}
+
+template <int W>
+static hipError_t launch_linv_solve_as(Context &c, const double *r, double *z, double *w, int m) {
+    const int N = (int)c.N, Np = (int)c.Np;
+    const unsigned groups = (unsigned)((m + QM_PTS - 1) / QM_PTS);
+    hipLaunchKernelGGL(q_rows_mfma_kernel<W>, dim3(Np / 16, groups), dim3(64 * W), 0, c.stream, c.d_Linv, r, z, Np, m);
+    TGP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(q_cols_mfma_kernel<W>, dim3((N + 15) / 16, groups), dim3(64 * W), 0, c.stream, c.d_Linv, z, w, N, Np, m);
+    return hipGetLastError();
+}
+// z = Linv r and w = Linv^T z for m vectors at once (launch_query's points; tgp_ts_draw: the S residuals, ts_kernels.hip),
+// on the matrix-core products in groups of 16; r is zero from N on, as q_kvec_kernel leaves ks
+hipError_t launch_linv_solve(Context &c, const double *r, double *z, double *w, int m) {
+    switch (query_waves((int)c.Np)) {
+        case 4: return launch_linv_solve_as<4>(c, r, z, w, m);
+        case 8: return launch_linv_solve_as<8>(c, r, z, w, m);
+        default: return launch_linv_solve_as<16>(c, r, z, w, m);
+    }
+}
+
+// workspace per query point: uq (Dp) | ks, hw, v (3 Np) | w's QCOLS_SPLIT shares (16 Np) | red (2 + 2 D)  [query_ws].
+// d_val == nullptr: stop after the sums (the caller turns QueryWs::red into value + gradient itself).
 hipError_t launch_query(Context &c, const double *d_Xq, int m, int acq, double sf, double incumbent,
                         double param, double *d_ws, double *d_val, double *d_grad, const Bell &bell) {
     hipStream_t s = c.stream;
@@ -469,38 +506,11 @@ hipError_t launch_query(Context &c, const double *d_Xq, int m, int acq, double s
     double *hw = ks + (long)m * Np;
     double *v = hw + (long)m * Np;
     double *w = v + (long)m * Np;
-    double *red = w + (long)QCOLS_SPLIT * m * Np;
-    unsigned long long *stamp = (d_val && bell.word) ? bell.word + 1 : nullptr;
-    const dim3 g1((Np + 255) / 256, m);
-    const size_t sh = (size_t)Dp * sizeof(double);
-    switch (c.kernel) {
-        case TGP_RBF: hipLaunchKernelGGL(q_kvec_kernel<TGP_RBF>, g1, dim3(256), sh, s, d_Xq, c.d_ls, c.d_Xs, uq, ks, hw, N, Np, D, Dp, c.constant, stamp); break;
-        case TGP_MATERN12: hipLaunchKernelGGL(q_kvec_kernel<TGP_MATERN12>, g1, dim3(256), sh, s, d_Xq, c.d_ls, c.d_Xs, uq, ks, hw, N, Np, D, Dp, c.constant, stamp); break;
-        case TGP_MATERN32: hipLaunchKernelGGL(q_kvec_kernel<TGP_MATERN32>, g1, dim3(256), sh, s, d_Xq, c.d_ls, c.d_Xs, uq, ks, hw, N, Np, D, Dp, c.constant, stamp); break;
-        default: hipLaunchKernelGGL(q_kvec_kernel<TGP_MATERN52>, g1, dim3(256), sh, s, d_Xq, c.d_ls, c.d_Xs, uq, ks, hw, N, Np, D, Dp, c.constant, stamp); break;
-    }
-    TGP_TRY(hipGetLastError());
+    double *red = query_red(c, d_ws, m);
+    TGP_TRY(launch_q_kvec(c, d_Xq, m, uq, ks, hw, (d_val && bell.word) ? bell.word + 1 : nullptr));
     const bool mfma = tuning().query_mfma != 0;      // A/B: 0 = round 6's earlier wave-per-row / split-column kernels
     if (mfma) {
-        const unsigned groups = (unsigned)((m + QM_PTS - 1) / QM_PTS);
-        const dim3 gr(Np / 16, groups), gc((N + 15) / 16, groups);
-        switch (query_waves(Np)) {
-            case 4:
-                hipLaunchKernelGGL(q_rows_mfma_kernel<4>, gr, dim3(256), 0, s, c.d_Linv, ks, v, Np, m);
-                TGP_TRY(hipGetLastError());
-                hipLaunchKernelGGL(q_cols_mfma_kernel<4>, gc, dim3(256), 0, s, c.d_Linv, v, w, N, Np, m);
-                break;
-            case 8:
-                hipLaunchKernelGGL(q_rows_mfma_kernel<8>, gr, dim3(512), 0, s, c.d_Linv, ks, v, Np, m);
-                TGP_TRY(hipGetLastError());
-                hipLaunchKernelGGL(q_cols_mfma_kernel<8>, gc, dim3(512), 0, s, c.d_Linv, v, w, N, Np, m);
-                break;
-            default:
-                hipLaunchKernelGGL(q_rows_mfma_kernel<16>, gr, dim3(1024), 0, s, c.d_Linv, ks, v, Np, m);
-                TGP_TRY(hipGetLastError());
-                hipLaunchKernelGGL(q_cols_mfma_kernel<16>, gc, dim3(1024), 0, s, c.d_Linv, v, w, N, Np, m);
-                break;
-        }
+        TGP_TRY(launch_linv_solve(c, ks, v, w, m));
     } else if (m > QROWS_QB) {
         hipLaunchKernelGGL(q_gemv_rows_kernel<2 * QROWS_QB>, dim3((Np + 3) / 4, (m + 2 * QROWS_QB - 1) / (2 * QROWS_QB)), dim3(256), 0, s, c.d_Linv, ks, v, Np, m);
         TGP_TRY(hipGetLastError());
@@ -533,64 +543,8 @@ hipError_t launch_query(Context &c, const double *d_Xq, int m, int acq, double s
 // conditioned on next, batch_kernels.hip): uq = x / l (Dp), ks = c k0(x, X) (Np, 0 from N on), v = Linv ks,
 // w = Linv^T v = K^-1 k* -- on the matrix-core products whatever TGP_QUERY_MFMA says (one split of w, nothing to add).
 hipError_t launch_query_front(Context &c, const double *d_xq, double *uq, double *ks, double *hw, double *v, double *w) {
-    hipStream_t s = c.stream;
-    const int N = (int)c.N, Np = (int)c.Np, D = (int)c.D, Dp = (int)c.Dp;
-    const dim3 g1((Np + 255) / 256, 1);
-    const size_t sh = (size_t)Dp * sizeof(double);
-    unsigned long long *stamp = nullptr;
-    switch (c.kernel) {
-        case TGP_RBF: hipLaunchKernelGGL(q_kvec_kernel<TGP_RBF>, g1, dim3(256), sh, s, d_xq, c.d_ls, c.d_Xs, uq, ks, hw, N, Np, D, Dp, c.constant, stamp); break;
-        case TGP_MATERN12: hipLaunchKernelGGL(q_kvec_kernel<TGP_MATERN12>, g1, dim3(256), sh, s, d_xq, c.d_ls, c.d_Xs, uq, ks, hw, N, Np, D, Dp, c.constant, stamp); break;
-        case TGP_MATERN32: hipLaunchKernelGGL(q_kvec_kernel<TGP_MATERN32>, g1, dim3(256), sh, s, d_xq, c.d_ls, c.d_Xs, uq, ks, hw, N, Np, D, Dp, c.constant, stamp); break;
-        default: hipLaunchKernelGGL(q_kvec_kernel<TGP_MATERN52>, g1, dim3(256), sh, s, d_xq, c.d_ls, c.d_Xs, uq, ks, hw, N, Np, D, Dp, c.constant, stamp); break;
-    }
-    TGP_TRY(hipGetLastError());
-    const dim3 gr(Np / 16, 1), gc((N + 15) / 16, 1);
-    switch (query_waves(Np)) {
-        case 4:
-            hipLaunchKernelGGL(q_rows_mfma_kernel<4>, gr, dim3(256), 0, s, c.d_Linv, ks, v, Np, 1);
-            TGP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(q_cols_mfma_kernel<4>, gc, dim3(256), 0, s, c.d_Linv, v, w, N, Np, 1);
-            break;
-        case 8:
-            hipLaunchKernelGGL(q_rows_mfma_kernel<8>, gr, dim3(512), 0, s, c.d_Linv, ks, v, Np, 1);
-            TGP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(q_cols_mfma_kernel<8>, gc, dim3(512), 0, s, c.d_Linv, v, w, N, Np, 1);
-            break;
-        default:
-            hipLaunchKernelGGL(q_rows_mfma_kernel<16>, gr, dim3(1024), 0, s, c.d_Linv, ks, v, Np, 1);
-            TGP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(q_cols_mfma_kernel<16>, gc, dim3(1024), 0, s, c.d_Linv, v, w, N, Np, 1);
-            break;
-    }
-    return hipGetLastError();
-}
-
-// z = Linv r and w = Linv^T z for m vectors at once (tgp_ts_draw: the S residuals, ts_kernels.hip), on the matrix-core
-// products in groups of 16; r is zero from N on, as q_kvec_kernel leaves ks
-hipError_t launch_linv_solve(Context &c, const double *r, double *z, double *w, int m) {
-    hipStream_t s = c.stream;
-    const int N = (int)c.N, Np = (int)c.Np;
-    const unsigned groups = (unsigned)((m + QM_PTS - 1) / QM_PTS);
-    const dim3 gr(Np / 16, groups), gc((N + 15) / 16, groups);
-    switch (query_waves(Np)) {
-        case 4:
-            hipLaunchKernelGGL(q_rows_mfma_kernel<4>, gr, dim3(256), 0, s, c.d_Linv, r, z, Np, m);
-            TGP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(q_cols_mfma_kernel<4>, gc, dim3(256), 0, s, c.d_Linv, z, w, N, Np, m);
-            break;
-        case 8:
-            hipLaunchKernelGGL(q_rows_mfma_kernel<8>, gr, dim3(512), 0, s, c.d_Linv, r, z, Np, m);
-            TGP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(q_cols_mfma_kernel<8>, gc, dim3(512), 0, s, c.d_Linv, z, w, N, Np, m);
-            break;
-        default:
-            hipLaunchKernelGGL(q_rows_mfma_kernel<16>, gr, dim3(1024), 0, s, c.d_Linv, r, z, Np, m);
-            TGP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(q_cols_mfma_kernel<16>, gc, dim3(1024), 0, s, c.d_Linv, z, w, N, Np, m);
-            break;
-    }
-    return hipGetLastError();
+    TGP_TRY(launch_q_kvec(c, d_xq, 1, uq, ks, hw, nullptr));
+    return launch_linv_solve(c, ks, v, w, 1);
 }
 
 }  // namespace tgp

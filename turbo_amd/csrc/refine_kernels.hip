@@ -549,13 +549,7 @@ hipError_t launch_small_query(Context &c, const double *d_xq, int m, int acq, do
     a.constant = c.constant; a.kss = c.constant + c.noise; a.y_mean = c.y_mean; a.y_std = c.y_std;
     a.sf = sf; a.incumbent = incumbent; a.param = param;
     a.bell = bell;
-    void (*k)(SmallQueryArgs);
-    switch (c.kernel) {
-        case TGP_RBF: k = small_query_kernel<TGP_RBF>; break;
-        case TGP_MATERN12: k = small_query_kernel<TGP_MATERN12>; break;
-        case TGP_MATERN32: k = small_query_kernel<TGP_MATERN32>; break;
-        default: k = small_query_kernel<TGP_MATERN52>; break;
-    }
+    auto k = by_kind(c.kernel, [](auto K) { return small_query_kernel<K()>; });
     const size_t lds = small_refine_lds_doubles(a.Np, (int)c.N, (int)c.Dp) * sizeof(double);
     static LdsOptIn opt_in[4];
     TGP_TRY(opt_in[c.kernel & 3].ensure(reinterpret_cast<const void *>(k), c.device, 160 * 1024));   // (once per device: the most)
@@ -640,13 +634,7 @@ hipError_t launch_small_refine(Context &c, const double *d_x0, const double *d_l
     a.D = (int)c.D; a.Dp = (int)c.Dp; a.max_iter = max_iter; a.acq = acq;
     a.constant = c.constant; a.kss = c.constant + c.noise; a.y_mean = c.y_mean; a.y_std = c.y_std;
     a.sf = sf; a.incumbent = incumbent; a.param = param; a.pgtol = pgtol; a.ftol = ftol;
-    void (*k)(SmallRefineArgs);
-    switch (c.kernel) {
-        case TGP_RBF: k = small_refine_kernel<TGP_RBF>; break;
-        case TGP_MATERN12: k = small_refine_kernel<TGP_MATERN12>; break;
-        case TGP_MATERN32: k = small_refine_kernel<TGP_MATERN32>; break;
-        default: k = small_refine_kernel<TGP_MATERN52>; break;
-    }
+    auto k = by_kind(c.kernel, [](auto K) { return small_refine_kernel<K()>; });
     const size_t lds = small_refine_lds_doubles(a.Np, (int)c.N, (int)c.Dp) * sizeof(double);
     static LdsOptIn opt_in[4];
     TGP_TRY(opt_in[c.kernel & 3].ensure(reinterpret_cast<const void *>(k), c.device, 160 * 1024));   // (once per device: the most)

@@ -23,6 +23,7 @@
 
 #include "acq_math.hpp"
 #include "chol64.hpp"
+#include "host_lbfgsb.hpp"
 #include "lbfgs_wave.hpp"
 #include "lds_opt_in.hpp"
 #include "pairwise.hpp"
@@ -364,13 +365,7 @@ static SmallFitArgs small_fit_args(Context &c, const Bell &bell) {
 
 hipError_t launch_small_fit(Context &c, const Bell &bell) {
     const SmallFitArgs a = small_fit_args(c, bell);
-    void (*k)(SmallFitArgs);
-    switch (c.kernel) {
-        case TGP_RBF: k = small_fit_kernel<TGP_RBF>; break;
-        case TGP_MATERN12: k = small_fit_kernel<TGP_MATERN12>; break;
-        case TGP_MATERN32: k = small_fit_kernel<TGP_MATERN32>; break;
-        default: k = small_fit_kernel<TGP_MATERN52>; break;
-    }
+    auto k = by_kind(c.kernel, [](auto K) { return small_fit_kernel<K()>; });
     static LdsOptIn opt_in[4];
     TGP_TRY(opt_in[c.kernel & 3].ensure(reinterpret_cast<const void *>(k), c.device, SMALL_FIT_LDS));
     hipLaunchKernelGGL(k, dim3(1), dim3(256), SMALL_FIT_LDS, c.stream, a);
@@ -493,13 +488,7 @@ hipError_t launch_small_fit_grad(Context &c, bool ard, double *gout_host, const 
     const unsigned npair = c.N > NB ? 3 : 1;
     a.ws = c.d_sfg;
     a.ws_stride = small_fit_grad_ws_doubles(Nin, (int)c.D, (int)c.Dp);
-    void (*k)(SmallFitGradArgs);
-    switch (c.kernel) {
-        case TGP_RBF: k = small_fit_grad_kernel<TGP_RBF>; break;
-        case TGP_MATERN12: k = small_fit_grad_kernel<TGP_MATERN12>; break;
-        case TGP_MATERN32: k = small_fit_grad_kernel<TGP_MATERN32>; break;
-        default: k = small_fit_grad_kernel<TGP_MATERN52>; break;
-    }
+    auto k = by_kind(c.kernel, [](auto K) { return small_fit_grad_kernel<K()>; });
     static LdsOptIn opt_in[4];
     TGP_TRY(opt_in[c.kernel & 3].ensure(reinterpret_cast<const void *>(k), c.device, SMALL_HYPER_BODY_LDS));
     hipLaunchKernelGGL(k, dim3(npair), dim3(256), SMALL_HYPER_BODY_LDS, c.stream, a);
@@ -666,7 +655,7 @@ hipError_t launch_small_hyper(Context &c, int kernel, const double *d_X, const d
     a.theta_out = d_theta; a.f_out = d_f; a.info = d_info;
     a.ws_stride = small_hyper_ws_doubles(N, D, Dp);
     a.N = N; a.D = D; a.Dp = Dp; a.n_ls = n_ls; a.max_iter = max_iter;
-    a.jitter = jitter; a.pgtol = 1e-5; a.ftol = 2.220446049250313e-09;   // SciPy's L-BFGS-B defaults (factr 1e7)
+    a.jitter = jitter; a.pgtol = LBFGSB_PGTOL; a.ftol = LBFGSB_FTOL;   // SciPy's L-BFGS-B defaults
     a.legacy = tuning().small_live == 0 ? 1 : 0;
     // Three workgroups per start when the gradient has three block pairs (64 < N <= 128) AND all 3 S
     // workgroups can be resident at once (one per CU at this LDS size): the barrier between a start's
@@ -680,13 +669,7 @@ hipError_t launch_small_hyper(Context &c, int kernel, const double *d_X, const d
     a.ws = d_ws + HYPER_BAR_DOUBLES;
     a.shares = a.ws + (long)S * 3 * a.ws_stride;
     TGP_TRY(hipMemsetAsync(a.bar, 0, (size_t)HYPER_BAR_DOUBLES * sizeof(double), c.stream));
-    void (*k)(SmallHyperArgs);
-    switch (kernel) {
-        case TGP_RBF: k = small_hyper_kernel<TGP_RBF>; break;
-        case TGP_MATERN12: k = small_hyper_kernel<TGP_MATERN12>; break;
-        case TGP_MATERN32: k = small_hyper_kernel<TGP_MATERN32>; break;
-        default: k = small_hyper_kernel<TGP_MATERN52>; break;
-    }
+    auto k = by_kind(kernel, [](auto K) { return small_hyper_kernel<K()>; });
     static LdsOptIn opt_in[4];
     TGP_TRY(opt_in[kernel & 3].ensure(reinterpret_cast<const void *>(k), c.device, SMALL_HYPER_LDS));
     hipLaunchKernelGGL(k, dim3((unsigned)(S * a.wgs)), dim3(256), SMALL_HYPER_LDS, c.stream, a);
@@ -1378,13 +1361,7 @@ int mid_sweep_cpw(const Context &c, int64_t M) {
 
 template <int CPW>
 static hipError_t launch_mid_sweep_mes_as(Context &c, const SmallSweepArgs &a, const MidFinal &f, const MesArgs &mes) {
-    void (*k)(SmallSweepArgs, MidFinal, MesArgs);
-    switch (c.kernel) {
-        case TGP_RBF: k = mid_sweep_mes_kernel<TGP_RBF, CPW>; break;
-        case TGP_MATERN12: k = mid_sweep_mes_kernel<TGP_MATERN12, CPW>; break;
-        case TGP_MATERN32: k = mid_sweep_mes_kernel<TGP_MATERN32, CPW>; break;
-        default: k = mid_sweep_mes_kernel<TGP_MATERN52, CPW>; break;
-    }
+    auto k = by_kind(c.kernel, [](auto K) { return mid_sweep_mes_kernel<K(), CPW>; });
     static LdsOptIn opt_in[4];
     TGP_TRY(opt_in[c.kernel & 3].ensure(reinterpret_cast<const void *>(k), c.device, MidCfg<CPW>::LDS));
     const unsigned nblk = (unsigned)((c.M + CPW - 1) / CPW);
@@ -1394,13 +1371,7 @@ static hipError_t launch_mid_sweep_mes_as(Context &c, const SmallSweepArgs &a, c
 
 template <int CPW>
 static hipError_t launch_mid_sweep_as(Context &c, const SmallSweepArgs &a, const MidFinal &f) {
-    void (*k)(SmallSweepArgs, MidFinal);
-    switch (c.kernel) {
-        case TGP_RBF: k = mid_sweep_kernel<TGP_RBF, CPW>; break;
-        case TGP_MATERN12: k = mid_sweep_kernel<TGP_MATERN12, CPW>; break;
-        case TGP_MATERN32: k = mid_sweep_kernel<TGP_MATERN32, CPW>; break;
-        default: k = mid_sweep_kernel<TGP_MATERN52, CPW>; break;
-    }
+    auto k = by_kind(c.kernel, [](auto K) { return mid_sweep_kernel<K(), CPW>; });
     static LdsOptIn opt_in[4];
     TGP_TRY(opt_in[c.kernel & 3].ensure(reinterpret_cast<const void *>(k), c.device, MidCfg<CPW>::LDS));
     const unsigned nblk = (unsigned)((c.M + CPW - 1) / CPW);
@@ -1432,25 +1403,13 @@ hipError_t launch_small_sweep(Context &c, const SweepCall &s) {
     const SmallSweepArgs a = sweep_args(c, s);
     const unsigned nblk = (unsigned)((c.M + NB - 1) / NB);
     if (s.acq == TGP_ACQ_MES) {
-        void (*km)(SmallSweepArgs, MesArgs);
-        switch (c.kernel) {
-            case TGP_RBF: km = small_sweep_mes_kernel<TGP_RBF>; break;
-            case TGP_MATERN12: km = small_sweep_mes_kernel<TGP_MATERN12>; break;
-            case TGP_MATERN32: km = small_sweep_mes_kernel<TGP_MATERN32>; break;
-            default: km = small_sweep_mes_kernel<TGP_MATERN52>; break;
-        }
+        auto km = by_kind(c.kernel, [](auto K) { return small_sweep_mes_kernel<K()>; });
         static LdsOptIn opt_mes[4];
         TGP_TRY(opt_mes[c.kernel & 3].ensure(reinterpret_cast<const void *>(km), c.device, SMALL_SWEEP_LDS));
         hipLaunchKernelGGL(km, dim3(nblk), dim3(256), SMALL_SWEEP_LDS, c.stream, a, s.mes);
         return hipGetLastError();
     }
-    void (*k)(SmallSweepArgs);
-    switch (c.kernel) {
-        case TGP_RBF: k = small_sweep_kernel<TGP_RBF>; break;
-        case TGP_MATERN12: k = small_sweep_kernel<TGP_MATERN12>; break;
-        case TGP_MATERN32: k = small_sweep_kernel<TGP_MATERN32>; break;
-        default: k = small_sweep_kernel<TGP_MATERN52>; break;
-    }
+    auto k = by_kind(c.kernel, [](auto K) { return small_sweep_kernel<K()>; });
     static LdsOptIn opt_in[4];
     TGP_TRY(opt_in[c.kernel & 3].ensure(reinterpret_cast<const void *>(k), c.device, SMALL_SWEEP_LDS));
     hipLaunchKernelGGL(k, dim3(nblk), dim3(256), SMALL_SWEEP_LDS, c.stream, a);
@@ -1521,14 +1480,7 @@ void fill_mid_batch_args(void *fit_args, void *sweep_args, int64_t t, const doub
 }
 
 hipError_t launch_mid_batch(Context &c, int kernel, const void *fit_args_dev, const void *sweep_args_dev, int64_t T, int64_t M) {
-    void (*kf)(const SmallFitArgs *);
-    void (*ks)(const SmallSweepArgs *);
-    switch (kernel) {
-        case TGP_RBF: kf = mid_fit_batch_kernel<TGP_RBF>; ks = mid_sweep_batch_kernel<TGP_RBF>; break;
-        case TGP_MATERN12: kf = mid_fit_batch_kernel<TGP_MATERN12>; ks = mid_sweep_batch_kernel<TGP_MATERN12>; break;
-        case TGP_MATERN32: kf = mid_fit_batch_kernel<TGP_MATERN32>; ks = mid_sweep_batch_kernel<TGP_MATERN32>; break;
-        default: kf = mid_fit_batch_kernel<TGP_MATERN52>; ks = mid_sweep_batch_kernel<TGP_MATERN52>; break;
-    }
+    const auto [kf, ks] = by_kind(kernel, [](auto K) { return std::make_pair(mid_fit_batch_kernel<K()>, mid_sweep_batch_kernel<K()>); });
     static LdsOptIn opt_f[4], opt_s[4];
     TGP_TRY(opt_f[kernel & 3].ensure(reinterpret_cast<const void *>(kf), c.device, SMALL_FIT_LDS));
     hipLaunchKernelGGL(kf, dim3((unsigned)T), dim3(256), SMALL_FIT_LDS, c.stream, reinterpret_cast<const SmallFitArgs *>(fit_args_dev));
@@ -1541,14 +1493,7 @@ hipError_t launch_mid_batch(Context &c, int kernel, const void *fit_args_dev, co
 
 hipError_t launch_small_batch(Context &c, int kernel, const void *fit_args_dev, const void *sweep_args_dev,
                               int64_t T, int64_t M, bool fit, bool sweep) {
-    void (*kf)(const SmallFitArgs *);
-    void (*ks)(const SmallSweepArgs *);
-    switch (kernel) {
-        case TGP_RBF: kf = small_fit_batch_kernel<TGP_RBF>; ks = small_sweep_batch_kernel<TGP_RBF>; break;
-        case TGP_MATERN12: kf = small_fit_batch_kernel<TGP_MATERN12>; ks = small_sweep_batch_kernel<TGP_MATERN12>; break;
-        case TGP_MATERN32: kf = small_fit_batch_kernel<TGP_MATERN32>; ks = small_sweep_batch_kernel<TGP_MATERN32>; break;
-        default: kf = small_fit_batch_kernel<TGP_MATERN52>; ks = small_sweep_batch_kernel<TGP_MATERN52>; break;
-    }
+    const auto [kf, ks] = by_kind(kernel, [](auto K) { return std::make_pair(small_fit_batch_kernel<K()>, small_sweep_batch_kernel<K()>); });
     static LdsOptIn opt_f[4], opt_s[4];
     if (fit) {
         TGP_TRY(opt_f[kernel & 3].ensure(reinterpret_cast<const void *>(kf), c.device, SMALL_FIT_LDS));

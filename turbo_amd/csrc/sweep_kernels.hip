@@ -742,12 +742,7 @@ static KstarFn<T> kstar_of_kind(Kstar which) {
 }
 template <typename T>
 static KstarFn<T> kstar_fn(int kernel, Kstar which) {
-    switch (kernel) {
-        case TGP_RBF: return kstar_of_kind<T, TGP_RBF>(which);
-        case TGP_MATERN12: return kstar_of_kind<T, TGP_MATERN12>(which);
-        case TGP_MATERN32: return kstar_of_kind<T, TGP_MATERN32>(which);
-        default: return kstar_of_kind<T, TGP_MATERN52>(which);
-    }
+    return by_kind(kernel, [which](auto K) { return kstar_of_kind<T, K()>(which); });
 }
 
 // THE launch of the cross-kernel: `rows` scaled candidates at `src` (a multiple of its candidate tile) against the training

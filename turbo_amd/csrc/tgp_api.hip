@@ -1457,6 +1457,28 @@ static int mes_check(Context &c, int acq, const char *fn) {
     return TGP_OK;
 }
 
+// the checks every entry that takes an acquisition makes, in the order they report.  acq_check: the acquisition is one of
+// NONE .. acq_max (with its maxima, if it is MES) and sf a sign; acq_check_args: a fitted model and the entry's own check
+// (`own`: its text when it failed, else null) in front of that.  An entry whose text for one of them differs reports that
+// one itself (through `own`, or in front of acq_check).
+static int acq_check(Context &c, const char *fn, int acq, int acq_max, double sf) {
+    if (acq < TGP_ACQ_NONE || acq > acq_max) return fail(c, TGP_BAD_ARG, std::string(fn) + ": unknown acquisition");
+    if (int mrc = mes_check(c, acq, fn); mrc != TGP_OK) return mrc;
+    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, std::string(fn) + ": sf must be +1 or -1");
+    return TGP_OK;
+}
+static int acq_check_args(Context &c, const char *fn, const char *own, int acq, int acq_max, double sf) {
+    if (!c.fitted) return fail(c, TGP_NOT_FITTED, std::string(fn) + ": no fitted model");
+    if (own) return fail(c, TGP_BAD_ARG, std::string(fn) + ": " + own);
+    return acq_check(c, fn, acq, acq_max, sf);
+}
+// the box of a gradient-stage entry: D lower and upper bounds
+static int box_check(Context &c, const char *fn, const double *lo, const double *hi) {
+    for (int64_t d = 0; d < c.D; ++d)
+        if (!(lo[d] <= hi[d])) return fail(c, TGP_BAD_ARG, std::string(fn) + ": need lo <= hi in every dimension");
+    return TGP_OK;
+}
+
 // the winner record is packed: what tgp_winner_wait makes another stream (RCCL's) wait for -- a polled call
 // returns without a stream synchronisation, so the ordering rests on this event
 static int winner_mark(Context &c, const SweepCall &s) {
@@ -1530,11 +1552,7 @@ int tgp_sweep(tgp_handle h, int acq, double sf, double incumbent, double param, 
     if (!h) return TGP_BAD_ARG;
     if (h->host) return h->host->sweep(acq, sf, incumbent, param, mu, sigma, acq_out, best_val, best_idx, n_clamped);
     Context &c = h->c;
-    if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_sweep: no fitted model");
-    if (!c.d_cand || c.M < 1) return fail(c, TGP_BAD_ARG, "tgp_sweep: no candidates set");
-    if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_MES) return fail(c, TGP_BAD_ARG, "tgp_sweep: unknown acquisition");
-    if (int mrc = mes_check(c, acq, "tgp_sweep"); mrc != TGP_OK) return mrc;
-    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_sweep: sf must be +1 or -1");
+    if (int arc = acq_check_args(c, "tgp_sweep", (!c.d_cand || c.M < 1) ? "no candidates set" : nullptr, acq, TGP_ACQ_MES, sf); arc != TGP_OK) return arc;
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
     SweepCall s;
     s.acq = acq; s.sf = sf; s.incumbent = incumbent; s.param = param;
@@ -1569,11 +1587,8 @@ int tgp_acq_grad(tgp_handle h, const double *Xq, int64_t m, int acq, double sf, 
     if (!h) return TGP_BAD_ARG;
     HOST_NA("tgp_acq_grad");
     Context &c = h->c;
-    if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_acq_grad: no fitted model");
-    if (!Xq || !val || !grad || m < 1 || m > 4096) return fail(c, TGP_BAD_ARG, "tgp_acq_grad: need Xq, val, grad and 1 <= m <= 4096");
-    if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_MES) return fail(c, TGP_BAD_ARG, "tgp_acq_grad: unknown acquisition");
-    if (int mrc = mes_check(c, acq, "tgp_acq_grad"); mrc != TGP_OK) return mrc;
-    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_acq_grad: sf must be +1 or -1");
+    const char *own = (!Xq || !val || !grad || m < 1 || m > 4096) ? "need Xq, val, grad and 1 <= m <= 4096" : nullptr;
+    if (int arc = acq_check_args(c, "tgp_acq_grad", own, acq, TGP_ACQ_MES, sf); arc != TGP_OK) return arc;
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
     API_HIP(pre_join(c), "hipStreamWaitEvent");
     // Round 6: a POLLED call when the batch fits the pinned staging -- the points are read from, value + gradient
@@ -1595,10 +1610,8 @@ int tgp_acq_grad(tgp_handle h, const double *Xq, int64_t m, int acq, double sf, 
         if (small_q) {
             le = launch_small_query(c, c.h_pin_in.dev(), (int)m, acq, sf, incumbent, param, o_val, o_grad, bell);
         } else {
-            const int64_t per = query_ws_doubles(c);   // launch_query's workspace
-            const int64_t need = m * (2 * D + 1) + m * per;     // (the layout of the copying path below, so both share d_qws)
-            API_MEM(grow(c, c.d_qws, (size_t)need * sizeof(double), "hipMalloc query workspace"));
-            le = launch_query(c, c.h_pin_in.dev(), (int)m, acq, sf, incumbent, param, c.d_qws + m * (2 * D + 1), o_val, o_grad, bell);
+            API_MEM(grow(c, c.d_qws, query_ws(c, (int)m).bytes, "hipMalloc query workspace"));
+            le = launch_query(c, c.h_pin_in.dev(), (int)m, acq, sf, incumbent, param, query_ws(c, (int)m).ws, o_val, o_grad, bell);   // (the layout of the copying path below, so both share d_qws)
         }
         if (le != hipSuccess) return hip_fail(c, le, "launch_query");
         int wrc = bell_wait(c, bell, "query sync");
@@ -1607,16 +1620,13 @@ int tgp_acq_grad(tgp_handle h, const double *Xq, int64_t m, int acq, double sf, 
         memcpy(grad, c.h_pin_out + 8 + m, (size_t)(m * D) * sizeof(double));
         return TGP_OK;
     }
-    // [Xq (m D) | val (m) | grad (m D) | workspace]
-    const int64_t per = query_ws_doubles(c);   // launch_query's workspace
-    const int64_t need = m * (2 * c.D + 1) + m * per;
-    API_MEM(grow(c, c.d_qws, (size_t)need * sizeof(double), "hipMalloc query workspace"));
-    double *d_Xq = c.d_qws, *d_val = d_Xq + m * c.D, *d_grad = d_val + m, *d_ws = d_grad + m * c.D;
-    API_HIP(hipMemcpyAsync(d_Xq, Xq, (size_t)(m * c.D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D Xq");
-    hipError_t le = launch_query(c, d_Xq, (int)m, acq, sf, incumbent, param, d_ws, d_val, d_grad);
+    API_MEM(grow(c, c.d_qws, query_ws(c, (int)m).bytes, "hipMalloc query workspace"));
+    const QueryWs q = query_ws(c, (int)m);
+    API_HIP(hipMemcpyAsync(q.Xq, Xq, (size_t)(m * c.D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D Xq");
+    hipError_t le = launch_query(c, q.Xq, (int)m, acq, sf, incumbent, param, q.ws, q.val, q.grad);
     if (le != hipSuccess) return hip_fail(c, le, "launch_query");
-    API_HIP(hipMemcpyAsync(val, d_val, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H val");
-    API_HIP(hipMemcpyAsync(grad, d_grad, (size_t)(m * c.D) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H grad");
+    API_HIP(hipMemcpyAsync(val, q.val, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H val");
+    API_HIP(hipMemcpyAsync(grad, q.grad, (size_t)(m * c.D) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H grad");
     API_HIP(hipStreamSynchronize(c.stream), "query sync");
     return TGP_OK;
 } TGP_CATCH
@@ -2193,12 +2203,10 @@ int tgp_sweep_topk(tgp_handle h, int acq, double sf, double incumbent, double pa
     if (!h) return TGP_BAD_ARG;
     HOST_NA("tgp_sweep_topk");
     Context &c = h->c;
-    if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_sweep_topk: no fitted model");
-    if (!c.d_cand || c.M < 1) return fail(c, TGP_BAD_ARG, "tgp_sweep_topk: no candidates set");
-    if (acq <= TGP_ACQ_NONE || acq > TGP_ACQ_MES) return fail(c, TGP_BAD_ARG, "tgp_sweep_topk: needs an acquisition");
-    if (int mrc = mes_check(c, acq, "tgp_sweep_topk"); mrc != TGP_OK) return mrc;
+    const char *own = (!c.d_cand || c.M < 1) ? "no candidates set"
+                      : (acq <= TGP_ACQ_NONE || acq > TGP_ACQ_MES) ? "needs an acquisition" : nullptr;
+    if (int arc = acq_check_args(c, "tgp_sweep_topk", own, acq, TGP_ACQ_MES, sf); arc != TGP_OK) return arc;
     if (k < 1 || k > 64 || !vals || !idxs) return fail(c, TGP_BAD_ARG, "tgp_sweep_topk: need 1 <= k <= 64, vals and idxs");
-    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_sweep_topk: sf must be +1 or -1");
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
     API_HIP(pre_join(c), "hipStreamWaitEvent");
     int rc = ensure_outputs(c, false, false, true);           // the (M,) acquisition vector stays on the device
@@ -2250,14 +2258,10 @@ int tgp_acq_refine(tgp_handle h, const double *X0, int64_t R, const double *lo, 
     if (!h) return TGP_BAD_ARG;
     HOST_NA("tgp_acq_refine");
     Context &c = h->c;
-    if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_acq_refine: no fitted model");
-    if (!X0 || !lo || !hi || !x_out || !val_out || R < 1 || R > 4096)
-        return fail(c, TGP_BAD_ARG, "tgp_acq_refine: need X0, lo, hi, x_out, val_out and 1 <= R <= 4096");
-    if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_SIGMA) return fail(c, TGP_BAD_ARG, "tgp_acq_refine: unknown acquisition");
-    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_acq_refine: sf must be +1 or -1");
+    const char *own = (!X0 || !lo || !hi || !x_out || !val_out || R < 1 || R > 4096) ? "need X0, lo, hi, x_out, val_out and 1 <= R <= 4096" : nullptr;
+    if (int arc = acq_check_args(c, "tgp_acq_refine", own, acq, TGP_ACQ_SIGMA, sf); arc != TGP_OK) return arc;
     if (max_iter < 1) return fail(c, TGP_BAD_ARG, "tgp_acq_refine: max_iter >= 1");
-    for (int64_t d = 0; d < c.D; ++d)
-        if (!(lo[d] <= hi[d])) return fail(c, TGP_BAD_ARG, "tgp_acq_refine: need lo <= hi in every dimension");
+    if (int brc = box_check(c, "tgp_acq_refine", lo, hi); brc != TGP_OK) return brc;
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
     API_HIP(pre_join(c), "hipStreamWaitEvent");
     const int64_t D = c.D, m = R;
@@ -2274,8 +2278,8 @@ int tgp_acq_refine(tgp_handle h, const double *X0, int64_t R, const double *lo, 
         CallClock clk;
         if ((prc = call_begin(c, clk)) != TGP_OK) return prc;
         hipError_t le = launch_small_refine(c, c.h_pin_in.dev(), c.h_pin_in.dev() + R * D, c.h_pin_in.dev() + R * D + D, (int)R, acq, sf,
-                                            incumbent, param, (int)std::min<int64_t>(max_iter, 1 << 30), 1e-5,
-                                            2.220446049250313e-09, o_x, o_v, o_info);
+                                            incumbent, param, (int)std::min<int64_t>(max_iter, 1 << 30), LBFGSB_PGTOL,
+                                            LBFGSB_FTOL, o_x, o_v, o_info);
         if (le != hipSuccess) return hip_fail(c, le, "launch_small_refine");
         if ((prc = call_finish(c, clk, c.last_sweep_ms, "refine sync")) != TGP_OK) return prc;
         const double *h_x = c.h_pin_out + 8, *h_v = h_x + R * D, *h_info = h_v + R;
@@ -2289,10 +2293,7 @@ int tgp_acq_refine(tgp_handle h, const double *X0, int64_t R, const double *lo, 
         if (iterations) *iterations = ev;      // evaluations of the slowest restart (what the lock-step path counts)
         return TGP_OK;
     }
-    // query workspace as tgp_acq_grad: [Xq (m D) | val (m) | grad (m D) | workspace]
-    const int64_t per = query_ws_doubles(c);
-    const int64_t need = m * (2 * D + 1) + m * per;
-    API_MEM(grow(c, c.d_qws, (size_t)need * sizeof(double), "hipMalloc query workspace"));
+    API_MEM(grow(c, c.d_qws, query_ws(c, (int)m).bytes, "hipMalloc query workspace"));   // as tgp_acq_grad
     // optimiser state: [state (R stride) | history of the eight-wave teams (D > 1024) | lo (D) | hi (D) | x_out (R D) |
     //                   v_out (R) | info (2 R) | active (int)]
     const int64_t stride = refine_state_stride((int)D);
@@ -2300,7 +2301,8 @@ int tgp_acq_refine(tgp_handle h, const double *X0, int64_t R, const double *lo, 
     const size_t rf_need = (size_t)(R * stride + hist + 2 * D + R * D + R + 2 * R + 2) * sizeof(double);
     int rc = grow(c, c.d_rf, rf_need, "hipMalloc refine state");
     if (rc != TGP_OK) return rc;
-    double *d_Xq = c.d_qws, *d_val = d_Xq + m * D, *d_grad = d_val + m, *d_ws = d_grad + m * D;
+    const QueryWs q = query_ws(c, (int)m);
+    double *d_Xq = q.Xq, *d_val = q.val, *d_grad = q.grad, *d_ws = q.ws;
     double *d_state = c.d_rf, *d_lo = d_state + R * stride + hist, *d_hi = d_lo + D, *d_xo = d_hi + D;
     double *d_vo = d_xo + R * D, *d_info = d_vo + R;
     int *d_active = reinterpret_cast<int *>(d_info + 2 * R);
@@ -2321,8 +2323,8 @@ int tgp_acq_refine(tgp_handle h, const double *X0, int64_t R, const double *lo, 
         const bool fused = true;
         le = launch_query(c, d_Xq, (int)m, acq, sf, incumbent, param, d_ws, fused ? nullptr : d_val, d_grad);
         if (le != hipSuccess) return hip_fail(c, le, "launch_query");
-        le = launch_refine_step(c, d_state, d_Xq, d_val, d_grad, d_lo, d_hi, (int)R, (int)it, 1e-5, 2.220446049250313e-09, d_active,
-                                fused ? query_red(c, d_ws, (int)m) : nullptr, acq, sf, incumbent, param);
+        le = launch_refine_step(c, d_state, d_Xq, d_val, d_grad, d_lo, d_hi, (int)R, (int)it, LBFGSB_PGTOL, LBFGSB_FTOL, d_active,
+                                fused ? q.red : nullptr, acq, sf, incumbent, param);
         if (le != hipSuccess) return hip_fail(c, le, "launch_refine_step");
         if ((it & 3) == 3 || it == max_iter) {
             API_HIP(hipMemcpyAsync(&active, d_active + (it & 1), sizeof(int), hipMemcpyDeviceToHost, c.stream), "D2H active");
@@ -2343,7 +2345,7 @@ int tgp_acq_refine(tgp_handle h, const double *X0, int64_t R, const double *lo, 
     return TGP_OK;
 } TGP_CATCH
 
-// The gradient stage as the reference runs it -- scipy.optimize.minimize(method='L-BFGS-B', maxiter = 15000) on the
+// The gradient stage as the reference runs it -- scipy.optimize.minimize(method='L-BFGS-B', default limits) on the
 // negated acquisition from every start (turbo/modules/auxiliary_optimisers.py:80-99) -- inside the library: one
 // host_lbfgsb.hpp optimiser per restart, all of them in LOCK-STEP on the calling thread (reverse communication needs no
 // threads): every round gathers the trial points of the restarts still running, ONE batched closed-form value +
@@ -2356,16 +2358,11 @@ int tgp_acq_lbfgsb(tgp_handle h, const double *X0, int64_t R, const double *lo, 
     if (!h) return TGP_BAD_ARG;
     HOST_NA("tgp_acq_lbfgsb");
     Context &c = h->c;
-    if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_acq_lbfgsb: no fitted model");
-    if (!X0 || !lo || !hi || !x_out || !val_out || R < 1 || R > 4096)
-        return fail(c, TGP_BAD_ARG, "tgp_acq_lbfgsb: need X0, lo, hi, x_out, val_out and 1 <= R <= 4096");
-    if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_MES) return fail(c, TGP_BAD_ARG, "tgp_acq_lbfgsb: unknown acquisition");
-    if (int mrc = mes_check(c, acq, "tgp_acq_lbfgsb"); mrc != TGP_OK) return mrc;
-    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_acq_lbfgsb: sf must be +1 or -1");
+    const char *own = (!X0 || !lo || !hi || !x_out || !val_out || R < 1 || R > 4096) ? "need X0, lo, hi, x_out, val_out and 1 <= R <= 4096" : nullptr;
+    if (int arc = acq_check_args(c, "tgp_acq_lbfgsb", own, acq, TGP_ACQ_MES, sf); arc != TGP_OK) return arc;
     if (max_iter < 1) return fail(c, TGP_BAD_ARG, "tgp_acq_lbfgsb: max_iter >= 1");
+    if (int brc = box_check(c, "tgp_acq_lbfgsb", lo, hi); brc != TGP_OK) return brc;
     const int D = (int)c.D;
-    for (int d = 0; d < D; ++d)
-        if (!(lo[d] <= hi[d])) return fail(c, TGP_BAD_ARG, "tgp_acq_lbfgsb: need lo <= hi in every dimension");
     std::vector<HostLbfgsb> opts;
     opts.reserve((size_t)R);
     std::vector<std::vector<double>> xt((size_t)R, std::vector<double>((size_t)D));
@@ -2385,11 +2382,8 @@ int tgp_acq_lbfgsb(tgp_handle h, const double *X0, int64_t R, const double *lo, 
         for (int64_t r = 0; r < R; ++r) {
             if (!live[(size_t)r]) continue;
             HostLbfgsb &o = opts[(size_t)r];
-            while (live[(size_t)r] && started[(size_t)r] && o.evaluated(xt[(size_t)r])) {
-                gt = o.g_eval;
-                o.step(xt[(size_t)r], gt, o.f_eval, false, 1e-5, 2.220446049250313e-09);
-                if (o.status != 0 || o.iters >= max_iter || ++rounds[(size_t)r] >= 15000) { live[(size_t)r] = 0; --n_live; }
-            }
+            while (live[(size_t)r] && o.step_from_cache(xt[(size_t)r]))
+                if (o.status != 0 || o.iters >= max_iter || ++rounds[(size_t)r] >= LBFGSB_MAXFUN) { live[(size_t)r] = 0; --n_live; }
             if (!live[(size_t)r]) continue;
             memcpy(&Xq[(size_t)(m * D)], xt[(size_t)r].data(), (size_t)D * sizeof(double));
             who[(size_t)m++] = r;
@@ -2402,9 +2396,9 @@ int tgp_acq_lbfgsb(tgp_handle h, const double *X0, int64_t R, const double *lo, 
             const int64_t r = who[(size_t)i];
             HostLbfgsb &o = opts[(size_t)r];
             for (int d = 0; d < D; ++d) gt[(size_t)d] = -grad[(size_t)(i * D + d)];     // maximise = minimise the negation
-            o.step(xt[(size_t)r], gt, -val[(size_t)i], !started[(size_t)r], 1e-5, 2.220446049250313e-09);
+            o.step(xt[(size_t)r], gt, -val[(size_t)i], !started[(size_t)r]);
             started[(size_t)r] = 1;
-            if (o.status != 0 || o.iters >= max_iter || ++rounds[(size_t)r] >= 15000) { live[(size_t)r] = 0; --n_live; }
+            if (o.status != 0 || o.iters >= max_iter || ++rounds[(size_t)r] >= LBFGSB_MAXFUN) { live[(size_t)r] = 0; --n_live; }
         }
     }
     for (int64_t r = 0; r < R; ++r) {
@@ -2477,13 +2471,11 @@ static int fit_optimise_streams(tgp_handle h, const double *X, int64_t N, int64_
             HostLbfgsb opt(lo_f.data(), hi_f.data(), Pf);
             for (int k = 0; k < Pf; ++k) xt[(size_t)k] = th[(size_t)fr[(size_t)k]];
             // max_iter bounds ACCEPTED iterations (opt.iters), as in the one-launch path and as SciPy's maxiter does;
-            // the line searches' trial evaluations have a cap of their own, SciPy's maxfun = 15000 (round-4 advisor:
+            // the line searches' trial evaluations have a cap of their own, SciPy's maxfun (LBFGSB_MAXFUN; round-4 advisor:
             // every trial used to count against max_iter, so an ARD fit could stop early with status 0)
             int64_t it = 0;
-            for (; opt.iters < max_iter && it < 15000; ++it) {
-                if (it > 0 && opt.evaluated(xt)) {      // the search's best point once more: answered from the last evaluation
-                    gt = opt.g_eval;
-                    opt.step(xt, gt, opt.f_eval, false, 1e-5, 2.220446049250313e-09);
+            for (; opt.iters < max_iter && it < LBFGSB_MAXFUN; ++it) {
+                if (opt.step_from_cache(xt)) {      // the search's best point once more: answered from the last evaluation
                     if (opt.status != 0) break;
                     continue;
                 }
@@ -2510,7 +2502,7 @@ static int fit_optimise_streams(tgp_handle h, const double *X, int64_t N, int64_
                     opt.status = 1;
                     break;
                 }
-                opt.step(xt, gt, phit, it == 0, 1e-5, 2.220446049250313e-09);   // SciPy's L-BFGS-B defaults: pgtol, factr 1e7 x eps
+                opt.step(xt, gt, phit, it == 0);
                 if (opt.status != 0) break;
             }
             status[(size_t)s] = opt.status;
@@ -2672,8 +2664,7 @@ int tgp_sweep_integrated(tgp_handle h, const double *X, int64_t N, int64_t D, co
     if (D < 1 || (n_ls != 1 && n_ls != D)) return fail(c, TGP_BAD_ARG, "tgp_sweep_integrated: n_ls must be 1 or D");
     if (acq == TGP_ACQ_MES)
         return fail(c, TGP_BAD_ARG, "tgp_sweep_integrated: TGP_ACQ_MES is not integrated (its maxima belong to one fit)");
-    if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_SIGMA) return fail(c, TGP_BAD_ARG, "tgp_sweep_integrated: unknown acquisition");
-    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_sweep_integrated: sf must be +1 or -1");
+    if (int arc = acq_check(c, "tgp_sweep_integrated", acq, TGP_ACQ_SIGMA, sf); arc != TGP_OK) return arc;
     if (!c.d_cand || c.M < 1 || c.D != D)
         return fail(c, TGP_BAD_ARG, "tgp_sweep_integrated: no candidates set for this D (tgp_set_candidates* after a fit with the same D)");
     API_HIP(hipSetDevice(c.device), "hipSetDevice");
@@ -2750,11 +2741,7 @@ int tgp_evaluate(tgp_handle h, const double *Xc, int64_t M, int acq, double sf, 
         return rc != TGP_OK ? rc : h->host->sweep(acq, sf, incumbent, param, mu, sigma, acq_out, best_val, best_idx, n_clamped);
     }
     Context &c = h->c;
-    if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_evaluate: no fitted model");
-    if (!Xc || M < 1) return fail(c, TGP_BAD_ARG, "tgp_evaluate: need Xc and M >= 1");
-    if (acq < TGP_ACQ_NONE || acq > TGP_ACQ_MES) return fail(c, TGP_BAD_ARG, "tgp_evaluate: unknown acquisition");
-    if (int mrc = mes_check(c, acq, "tgp_evaluate"); mrc != TGP_OK) return mrc;
-    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_evaluate: sf must be +1 or -1");
+    if (int arc = acq_check_args(c, "tgp_evaluate", (!Xc || M < 1) ? "need Xc and M >= 1" : nullptr, acq, TGP_ACQ_MES, sf); arc != TGP_OK) return arc;
     const size_t in_bytes = (size_t)M * (size_t)c.D * sizeof(double);
     // (the one question about the kernel family: only the one-workgroup / one-launch kernels write their outputs straight
     // into mapped host memory)

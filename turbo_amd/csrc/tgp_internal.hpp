@@ -4,6 +4,8 @@
 #include <stdint.h>
 
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/turbogp.h"
@@ -26,6 +28,19 @@ constexpr int CONTRACT_MIN_WGS = 512;   // a gathered set's contraction takes th
 constexpr int GATHER_KS_MIN_WGS = 256;   // ... and its cross-kernel splits the training points until its grid has one workgroup per CU (it writes no mupart row: KS_JS does not bind it)
 constexpr int SCREEN_MIN_WGS = 1024;    // ... and the screen in front of it (prune_screen.hpp; 128 candidates per workgroup, two workgroups per CU)
 constexpr int BOUND_MIN_WGS = 2048;     // the bound pass splits the training points only as far as its grid needs to reach this many workgroups
+
+// THE dispatch on the covariance kind: f(std::integral_constant<int, KIND>{}) for the handle's kind, anything that is not
+// one of the first three being Matern-5/2.  A launcher picks its kernel's instance with it and launches that once:
+//     auto k = by_kind(c.kernel, [](auto K) { return small_fit_kernel<K()>; });
+template <class F>
+inline auto by_kind(int kernel, F &&f) {
+    switch (kernel) {
+        case TGP_RBF: return f(std::integral_constant<int, TGP_RBF>{});
+        case TGP_MATERN12: return f(std::integral_constant<int, TGP_MATERN12>{});
+        case TGP_MATERN32: return f(std::integral_constant<int, TGP_MATERN32>{});
+        default: return f(std::integral_constant<int, TGP_MATERN52>{});
+    }
+}
 
 struct ProfSeg { int a, b, kind; double flops; };   // pooled events a -> b bracket one launch; kind: 0 trmm, 1 kstar, 2 the pruned sweep's screen (counted apart: screen_ms); flops: the contraction's algorithmic flops of that launch (a launch a fit took row tiles of has fewer)
 
@@ -210,8 +225,15 @@ hipError_t launch_small_grad(Context &c, bool ard, double *out);
 hipError_t launch_query(Context &c, const double *d_Xq, int m, int acq, double sf, double incumbent,
                         double param, double *d_ws, double *d_val, double *d_grad,   // d_val == nullptr: the sums only
                         const Bell &bell = Bell{nullptr, 0, nullptr});   // bell.word != null: value + gradient formed by the reduction's last workgroup, which rings it (d_Xq / d_val / d_grad may then be device-mapped host memory)
-int64_t query_ws_doubles(const Context &c);   // doubles of d_ws per query point
-double *query_red(const Context &c, double *d_ws, int m);   // per query point [k.alpha, v.v, gm (D), gv (D)]
+// c.d_qws as tgp_acq_grad and tgp_acq_refine use it for m points, laid out in ONE place (query_kernels.hip):
+// [Xq (m D) | val (m) | grad (m D) | up to 3 doubles of padding | launch_query's workspace]
+struct QueryWs {
+    size_t bytes;                  // what c.d_qws has to hold
+    double *Xq, *val, *grad;       // the entry's points and results
+    double *ws;                    // launch_query's d_ws: 32-byte aligned for every m (its kernels load 2 and 4 doubles at once)
+    double *red;                   // ... and in it, per query point, [k.alpha, v.v, gm (D), gv (D)]
+};
+QueryWs query_ws(const Context &c, int m);   // the pointers are into c.d_qws as it is: take them once it holds `bytes`
 hipError_t launch_gen_candidates(Context &c, double *dst, int64_t M, unsigned long long seed,
                                  unsigned long long first_candidate, const double *d_lo,
                                  const double *d_hi);

@@ -428,16 +428,6 @@ __global__ __launch_bounds__(256) void ts_eval_kernel(TsEval p) {
 }
 
 // ---- launchers ----
-#define TS_KIND_DISPATCH(kernel_tmpl, grid, block, shmem, ...)                                                              \
-    do {                                                                                                                  \
-        switch (c.kernel) {                                                                                               \
-            case TGP_RBF: hipLaunchKernelGGL(kernel_tmpl<TGP_RBF>, grid, block, shmem, c.stream, __VA_ARGS__); break;      \
-            case TGP_MATERN12: hipLaunchKernelGGL(kernel_tmpl<TGP_MATERN12>, grid, block, shmem, c.stream, __VA_ARGS__); break; \
-            case TGP_MATERN32: hipLaunchKernelGGL(kernel_tmpl<TGP_MATERN32>, grid, block, shmem, c.stream, __VA_ARGS__); break; \
-            default: hipLaunchKernelGGL(kernel_tmpl<TGP_MATERN52>, grid, block, shmem, c.stream, __VA_ARGS__); break;      \
-        }                                                                                                                 \
-    } while (0)
-
 int ts_spad(int64_t S) { return S <= 16 ? 16 : (S <= 32 ? 32 : 64); }
 
 hipError_t launch_ts_pass(Context &c, const TsDraw &t, const double *P, int64_t rows, bool update, double *out,
@@ -448,7 +438,7 @@ hipError_t launch_ts_pass(Context &c, const TsDraw &t, const double *P, int64_t 
     p.Xs = c.d_Xs; p.V = t.V; p.N = update ? (int)c.N : 0; p.Np = (int)c.Np; p.Dp = (int)c.Dp; p.constant = c.constant;
     p.out = out; p.S = (int)t.S; p.o0 = o0; p.o1 = o1;
     const dim3 grid((unsigned)((rows + TS_CT - 1) / TS_CT), (unsigned)(ts_spad(t.S) / 16));
-    TS_KIND_DISPATCH(ts_pass_kernel, grid, dim3(256), 0, p);
+    hipLaunchKernelGGL(by_kind(c.kernel, [](auto K) { return ts_pass_kernel<K()>; }), grid, dim3(256), 0, c.stream, p);
     return hipGetLastError();
 }
 
@@ -514,7 +504,7 @@ hipError_t launch_ts_eval(Context &c, const TsDraw &t, const double *Xq, int m, 
     p.pscale = sqrt(2.0 * c.constant / (double)t.F); p.constant = c.constant; p.y_mean = c.y_mean; p.y_std = c.y_std;
     p.fout = fout; p.gout = gout;
     const size_t sh = ts_eval_lds_bytes(c, t.S);
-    TS_KIND_DISPATCH(ts_eval_kernel, dim3((unsigned)m), dim3(256), sh, p);
+    hipLaunchKernelGGL(by_kind(c.kernel, [](auto K) { return ts_eval_kernel<K()>; }), dim3((unsigned)m), dim3(256), sh, c.stream, p);
     return hipGetLastError();
 }
 
