@@ -1269,223 +1269,12 @@ __global__ __launch_bounds__(256) void zero_fill_kernel(double2 *__restrict__ p,
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n2; i += (long)gridDim.x * 256) p[i] = z;
 }
 
-// ---- the two streams of a device ----------------------------------------------------------
-// ONE pair per device for the whole process, shared by every handle on that device: the main
-// stream (every call runs on it, in order) and the background stream of the fit (the inverse
-// factor's GEMMs behind the panel chain), confined to a subset of the CUs (TGP_BG_CUS of the
-// 256) so that the chain's small launches always find free CUs.
-// Why shared: whether two hardware queues really run side by side depends on where the driver
-// puts them.  With a stream pair per handle, every few handles one pair ended up time-sliced
-// instead of concurrent and its fit took twice as long (N = 1000: 0.51 -> 1.1-1.3 ms in the
-// ninth live handle; every CU-masked stream is a hardware queue of its own).  One pair, probed
-// once: probe_wait spins (bounded, 300 us) on the main stream for a flag that probe_set raises
-// from the background stream; if it times out the two are serialised and the background stream
-// is created again (another queue), at most three times.
-// The calls of this library are synchronous, so handles sharing a stream lose nothing but the
-// overlap of two threads' calls on one device.
-__global__ void probe_wait_kernel(int *flag, int *result, long long max_ticks) {
-    const long long t0 = (long long)__builtin_readcyclecounter();
-    int seen = 0;
-    while (!(seen = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) &&
-           (long long)__builtin_readcyclecounter() - t0 < max_ticks)
-        __builtin_amdgcn_s_sleep(32);
-    *result = seen;
-}
-__global__ void probe_set_kernel(int *flag) { __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+}  // namespace tgp
 
-static hipError_t create_bg_stream(int device, hipStream_t *out, int cus_env, int cu0 = 0) {
-    // measured at N = 4096 on the 256-CU part: 2.50 ms with 192 CUs, 2.55 with 224, 2.61 with 128, 2.66 unmasked
-    // -> three quarters of whatever this device (or partition: CPX / DPX modes expose fewer CUs per
-    // device) reports, unless TGP_BG_CUS names a count; 0 or >= the device's count = unmasked
-    const int bg_env = cus_env;
-    int ncu = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu <= 0) {
-        (void)hipGetLastError();
-        ncu = 0;
-    }
-    const int bg_cus = bg_env >= 0 ? bg_env : (ncu * 3) / 4;
-    hipStream_t st = nullptr;
-    if (bg_cus > 0 && bg_cus < ncu) {
-        std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
-        for (int i = 0; i < bg_cus; ++i) {
-            const int cu = (cu0 + i) % ncu;
-            mask[(size_t)(cu >> 5)] |= 1u << (cu & 31);
-        }
-        if (hipExtStreamCreateWithCUMask(&st, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
-            (void)hipGetLastError();
-            st = nullptr;
-        }
-    }
-    if (!st) TGP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    *out = st;
-    return hipSuccess;
-}
+// the streams of a device (device_streams, private_fit_begin / _end, ensure_lookahead): part of this translation unit
+#include "fit_streams.hpp"
 
-// Round 6, measured and NOT kept: the XCD of the pivot workgroup out of the background / third streams' masks.  Stamps of
-// the panel chain with the pivot workgroup's HW_ID (profiles/r06_pivot_cu_stamps.txt): workgroup 0 of every launch on a
-// stream lands on ONE XCD (the dispatcher deals a launch's workgroups round-robin over the XCDs from a start that is fixed
-// per queue), on any of its 32 CUs; the mask of bits [0, 192) covers 24 CUs of every XCD (bit i = XCD i mod 8, CU i / 8 of
-// it); and every panel of five fits whose factor phase took 19-29 us instead of 11 had its pivot workgroup on a CU the
-// background stream's GEMMs run on -- none of those on the other CUs did.  The cause, then; but no mask cures it: an XCD
-// with NO bit set comes back fully enabled, and with ONE CU left in it an eighth of every background launch's
-// workgroups -- they are dealt over the XCDs whatever each has to offer -- queue on that CU (fit at N = 4096: 12.6 ms
-// instead of 2.15; tools/microbench/cu_mask_probe.hip, profiles/r06_pivot_cu_stamps.txt).  Masks have to leave every XCD
-// the same number of CUs; which of an XCD's CUs the pivot workgroup gets is the dispatcher's choice.
-
-// 1 = the two streams overlap, 0 = serialised
-static hipError_t streams_overlap(hipStream_t main, hipStream_t bg, int *overlap) {
-    int *d = nullptr;
-    TGP_TRY(hipMalloc((void **)&d, 2 * sizeof(int)));
-    hipError_t e = hipMemsetAsync(d, 0, 2 * sizeof(int), main);
-    if (e == hipSuccess) e = hipStreamSynchronize(main);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(probe_wait_kernel, dim3(1), dim3(1), 0, main, d, d + 1, 700000LL);   // ~300 us of shader clocks
-        hipLaunchKernelGGL(probe_set_kernel, dim3(1), dim3(1), 0, bg, d);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(main);
-    if (e == hipSuccess) e = hipStreamSynchronize(bg);
-    int h[2] = {0, 0};
-    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    *overlap = h[1];
-    return e;
-}
-
-// The pair lives while a handle on the device does (tgp_create takes a reference, tgp_destroy
-// drops it) and whatever is left is destroyed by an atexit handler, i.e. before the HIP
-// runtime's own tear-down: a CU-masked stream still alive in the static destructors crashed
-// rocprofv3 runs at exit.
-namespace {
-struct StreamPair { hipStream_t main = nullptr, bg = nullptr, pre = nullptr; bool pre_failed = false; int refs = 0;
-                    int bg_ok = -1, pre_ok = -1; };   // what the probes said: 1 runs beside the main stream, 0 serialised, -1 not probed
-std::mutex g_pair_mu;
-StreamPair g_pairs[64];
-// the background stream on loan to the fit of a private-stream handle (below)
-std::atomic<bool> g_bg_on_loan[64];
-std::atomic<int> g_private_fits[64];
-bool g_pair_atexit = false;
-
-void destroy_pair(int dev) {   // g_pair_mu held
-    StreamPair &p = g_pairs[dev];
-    if (!p.main && !p.bg && !p.pre) return;
-    if (hipSetDevice(dev) == hipSuccess) {
-        if (p.pre) { (void)hipStreamSynchronize(p.pre); (void)hipStreamDestroy(p.pre); }
-        if (p.bg) { (void)hipStreamSynchronize(p.bg); (void)hipStreamDestroy(p.bg); }
-        if (p.main) { (void)hipStreamSynchronize(p.main); (void)hipStreamDestroy(p.main); }
-    }
-    p.main = p.bg = p.pre = nullptr;
-    p.pre_failed = false;
-}
-void destroy_all_pairs() {
-    std::lock_guard<std::mutex> lock(g_pair_mu);
-    for (int d = 0; d < 64; ++d) destroy_pair(d);
-}
-}  // namespace
-
-// The device's background stream on loan to the fit of a handle on a PRIVATE stream (the workers of a hyper-parameter
-// fit).  Such a fit runs its share of the inverse in line, because the device has ONE background stream and inverses of
-// several fits queued on it wait for each other -- but a fit that is the only private-stream fit in flight (the last
-// start of a hyper-parameter fit still running, a lone worker) can have that stream to itself: it then issues the
-// launches a handle on the shared stream issues (same bits), the inverse behind the panel chain (an evaluation at
-// N = 1000: 0.72 -> 0.57 ms, what the caller's handle takes).  Only when alone: with one holder and one fit in line both
-// lose (0.84 / 1.18 ms against 0.785 / 0.785 both in line); and more background streams, one per worker, were measured
-// too (round 5: two workers 0.64 / 0.64, but with three two of them ran one behind the other, 1.31 / 0.65 / 1.31, whatever
-// GPU_MAX_HW_QUEUES said) -- not kept.  private_fit_begin returns the stream on loan or null; never blocks.
-hipStream_t private_fit_begin(int device, bool may_borrow) {
-    if (device < 0 || device >= 64) return nullptr;
-    const int in_flight = ++g_private_fits[device];
-    if (!may_borrow || in_flight != 1) return nullptr;
-    bool expected = false;
-    if (!g_bg_on_loan[device].compare_exchange_strong(expected, true)) return nullptr;
-    hipStream_t bg = nullptr;
-    if (device_streams(device, nullptr, &bg) == hipSuccess && bg) return bg;
-    (void)hipGetLastError();
-    g_bg_on_loan[device].store(false);
-    return nullptr;
-}
-void private_fit_end(int device, bool held) {
-    if (device < 0 || device >= 64) return;
-    if (held) g_bg_on_loan[device].store(false);
-    --g_private_fits[device];
-}
-
-// main != null: take a reference (tgp_create); bg != null: the background stream.
-// BOTH streams are created together, at the first call (round 4).  The runtime deals its streams round-robin
-// onto a fixed number of hardware queues (4 per process unless GPU_MAX_HW_QUEUES says otherwise) and never
-// re-deals: a background stream created later, as the 5th stream of the process behind three private streams
-// of a threaded hyper-parameter fit (tgp_set_private_stream), landed on the MAIN stream's queue, the inverse
-// ran after the panel chain instead of beside it, and every fit of the process took twice as long from then
-// on (N = 2048: 1.00 -> 2.02 ms; tools/ab_private_streams.py reproduces it, and shows it gone with 8 queues).
-// Created back to back the two always sit on neighbouring queues, whatever was created before them.
-// Round 5: a THIRD stream of the set, created with the other two -- the front of the next sweep inside a fit
-// (tgp_set_overlap): candidate scaling, the first cross-kernel, the contraction's early row tiles.  CU-masked like the
-// background stream (TGP_PRE_CUS), so the panel chain's small launches keep a quarter of the device to themselves.
-hipError_t device_streams(int device, hipStream_t *main, hipStream_t *bg, hipStream_t *pre) {
-    std::lock_guard<std::mutex> lock(g_pair_mu);
-    StreamPair &p = g_pairs[device & 63];
-    if (!g_pair_atexit) { g_pair_atexit = true; atexit(destroy_all_pairs); }
-    if (!p.main) TGP_TRY(hipStreamCreateWithFlags(&p.main, hipStreamNonBlocking));
-    const bool probe = tuning().bg_probe != 0;
-
-    if (!p.bg) {
-        for (int attempt = 0; attempt < 3; ++attempt) {
-            hipStream_t st = nullptr;
-            TGP_TRY(create_bg_stream(device, &st, tuning().bg_cus));
-            int ok = 1;
-            if (probe) TGP_TRY(streams_overlap(p.main, st, &ok));
-            if (ok || attempt == 2) { p.bg = st; p.bg_ok = probe ? ok : -1; break; }
-            (void)hipStreamDestroy(st);
-        }
-    }
-    if (!p.pre && !p.pre_failed) {
-        // the third stream has to run beside BOTH others: on a process with too few hardware queues (GPU_MAX_HW_QUEUES,
-        // 4 by default; turbo_amd/_lib.py asks for 8 before the runtime initialises) it can land on the main stream's
-        // queue, and a sweep front "inside" the fit would then simply lengthen it.  Probed like the background stream;
-        // if no attempt overlaps, the device has no third stream and tgp_set_overlap is a no-op on it.
-        for (int attempt = 0; attempt < 3 && !p.pre; ++attempt) {
-            hipStream_t st = nullptr;
-            TGP_TRY(create_bg_stream(device, &st, tuning().pre_cus, tuning().pre_cu0));
-            int ok1 = 1, ok2 = 1;
-            if (probe) {
-                TGP_TRY(streams_overlap(p.main, st, &ok1));
-                TGP_TRY(streams_overlap(p.bg, st, &ok2));
-            }
-            if (ok1 && ok2) { p.pre = st; p.pre_ok = probe ? 1 : -1; break; }
-            (void)hipStreamDestroy(st);
-        }
-        if (!p.pre) { p.pre_failed = true; p.pre_ok = 0; }
-    }
-    if (main) { *main = p.main; ++p.refs; }
-    if (bg) *bg = p.bg;
-    if (pre) *pre = p.pre;
-    return hipSuccess;
-}
-
-// what the probes of the device's shared streams said when they were created (tgp_stream_status)
-void device_stream_status(int device, int *bg_ok, int *pre_ok) {
-    std::lock_guard<std::mutex> lock(g_pair_mu);
-    const StreamPair &p = g_pairs[device & 63];
-    if (bg_ok) *bg_ok = p.bg_ok;
-    if (pre_ok) *pre_ok = p.pre_ok;
-}
-
-// tgp_destroy: the last handle on a device takes the pair with it
-void device_streams_release(int device) {
-    std::lock_guard<std::mutex> lock(g_pair_mu);
-    StreamPair &p = g_pairs[device & 63];
-    if (p.refs > 0 && --p.refs == 0) destroy_pair(device & 63);
-}
-
-static hipError_t ensure_lookahead(Context &c, size_t nev) {
-    if (!c.stream_bg) TGP_TRY(device_streams(c.device, nullptr, &c.stream_bg, &c.stream_pre));
-    while (c.ev_la.size() < nev) {
-        Ev e;
-        TGP_TRY(e.create(hipEventDisableTiming));   // (hipEventDisableSystemFence on top: 2.49 vs 2.51 ms, not worth the weaker visibility)
-        c.ev_la.push_back(std::move(e));
-    }
-    return hipSuccess;
-}
+namespace tgp {
 
 // First launch of a fit: Linv = 0, the pivot flag and the two scalars = 0, and -- when the inputs
 // were staged in device-mapped host memory (src = [Xs | yn | ls]) -- their copy into HBM, so that a
@@ -1524,463 +1313,7 @@ hipError_t launch_ring(Context &c, const Bell &bell) {
     return hipGetLastError();
 }
 
-hipError_t launch_fit(Context &c, const double *staged_in, double *res_host, bool zero_linv, unsigned long long *start_stamp) {
-    hipStream_t s = c.stream;
-    const int N = (int)c.N, Np = (int)c.Np, Dp = (int)c.Dp;
-    const long NN = (long)Np * Np;
-
-    {
-        long blocks = NN / 2 / 256;
-        if (blocks > 4096) blocks = 4096;
-        // Linv = 0: only when something other than zeros can sit above the diagonal or in the rows this fit
-        // skips (a fresh allocation, another leading dimension, an older fit with more rows): everything on
-        // and below the diagonal of the rows it does not skip is written by this fit anyway (27 us at Np = 4096,
-        // 96 us at 8192 when it has to run)
-        if (!zero_linv) blocks = std::min<long>(blocks, std::max<long>(1, ((long)Np * Dp + 255) / 256));
-        hipLaunchKernelGGL(fit_prologue_kernel, dim3((unsigned)blocks), dim3(256), 0, s,
-                           reinterpret_cast<double2 *>(c.d_Linv.get()), zero_linv ? NN / 2 : 0L, staged_in, c.d_Xs, (long)Np * Dp,
-                           c.d_yn, (long)Np, c.d_ls, (long)c.D, Dp, c.d_flag, c.d_scal, start_stamp);
-        TGP_TRY(hipGetLastError());
-    }
-
-    // the f32 copy of Xs right away (it used to be the fit's last launch): the cross-kernel of an f32 sweep that
-    // starts inside this fit reads it
-    if (c.dtype != TGP_F64) {
-        hipLaunchKernelGGL(f64_to_f32_kernel, dim3(64), dim3(256), 0, s, c.d_Xs, c.d_Xs32,
-                           (long)Np * Dp);
-        TGP_TRY(hipGetLastError());
-    }
-    // ---- the front of the next sweep, beside everything that follows (tgp_set_overlap; sweep_kernels.hip) ----
-    hipStream_t spre = nullptr;
-    int pre_budget128 = 0;
-    if (c.pre.issue > 0) {
-        if (!c.stream_pre) TGP_TRY(device_streams(c.device, nullptr, &c.stream_bg, &c.stream_pre));
-        spre = c.stream_pre;   // (null: this process has no hardware queue left for a third stream -- no front)
-    }
-    if (spre) {
-        TGP_TRY(hipEventRecord(c.pre.ev_in, s));
-        TGP_TRY(hipStreamWaitEvent(spre, c.pre.ev_in, 0));
-        TGP_TRY(presweep_front(c, spre));
-        if (c.pre.issue >= 2 && c.pre.front) {
-            // how many 128-row tiles of launch pair 0 the fit takes: a quarter of the rows unless TGP_PRE_TILES says otherwise
-            const int n128 = (N + 127) / 128;
-            pre_budget128 = tuning().pre_tiles >= 0 ? tuning().pre_tiles : n128 / 4;
-        }
-    }
-
-    // ---- K ----
-    {
-        const int nt = Np / PW_T;
-        const dim3 grid(nt * (nt + 1) / 2);
-        hipLaunchKernelGGL(by_kind(c.kernel, [](auto K) { return kernel_matrix_kernel<K()>; }), grid, dim3(256), 0, s, c.d_Xs, c.d_K, N, Np, Dp, c.constant, c.noise, c.jitter);
-        TGP_TRY(hipGetLastError());
-    }
-    // ---- blocked Cholesky, two levels ----
-    // Panels of NB = 64 columns (LDS factorisation + MFMA panel solve) are grouped into outer
-    // blocks of OB = 512: inside an outer block a panel only updates the remaining columns of
-    // that block (narrow, K = 64); the trailing matrix gets ONE rank-OB update per outer block
-    // on the direct-to-LDS NT kernel (OB/16 k-tiles per tile instead of OB/64 launches of 4).
-    // outer block (multiple of 256).  With the inverse behind the chain: 256 wins from Np = 1024 to
-    // 3072 (1.06 vs 1.10 ms at N = 2048), 512 at N = 4096 (2.53 vs 2.59) and beyond.
-    const int OB_env = tuning().ob;
-    // (round 3, with the fused panel launches: 512 is now equal or better from Np = 1536 on -- 2560: 1.293 vs 1.334 ms,
-    // 3072: 1.617 vs 1.713 -- and 256 only wins where 512 leaves a half-empty last block: Np = 1280 0.618 vs 0.667)
-    // (round 4, after the f64 kernels got faster: 1024 from Np = 6144 on -- 6144: 4.66 -> 4.48 ms, 8192: 8.87 -> 8.62 --
-    // half as many trailing updates and event hops; still 512 at 4096: 2.20 vs 2.26)
-    // (round 5, late: up to Np = 1024 ONE outer block -- no trailing update, the inverse level by level behind the last
-    // panel.  With the one-launch panels the in-block updates cost no more than the rank-256 ones did, and the chain
-    // loses its hand-overs to the background stream: fit 0.455 -> 0.417 / 0.452 -> 0.439 ms at N = 900 / 1000, an
-    // evaluation of the hyper-parameter objective at N = 1000 0.562 -> 0.544 ms on the caller's handle and, on the
-    // pooled workers whose inverse runs in line, 0.73 -> 0.55 alone, 0.88 -> 0.63 three side by side; Np = 768 equal)
-    int OB = OB_env ? OB_env : (Np <= 1024 ? Np : (Np <= 1280 ? 256 : (Np >= 6144 ? 1024 : 512)));
-    // The last, partial outer block builds its own inverse by merging halves (inverse_block below): its length has to
-    // be a power of two.  Np is a multiple of 256, so 256 and 512 always leave 0 or 256; 1024 can leave 768 (Np = 6912,
-    // 7936, 8960: `invalid configuration argument` from a merge of zero pairs before this check) -> 512 there.
-    if (const int tail = Np % OB; (tail & (tail - 1)) != 0) OB = 512;
-    const double tiny = 8.0 * 2.220446049250313e-16 * ((c.constant + c.noise) + c.jitter);
-    // Rows >= N are padding: K is the identity there, so its factor is the identity too and the
-    // panels, panel rows and trailing tiles that hold nothing but padding are skipped (their L
-    // stays as kernel_matrix_kernel wrote it; Linv stays zero, which is all the sweep needs since
-    // the cross-kernel slab is zero in those columns).
-    const int Nr = ((N + NB - 1) / NB) * NB;   // real rows, rounded up to whole panels
-    // ---- the inverse factor: [[A,0],[C,B]]^-1 = [[Ai,0],[-Bi*C*Ai,Bi]] ----
-    // Level 64 -> 128 on the k-major GEMM template; from 128 up the transpose U = Linv^T is kept
-    // alongside so both products of a merge are NT:
-    //     T^T   = U11 * L21^T            (U11 upper triangular: k from the tile's own row on)  -> W
-    //     Linv21 = -Linv22 * (T^T)^T     (Linv22 lower triangular), stored to Linv and, transposed, to U
-    // level64(st, o, pairs): the `pairs` 128-blocks from row o on, one batched launch per product.
-    const int panel_var = tuning().panel;   // A/B: 5 = variant D (block in LDS, MFMA), 3 / 38 = variant C with 4 / 8 columns per barrier, 4 / 8 = variant B, 0 = round-1 form
-    auto level64 = [&](hipStream_t st, long o, int pairs) -> hipError_t {
-        const long bs64 = (long)2 * NB * ((long)Np + 1);
-        const long d = o * ((long)Np + 1);
-        GemmArgs t{};   // T = L21 * L11inv -> W
-        t.A = c.d_K + d + (long)NB * Np; t.lda = Np; t.strideA = bs64;
-        t.B = c.d_Linv + d; t.ldb = Np; t.strideB = bs64;
-        t.C = c.d_W + d + (long)NB * Np; t.ldc = Np; t.strideC = bs64;
-        t.ntm = t.ntn = 1; t.K = NB; t.alpha = 1.0; t.beta = 0.0;
-        GemmArgs u{};   // Linv21 = -L22inv * T
-        u.A = c.d_Linv + d + (long)NB * Np + NB; u.lda = Np; u.strideA = bs64;
-        u.B = c.d_W + d + (long)NB * Np; u.ldb = Np; u.strideB = bs64;
-        u.C = c.d_Linv + d + (long)NB * Np; u.ldc = Np; u.strideC = bs64;
-        u.ntm = u.ntn = 1; u.K = NB; u.alpha = -1.0; u.beta = 0.0;
-        if (tuning().level64_fused) {
-            hipLaunchKernelGGL(level64_fused_kernel, dim3(pairs), dim3(256), 0, st, c.d_K, c.d_Linv, c.d_U, Np, o);
-            return hipGetLastError();
-        }
-        TGP_TRY((launch_gemm64<64, 64, false, KR_LOWER_B, TM_FULL>(st, c.device, t, 1, pairs)));
-        TGP_TRY((launch_gemm64<64, 64, false, KR_LOWER_A, TM_FULL>(st, c.device, u, 1, pairs)));
-        hipLaunchKernelGGL(transpose_diag128_kernel, dim3(pairs, 16), dim3(256), 0, st, c.d_Linv + d,
-                           c.d_U + d, Np);
-        return hipGetLastError();
-    };
-    // Merges with a leading block up to MERGE64 (few, very unequal 128-tiles) go to the 64 x 64
-    // register-staged template like the small trailing updates.  Measured: fit 4.52 -> 4.13 ms
-    // at N = 4096, 0.54 -> 0.46 ms at N = 512; the 4096-level of N = 8192 is faster on the
-    // 128-tile direct-to-LDS kernel (13.39 vs 13.59 ms), hence 2048.
-    const int MERGE64 = tuning().merge64;
-    // leading block [o, o+a), trailing block [o+a, o+a+b); a, b multiples of 128 (64 with small = true)
-    auto merge_t = [&](hipStream_t st, long o, int a, int b, int nprob, long bstride, bool small) -> hipError_t {
-        if (small || a <= MERGE64) {
-            GemmArgs tt{};   // T^T (a x b) -> W[o.., o+a..]
-            tt.A = c.d_U + o * Np + o; tt.lda = Np; tt.strideA = bstride;
-            tt.B = c.d_K + (o + a) * Np + o; tt.ldb = Np; tt.strideB = bstride;
-            tt.C = c.d_W + o * Np + (o + a); tt.ldc = Np; tt.strideC = bstride;
-            tt.ntm = a / NB; tt.ntn = b / NB; tt.K = a; tt.alpha = 1.0; tt.beta = 0.0;
-            return launch_gemm64<64, 64, true, KR_UPPER_A, TM_FULL>(st, c.device, tt, tt.ntm * tt.ntn, nprob);
-        }
-        GemmNtArgs tt{};
-        tt.A = c.d_U + o * Np + o; tt.lda = Np; tt.strideA = bstride;
-        tt.B = c.d_K + (o + a) * Np + o; tt.ldb = Np; tt.strideB = bstride;
-        tt.C = c.d_W + o * Np + (o + a); tt.ldc = Np; tt.strideC = bstride;
-        tt.Ct = nullptr;
-        tt.ntm = a / 128; tt.ntn = b / 128; tt.K = a; tt.alpha = 1.0; tt.beta = 0.0;
-        return launch_gemm_nt_glds<double, KN_UPPER_A, TM_FULL>(st, c.device, tt, tt.ntm * tt.ntn, nprob);
-    };
-    auto merge_u = [&](hipStream_t st, long o, int a, int b, int nprob, long bstride, bool small) -> hipError_t {
-        if (small || a <= MERGE64) {
-            GemmArgs uu{};   // Linv21 (b x a) and its transpose into U
-            uu.A = c.d_Linv + (o + a) * Np + (o + a); uu.lda = Np; uu.strideA = bstride;
-            uu.B = c.d_W + o * Np + (o + a); uu.ldb = Np; uu.strideB = bstride;
-            uu.C = c.d_Linv + (o + a) * Np + o; uu.ldc = Np; uu.strideC = bstride;
-            uu.Ct = c.d_U + o * Np + (o + a); uu.ldct = Np; uu.strideCt = bstride;
-            uu.ntm = b / NB; uu.ntn = a / NB; uu.K = b; uu.alpha = -1.0; uu.beta = 0.0;
-            return launch_gemm64<64, 64, true, KR_LOWER_A, TM_FULL>(st, c.device, uu, uu.ntm * uu.ntn, nprob);
-        }
-        GemmNtArgs uu{};
-        uu.A = c.d_Linv + (o + a) * Np + (o + a); uu.lda = Np; uu.strideA = bstride;
-        uu.B = c.d_W + o * Np + (o + a); uu.ldb = Np; uu.strideB = bstride;
-        uu.C = c.d_Linv + (o + a) * Np + o; uu.ldc = Np; uu.strideC = bstride;
-        uu.Ct = c.d_U + o * Np + (o + a); uu.ldct = Np; uu.strideCt = bstride;
-        uu.ntm = b / 128; uu.ntn = a / 128; uu.K = b; uu.alpha = -1.0; uu.beta = 0.0;
-        return launch_gemm_nt_glds<double, KN_LOWER_A, TM_FULL>(st, c.device, uu, uu.ntm * uu.ntn, nprob);
-    };
-    auto merge = [&](hipStream_t st, long o, int a, int b, int nprob, long bstride) -> hipError_t {
-        TGP_TRY(merge_t(st, o, a, b, nprob, bstride, false));
-        return merge_u(st, o, a, b, nprob, bstride, false);
-    };
-    // (1) level by level over the whole matrix, after the factorisation: all complete pairs of a
-    // level share one batched launch; an odd segment out (Np is a multiple of 256, not necessarily
-    // a power of two) is merged separately when it finds a partner.
-    auto inverse_levels = [&](hipStream_t st) -> hipError_t {
-        TGP_TRY(level64(st, 0, Np / (2 * NB)));
-        int nfull = Np / 128;  // complete segments of size sz
-        int tail = 0;          // size of the trailing odd segment (0 = none)
-        for (int sz = 128; nfull + (tail ? 1 : 0) > 1; sz *= 2) {
-            const int pairs = nfull / 2;
-            if (pairs > 0) TGP_TRY(merge(st, 0, sz, sz, pairs, (long)2 * sz * ((long)Np + 1)));
-            if (nfull & 1) {
-                const long o = (long)(nfull - 1) * sz;
-                if (tail) {   // odd full segment + tail -> new tail
-                    TGP_TRY(merge(st, o, sz, tail, 1, 0));
-                    tail += sz;
-                } else {
-                    tail = sz;
-                }
-            }
-            nfull = pairs;
-        }
-        return hipSuccess;
-    };
-    // (2) outer block by outer block, BEHIND the panel chain on the background stream: once the
-    // panels of block [O, E) are final,
-    //     X_bb              the block's own inverse (levels 64, 128, 256 inside the block)
-    //     Linv[O:E, 0:O]  = -X_bb * T[O:E, 0:O]                       (T^T sits in W above the diagonal)
-    //     T[E:, 0:E]     +=  L[E:, O:E] * Linv[O:E, 0:E]              (every later row block's share)
-    // so that after the last panel only the last block's X_bb and row block are left to do.
-    // `inner` = the block's own inverse X_bb (false: already there, see inverse_inner_all)
-    auto inverse_block = [&](hipStream_t st, long O, long E, bool inner = true) -> hipError_t {
-        const int len = (int)(E - O);
-        if (inner) {
-            TGP_TRY(level64(st, O, len / 128));
-            for (int sz = 128; sz < len; sz *= 2)
-                TGP_TRY(merge(st, O, sz, sz, len / (2 * sz), (long)2 * sz * ((long)Np + 1)));
-        }
-        if (O > 0) TGP_TRY(merge_u(st, 0, (int)O, len, 1, 0, true));
-        if (E < Np) {
-            if (O > 0) {   // rows 0:O of T^T: W[0:O, E:] += U[0:O, O:E] * L[E:, O:E]^T
-                GemmArgs g{};
-                g.A = c.d_U + O; g.lda = Np;
-                g.B = c.d_K + E * Np + O; g.ldb = Np;
-                g.C = c.d_W + E; g.ldc = Np;
-                g.ntm = (int)(O / NB); g.ntn = (int)((Np - E) / NB); g.K = len; g.alpha = 1.0; g.beta = 1.0;
-                TGP_TRY((launch_gemm64<64, 64, true, KR_FULL, TM_FULL>(st, c.device, g, g.ntm * g.ntn, 1)));
-            }
-            TGP_TRY(merge_t(st, O, len, (int)(Np - E), 1, 0, true));   // rows O:E, first contribution
-        }
-        return hipSuccess;
-    };
-    // The X_bb of EVERY outer block at once, after the factorisation: the launches of inverse_block's first part batched
-    // over the blocks (a pair of 64-, 128-, ... row segments never straddles an outer block: OB and the tail are powers
-    // of two times 128) -- the same tiles with the same operands in the same k order, i.e. the same bits, in 1 + 2 log2(OB /
-    // 128) launches instead of that many per block.  For a fit that cannot put its inverse behind the chain (a handle on a
-    // private stream): 40 -> 25 launches at Np = 2048, 80 -> 45 at 4096.
-    auto inverse_inner_all = [&](hipStream_t st) -> hipError_t {
-        TGP_TRY(level64(st, 0, Np / (2 * NB)));
-        for (int sz = 128; sz < OB; sz *= 2) {
-            const int pairs = Np / (2 * sz);
-            if (pairs > 0) TGP_TRY(merge(st, 0, sz, sz, pairs, (long)2 * sz * ((long)Np + 1)));
-        }
-        return hipSuccess;
-    };
-    // ... and with a row block of Linv final: its rows of z = Linv yn, its share of alpha = Linv^T z,
-    // its f32 copy for an f32 sweep
-    auto finish_block = [&](hipStream_t st, long O, long E) -> hipError_t {
-        hipLaunchKernelGGL(rowblock_finish_kernel, dim3((unsigned)(E - O)), dim3(256), 0, st, c.d_Linv, c.d_yn,
-                           c.d_z, c.dtype != TGP_F64 ? c.d_Linv32 : nullptr, Np, (int)O);
-        TGP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(rowblock_cols_kernel, dim3((unsigned)(E / 64), (unsigned)((E - O) / GEMV_SLICE)), dim3(256), 0, st,
-                           c.d_Linv, c.d_z, c.d_apart, c.d_apart + (long)(Np / GEMV_SLICE) * Np, Np, (int)O);
-        return hipGetLastError();
-    };
-    const int bginv_on = tuning().bginv;
-    // up to Np = 9216: beyond, the inverse's products want the 128-tile direct-to-LDS kernel and the whole
-    // chip (N = 10000: 17.7 vs 17.2 ms, 16384: 63.0 vs 57.5, 20000: 114 vs 101 for the level-by-level path)
-    const int bginv_max = tuning().bginv_max;
-    const bool bginv = bginv_on && Np > OB && Np <= bginv_max;
-    const int nblk = (Np + OB - 1) / OB;
-    // A handle on a PRIVATE stream (the workers of a threaded hyper-parameter fit) keeps its share of the inverse on that
-    // stream: the device has ONE background stream, and the workers' inverses queued on it one behind the other while
-    // every worker's chain waited for its own -- three starts side by side at N = 1000 took as long as one after the
-    // other (28.5 vs 28.6 ms; 19.1 with the inverses in line, N = 2048 101 -> 83).  Same launches in the same order of
-    // arithmetic, so the results are those of the shared-stream path bit for bit.
-    const bool bg_shared = c.stream_own == nullptr || c.bg_lease != nullptr;   // (bg_lease: the background stream this fit holds on loan)
-    if (bginv && bg_shared) TGP_TRY(ensure_lookahead(c, (size_t)2 * nblk));
-    const hipStream_t sbg = c.bg_lease ? c.bg_lease : c.stream_bg;
-    // debug: TGP_STAMP_FILE=path makes every fused panel launch leave in-kernel time stamps (10 ns
-    // ticks) and the fit dump them there (tools/stamp_summary.py reads the file); Np <= 8192 only
-    constexpr size_t STAMP_STRIDE = FUSED_STAMP_STRIDE;
-    const char *stamp_path = tuning().stamp_file.empty() ? nullptr : tuning().stamp_file.c_str();
-    // (debug only.  The buffer belongs to the handle -- it goes with the fit's memory -- so fits on several handles, e.g.
-    // the threaded hyper-parameter starts, stamp buffers of their own; the FILE is the last finisher's)
-    unsigned long long *stamp_dev = nullptr;
-    if (stamp_path && Np <= 8192) {
-        TGP_TRY(c.d_stamp.reserve(2 * 128 * STAMP_STRIDE * sizeof(unsigned long long)));
-        TGP_TRY(hipMemsetAsync(c.d_stamp, 0, 2 * 128 * STAMP_STRIDE * sizeof(unsigned long long), s));
-        stamp_dev = c.d_stamp;
-    }
-    for (int O = 0; O < Nr; O += OB) {
-        for (int kk = 0; kk < OB / NB; ++kk) {
-            const int o = O + kk * NB;
-            if (o >= Nr) break;
-            const int rem = (Nr - o - NB) / NB;   // real block rows below
-            const int panel_la = tuning().panel_la;
-            const int panel_fuse = tuning().panel_fuse;
-            // Decided per OUTER BLOCK by the tiles of its first update.  Each fused tile is three f64 products on
-            // a CU of its own (10 us against 3 for a plain update tile), so a block with hundreds of them holds
-            // CUs the background stream's inverse wants: measured on one box, fit ms at N = 2048 / 4096 / 8192 with
-            // the limit at 0 (never): 1.037 / 2.379 / 9.997, 128: 1.004 / 2.373 / 9.953, 256: 1.010 / 2.428 / 9.967,
-            // no limit: 1.000 / 2.418 / 10.185 -- the fused launch is kept for blocks of up to 128 tiles
-            // (everything up to N = 2048, the last two outer blocks beyond).  TGP_PANEL_FUSE_TILES overrides.
-            // Round 4 (MFMAs in VGPR form: a fused tile is shorter): 384 -- N = 2048 0.949 -> 0.903 ms, 3072 1.506 -> 1.427,
-            // 4096 / 6144 / 8192 unchanged; 512: 6144 +2 %, no limit: 8192 +3 %.
-            const int panel_fuse_tiles = tuning().panel_fuse_tiles;
-            const int rem0 = (Nr - O - NB) / NB;                                  // row blocks below the block's first panel
-            const int tiles0 = rem0 * (OB / NB - 1 < rem0 ? OB / NB - 1 : rem0);  // tiles of its first update
-            if (panel_fuse && tiles0 <= panel_fuse_tiles && panel_la && panel_var == 5) {
-                // one launch per panel: see fused_panel_kernel.  Slot kk & 1 of Apan holds this panel's
-                // unsolved blocks; the last panel of an outer block (no update follows) is solved in place.
-                const long slot = (long)(Np / NB) * NB * NB;
-                int ncol = OB / NB - 1 - kk;
-                if (ncol > rem) ncol = rem;
-                unsigned long long *st0 = stamp_dev ? stamp_dev + (size_t)(2 * (o / NB)) * STAMP_STRIDE : nullptr;
-                if (kk == 0) {
-                    hipLaunchKernelGGL(fused_panel_kernel, dim3(1 + (ncol > 0 ? rem : 0)), dim3(256), 0, s, c.d_K, Np, o, 0, 1,
-                                       c.d_Apan, c.d_Apan, c.d_Dinv, c.d_Linv, c.d_scal, c.d_flag, tiny, st0);
-                    TGP_TRY(hipGetLastError());
-                }
-                if (rem == 0) break;
-                if (ncol > 0) {
-                    hipLaunchKernelGGL(fused_panel_kernel, dim3(1 + rem * ncol), dim3(256), 0, s, c.d_K, Np, o, 1, ncol,
-                                       c.d_Apan + (kk & 1) * slot, c.d_Apan + ((kk + 1) & 1) * slot, c.d_Dinv,
-                                       c.d_Linv, c.d_scal, c.d_flag, tiny, st0 ? st0 + STAMP_STRIDE : nullptr);
-                } else {
-                    hipLaunchKernelGGL(panel_solve_kernel, dim3(rem), dim3(256), 0, s, c.d_K, Np, o, c.d_Dinv);
-                }
-                TGP_TRY(hipGetLastError());
-                continue;
-            }
-            if (panel_la && panel_var == 5) {
-                // the pivot off the update's back: see pivot_update_kernel.  The first panel of an outer block
-                // factors its pivot alone (the trailing update before it has touched everything); every
-                // later pivot was factored beside the previous panel's update.
-                if (kk == 0) {
-                    hipLaunchKernelGGL(pivot_update_kernel, dim3(1), dim3(256), 0, s, c.d_K, Np, o, 0, 1, c.d_Dinv, c.d_Linv,
-                                       c.d_scal, c.d_flag, tiny);
-                    TGP_TRY(hipGetLastError());
-                }
-                if (rem == 0) break;
-                hipLaunchKernelGGL(panel_solve_kernel, dim3(rem), dim3(256), 0, s, c.d_K, Np, o, c.d_Dinv);
-                TGP_TRY(hipGetLastError());
-                int ncol = OB / NB - 1 - kk;
-                if (ncol > rem) ncol = rem;
-                if (ncol > 0) {
-                    hipLaunchKernelGGL(pivot_update_kernel, dim3(1 + rem * ncol), dim3(256), 0, s, c.d_K, Np, o + NB, 1, ncol,
-                                       c.d_Dinv, c.d_Linv, c.d_scal, c.d_flag, tiny);
-                    TGP_TRY(hipGetLastError());
-                }
-                continue;
-            }
-            // diagonal block (factor + inverse) and, in the same launch, the panel solve of every
-            // row block below it
-            auto pk = panel_kernel<3>;
-            if (panel_var == 38) pk = panel_kernel<38>;
-            else if (panel_var == 8) pk = panel_kernel<8>;
-            else if (panel_var == 4) pk = panel_kernel<4>;
-            else if (panel_var == 0) pk = panel_kernel<0>;
-            if (panel_var == 5) pk = panel_d_kernel;
-            hipLaunchKernelGGL(pk,
-                               dim3(rem + 1), dim3(256), 0, s, c.d_K, Np, o, c.d_Dinv,
-                               c.d_Linv, c.d_Dinv + (long)(Np / NB) * NB * NB, c.d_scal, c.d_flag, tiny);   // second half of Dinv: where a diagonal block waits
-            TGP_TRY(hipGetLastError());
-            if (rem == 0) break;
-            double *panel = c.d_K + (long)(o + NB) * Np + o;
-            int ncol = OB / NB - 1 - kk;          // panels left inside this outer block
-            if (ncol > rem) ncol = rem;           // ... that exist (last, partial outer block)
-            const bool inner_generic = tuning().inner_generic;
-            if (ncol > 0 && !inner_generic) {   // A[:, o+64 : O+OB] -= L_:k * L_jk^T
-                hipLaunchKernelGGL(rank64_update_kernel, dim3(rem * ncol), dim3(256), 0, s, c.d_K, Np, o, ncol);
-                TGP_TRY(hipGetLastError());
-            } else if (ncol > 0) {
-                GemmArgs g{};
-                g.A = panel; g.lda = Np;
-                g.B = panel; g.ldb = Np;
-                g.C = c.d_K + (long)(o + NB) * Np + (o + NB); g.ldc = Np;
-                g.ntm = rem; g.ntn = ncol; g.K = NB; g.alpha = -1.0; g.beta = 1.0;
-                TGP_TRY((launch_gemm64<64, 64, true, KR_FULL, TM_FULL>(s, c.device, g, rem * ncol, 1)));
-            }
-        }
-        if (bginv && O + OB < Np) {   // every block but the last: its share of the inverse goes behind the chain
-            const int b = O / OB;
-            if (bg_shared) {
-                TGP_TRY(hipEventRecord(c.ev_la[2 * b], s));
-                TGP_TRY(hipStreamWaitEvent(sbg, c.ev_la[2 * b], 0));
-                TGP_TRY(inverse_block(sbg, O, O + OB));
-                TGP_TRY(finish_block(sbg, O, O + OB));
-                TGP_TRY(hipEventRecord(c.ev_la[2 * b + 1], sbg));
-                if (spre && pre_budget128 > c.pre.rows128) {   // rows < O + OB of Linv (and its f32 copy) are final behind that event
-                    TGP_TRY(hipStreamWaitEvent(spre, c.ev_la[2 * b + 1], 0));
-                    TGP_TRY(presweep_rows(c, spre, O + OB, pre_budget128));
-                }
-            }   // (a handle on a private stream without the background stream on loan: after the last panel, below)
-        }
-        const int R = ((Nr - O - OB + 127) / 128) * 128;   // real trailing rows in whole 128-tiles (<= Np - O - OB)
-        // Trailing matrices up to TRAIL64 rows have too few 128-tiles to fill the chip and each tile
-        // then runs its whole k-range alone on a CU: use 64 x 64 tiles (4x the tiles, a quarter of
-        // the critical path) on the register-staged template.  Measured: fit 4.73 -> 4.50 ms at
-        // N = 4096, 14.35 -> 13.59 ms at N = 8192; from N = 20000 on the 128-tile direct-to-LDS
-        // kernel wins again (448 vs 419 ms at N = 33000), hence the threshold.
-        const int TRAIL64 = tuning().trail64;
-        if (R > 0 && R <= TRAIL64) {
-            GemmArgs g{};
-            g.A = c.d_K + (long)(O + OB) * Np + O; g.lda = Np;
-            g.B = g.A; g.ldb = Np;
-            g.C = c.d_K + (long)(O + OB) * Np + (O + OB); g.ldc = Np;
-            g.ntm = g.ntn = R / NB; g.K = OB; g.alpha = -1.0; g.beta = 1.0;
-            const int nt = R / NB;
-            TGP_TRY((launch_gemm64<64, 64, true, KR_FULL, TM_LOWER>(s, c.device, g, nt * (nt + 1) / 2, 1)));
-        } else if (R > 0) {   // A[i][j] -= L[i][O:O+OB] * L[j][O:O+OB]^T, i >= j >= O+OB
-            GemmNtArgs g{};
-            g.A = c.d_K + (long)(O + OB) * Np + O; g.lda = Np;
-            g.B = g.A; g.ldb = Np;
-            g.C = c.d_K + (long)(O + OB) * Np + (O + OB); g.ldc = Np;
-            g.Ct = nullptr;
-            g.ntm = g.ntn = R / 128; g.K = OB; g.alpha = -1.0; g.beta = 1.0;
-            const int nt = R / 128;
-            TGP_TRY((launch_gemm_nt_glds<double, KN_FULL, TM_LOWER>(s, c.device, g, nt * (nt + 1) / 2, 1)));
-        }
-    }
-    if (bginv) {
-        const long O = (long)(nblk - 1) * OB;
-        if (bg_shared) {
-            TGP_TRY(hipStreamWaitEvent(s, c.ev_la[2 * (nblk - 2) + 1], 0));
-            TGP_TRY(inverse_block(s, O, Np));
-        } else {
-            // in line, on the private stream: every block's own inverse in batched launches, then block by block what
-            // depends on the blocks before it -- the arithmetic of the background schedule, operation for operation
-            TGP_TRY(inverse_inner_all(s));
-            for (long Ob = 0; Ob < O; Ob += OB) {
-                TGP_TRY(inverse_block(s, Ob, Ob + OB, false));
-                TGP_TRY(finish_block(s, Ob, Ob + OB));
-            }
-            TGP_TRY(inverse_block(s, O, Np, false));
-        }
-        TGP_TRY(finish_block(s, O, Np));
-        hipLaunchKernelGGL(alpha_finish_sliced_kernel, dim3(Np / 64), dim3(256), 0, s, c.d_apart,
-                           c.d_apart + (long)(Np / GEMV_SLICE) * Np, c.d_alpha, c.d_scal, Np, c.d_flag, res_host);
-        TGP_TRY(hipGetLastError());
-    } else {
-        TGP_TRY(inverse_levels(s));
-        // ---- alpha = Linv^T (Linv yn),  yn . alpha ----
-        hipLaunchKernelGGL(gemv_lower_rows_kernel, dim3((Np + 3) / 4), dim3(256), 0, s, c.d_Linv,
-                           c.d_yn, c.d_z, Np);
-        TGP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(gemv_lower_cols_kernel, dim3(Np / 64, GEMV_RS), dim3(256), 0, s, c.d_Linv,
-                           c.d_z, c.d_W, Np);   // W is free again after the inverse
-        TGP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(alpha_finish_kernel, dim3(1), dim3(256), 0, s, c.d_W, c.d_yn, c.d_alpha,
-                           c.d_scal, Np, c.d_flag, res_host);
-        TGP_TRY(hipGetLastError());
-        if (c.dtype != TGP_F64) {
-            hipLaunchKernelGGL(f64_to_f32_kernel, dim3(2048), dim3(256), 0, s, c.d_Linv, c.d_Linv32, NN);
-            TGP_TRY(hipGetLastError());
-        }
-    }
-    if (spre) {
-        TGP_TRY(hipEventRecord(c.pre.ev, spre));
-        c.pre.pending = true;
-    }
-    if (stamp_dev) {
-        std::vector<unsigned long long> hst(2 * 128 * STAMP_STRIDE);
-        TGP_TRY(hipStreamSynchronize(s));
-        TGP_TRY(hipMemcpy(hst.data(), stamp_dev, hst.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        if (FILE *fh = fopen(stamp_path, "wb")) {
-            fwrite(hst.data(), sizeof(unsigned long long), hst.size(), fh);
-            fclose(fh);
-        }
-        // round 6: the CUs each of the fit's streams reaches (main | background | third), HW_PROBE_WGS workgroups each, in
-        // <path>.cus -- so that tools/stamp_summary.py can say whether a panel's pivot workgroup sat on a CU the
-        // background stream's GEMMs can run on
-        constexpr int HW_PROBE_WGS = 16384;
-        unsigned long long *pd = nullptr;
-        TGP_TRY(hipMalloc((void **)&pd, 3 * HW_PROBE_WGS * sizeof(unsigned long long)));
-        TGP_TRY(hipMemset(pd, 0, 3 * HW_PROBE_WGS * sizeof(unsigned long long)));
-        const hipStream_t probe_on[3] = {s, sbg, c.stream_pre};
-        for (int k = 0; k < 3; ++k) {
-            if (!probe_on[k]) continue;
-            hipLaunchKernelGGL(hw_probe_kernel, dim3(HW_PROBE_WGS), dim3(64), 0, probe_on[k], pd + (size_t)k * HW_PROBE_WGS);
-            TGP_TRY(hipGetLastError());
-            TGP_TRY(hipStreamSynchronize(probe_on[k]));
-        }
-        std::vector<unsigned long long> hp(3 * HW_PROBE_WGS);
-        TGP_TRY(hipMemcpy(hp.data(), pd, hp.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        (void)hipFree(pd);
-        const std::string cus = std::string(stamp_path) + ".cus";
-        if (FILE *fh = fopen(cus.c_str(), "wb")) {
-            fwrite(hp.data(), sizeof(unsigned long long), hp.size(), fh);
-            fclose(fh);
-        }
-    }
-    return hipSuccess;
-}
-
 }  // namespace tgp
+
+// the schedule of the blocked fit (launch_fit): part of this translation unit -- the same flags, the same code object
+#include "fit_blocked.hpp"

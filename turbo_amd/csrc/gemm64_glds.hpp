@@ -22,7 +22,7 @@
 // operands costs the same), without DMA the MFMA loop 128 us; a k-split inside the workgroup (8 or 16
 // waves per tile) measured equal or slower -- a tile's 576 KB arrive through ONE CU either way -- and is
 // not kept.  Bigger tiles halve the bytes per flop: launches with enough 128 x 128 tiles take
-// gemm_nt_glds.hpp (TGP_TRAIL64 / TGP_MERGE64 in fit_kernels.hip).
+// gemm_nt_glds.hpp (TGP_TRAIL64 / TGP_MERGE64 in fit_blocked.hpp).
 //
 // Requirements: rows of A / B / C in whole 64-tiles; every k-range a multiple of 16 doubles (all callers
 // use multiples of 64); lda, ldb multiples of 2 doubles; beta is 0 or 1.

@@ -18,6 +18,7 @@
 #include "gemm_nt_glds.hpp"
 #include "lds_opt_in.hpp"
 #include "mfma_gemm.hpp"
+#include "nt_product.hpp"
 #include "pairwise.hpp"
 #include "small_grad.hpp"
 #include "tgp_internal.hpp"
@@ -175,23 +176,18 @@ hipError_t launch_lml_grad(Context &c, bool ard, double *gout, bool timed) {
         TGP_TRY(hipEventRecord(c.evg[0], s));
     }
     const int kinv64 = tuning().kinv64;   // Np up to which the 64-tile template is used (0.44 vs 0.65 ms at N = 4096, 0.031 vs 0.071 at 512: the 128-tile grid is short and very unequal)
-    if (Np <= kinv64) {   // K^-1 = U U^T, lower 64-tiles, into W
-        GemmArgs g{};
-        g.A = c.d_U; g.lda = Np;
-        g.B = c.d_U; g.ldb = Np;
-        g.C = c.d_W; g.ldc = Np;
-        g.ntm = g.ntn = Np / 64; g.K = Np; g.alpha = 1.0; g.beta = 0.0;
+    NtProduct g;   // K^-1 = U U^T, lower tiles, into W
+    g.device = c.device;
+    g.A = c.d_U; g.lda = Np;
+    g.B = c.d_U; g.ldb = Np;
+    g.C = c.d_W; g.ldc = Np;
+    g.rows = g.cols = Np; g.K = Np; g.alpha = 1.0; g.beta = 0.0;
+    if (Np <= kinv64) {
         const int nt = Np / 64;
-        TGP_TRY((launch_gemm64_glds<KR_UPPER_A, TM_LOWER>(s, c.device, g, nt * (nt + 1) / 2, 1)));
-    } else {   // K^-1 = U U^T, lower 128-tiles, into W
-        GemmNtArgs g{};
-        g.A = c.d_U; g.lda = Np;
-        g.B = c.d_U; g.ldb = Np;
-        g.C = c.d_W; g.ldc = Np;
-        g.Ct = nullptr;
-        g.ntm = g.ntn = Np / 128; g.K = Np; g.alpha = 1.0; g.beta = 0.0;
+        TGP_TRY((g.on64<KR_UPPER_A, TM_LOWER>(s, nt * (nt + 1) / 2, 1)));
+    } else {
         const int nt = Np / 128;
-        TGP_TRY((launch_gemm_nt_glds<double, KN_UPPER_A, TM_LOWER>(s, c.device, g, nt * (nt + 1) / 2, 1)));
+        TGP_TRY((g.on128<KN_UPPER_A, TM_LOWER>(s, nt * (nt + 1) / 2, 1)));
     }
     if (timed) TGP_TRY(hipEventRecord(c.evg[1], s));
     const int nt = (N + PW_T - 1) / PW_T;

@@ -208,11 +208,11 @@ struct Context : FitMem, WsMem, OutMem {
 };
 
 // launchers (fit_kernels.hip / sweep_kernels.hip); return hipSuccess or the first error
-hipStream_t private_fit_begin(int device, bool may_borrow);   // fit_kernels.hip: a fit of a private-stream handle starts; the device's background stream if it gets it on loan, else null
+hipStream_t private_fit_begin(int device, bool may_borrow);   // fit_streams.hpp: a fit of a private-stream handle starts; the device's background stream if it gets it on loan, else null
 void private_fit_end(int device, bool held);
 hipError_t launch_fit(Context &c, const double *staged_in, double *res_host, bool zero_linv = true, unsigned long long *start_stamp = nullptr);   // start_stamp: device view of a mapped word the first kernel leaves its wall_clock64() in (a polled call)
 hipError_t launch_ring(Context &c, const Bell &bell);   // a one-wave kernel behind everything queued on c.stream: rings the doorbell   // staged_in: device-mapped [Xs | yn | ls] or null (already in HBM); res_host: device-mapped [sum log, yn.alpha, flag] or null; zero_linv: false when Linv is known to be zero above the diagonal and from row Nr on
-// the device's shared main / background stream (fit_kernels.hip); either pointer may be null
+// the device's shared main / background stream (fit_streams.hpp); either pointer may be null
 hipError_t device_streams(int device, hipStream_t *main, hipStream_t *bg, hipStream_t *pre = nullptr);   // main != null takes a reference
 void device_streams_release(int device);
 void device_stream_status(int device, int *bg_ok, int *pre_ok);   // 1 runs beside the main stream, 0 serialised (one hardware queue), -1 not probed
