@@ -7,9 +7,11 @@ Bar (b): end to end against the oracle's predict + the reference, f64 handles: r
 index where the reference's top two differ by more than that (tests/test_gpu_batch.py's bar); the f32 handle: the f32
 bars of tests/test_gpu_configs.py (rtol 1e-5 on the vector against the f64 handle's neighbourhood is not applicable to
 an entropy whose gamma divides by sigma_f, so its REGRET bar is used: regret < 1e-3 relative).
-Gradient: tests/test_gpu_round5.py holds the gradient stage to SciPy's walk and states no bar for the EI gradient
-itself; the project's bar for it is tests/test_gpu_parity.py's (rtol 2e-4, atol max(2e-6 scale, 2e-9) against central
-differences with h = 1e-6), used here."""
+Gradient: the bar for tgp_acq_grad's ACQ_NONE / ACQ_SIGMA / UCB / PI / EI gradients themselves is
+tests/test_gpu_acq_grad_edges.py's (an 80-bit closed form, 64 max(e_ref, N u) of the batch maximum under a cap of 1e-9).
+The MES gradient is held here to its closed form over the device's own ACQ_NONE / ACQ_SIGMA gradients -- which that
+file pins -- and to central differences at tests/test_gpu_parity.py's bar (rtol 2e-4, atol max(2e-6 scale, 2e-9),
+h = 1e-6)."""
 import numpy as np
 import pytest
 
