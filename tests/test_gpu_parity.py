@@ -474,6 +474,8 @@ GRAD_CASES = ["grad_rbf_iso_3d", "grad_rbf_ard_3d", "grad_matern52_ard_5d", "gra
 
 @pytest.mark.parametrize("name", GRAD_CASES)
 def test_lml_gradient(ta, name):
+    """the golden cases (scikit-learn's values) at rtol 1e-6 of the entry; tests/test_gpu_lml_grad_edges.py holds the same
+    entry to an 80-bit closed form at the size and path edges, as a fraction of the entry's sum of absolute terms"""
     with np.load(golden_path(name), allow_pickle=False) as z:
         c = {k: z[k] for k in z.files}
     noise = float(c["noise"])
@@ -492,6 +494,8 @@ def test_lml_gradient(ta, name):
 
 
 def test_lml_gradient_larger_vs_oracle(ta):
+    """one blocked size against the f64 oracle; the tile, padding and ARD-pass edges of the blocked path, the 128-tile
+    K^-1 product and N = 4097 are tests/test_gpu_lml_grad_edges.py's, against an 80-bit reference"""
     X, y, _ = _synth(77, 700, 6, 1)
     ls = np.linspace(0.6, 1.4, 6)
     gp = ta.NativeGP(0, "f64")
@@ -509,7 +513,8 @@ def test_lml_gradient_larger_vs_oracle(ta):
 def test_lml_gradient_small_problems_vs_oracle(ta, N, D, kind):
     """N <= 128 (and D <= 64): fit and gradient are two one-workgroup launches (small_kernels.hip,
     grad_kernels.hip small_grad_kernel), ARD and isotropic; (97, 65) is one dimension too wide and
-    takes the blocked path -- same answers"""
+    takes the blocked path -- same answers.  (The fused one-launch kernel, TGP_SMALL_FUSED=0 and TGP_SMALL=0 at the
+    edges of N and D, each against an 80-bit reference: tests/test_gpu_lml_grad_edges.py.)"""
     X, y, _ = _synth(500 + N + D, N, D, 1)
     gp = ta.NativeGP(0, "f64")
     ls_ard = np.linspace(0.7, 1.6, D) * np.sqrt(D / 6.0)
