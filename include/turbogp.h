@@ -113,6 +113,39 @@ int tgp_fit_grad(tgp_handle h, const double *X, int64_t N, int64_t D, const doub
                  double noise, double jitter, int normalize_y,
                  double *lml, double *y_mean, double *y_std, double *grad);
 
+/* Leave-one-out cross-validation of the fitted model in closed form (Rasmussen & Williams, Gaussian Processes for
+ * Machine Learning, section 5.4.2, eqs. 5.10-5.12): with K = c k0 + (noise + jitter) I in normalised units,
+ * alpha = K^-1 y~ and kappa_i = (K^-1)_ii,
+ *   mu_-i = y~_i - alpha_i / kappa_i,  sigma^2_-i = 1 / kappa_i                                           (5.12)
+ *   lpd_i = -1/2 log sigma^2_-i - (y~_i - mu_-i)^2 / (2 sigma^2_-i) - 1/2 log 2 pi,  L_LOO = sum_i lpd_i  (5.10, 5.11)
+ * The normalisation (y_mean, y_std of ALL N points) and the hyper-parameters are held across the folds: that is what the
+ * closed form means; no model is refitted.  Outputs, all nullable:
+ *   resid (N)   y_i - mu_-i in RAW units (y_std alpha_i / kappa_i); the held-out mean is y_i - resid_i.  The residual
+ *               and not the mean, because a handle that received its factor (tgp_import_factor_dev) holds no y.
+ *   sigma (N)   y_std / sqrt(kappa_i), RAW units: the predictive deviation of the held-out OBSERVATION.  It contains
+ *               the noise AND the jitter, because K carries both; tgp_predict's sigma has the noise but no jitter.
+ *   lpd (N), *loo   NORMALISED units, as `lml` is; *loo is the sum of lpd in a fixed order (the same bits run to run).
+ * TGP_NOT_FITTED without a model; TGP_NOT_PD if a kappa_i is <= 0 or not finite (nothing is clamped; it cannot happen
+ * after a successful fit).  Works on every fitted handle -- the one-workgroup fits, the blocked fit, a fit extended by
+ * tgp_fit_append, a received factor, TGP_DEVICE_HOST handles (plain C++, csrc/host_backend.cpp) -- always in float64
+ * whatever the handle's dtype, and touches neither the fit, the resident candidates, the winner record, a Thompson
+ * draw nor the MES maxima. */
+int tgp_loo(tgp_handle h, double *resid, double *sigma, double *lpd, double *loo);
+
+/* Fit (as tgp_fit; arguments through y_std as tgp_fit_grad's) plus the leave-one-out score `loo` = L_LOO and ITS
+ * gradient with respect to the LOG hyper-parameters (R&W eq. 5.13, taken as one trace 1/2 tr(G dK/dtheta) with
+ * G = b alpha^T + alpha b^T - 2 K^-1 diag(w) K^-1, p_i = alpha_i / kappa_i, w_i = (1 / kappa_i + p_i^2) / 2,
+ * b = K^-1 p): `grad` = [d/dlog(constant), d/dlog(ls[0..n_ls)), d/dlog(noise)], 2 + n_ls doubles in normalised units,
+ * the noise entry exactly 0.0 when noise == 0 -- tgp_fit_grad's layout.  `lml` is the log marginal likelihood as
+ * tgp_fit returns it.  The fit takes the BLOCKED route for every N (the gradient needs Linv^T and the N^2 workspaces
+ * only that route guarantees), so `lml` has the bytes of tgp_fit_grad under TGP_SMALL=0; *loo is byte for byte what
+ * tgp_loo returns on the handle afterwards.  The model is left fitted at these hyper-parameters.  GPU only: a host
+ * handle answers TGP_BAD_ARG.  Status as tgp_fit, plus TGP_NOT_PD for a kappa_i <= 0 or not finite. */
+int tgp_fit_loo_grad(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y,
+                     int kernel, double constant, const double *ls, int64_t n_ls,
+                     double noise, double jitter, int normalize_y,
+                     double *lml, double *y_mean, double *y_std, double *loo, double *grad);
+
 /* Fit like tgp_fit, but when the handle already holds a fit with the same kernel, hyper-parameters,
  * jitter and normalisation whose training inputs are bit-for-bit the first N-1 rows of X, extend
  * the factor by ONE row in O(N^2) (four triangular GEMVs) instead of refactorising in O(N^3):
@@ -710,7 +743,9 @@ int tgp_profile_reset(tgp_handle h);
  * handles, TGP_PRUNE_SCREEN; `survivors` of slot 14 are those that went on to the exact contraction), -1 when the screen
  * did not apply.  Slot [17]: profiled time (ms) of the screen's launches since tgp_profile_reset, kept apart from
  * tgp_profile_read's cross-kernel and contraction times.  Slot [18] (not a time): that screen's arithmetic, 0 none,
- * 1 the f32 matrix pipe, 2 fp16 planes with the k-weighted error (TGP_SCREEN_ARITH). */
+ * 1 the f32 matrix pipe, 2 fp16 planes with the k-weighted error (TGP_SCREEN_ARITH).
+ * Slot [19]: device time (ms) of the kernels of the last tgp_loo, the copies back left out (0 on host handles).  After
+ * tgp_fit_loo_grad slot [2] holds everything up to B = A A^T (K^-1, kappa, b, A, B), slots [3] and [4] as for tgp_fit_grad. */
 int tgp_last_timings(tgp_handle h, double *out, int64_t n);
 /* Candidates per trmm launch (chunk) and padded N used by the sweep, for the roofline maths. */
 int tgp_sweep_geometry(tgp_handle h, int64_t *chunk, int64_t *n_padded);

@@ -36,7 +36,7 @@ BATCH_KB, BATCH_CL = 0, 1    # tgp_sweep_batch strategies: Kriging Believer, Con
 
 # every symbol include/turbogp.h declares
 SYMBOLS = (
-    "tgp_create", "tgp_destroy", "tgp_last_error", "tgp_version", "tgp_fit", "tgp_fit_grad", "tgp_fit_optimise", "tgp_fit_lbfgsb", "tgp_set_private_stream",
+    "tgp_create", "tgp_destroy", "tgp_last_error", "tgp_version", "tgp_fit", "tgp_fit_grad", "tgp_loo", "tgp_fit_loo_grad", "tgp_fit_optimise", "tgp_fit_lbfgsb", "tgp_set_private_stream",
     "tgp_set_overlap", "tgp_tuning", "tgp_mt19937_uniform_columns", "tgp_set_candidates_mt19937", "tgp_stream_status", "tgp_workers_acquire", "tgp_workers_release",
     "tgp_fit_append", "tgp_export_state", "tgp_import_state", "tgp_export_factor_dev", "tgp_import_factor_dev", "tgp_debug_read",
     "tgp_set_candidates", "tgp_set_candidates_dev", "tgp_gen_candidates", "tgp_gen_candidates_lhs", "tgp_lhs_design",
@@ -115,6 +115,8 @@ def _argtypes():
         "tgp_destroy": [_vp],
         "tgp_fit": fit,
         "tgp_fit_grad": fit + [_dp],
+        "tgp_loo": [_vp, _dp, _dp, _dp, _dp],
+        "tgp_fit_loo_grad": fit + [_dp, _dp],
         "tgp_fit_append": fit + [c.POINTER(c.c_int)],
         "tgp_fit_optimise": [_vp, _dp, c.c_int64, c.c_int64, _dp, c.c_int, _dp, c.c_int64, c.c_int64, _dp, _dp,
                              c.c_double, c.c_int, c.c_int64, _dp, _dp, _i64p, _i64p],
@@ -495,6 +497,32 @@ class NativeGP:
             ctypes.byref(lml), ctypes.byref(ym), ctypes.byref(ys), _ptr(grad)))
         self.N, self.D = X.shape
         return lml.value, grad
+
+    def loo(self):
+        """``tgp_loo``: closed-form leave-one-out cross-validation of the fitted model.  Returns a dict with ``resid``
+        (y_i - mu_-i, raw units), ``sigma`` (the held-out observation's deviation, raw units, noise and jitter
+        included), ``lpd`` (log predictive densities, normalised units) and ``loo`` (their sum)"""
+        n = int(self.N)
+        resid, sigma, lpd = np.zeros(n), np.zeros(n), np.zeros(n)
+        loo = ctypes.c_double()
+        self._check(self.lib.tgp_loo(self._h, _ptr(resid), _ptr(sigma), _ptr(lpd), ctypes.byref(loo)))
+        return dict(resid=resid, sigma=sigma, lpd=lpd, loo=loo.value)
+
+    def fit_loo_grad(self, X, y, kind, constant, length_scale, noise, jitter, normalize_y):
+        """fit + the leave-one-out score and d L_LOO / d log(theta): returns (lml, loo, grad [c, ls..., noise])"""
+        X = _f64c(X)
+        y = _f64c(y).reshape(-1)
+        assert X.ndim == 2 and X.shape[0] == y.shape[0], "X must be (N, D) and y (N,)"
+        ls = _f64c(np.atleast_1d(length_scale))
+        lml, ym, ys, loo = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        grad = np.zeros(2 + ls.shape[0])
+        self.fit_gen += 1
+        self._check(self.lib.tgp_fit_loo_grad(
+            self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(y), KERNELS[kind], float(constant),
+            _ptr(ls), ls.shape[0], float(noise), float(jitter), 1 if normalize_y else 0,
+            ctypes.byref(lml), ctypes.byref(ym), ctypes.byref(ys), ctypes.byref(loo), _ptr(grad)))
+        self.N, self.D = X.shape
+        return lml.value, loo.value, grad
 
     def set_private_stream(self, on=True):
         """submit this handle's work to a stream of its own (handles of a device share one by default),

@@ -37,10 +37,25 @@ namespace tgp {
 // registers.  (The weights used to be written out, N x N, and contracted with [X | 1] by a skinny
 // GEMM: 0.36 ms of a 3.4 ms evaluation at N = 4096, mostly the 256 MiB of writes and a 64-workgroup
 // GEMM; this way nothing N x N leaves the kernel.)
-template <int KIND>
-__global__ __launch_bounds__(256) void lml_weights_kernel(const double *__restrict__ Xs,
-                                                          const double *__restrict__ alpha,
-                                                          const double *__restrict__ Kinv,
+//
+// The pair weight G_ij is a compile-time policy: everything after it (distances, ls_weight, the ARD passes, the sums)
+// is one spelling for both traces 1/2 tr(G dK).
+struct LmlPairWeight {      // G = alpha alpha^T - K^-1: the log marginal likelihood
+    const double *__restrict__ alpha;
+    const double *__restrict__ Kinv;      // lower triangle read
+    __device__ double row(int i) const { return alpha[i]; }
+    __device__ double G(double ai, int, int j, long lower) const { return ai * alpha[j] - Kinv[lower]; }
+};
+struct LooPairWeight {      // G = b alpha^T + alpha b^T - 2 B: the leave-one-out score (loo_kernels.hip)
+    const double *__restrict__ alpha;
+    const double *__restrict__ b;
+    const double *__restrict__ B;         // lower triangle read
+    __device__ double row(int i) const { return alpha[i]; }
+    __device__ double G(double ai, int i, int j, long lower) const { return (b[i] * alpha[j] + ai * b[j]) - 2.0 * B[lower]; }
+};
+
+template <int KIND, class PW>
+__global__ __launch_bounds__(256) void lml_weights_kernel(const double *__restrict__ Xs, const PW pw,
                                                           double *__restrict__ partial, int N,
                                                           int Np, int Dp, int ard) {
     __shared__ double Ct[PwCfg<double>::DC][PwCfg<double>::LD];
@@ -62,14 +77,14 @@ __global__ __launch_bounds__(256) void lml_weights_kernel(const double *__restri
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
         const int i = i0 + 4 * ty + a;
-        const double ai = (i < N) ? alpha[i] : 0.0;
+        const double ai = (i < N) ? pw.row(i) : 0.0;
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             const int j = j0 + 4 * tx + b;
             w[a][b] = 0.0;
             if (i < N && j < N) {
                 const int hi = i > j ? i : j, lo = i > j ? j : i;
-                const double G = ai * alpha[j] - Kinv[(long)hi * Np + lo];
+                const double G = pw.G(ai, i, j, (long)hi * Np + lo);
                 if (i == j) {
                     sc += G;          // k0_ii = 1 (np.fill_diagonal(K, 1))
                     sdiag += G;
@@ -165,18 +180,11 @@ __global__ __launch_bounds__(256) void sum_partials_kernel(const double *__restr
     if (threadIdx.x == 0) out[c] = red[0];
 }
 
-// results land in gout (device memory or device-mapped host memory): [S_c, S_iso, S_diag, gd[0..Dp)]
-// timed = false (a polled call, round 6): no event records between the stages (tgp_last_timings then has no stage times)
-hipError_t launch_lml_grad(Context &c, bool ard, double *gout, bool timed) {
-    hipStream_t s = c.stream;
-    const int N = (int)c.N, Np = (int)c.Np, Dp = (int)c.Dp;
-    if (timed) {
-        for (int i = 0; i < 4; ++i)
-            TGP_TRY(c.evg[i].create(hipEventDefault));
-        TGP_TRY(hipEventRecord(c.evg[0], s));
-    }
+// K^-1 = U U^T over the lower tiles into W
+hipError_t launch_kinv_product(Context &c) {
+    const int Np = (int)c.Np;
     const int kinv64 = tuning().kinv64;   // Np up to which the 64-tile template is used (0.44 vs 0.65 ms at N = 4096, 0.031 vs 0.071 at 512: the 128-tile grid is short and very unequal)
-    NtProduct g;   // K^-1 = U U^T, lower tiles, into W
+    NtProduct g;
     g.device = c.device;
     g.A = c.d_U; g.lda = Np;
     g.B = c.d_U; g.ldb = Np;
@@ -184,17 +192,25 @@ hipError_t launch_lml_grad(Context &c, bool ard, double *gout, bool timed) {
     g.rows = g.cols = Np; g.K = Np; g.alpha = 1.0; g.beta = 0.0;
     if (Np <= kinv64) {
         const int nt = Np / 64;
-        TGP_TRY((g.on64<KR_UPPER_A, TM_LOWER>(s, nt * (nt + 1) / 2, 1)));
-    } else {
-        const int nt = Np / 128;
-        TGP_TRY((g.on128<KN_UPPER_A, TM_LOWER>(s, nt * (nt + 1) / 2, 1)));
+        return g.on64<KR_UPPER_A, TM_LOWER>(c.stream, nt * (nt + 1) / 2, 1);
     }
-    if (timed) TGP_TRY(hipEventRecord(c.evg[1], s));
+    const int nt = Np / 128;
+    return g.on128<KN_UPPER_A, TM_LOWER>(c.stream, nt * (nt + 1) / 2, 1);
+}
+
+// the pairwise pass over W and the tiles' sums into gout.  loo_b == null: W = K^-1, the LML's weight; else W = B and
+// loo_b = b, the leave-one-out weight
+hipError_t launch_pair_sums(Context &c, bool ard, const double *loo_b, double *gout, bool timed) {
+    hipStream_t s = c.stream;
+    const int N = (int)c.N, Np = (int)c.Np, Dp = (int)c.Dp;
     const int nt = (N + PW_T - 1) / PW_T;
     const int nblk = nt * (nt + 1) / 2;
     const dim3 grid(nblk);
     const int wr = ard ? 1 : 0;
-    hipLaunchKernelGGL(by_kind(c.kernel, [](auto K) { return lml_weights_kernel<K()>; }), grid, dim3(256), 0, s, c.d_Xs, c.d_alpha, c.d_W, c.d_gpart, N, Np, Dp, wr);
+    if (loo_b)
+        hipLaunchKernelGGL(by_kind(c.kernel, [](auto K) { return lml_weights_kernel<K(), LooPairWeight>; }), grid, dim3(256), 0, s, c.d_Xs, LooPairWeight{c.d_alpha, loo_b, c.d_W}, c.d_gpart, N, Np, Dp, wr);
+    else
+        hipLaunchKernelGGL(by_kind(c.kernel, [](auto K) { return lml_weights_kernel<K(), LmlPairWeight>; }), grid, dim3(256), 0, s, c.d_Xs, LmlPairWeight{c.d_alpha, c.d_W}, c.d_gpart, N, Np, Dp, wr);
     TGP_TRY(hipGetLastError());
     if (timed) TGP_TRY(hipEventRecord(c.evg[2], s));
     const int ncols = ard ? 3 + Dp : 3;
@@ -202,6 +218,20 @@ hipError_t launch_lml_grad(Context &c, bool ard, double *gout, bool timed) {
     TGP_TRY(hipGetLastError());
     if (timed) TGP_TRY(hipEventRecord(c.evg[3], s));
     return hipSuccess;
+}
+
+// results land in gout (device memory or device-mapped host memory): [S_c, S_iso, S_diag, gd[0..Dp)]
+// timed = false (a polled call, round 6): no event records between the stages (tgp_last_timings then has no stage times)
+hipError_t launch_lml_grad(Context &c, bool ard, double *gout, bool timed) {
+    hipStream_t s = c.stream;
+    if (timed) {
+        for (int i = 0; i < 4; ++i)
+            TGP_TRY(c.evg[i].create(hipEventDefault));
+        TGP_TRY(hipEventRecord(c.evg[0], s));
+    }
+    TGP_TRY(launch_kinv_product(c));
+    if (timed) TGP_TRY(hipEventRecord(c.evg[1], s));
+    return launch_pair_sums(c, ard, nullptr, gout, timed);
 }
 
 }  // namespace tgp

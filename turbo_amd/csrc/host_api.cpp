@@ -72,6 +72,21 @@ int tgp_fit_append(tgp_handle h, const double *X, int64_t N, int64_t D, const do
     HOST_TRY(h->g.fit(X, N, D, y, kernel, constant, ls, n_ls, noise, jitter, normalize_y, lml, y_mean, y_std))
 }
 
+int tgp_loo(tgp_handle h, double *resid, double *sigma, double *lpd, double *loo) {
+    if (!h) return TGP_BAD_ARG;
+    HOST_TRY(h->g.loo(resid, sigma, lpd, loo))
+}
+
+int tgp_fit_loo_grad(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel, double constant,
+                     const double *ls, int64_t n_ls, double noise, double jitter, int normalize_y, double *lml,
+                     double *y_mean, double *y_std, double *loo, double *grad) {
+    (void)X; (void)N; (void)D; (void)y; (void)kernel; (void)constant; (void)ls; (void)n_ls; (void)noise; (void)jitter;
+    (void)normalize_y; (void)lml; (void)y_mean; (void)y_std; (void)loo; (void)grad;
+    if (!h) return TGP_BAD_ARG;
+    h->g.err = "tgp_fit_loo_grad: not available on the host backend (the gradient's chain is GPU code); tgp_loo is";
+    return TGP_BAD_ARG;
+}
+
 int tgp_export_state(tgp_handle h, void *buf, int64_t cap, int64_t *size) {
     if (!h) return TGP_BAD_ARG;
     HOST_TRY(h->g.export_state(buf, cap, size))

@@ -245,6 +245,52 @@ int HostGP::fit(const double *Xin, int64_t n, int64_t d, const double *yin, int 
     return TGP_OK;
 }
 
+// kappa_i = sum_{k >= i} Linv[k,i]^2 with column i of L^-1 by forward substitution (x_i = 1 / L_ii, x_k = -(sum_{i <= j < k}
+// L_kj x_j) / L_kk), the columns in parallel; the sums run top down, L_LOO in index order.  Nothing is clamped.
+int HostGP::loo(double *resid, double *sigma, double *lpd, double *loo_out) {
+    if (!fitted) { err = "tgp_loo: no fitted model"; return TGP_NOT_FITTED; }
+    const int64_t n = N;
+    std::vector<double> kappa((size_t)n, 0.0);
+    const double *Lp = L.data();
+    double *kp = kappa.data();
+    parallel_for(n, threads_for((double)n * (double)n * (double)n / 6.0), [=](int64_t b, int64_t e) {
+        std::vector<double> x((size_t)n);
+        for (int64_t i = b; i < e; ++i) {
+            x[(size_t)i] = 1.0 / Lp[i * n + i];
+            double s = x[(size_t)i] * x[(size_t)i];
+            for (int64_t k = i + 1; k < n; ++k) {
+                const double *rk = Lp + k * n;
+                double t = 0.0;
+                for (int64_t j = i; j < k; ++j) t += rk[j] * x[(size_t)j];
+                const double v = -t / rk[k];
+                x[(size_t)k] = v;
+                s += v * v;
+            }
+            kp[i] = s;
+        }
+    });
+    int64_t bad = 0;
+    for (int64_t i = 0; i < n; ++i)
+        if (!(kappa[(size_t)i] > 0.0) || !isfinite(kappa[(size_t)i])) ++bad;
+    if (bad) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "tgp_loo: %lld diagonal entries of K^-1 are <= 0 or not finite", (long long)bad);
+        err = buf;
+        return TGP_NOT_PD;
+    }
+    double total = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+        const double k = kappa[(size_t)i], a = alpha[(size_t)i], p = a / k;
+        const double lp = 0.5 * log(k) - 0.5 * (a * p) - 0.5 * log(2.0 * M_PI);
+        if (resid) resid[i] = y_std * p;
+        if (sigma) sigma[i] = y_std / sqrt(k);
+        if (lpd) lpd[i] = lp;
+        total += lp;
+    }
+    if (loo_out) *loo_out = total;
+    return TGP_OK;
+}
+
 int HostGP::export_state(void *buf, int64_t cap, int64_t *size) {
     if (!fitted) { err = "tgp_export_state: no fitted model"; return TGP_NOT_FITTED; }
     const int64_t need = (8 + D + N * D + N) * 8;

@@ -17,6 +17,8 @@
 //                        substitution on tiles of 16 candidates, var = (c + noise) - |v|^2, clamp
 //   joint posterior      _gpr.py:454-462 (y_cov = kernel_(X) - V^T V, lower triangle computed, mirrored) and :497-535
 //                        (sample_y) with the normals handed in: Cholesky of Sigma + nugget I under the fit's pivot rule
+//   leave-one-out        R&W section 5.4.2: kappa_i = (K^-1)_ii from the columns of L^-1 (this backend keeps L: each column is
+//                        one forward substitution), then alpha_i / kappa_i, 1 / sqrt(kappa_i) and the log densities
 //   acquisition          turbo/modules/acquisition_functions.py UCB :147-158, PI :225-247, EI :336-358;
 //                        max-value entropy search (TGP_ACQ_MES) from the maxima of mes_set_maxima, with an
 //                        erfcx of its own (the standard library has none)
@@ -61,6 +63,9 @@ struct HostGP {
     int predict_cov(const double *Xq, int64_t m, int latent, double *mu_out, double *cov_out, int64_t *n_negative_diag);
     int sample_joint(const double *Xq, int64_t m, int64_t S, int latent, double nugget, const double *eps_in,
                      double *y_out, double *eps_out, double *mu_out);
+
+    // leave-one-out cross-validation in closed form (tgp_loo; R&W eqs. 5.10-5.12): all outputs nullable
+    int loo(double *resid, double *sigma, double *lpd, double *loo_out);
 
 private:
     // mu (m) raw and Sigma (m, m) in normalised units, both triangles, diag_add on the diagonal

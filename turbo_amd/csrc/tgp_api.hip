@@ -574,6 +574,25 @@ static int ensure_grad_workspace(Context &c) {
     return TGP_OK;
 }
 
+// leave-one-out workspaces, grown with the fit like the gradient's: the vectors (tgp_loo), and for the gradient also
+// A (Np, Np) and the pairwise pass's partials
+static int ensure_loo_workspace(Context &c, bool grad) {
+    if (c.Np > c.loov_cap_Np) {
+        c.loov_cap_Np = 0;
+        API_MEM(grow(c, c.d_loov, (loo_vec_doubles(c.Np) + 2) * sizeof(double), "hipMalloc LOO vectors"));
+        c.loov_cap_Np = c.Np;
+    }
+    if (!grad) return TGP_OK;
+    if (c.Np > c.looA_cap_Np) {
+        c.looA_cap_Np = 0;
+        API_MEM(grow(c, c.d_looA, (size_t)c.Np * c.Np * sizeof(double), "hipMalloc LOO A"));
+        c.looA_cap_Np = c.Np;
+    }
+    return ensure_grad_workspace(c);
+}
+// where launch_loo_points leaves [L_LOO, bad count] when the caller has no device-mapped place for them
+static double *loo_scal_dev(Context &c) { return c.d_loov + loo_vec_doubles(c.loov_cap_Np); }
+
 // the fit state's device buffers for Np padded rows and D dimensions.  full: everything a fit needs; otherwise only what
 // a handle that RECEIVES a factor needs to sweep with it (tgp_import_factor_dev: no K, no inverse workspaces -- 4 N^2
 // doubles less); a later fit on such a handle allocates the rest
@@ -731,7 +750,7 @@ static int stage_blocked_inputs(Context &c, const FitArgs &a, const std::vector<
     const size_t n_in = (size_t)Np * Dp + (size_t)Np + (size_t)D;
     staged = n_in * sizeof(double) <= ((size_t)64 << 20);
     if (staged) {
-        API_MEM(ensure_pinned(c, n_in * sizeof(double), (size_t)(8 + 3 + Dp) * sizeof(double)));
+        API_MEM(ensure_pinned(c, n_in * sizeof(double), (size_t)(8 + 3 + Dp + 2) * sizeof(double)));   // (+ 2: tgp_fit_loo_grad's [L_LOO, bad count])
         double *xs = c.h_pin_in;
         if (D == Dp) memset(xs + (size_t)N * Dp, 0, (size_t)(Np - N) * Dp * sizeof(double));   // (the rows are about to be overwritten whole)
         else memset(xs, 0, (size_t)Np * Dp * sizeof(double));
@@ -766,7 +785,9 @@ static int decide_overlap_front(Context &c, int grad_mode) {
     return TGP_OK;
 }
 
-// grad_mode: 1 / 2 = the LML gradient (iso / ARD) is launched behind the fit, before the one synchronisation
+// grad_mode: 1 / 2 = the LML gradient (iso / ARD) is launched behind the fit, before the one synchronisation;
+// + GRAD_LOO: the leave-one-out score and ITS gradient instead (tgp_fit_loo_grad)
+constexpr int GRAD_LOO = 4;
 static int fit_blocked(Context &c, const FitArgs &a, const std::vector<double> &yn, int grad_mode, FitResult &r) {
     const int64_t N = a.N, D = a.D, Np = c.Np, Dp = c.Dp;
     bool staged;
@@ -784,7 +805,8 @@ static int fit_blocked(Context &c, const FitArgs &a, const std::vector<double> &
         API_HIP(hipMemcpyAsync(c.d_ls, c.ls.data(), (size_t)D * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D ls");
         API_HIP(hipMemcpyAsync(c.d_yn, yn.data(), (size_t)Np * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D yn");
     }
-    if (grad_mode) API_MEM(ensure_grad_workspace(c));
+    if (grad_mode & GRAD_LOO) API_MEM(ensure_loo_workspace(c, true));
+    else if (grad_mode) API_MEM(ensure_grad_workspace(c));
     // Linv is zero above the diagonal whenever its leading dimension is known (nothing ever writes there) and
     // zero from row linv_extent on; this fit writes everything on and below the diagonal of its Nr rows and
     // skips the panels of pure padding: the zero fill is only needed when an older fit reached further down
@@ -820,8 +842,10 @@ static int fit_blocked(Context &c, const FitArgs &a, const std::vector<double> &
     if (grad_mode) {   // behind the fit, in front of the call's one synchronisation
         c.grad_staged = staged;
         c.grad_timed = !bell.word;
-        le = launch_lml_grad(c, grad_mode == 2, staged ? c.h_pin_out.dev() + 8 : c.d_gout, c.grad_timed);
-        if (le != hipSuccess) return hip_fail(c, le, "launch_lml_grad");
+        double *gout = staged ? c.h_pin_out.dev() + 8 : c.d_gout;
+        if (grad_mode & GRAD_LOO) le = launch_loo_grad(c, (grad_mode & 3) == 2, gout, staged ? gout + 3 + Dp : loo_scal_dev(c), c.grad_timed);
+        else le = launch_lml_grad(c, grad_mode == 2, gout, c.grad_timed);
+        if (le != hipSuccess) return hip_fail(c, le, (grad_mode & GRAD_LOO) ? "launch_loo_grad" : "launch_lml_grad");
     }
     if (bell.word) {
         le = launch_ring(c, bell);
@@ -990,6 +1014,79 @@ int tgp_fit_grad(tgp_handle h, const double *X, int64_t N, int64_t D, const doub
                  int normalize_y, double *lml, double *y_mean, double *y_std, double *grad) {
     return fit_grad_entry(h, FitArgs{X, N, D, y, kernel, constant, ls, n_ls, noise, jitter, normalize_y}, FitOut{lml, y_mean, y_std}, grad);
 }
+
+// ---- leave-one-out cross-validation (include/turbogp.h; loo_kernels.hip) ----
+static int loo_not_pd(Context &c, const char *fn, double bad) {
+    char buf[160];
+    snprintf(buf, sizeof buf, "%s: %d diagonal entries of K^-1 are <= 0 or not finite", fn, (int)bad);
+    return fail(c, TGP_NOT_PD, buf);
+}
+
+int tgp_loo(tgp_handle h, double *resid, double *sigma, double *lpd, double *loo) try {
+    if (!h) return TGP_BAD_ARG;
+    if (h->host) return h->host->loo(resid, sigma, lpd, loo);
+    Context &c = h->c;
+    if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_loo: no fitted model");
+    API_HIP(hipSetDevice(c.device), "hipSetDevice");
+    API_HIP(pre_join(c), "hipStreamWaitEvent");
+    API_MEM(ensure_loo_workspace(c, false));
+    double *sd = loo_scal_dev(c);
+    API_HIP(hipEventRecord(c.ev0, c.stream), "hipEventRecord");
+    const hipError_t le = launch_loo_points(c, sd);
+    if (le != hipSuccess) return hip_fail(c, le, "launch_loo_points");
+    API_HIP(hipEventRecord(c.ev1, c.stream), "hipEventRecord");
+    double scal[2] = {0.0, 0.0};
+    const size_t nb = (size_t)c.N * sizeof(double);
+    API_HIP(hipMemcpyAsync(scal, sd, sizeof scal, hipMemcpyDeviceToHost, c.stream), "D2H LOO scalars");
+    if (resid) API_HIP(hipMemcpyAsync(resid, c.d_loov + c.Np, nb, hipMemcpyDeviceToHost, c.stream), "D2H resid");
+    if (sigma) API_HIP(hipMemcpyAsync(sigma, c.d_loov + 2 * c.Np, nb, hipMemcpyDeviceToHost, c.stream), "D2H sigma");
+    if (lpd) API_HIP(hipMemcpyAsync(lpd, c.d_loov + 3 * c.Np, nb, hipMemcpyDeviceToHost, c.stream), "D2H lpd");
+    API_HIP(hipStreamSynchronize(c.stream), "loo sync");
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, c.ev0, c.ev1);
+    c.last_loo_ms = ms;
+    if (scal[1] != 0.0) return loo_not_pd(c, "tgp_loo", scal[1]);
+    if (loo) *loo = scal[0];
+    return TGP_OK;
+} TGP_CATCH
+
+int tgp_fit_loo_grad(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
+                     double constant, const double *ls, int64_t n_ls, double noise, double jitter,
+                     int normalize_y, double *lml, double *y_mean, double *y_std, double *loo, double *grad) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_fit_loo_grad");
+    Context &c = h->c;
+    if (!grad) return fail(c, TGP_BAD_ARG, "tgp_fit_loo_grad: grad is NULL");
+    const FitArgs a{X, N, D, y, kernel, constant, ls, n_ls, noise, jitter, normalize_y};
+    const bool ard = n_ls > 1;
+    // the blocked route for every N: the gradient needs U = Linv^T and the N^2 workspaces only that route guarantees
+    const int rc = fit_impl(h, a, FitOut{lml, y_mean, y_std}, false, (ard ? 2 : 1) | GRAD_LOO);
+    if (rc != TGP_OK) return rc;
+    const int nout = ard ? 3 + (int)c.Dp : 3;
+    std::vector<double> sums((size_t)(3 + c.Dp), 0.0);
+    double scal[2] = {0.0, 0.0};
+    if (c.grad_staged) {
+        memcpy(sums.data(), c.h_pin_out + 8, (size_t)nout * sizeof(double));
+        memcpy(scal, c.h_pin_out + 8 + 3 + c.Dp, sizeof scal);
+    } else {
+        API_HIP(hipSetDevice(c.device), "hipSetDevice");
+        API_HIP(hipMemcpy(sums.data(), c.d_gout, (size_t)nout * sizeof(double), hipMemcpyDeviceToHost), "D2H grad");
+        API_HIP(hipMemcpy(scal, loo_scal_dev(c), sizeof scal, hipMemcpyDeviceToHost), "D2H LOO scalars");
+    }
+    for (int i = 0; i < 3; ++i) {
+        float gms = 0.f;
+        if (c.grad_timed) (void)hipEventElapsedTime(&gms, c.evg[i], c.evg[i + 1]);
+        c.last_grad_ms[i] = gms;   // [0]: K^-1, kappa, b, A and B = A A^T
+    }
+    if (scal[1] != 0.0) {
+        c.fitted = false;
+        return loo_not_pd(c, "tgp_fit_loo_grad", scal[1]);
+    }
+    if (loo) *loo = scal[0];
+    lml_grad_from_sums(a, sums.data(), grad);
+    if (noise == 0.0) grad[1 + n_ls] = 0.0;   // (exactly +0.0, whatever the sign of the trace)
+    return TGP_OK;
+} TGP_CATCH
 
 // State blob: what defines the fitted model, not the factor (the factor is N^2 and is rebuilt in
 // milliseconds; X, y and theta are N*(D+1) + D + 3 doubles).  Layout, all little-endian 8-byte
@@ -2932,15 +3029,16 @@ int tgp_last_timings(tgp_handle h, double *out, int64_t n) try {
     // [16]: the survivors of that sweep's screen (prune_screen.hpp), -1 when the screen did not apply; [17]: profiled time of
     // the screen's launches since tgp_profile_reset (ms; apart from the cross-kernel's and the contraction's); [18]: that
     // screen's arithmetic, 0 none, 1 f32, 2 fp16 planes (TGP_SCREEN_ARITH)
-    double v[19] = {c.last_fit_ms, c.last_sweep_ms, c.last_grad_ms[0], c.last_grad_ms[1], c.last_grad_ms[2], c.trmm_flops,
+    // [19]: device time of the last tgp_loo's three kernels (ms; the copies back left out)
+    double v[20] = {c.last_fit_ms, c.last_sweep_ms, c.last_grad_ms[0], c.last_grad_ms[1], c.last_grad_ms[2], c.trmm_flops,
                     (double)c.last_sweep_f64, 0.0, 0.0, 0.0, 0.0, 0.0, (double)c.prune_state, (double)c.prune_lbset,
-                    (double)c.prune_surv, c.last_cov_ms, (double)c.prune_screen, c.screen_ms, (double)c.prune_arith};
+                    (double)c.prune_surv, c.last_cov_ms, (double)c.prune_screen, c.screen_ms, (double)c.prune_arith, c.last_loo_ms};
     if (c.h_bell && c.h_bell[1]) {
         const unsigned long long t0 = c.h_bell[1];
         const int src[5] = {3, 4, 5, 6, 2};
         for (int k = 0; k < 5; ++k) v[7 + k] = c.h_bell[src[k]] >= t0 ? (double)(c.h_bell[src[k]] - t0) * 1e-2 : 0.0;
     }
-    for (int64_t i = 0; i < n; ++i) out[i] = i < 19 ? v[i] : 0.0;
+    for (int64_t i = 0; i < n; ++i) out[i] = i < 20 ? v[i] : 0.0;
     return TGP_OK;
 } TGP_CATCH
 

@@ -86,6 +86,10 @@ struct FitMem {
     Dev<double> d_gpart;           // (tiles, 3 + Dp) partial sums: [S_c, S_iso, S_diag, gd[0..Dp)] per 64 x 64 tile
     Dev<double> d_gout;            // [S_c, S_iso, S_diag, gd[Dp]]
     int64_t g_cap_Np = 0, g_cap_Dp = 0;   // the geometry those two were allocated for
+    // leave-one-out workspaces (allocated on first tgp_loo / tgp_fit_loo_grad)
+    Dev<double> d_loov;            // the per-point vectors, the kappa kernel's partials and [L_LOO, bad count] (loo_vec_doubles + 2)
+    Dev<double> d_looA;            // (Np, Np) A = K^-1 diag(sqrt(w)) of the LOO gradient
+    int64_t loov_cap_Np = 0, looA_cap_Np = 0;
     Dev<double> d_qws;             // small-batch query workspace (tgp_acq_grad)
     Dev<double> d_rf;              // on-device optimiser state (tgp_acq_refine)
     Dev<unsigned long long> d_stamp;   // TGP_STAMP_FILE (debug): in-kernel time stamps of the panel chain
@@ -151,6 +155,7 @@ struct Context : FitMem, WsMem, OutMem {
     Dev<int> d_flag;               // first failing pivot + 1, or 0
     bool grad_staged = false;      // the last tgp_fit_grad left its sums in the pinned result buffer (+8), not in d_gout
     bool grad_timed = true;        // ... and recorded the events its stage times are read from (false: a polled call)
+    double last_loo_ms = 0.0;      // device time of the last tgp_loo's kernels
     double last_cov_ms = 0.0;      // device time of the last joint-posterior call's kernels (the H2D / D2H copies not included)
     long fit_gen = 0;              // counts the fits, appends and imports: what a draw, the maxima and the planes of Linv belong to
     float linv16_sb = 0.f;         // TGP_F32H2: the cross-kernel scale the stored 1 / (s_a s_b) was formed with
@@ -217,6 +222,19 @@ hipError_t device_streams(int device, hipStream_t *main, hipStream_t *bg, hipStr
 void device_streams_release(int device);
 void device_stream_status(int device, int *bg_ok, int *pre_ok);   // 1 runs beside the main stream, 0 serialised (one hardware queue), -1 not probed
 hipError_t launch_lml_grad(Context &c, bool ard, double *gout, bool timed = true);   // timed = false: no event records between its stages
+// the two halves of launch_lml_grad, shared with the leave-one-out gradient (grad_kernels.hip): K^-1 = U U^T over the lower
+// tiles into d_W; the pairwise pass over d_W (loo_b == null: K^-1 and the LML's pair weight; else B and b, the LOO weight)
+hipError_t launch_kinv_product(Context &c);
+hipError_t launch_pair_sums(Context &c, bool ard, const double *loo_b, double *gout, bool timed);
+// leave-one-out cross-validation (loo_kernels.hip).  c.d_loov: [kappa | resid | sigma | lpd | p | sqrt(w) | b] (Np each), then
+// the (Np / LOO_ROWS, Np) partial column sums and the (2, Np / 256) sums of the points' workgroups; scal (device or
+// device-mapped): [L_LOO, count of kappa_i <= 0 or not finite]
+constexpr int LOO_ROWS = 256;                       // rows of Linv per chunk of the kappa kernel
+constexpr double LOO_LOG_2PI = 1.8378770664093453;  // log(2 pi)
+inline size_t loo_vec_doubles(int64_t Np) { return (size_t)(7 + Np / LOO_ROWS) * (size_t)Np + 2 * (size_t)(Np / 256); }
+hipError_t launch_loo_points(Context &c, double *scal);
+// behind a blocked fit: the gradient's sums into gout as launch_lml_grad leaves them; needs c.d_loov, c.d_looA (Np, Np)
+hipError_t launch_loo_grad(Context &c, bool ard, double *gout, double *scal, bool timed = true);
 hipError_t launch_f64_to_f32(Context &c, const double *in, float *out, long n);   // out[i] = (float)in[i] on c.stream (fit_kernels.hip: the cast every fit path uses)
 // N <= 128, Dp <= 64, behind launch_small_fit: one workgroup per block pair (1 or 3), workgroup g leaving
 // [S_c, S_iso, S_diag, gd[0..Dp)] for its pair at out + g * SMALL_GRAD_OUT_STRIDE; the caller adds them

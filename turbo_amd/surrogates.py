@@ -83,7 +83,7 @@ class HipGPSurrogate(Surrogate):
     }
 
     def __init__(self, model_params=None, training_iterations=None, param_continuity=True,
-                 dtype='f64', device=0, incremental=True, parallel_restarts_above='auto'):
+                 dtype='f64', device=0, incremental=True, parallel_restarts_above='auto', criterion='lml'):
         """
         Args:
             model_params (dict): see class docstring
@@ -111,7 +111,16 @@ class HipGPSurrogate(Surrogate):
                 N = 100 / 128 6.2 / 5.2 -> 5.8 / 4.8; below that the interpreter is the bottleneck and threads lose:
                 N = 32 3.7 -> 5.8).  None: never.  A
                 number: with more observations than that.
+            criterion: what the hyper-parameters maximise.  'lml' (default): the log marginal likelihood, as
+                scikit-learn does.  'loo': the leave-one-out log predictive density L_LOO (Rasmussen & Williams
+                section 5.4.2; ``tgp_fit_loo_grad``), the criterion that does not trust the kernel family: SciPy's
+                L-BFGS-B drives the GPU objective from Python for every ``optimizer`` but None (the in-library
+                optimisers know the LML only and are not used); ``fitting_info`` then carries 'criterion' and the
+                final 'loo'.
         """
+        if criterion not in ('lml', 'loo'):
+            raise ValueError("criterion must be 'lml' or 'loo'")
+        self.criterion = criterion
         _lib.load()   # fail loudly, now, when the native library is missing ...
         if _lib.HOST_ONLY:
             # ... or when only the host-only build could be loaded: that one serves RELOADED models
@@ -207,7 +216,17 @@ class HipGPSurrogate(Surrogate):
             # theta is log-transformed (surrogates.py:322-324)
             self._last_model_params = np.exp(kernel.theta.copy())
         fitting_info.update({'fit_ms': model.fit_ms})
+        if getattr(self, 'criterion', 'lml') == 'loo':
+            fitting_info.update({'criterion': 'loo', 'loo': model.get_loo_log_likelihood()})
         return model, fitting_info
+
+    def _criterion_grad(self, gp, k, X, y, jitter, normalize_y):
+        """(score, its gradient w.r.t. log(constant, length scale(s), noise)) of the model-selection criterion at the
+        hyper-parameters of kernel ``k``, on handle ``gp``: the one objective of every SciPy-driven route"""
+        if getattr(self, 'criterion', 'lml') == 'loo':
+            _, loo, grad = gp.fit_loo_grad(X, y, k.kind, k.constant, k.length_scale, k.noise_level, jitter, normalize_y)
+            return loo, grad
+        return gp.fit_grad(X, y, k.kind, k.constant, k.length_scale, k.noise_level, jitter, normalize_y)
 
     def _rng(self):
         # sklearn.utils.check_random_state(self.random_state), created per fit (_gpr.py:253)
@@ -231,8 +250,7 @@ class HipGPSurrogate(Surrogate):
             kernel.theta = theta
             count[0] += 1
             try:
-                lml, grad = ctx.fit_grad(X, y, kernel.kind, kernel.constant, kernel.length_scale,
-                                         kernel.noise_level, jitter, normalize_y)
+                lml, grad = self._criterion_grad(ctx, kernel, X, y, jitter, normalize_y)
             except np.linalg.LinAlgError:
                 # _gpr.py:586-589: not PD -> -inf likelihood, zero gradient
                 return (np.inf, np.zeros_like(theta)) if eval_gradient else np.inf
@@ -251,13 +269,13 @@ class HipGPSurrogate(Surrogate):
             raise ValueError('Unknown optimizer {}.'.format(optimizer))
 
         bounds = kernel.theta_bounds
-        if optimizer in ('device', 'fmin_l_bfgs_b'):
+        if optimizer in ('device', 'fmin_l_bfgs_b') and getattr(self, 'criterion', 'lml') == 'lml':   # (the library's optimisers maximise the LML)
             done = self._optimise_in_library(ctx, kernel, X, y, jitter, normalize_y, bounds, n_restarts,
                                              lbfgsb=optimizer == 'fmin_l_bfgs_b')
             if done is not None:
                 return done
         if optimizer in ('device', 'scipy'):
-            optimizer = 'fmin_l_bfgs_b'      # (or: unbounded theta) SciPy drives tgp_fit_grad
+            optimizer = 'fmin_l_bfgs_b'      # (or: unbounded theta, criterion='loo') SciPy drives tgp_fit_grad / tgp_fit_loo_grad
         starts = [kernel.theta.copy()]
         if n_restarts > 0:
             if not np.isfinite(bounds).all():
@@ -315,7 +333,7 @@ class HipGPSurrogate(Surrogate):
                 k.theta = theta
                 evals[j] += 1
                 try:
-                    lml, grad = w.fit_grad(X, y, k.kind, k.constant, k.length_scale, k.noise_level, jitter, normalize_y)
+                    lml, grad = self._criterion_grad(w, k, X, y, jitter, normalize_y)
                 except np.linalg.LinAlgError:
                     return np.inf, np.zeros_like(theta)      # _gpr.py:586-589
                 return -lml, -k.select_gradient(grad)
@@ -585,6 +603,18 @@ class HipGPSurrogate(Surrogate):
                 self._ensure_resident()
             return self.log_likelihood
 
+        def loo(self):
+            """Leave-one-out cross-validation in closed form (``tgp_loo``): ``(mu_loo (N,), sigma_loo (N,))`` in raw
+            units -- the mean and the deviation of the prediction of every training observation from the other N - 1,
+            with the hyper-parameters and the normalisation of y held.  sigma_loo is the deviation of the held-out
+            OBSERVATION (noise and jitter inside).  Works on a reloaded instance where no GPU is visible."""
+            r = self._ensure_resident().loo()
+            return self.y - r['resid'], r['sigma']
+
+        def get_loo_log_likelihood(self):
+            """L_LOO, the sum of the leave-one-out log predictive densities, in the units of get_log_likelihood"""
+            return self._ensure_resident().loo()['loo']
+
         def __getstate__(self):
             return dict(self.__dict__)
 
@@ -606,6 +636,8 @@ class MarginalisedHipGPSurrogate(HipGPSurrogate):
 
     def __init__(self, *args, n_hyper_samples=8, burn=20, thin=5, hyper_seed=None, **kwargs):
         super().__init__(*args, **kwargs)
+        if self.criterion == 'loo':
+            raise ValueError("criterion='loo' is a point estimate's criterion: the marginalised surrogate samples exp(LML)")
         n_hyper_samples, burn, thin = int(n_hyper_samples), int(burn), int(thin)
         if n_hyper_samples < 1 or n_hyper_samples > 64:
             raise ValueError('n_hyper_samples must be in [1, 64]')
