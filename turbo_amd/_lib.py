@@ -356,6 +356,40 @@ def _f64c(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _bounds(lo, hi, D=None):
+    """the box as two contiguous float64 vectors; with D, one entry per dimension or an AssertionError"""
+    lo, hi = _f64c(lo).reshape(-1), _f64c(hi).reshape(-1)
+    assert D is None or lo.shape == hi.shape == (D,), "bounds must have one entry per dimension"
+    return lo, hi
+
+
+def _pending(pending, D):
+    """the pending points of a batch selection as (Xp (P, D) or None, P); nothing pending: (None, 0)"""
+    Xp = None if pending is None else _f64c(np.atleast_2d(pending))
+    if Xp is None or Xp.size == 0:
+        return None, 0
+    assert Xp.ndim == 2 and Xp.shape[1] == D, "pending points must be (P, %d)" % D
+    return Xp, Xp.shape[0]
+
+
+class _SweepOut:
+    """what tgp_sweep / tgp_evaluate / tgp_sweep_integrated write: the (M,) vectors asked for and the winner"""
+
+    def __init__(self, M, want_mu, want_sigma, want_acq):
+        self.mu = np.empty(M) if want_mu else None
+        self.sg = np.empty(M) if want_sigma else None
+        self.aq = np.empty(M) if want_acq else None
+        self.bv, self.bi, self.nc = ctypes.c_double(float("nan")), ctypes.c_int64(-1), ctypes.c_int64(0)
+
+    def args(self):
+        return (_ptr(self.mu), _ptr(self.sg), _ptr(self.aq), ctypes.byref(self.bv), ctypes.byref(self.bi),
+                ctypes.byref(self.nc))
+
+    def result(self, **extra):
+        return dict(mu=self.mu, sigma=self.sg, acq=self.aq, best_val=self.bv.value, best_idx=self.bi.value,
+                    n_clamped=self.nc.value, **extra)
+
+
 class NativeGP:
     """One GPU context (tgp_handle).  Thin, stateful, not thread-safe per handle.
     ``device=DEVICE_HOST`` makes a host context instead (``self.host``): fit / predict / acquisition of
@@ -460,17 +494,22 @@ class NativeGP:
             raise MemoryError(msg)
         raise TurboGPLibraryError(msg)
 
-    def fit(self, X, y, kind, constant, length_scale, noise, jitter, normalize_y, append=False):
-        """full fit, or (append=True) a one-row extension of the resident factor when X is the
-        resident training set plus one row; ``self.appended`` tells which path ran"""
+    def _fit_args(self, X, y, kind, constant, length_scale, noise, jitter, normalize_y):
+        """what tgp_fit, tgp_fit_append, tgp_fit_grad and tgp_fit_loo_grad share: (X, number of length scales, their
+        common argument list, the (lml, y_mean, y_std) doubles it points at)"""
         X = _f64c(X)
         y = _f64c(y).reshape(-1)
         assert X.ndim == 2 and X.shape[0] == y.shape[0], "X must be (N, D) and y (N,)"
         ls = _f64c(np.atleast_1d(length_scale))
-        lml, ym, ys = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
-        args = (self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(y), KERNELS[kind], float(constant),
-                _ptr(ls), ls.shape[0], float(noise), float(jitter), 1 if normalize_y else 0,
-                ctypes.byref(lml), ctypes.byref(ym), ctypes.byref(ys))
+        out = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        return X, ls.shape[0], (self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(y), KERNELS[kind], float(constant),
+                                _ptr(ls), ls.shape[0], float(noise), float(jitter), 1 if normalize_y else 0,
+                                *map(ctypes.byref, out)), out
+
+    def fit(self, X, y, kind, constant, length_scale, noise, jitter, normalize_y, append=False):
+        """full fit, or (append=True) a one-row extension of the resident factor when X is the
+        resident training set plus one row; ``self.appended`` tells which path ran"""
+        X, _, args, (lml, ym, ys) = self._fit_args(X, y, kind, constant, length_scale, noise, jitter, normalize_y)
         self.appended = False
         if append:
             flag = ctypes.c_int(0)
@@ -484,17 +523,10 @@ class NativeGP:
 
     def fit_grad(self, X, y, kind, constant, length_scale, noise, jitter, normalize_y):
         """fit + d LML / d log(theta): returns (lml, grad [c, ls..., noise])"""
-        X = _f64c(X)
-        y = _f64c(y).reshape(-1)
-        assert X.ndim == 2 and X.shape[0] == y.shape[0], "X must be (N, D) and y (N,)"
-        ls = _f64c(np.atleast_1d(length_scale))
-        lml, ym, ys = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
-        grad = np.zeros(2 + ls.shape[0])
+        X, n_ls, args, (lml, _, _) = self._fit_args(X, y, kind, constant, length_scale, noise, jitter, normalize_y)
+        grad = np.zeros(2 + n_ls)
         self.fit_gen += 1
-        self._check(self.lib.tgp_fit_grad(
-            self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(y), KERNELS[kind], float(constant),
-            _ptr(ls), ls.shape[0], float(noise), float(jitter), 1 if normalize_y else 0,
-            ctypes.byref(lml), ctypes.byref(ym), ctypes.byref(ys), _ptr(grad)))
+        self._check(self.lib.tgp_fit_grad(*args, _ptr(grad)))
         self.N, self.D = X.shape
         return lml.value, grad
 
@@ -510,17 +542,11 @@ class NativeGP:
 
     def fit_loo_grad(self, X, y, kind, constant, length_scale, noise, jitter, normalize_y):
         """fit + the leave-one-out score and d L_LOO / d log(theta): returns (lml, loo, grad [c, ls..., noise])"""
-        X = _f64c(X)
-        y = _f64c(y).reshape(-1)
-        assert X.ndim == 2 and X.shape[0] == y.shape[0], "X must be (N, D) and y (N,)"
-        ls = _f64c(np.atleast_1d(length_scale))
-        lml, ym, ys, loo = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
-        grad = np.zeros(2 + ls.shape[0])
+        X, n_ls, args, (lml, _, _) = self._fit_args(X, y, kind, constant, length_scale, noise, jitter, normalize_y)
+        loo = ctypes.c_double()
+        grad = np.zeros(2 + n_ls)
         self.fit_gen += 1
-        self._check(self.lib.tgp_fit_loo_grad(
-            self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(y), KERNELS[kind], float(constant),
-            _ptr(ls), ls.shape[0], float(noise), float(jitter), 1 if normalize_y else 0,
-            ctypes.byref(lml), ctypes.byref(ym), ctypes.byref(ys), ctypes.byref(loo), _ptr(grad)))
+        self._check(self.lib.tgp_fit_loo_grad(*args, ctypes.byref(loo), _ptr(grad)))
         self.N, self.D = X.shape
         return lml.value, loo.value, grad
 
@@ -595,18 +621,13 @@ class NativeGP:
         y = _f64c(y).reshape(-1)
         thetas = _f64c(np.atleast_2d(thetas))
         assert thetas.shape[1] == 2 + int(n_ls), "thetas must be (S, 2 + n_ls)"
-        M = getattr(self, "M", 0)
-        mu = np.empty(M) if want_mu else None
-        sg = np.empty(M) if want_sigma else None
-        aq = np.empty(M) if want_acq else None
-        bv, bi, nc = ctypes.c_double(float("nan")), ctypes.c_int64(-1), ctypes.c_int64(0)
+        out = _SweepOut(getattr(self, "M", 0), want_mu, want_sigma, want_acq)
         self.fit_gen += 1
         self._check(self.lib.tgp_sweep_integrated(
             self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(y), KERNELS[kind], _ptr(thetas), thetas.shape[0], int(n_ls),
-            float(jitter), 1 if normalize_y else 0, int(acq), float(sf), float(incumbent), float(param),
-            _ptr(mu), _ptr(sg), _ptr(aq), ctypes.byref(bv), ctypes.byref(bi), ctypes.byref(nc)))
+            float(jitter), 1 if normalize_y else 0, int(acq), float(sf), float(incumbent), float(param), *out.args()))
         self.N, self.D = X.shape
-        return dict(mu=mu, sigma=sg, acq=aq, best_val=bv.value, best_idx=bi.value, n_clamped=nc.value)
+        return out.result()
 
     def export_state(self):
         """bytes that define the fitted model (theta, X, y) -- see tgp_export_state"""
@@ -649,13 +670,18 @@ class NativeGP:
         self._check(self.lib.tgp_debug_read(self._h, which, _ptr(out)))
         return out
 
+    def _batch_is(self, M, keepalive=None, gen_key=None):
+        """the resident batch changed: its row count, what keeps a caller's device memory alive, and -- when the GPU
+        generated it -- what it IS (``generate``'s key; None: not a generated batch, so nothing to find again)"""
+        self.M = int(M)
+        self._cand_keepalive = keepalive
+        self.gen_key = gen_key
+
     def set_candidates(self, Xc):
         Xc = _f64c(Xc)
         assert Xc.ndim == 2 and Xc.shape[1] == self.D, "candidates must be (M, %d)" % self.D
         self._check(self.lib.tgp_set_candidates(self._h, _ptr(Xc), Xc.shape[0]))
-        self.M = Xc.shape[0]
-        self._cand_keepalive = None
-        self.gen_key = None
+        self._batch_is(Xc.shape[0])
 
     def set_candidates_numpy_stream(self, M, lo, hi, first=0, count=None):
         """make resident the batch ``np.hstack([np.random.uniform(l, h, size=(M, 1)) for l, h in zip(lo, hi)])`` -- the
@@ -667,7 +693,7 @@ class NativeGP:
 
         ``first`` / ``count``: keep only rows [first, first + count) of that M-row batch resident -- a rank's shard of ONE
         batch -- while ``np.random`` still ends behind the whole batch (the other rows' numbers are passed over)."""
-        lo, hi = _f64c(lo).reshape(-1), _f64c(hi).reshape(-1)
+        lo, hi = _bounds(lo, hi)
         count = int(M) - int(first) if count is None else int(count)
         if getattr(self, "host", False) or HOST_ONLY or lo.shape != (self.D,) or hi.shape != (self.D,) or int(M) < 1:
             return False
@@ -685,42 +711,42 @@ class NativeGP:
             self._check(self.lib.tgp_set_candidates_mt19937(self._h, key.ctypes.data_as(_vp), ctypes.byref(pos), int(M), int(first), count,
                                                             _ptr(lo), _ptr(hi)))
             np.random.set_state((st[0], key, int(pos.value), st[3], st[4]))
-        self.M = count
-        self._cand_keepalive = None
-        self.gen_key = None
+        self._batch_is(count)
         return True
 
     def set_candidates_dev(self, dev_ptr, M, keepalive=None):
         self._check(self.lib.tgp_set_candidates_dev(self._h, _vp(int(dev_ptr)), int(M)))
-        self.M = int(M)
-        self._cand_keepalive = keepalive
-        self.gen_key = None
+        self._batch_is(M, keepalive=keepalive)
+
+    def generate(self, seed, first, M, lo, hi, lhs_total=None, reuse=False):
+        """The resident batch drawn ON the GPU, uniform or (``lhs_total`` given) rows first .. + M of an lhs_total-point
+        Latin hypercube: the one place that says what such a batch IS (``gen_key``) and how it is drawn.  ``reuse=True``
+        leaves a batch alone that is this very one already (the previous call prefetched it).  Returns whether it drew."""
+        lo, hi = _bounds(lo, hi, self.D)
+        lhs = lhs_total is not None
+        key = ("lhs" if lhs else "uniform", int(seed), int(first), int(M), int(lhs_total) if lhs else None,
+               lo.tobytes(), hi.tobytes())
+        if reuse and self.gen_key == key:
+            return False
+        if lhs:
+            self._check(self.lib.tgp_gen_candidates_lhs(self._h, int(seed), int(first), int(M), int(lhs_total), _ptr(lo), _ptr(hi)))
+        else:
+            self._check(self.lib.tgp_gen_candidates(self._h, int(seed), int(first), int(M), _ptr(lo), _ptr(hi)))
+        self._batch_is(M, gen_key=key)
+        return True
 
     def gen_candidates(self, seed, first_candidate, M, lo, hi):
         """M uniform candidates in [lo, hi) drawn on the GPU (Philox-4x32-10 stream `seed`)"""
-        lo, hi = _f64c(lo).reshape(-1), _f64c(hi).reshape(-1)
-        assert lo.shape == hi.shape == (self.D,), "bounds must have one entry per dimension"
-        self._check(self.lib.tgp_gen_candidates(self._h, int(seed), int(first_candidate), int(M),
-                                                _ptr(lo), _ptr(hi)))
-        self.M = int(M)
-        self._cand_keepalive = None
-        self.gen_key = ("uniform", int(seed), int(first_candidate), int(M), None, lo.tobytes(), hi.tobytes())
+        self.generate(seed, first_candidate, M, lo, hi)
 
     def gen_candidates_lhs(self, seed, first_sample, M, n_total, lo, hi):
-        """rows first_sample .. + M of an n_total-point Latin hypercube design drawn on the GPU become
-        the resident batch"""
-        lo, hi = _f64c(lo).reshape(-1), _f64c(hi).reshape(-1)
-        assert lo.shape == hi.shape == (self.D,), "bounds must have one entry per dimension"
-        self._check(self.lib.tgp_gen_candidates_lhs(self._h, int(seed), int(first_sample), int(M),
-                                                    int(n_total), _ptr(lo), _ptr(hi)))
-        self.M = int(M)
-        self._cand_keepalive = None
-        self.gen_key = ("lhs", int(seed), int(first_sample), int(M), int(n_total), lo.tobytes(), hi.tobytes())
+        """rows first_sample .. + M of an n_total-point Latin hypercube design drawn on the GPU become the resident batch"""
+        self.generate(seed, first_sample, M, lo, hi, lhs_total=n_total)
 
     def lhs_design(self, seed, first_sample, M, n_total, lo, hi):
         """(M, D) rows of an n_total-point Latin hypercube design, drawn on the GPU, as a host array
         (no fitted model needed)"""
-        lo, hi = _f64c(lo).reshape(-1), _f64c(hi).reshape(-1)
+        lo, hi = _bounds(lo, hi)
         assert lo.shape == hi.shape and lo.ndim == 1
         out = np.empty((int(M), lo.shape[0]))
         self.gen_key = None      # the design overwrites the handle's own batch: a generated batch is no longer resident
@@ -741,16 +767,9 @@ class NativeGP:
 
     def sweep(self, acq=ACQ_NONE, sf=1.0, incumbent=0.0, param=0.0, want_mu=False,
               want_sigma=False, want_acq=False):
-        M = self.M
-        mu = np.empty(M) if want_mu else None
-        sg = np.empty(M) if want_sigma else None
-        aq = np.empty(M) if want_acq else None
-        bv, bi, nc = ctypes.c_double(float("nan")), ctypes.c_int64(-1), ctypes.c_int64(0)
-        self._check(self.lib.tgp_sweep(self._h, acq, float(sf), float(incumbent), float(param),
-                                       _ptr(mu), _ptr(sg), _ptr(aq), ctypes.byref(bv),
-                                       ctypes.byref(bi), ctypes.byref(nc)))
-        return dict(mu=mu, sigma=sg, acq=aq, best_val=bv.value, best_idx=bi.value,
-                    n_clamped=nc.value, sweep_ms=self.profile_read()['last_sweep_ms'])
+        out = _SweepOut(self.M, want_mu, want_sigma, want_acq)
+        self._check(self.lib.tgp_sweep(self._h, acq, float(sf), float(incumbent), float(param), *out.args()))
+        return out.result(sweep_ms=self.profile_read()['last_sweep_ms'])
 
     def sweep_batch(self, q, strategy=BATCH_KB, lie=0.0, pending=None, acq=ACQ_EI, sf=1.0, incumbent=0.0, param=0.0,
                     want_posterior=False):
@@ -758,12 +777,7 @@ class NativeGP:
         on the pending points (P, D) first.  Returns a dict: idx (q,), val (q,), x (q, D), fantasies (P + q,) pending
         first, mu / sigma (M,) after all P + q points (want_posterior) or None, n_clamped"""
         q = int(q)
-        Xp = None if pending is None else _f64c(np.atleast_2d(pending))
-        if Xp is not None and Xp.size == 0:
-            Xp = None
-        P = 0 if Xp is None else Xp.shape[0]
-        if Xp is not None:
-            assert Xp.ndim == 2 and Xp.shape[1] == self.D, "pending points must be (P, %d)" % self.D
+        Xp, P = _pending(pending, self.D)
         idx = np.empty(max(q, 1), dtype=np.int64)
         val = np.empty(max(q, 1))
         x = np.empty((max(q, 1), self.D))
@@ -786,12 +800,7 @@ class NativeGP:
         (q, M) every step's averaged acquisition (want_acq) or None, sigma (M,) after all points (want_sigma) or None,
         n_clamped"""
         q, S = int(q), int(n_sim)
-        Xp = None if pending is None else _f64c(np.atleast_2d(pending))
-        if Xp is not None and Xp.size == 0:
-            Xp = None
-        P = 0 if Xp is None else Xp.shape[0]
-        if Xp is not None:
-            assert Xp.ndim == 2 and Xp.shape[1] == self.D, "pending points must be (P, %d)" % self.D
+        Xp, P = _pending(pending, self.D)
         J, Sa = max(P + q, 1), max(S, 1)
         if eps is not None:
             eps = _f64c(np.asarray(eps, dtype=np.float64))
@@ -906,8 +915,7 @@ class NativeGP:
         batched evaluation per round); returns (x (R, D), values (R,), status (R,), evaluations)"""
         X0 = _f64c(np.atleast_2d(X0))
         assert X0.ndim == 2 and X0.shape[1] == self.D, "start points must be (R, %d)" % self.D
-        lo, hi = _f64c(lo).reshape(-1), _f64c(hi).reshape(-1)
-        assert lo.shape == hi.shape == (self.D,), "bounds must have one entry per dimension"
+        lo, hi = _bounds(lo, hi, self.D)
         R = X0.shape[0]
         x = np.empty((R, self.D))
         v = np.empty(R)
@@ -937,19 +945,11 @@ class NativeGP:
         """set_candidates + sweep in ONE call (tgp_evaluate); same result dict as ``sweep``"""
         Xc = _f64c(Xc)
         assert Xc.ndim == 2 and Xc.shape[1] == self.D, "candidates must be (M, %d)" % self.D
-        M = Xc.shape[0]
-        mu = np.empty(M) if want_mu else None
-        sg = np.empty(M) if want_sigma else None
-        aq = np.empty(M) if want_acq else None
-        bv, bi, nc = ctypes.c_double(float("nan")), ctypes.c_int64(-1), ctypes.c_int64(0)
-        self._check(self.lib.tgp_evaluate(self._h, _ptr(Xc), M, acq, float(sf), float(incumbent),
-                                          float(param), _ptr(mu), _ptr(sg), _ptr(aq),
-                                          ctypes.byref(bv), ctypes.byref(bi), ctypes.byref(nc)))
-        self.M = M
-        self._cand_keepalive = None
-        self.gen_key = None
-        return dict(mu=mu, sigma=sg, acq=aq, best_val=bv.value, best_idx=bi.value,
-                    n_clamped=nc.value, sweep_ms=self.profile_read()['last_sweep_ms'])
+        out = _SweepOut(Xc.shape[0], want_mu, want_sigma, want_acq)
+        self._check(self.lib.tgp_evaluate(self._h, _ptr(Xc), Xc.shape[0], acq, float(sf), float(incumbent), float(param),
+                                          *out.args()))
+        self._batch_is(Xc.shape[0])
+        return out.result(sweep_ms=self.profile_read()['last_sweep_ms'])
 
     def predict_batch(self, models, Xc, want_sigma=True):
         """T stored models (N <= 256, same kernel kind / D / normalize_y) x one batch of points in one

@@ -44,6 +44,35 @@ def _require_native(model, what):
                         .format(what, type(model)))
 
 
+GOLDEN = 0x9E3779B97F4A7C15
+
+
+def _trial_seed(seed, trial_num):
+    """the seed trial ``trial_num`` draws with (TS, MES): ``(seed + trial_num * GOLDEN) mod 2**64``; ``seed`` None takes
+    one ``np.random.randint(0, 2**63)`` from NumPy's global RNG per trial"""
+    base = int(np.random.randint(0, 2**63)) if seed is None else int(seed)
+    return (base + int(trial_num) * GOLDEN) % (1 << 64)
+
+
+def _checked_n_features(n_features):
+    n_features = int(n_features)
+    if n_features < 64 or n_features > 16384 or n_features % 64 != 0:
+        raise ValueError('n_features must be a multiple of 64 in [64, 16384]')
+    return n_features
+
+
+def topk_tail(idx, vals, ranked_only=False):
+    """a top-k as the library fills it (index -1 where nothing ranked; ``ranked_only``: those slots are gone already) ->
+    (top = (indices, values) of the ranked slots, the winner's index, its value); nothing ranked (an all-NaN batch):
+    index 0 and -inf, as ``maximise`` reports it"""
+    if not ranked_only:
+        keep = idx >= 0
+        idx, vals = idx[keep], vals[keep]
+    if len(idx) > 0:
+        return (idx, vals), int(idx[0]), float(vals[0])
+    return (idx, vals), 0, -np.inf
+
+
 def _from_mu_sigma(acq, sf, incumbent, param, mu, sigma):
     """UCB / PI / EI / sigma from a foreign model's posterior, float64 on the host
     (turbo/modules/acquisition_functions.py:147-158, :225-247, :336-358):
@@ -93,11 +122,19 @@ class AcquisitionFunction:
             """(acq enum, incumbent, param)"""
             raise NotImplementedError()
 
+        def _prepare(self, X=None):
+            """Hook: called by every method below once the model is known to be native and before the library sweeps,
+            evaluates or refines -- X: the points about to be handed over, None: the batch already resident.  Returns X
+            as the method is to pass it on.  Nothing to do here; ``MES`` puts its maxima into the context."""
+            return X
+
         def __call__(self, X):
             acq, incumbent, param = self._native_args()
             if not _is_native(self.model):
                 mu, sigma = self.model.predict(X, return_std_dev=True)
                 return _from_mu_sigma(acq, self.scale_factor, incumbent, param, mu, sigma)
+            if np.size(X) > 0:      # (an empty batch has nothing to prepare for: empty results, nothing launched)
+                X = self._prepare(X)
             res = self.model._sweep(X, acq, self.scale_factor, incumbent, param, want_acq=True,
                                     want_sigma=False)
             return res['acq']
@@ -134,7 +171,7 @@ class AcquisitionFunction:
                 vals = np.where(np.isnan(vals), -np.inf, vals)      # NaN never wins, as on the GPU
                 i = int(np.argmax(vals))                            # first maximum = lowest index
                 return i, float(vals[i])
-            res = self.model._sweep(X, acq, self.scale_factor, incumbent, param)
+            res = self.model._sweep(self._prepare(X), acq, self.scale_factor, incumbent, param)
             self.last_sweep_ms = res.get('sweep_ms')
             return res['best_idx'], res['best_val']
 
@@ -143,11 +180,10 @@ class AcquisitionFunction:
             the (M,) acquisition vector stays on the GPU (``tgp_sweep_topk``)"""
             _require_native(self.model, 'maximise_topk')
             acq, incumbent, param = self._native_args()
+            X = self._prepare(X)
             ctx = self.model._ensure_resident()
             ctx.set_candidates(X)
-            idx, vals = ctx.sweep_topk(min(int(k), 64), acq, self.scale_factor, incumbent, param)
-            keep = idx >= 0
-            return idx[keep], vals[keep]
+            return topk_tail(*ctx.sweep_topk(min(int(k), 64), acq, self.scale_factor, incumbent, param))[0]
 
         BATCH_STRATEGIES = {'kriging_believer': _lib.BATCH_KB, 'constant_liar': _lib.BATCH_CL}
 
@@ -175,21 +211,13 @@ class AcquisitionFunction:
             if strategy != 'monte_carlo' and strategy not in self.BATCH_STRATEGIES:
                 raise ValueError('strategy must be one of {}'.format(sorted(list(self.BATCH_STRATEGIES) + ['monte_carlo'])))
             acq, incumbent, param = self._native_args()
-            if strategy == 'monte_carlo':
+            monte_carlo, lie_value = strategy == 'monte_carlo', 0.0
+            if monte_carlo:
                 n_sim = int(n_sim)
                 if n_sim < 1 or n_sim > 64:
                     raise ValueError('n_sim must be in [1, 64]')
                 seed = int(np.random.randint(0, 2**63)) if seed is None else int(seed) % (1 << 64)
-                ctx = self.model._ensure_resident()
-                if X is not None:
-                    ctx.set_candidates(np.asarray(X, dtype=np.float64))
-                res = ctx.sweep_batch_mc(q, n_sim, seed, None, pending, acq, self.scale_factor, incumbent, param,
-                                         want_sigma=want_posterior)
-                self.last_sweep_ms = res.get('sweep_ms')
-                res['n_sim'], res['seed'] = n_sim, seed
-                return res
-            lie_value = 0.0
-            if strategy == 'constant_liar':
+            elif strategy == 'constant_liar':
                 y = np.asarray(self.model.y, dtype=np.float64)
                 if isinstance(lie, str):
                     if lie not in ('min', 'max', 'mean'):
@@ -200,10 +228,15 @@ class AcquisitionFunction:
             ctx = self.model._ensure_resident()
             if X is not None:
                 ctx.set_candidates(np.asarray(X, dtype=np.float64))
-            res = ctx.sweep_batch(q, self.BATCH_STRATEGIES[strategy], lie_value, pending, acq, self.scale_factor,
-                                  incumbent, param, want_posterior=want_posterior)
+            if monte_carlo:
+                res = ctx.sweep_batch_mc(q, n_sim, seed, None, pending, acq, self.scale_factor, incumbent, param,
+                                         want_sigma=want_posterior)
+                res['n_sim'], res['seed'] = n_sim, seed
+            else:
+                res = ctx.sweep_batch(q, self.BATCH_STRATEGIES[strategy], lie_value, pending, acq, self.scale_factor,
+                                      incumbent, param, want_posterior=want_posterior)
+                res['lie'] = lie_value if strategy == 'constant_liar' else None
             self.last_sweep_ms = res.get('sweep_ms')
-            res['lie'] = lie_value if strategy == 'constant_liar' else None
             return res
 
         def refine(self, starting_points, bounds, max_iter=200):
@@ -228,6 +261,7 @@ class AcquisitionFunction:
             (x (R, D), values (R,), status (R,): 1 = SciPy's success, evaluations)"""
             _require_native(self.model, 'lbfgsb')
             acq, incumbent, param = self._native_args()
+            self._prepare(starting_points)
             ctx = self.model._ensure_resident()
             low, high = zip(*bounds)
             return ctx.acq_refine(starting_points, low, high, acq, self.scale_factor, incumbent, param, max_iter,
@@ -259,6 +293,7 @@ class AcquisitionFunction:
             if _is_marginalised(self.model):      # the mean of the samples' closed forms
                 return self.model.value_and_grad(X, acq, self.scale_factor, incumbent, param)
             _require_native(self.model, 'value_and_grad')
+            X = self._prepare(X)
             ctx = self.model._ensure_resident()
             return ctx.acq_grad(X, acq, self.scale_factor, incumbent, param)
 
@@ -277,13 +312,10 @@ class AcquisitionFunction:
             ctx = self.model._ensure_resident()
             if not hasattr(ctx, 'set_candidates_numpy_stream') or not ctx.set_candidates_numpy_stream(num_points, low, high, first=first, count=count):
                 return None
+            self._prepare(None)
             if topk > 0:
-                idx, vals = ctx.sweep_topk(min(int(topk), 64), acq, self.scale_factor, incumbent, param)
-                keep = idx >= 0
-                top = (idx[keep], vals[keep])
-                if len(top[0]) > 0:
-                    return ctx, int(top[0][0]), float(top[1][0]), top
-                return ctx, 0, -np.inf, top      # nothing ranked (an all-NaN batch): index 0, as maximise reports it
+                top, best_i, best_y = topk_tail(*ctx.sweep_topk(min(int(topk), 64), acq, self.scale_factor, incumbent, param))
+                return ctx, best_i, best_y, top
             res = ctx.sweep(acq, self.scale_factor, incumbent, param)
             self.last_sweep_ms = res.get('sweep_ms')
             return ctx, res['best_idx'], res['best_val'], None
@@ -307,18 +339,8 @@ class AcquisitionFunction:
             else:
                 _require_native(self.model, 'maximise_generated')
                 ctx = self.model._ensure_resident()
-
-            def draw(sd):
-                if lhs_total is not None:
-                    ctx.gen_candidates_lhs(sd, first_candidate, num_points, lhs_total, low, high)
-                else:
-                    ctx.gen_candidates(sd, first_candidate, num_points, low, high)
-
-            lo_b, hi_b = np.asarray(low, dtype=np.float64).tobytes(), np.asarray(high, dtype=np.float64).tobytes()
-            key = ("lhs" if lhs_total is not None else "uniform", int(seed), int(first_candidate), int(num_points),
-                   int(lhs_total) if lhs_total is not None else None, lo_b, hi_b)
-            if getattr(ctx, 'gen_key', None) != key:      # (resident already when the previous call prefetched it)
-                draw(seed)
+            # (resident already when the previous call prefetched it)
+            ctx.generate(seed, first_candidate, num_points, low, high, lhs_total, reuse=True)
             if marginalised:      # the resident batch under every hyper-parameter sample (tgp_sweep_integrated)
                 res = self.model._integrated(ctx, acq, self.scale_factor, incumbent, param, False, False, False)
                 return ctx.get_candidate(res['best_idx']), res['best_val'], res['best_idx']
@@ -326,8 +348,8 @@ class AcquisitionFunction:
             self.last_sweep_ms = res.get('sweep_ms')
             best = ctx.get_candidate(res['best_idx']), res['best_val'], res['best_idx']
             if prefetch_seed is not None and hasattr(ctx, 'set_overlap') and not getattr(ctx, 'host', False):
-                draw(prefetch_seed)
-                ctx.prefetched = True      # ModelInstance._ensure_resident arms tgp_set_overlap for the next fit
+                ctx.generate(prefetch_seed, first_candidate, num_points, low, high, lhs_total)
+                ctx.prefetched = True     # ModelInstance._ensure_resident arms tgp_set_overlap for the next fit
             return best
 
 
@@ -360,9 +382,10 @@ class UCB(AcquisitionFunction):
             return _lib.ACQ_UCB, 0.0, self.beta
 
 
-class PI(AcquisitionFunction):
+class _Improvement(AcquisitionFunction):
+    """PI and EI: xi (a constant float or a function of the trial number) against the incumbent's cost"""
+
     def __init__(self, xi):
-        """xi: a constant float or a function of the trial number (:164-170)"""
         self.xi = xi
 
     def get_type(self):
@@ -371,49 +394,37 @@ class PI(AcquisitionFunction):
     def construct_function(self, trial_num, model, desired_extremum, incumbent_cost):
         xi = self.xi(trial_num) if callable(self.xi) else self.xi
         acq_info = {'xi': xi}
-        return PI.FunctionInstance(model, desired_extremum, incumbent_cost, xi), acq_info
+        return self.FunctionInstance(model, desired_extremum, incumbent_cost, xi), acq_info
 
     class FunctionInstance(AcquisitionFunction.FunctionInstance):
+        NAME = ACQ = None       # what PI.FunctionInstance and EI.FunctionInstance differ in
+
+        def __init__(self, model, desired_extremum, incumbent_cost, xi):
+            super().__init__(model, desired_extremum)
+            self.incumbent_cost = incumbent_cost
+            self.xi = xi
+
+        def get_name(self):
+            return self.NAME
+
+        def _native_args(self):
+            return self.ACQ, self.incumbent_cost, self.xi
+
+
+class PI(_Improvement):
+    """xi: a constant float or a function of the trial number (:164-170)"""
+
+    class FunctionInstance(_Improvement.FunctionInstance):
         """Phi((sf * (mu - f+) - xi) / sigma), 0 where sigma == 0  (:225-247)"""
-
-        def __init__(self, model, desired_extremum, incumbent_cost, xi):
-            super().__init__(model, desired_extremum)
-            self.incumbent_cost = incumbent_cost
-            self.xi = xi
-
-        def get_name(self):
-            return 'PI'
-
-        def _native_args(self):
-            return _lib.ACQ_PI, self.incumbent_cost, self.xi
+        NAME, ACQ = 'PI', _lib.ACQ_PI
 
 
-class EI(AcquisitionFunction):
-    def __init__(self, xi):
-        """xi: a constant float or a function of the trial number (:251-257)"""
-        self.xi = xi
+class EI(_Improvement):
+    """xi: a constant float or a function of the trial number (:251-257)"""
 
-    def get_type(self):
-        return 'improvement'
-
-    def construct_function(self, trial_num, model, desired_extremum, incumbent_cost):
-        xi = self.xi(trial_num) if callable(self.xi) else self.xi
-        acq_info = {'xi': xi}
-        return EI.FunctionInstance(model, desired_extremum, incumbent_cost, xi), acq_info
-
-    class FunctionInstance(AcquisitionFunction.FunctionInstance):
+    class FunctionInstance(_Improvement.FunctionInstance):
         """diff * Phi(Z) + sigma * phi(Z), 0 where sigma == 0  (:336-358)"""
-
-        def __init__(self, model, desired_extremum, incumbent_cost, xi):
-            super().__init__(model, desired_extremum)
-            self.incumbent_cost = incumbent_cost
-            self.xi = xi
-
-        def get_name(self):
-            return 'EI'
-
-        def _native_args(self):
-            return _lib.ACQ_EI, self.incumbent_cost, self.xi
+        NAME, ACQ = 'EI', _lib.ACQ_EI
 
 
 class TS(AcquisitionFunction):
@@ -426,14 +437,11 @@ class TS(AcquisitionFunction):
     2**64``; ``seed=None`` takes one ``np.random.randint(0, 2**63)`` from NumPy's global RNG per trial, so a seeded run
     stays reproducible."""
 
-    GOLDEN = 0x9E3779B97F4A7C15
+    GOLDEN = GOLDEN
 
     def __init__(self, seed=None, n_features=2048):
-        n_features = int(n_features)
-        if n_features < 64 or n_features > 16384 or n_features % 64 != 0:
-            raise ValueError('n_features must be a multiple of 64 in [64, 16384]')
+        self.n_features = _checked_n_features(n_features)
         self.seed = seed
-        self.n_features = n_features
 
     def get_type(self):
         return 'optimism'
@@ -443,8 +451,7 @@ class TS(AcquisitionFunction):
         if not _is_native(model):
             raise NotImplementedError('TS draws its sample paths on the GPU: it needs a model built by HipGPSurrogate '
                                       '(got {!r})'.format(type(model)))
-        base = int(np.random.randint(0, 2**63)) if self.seed is None else int(self.seed)
-        seed = (base + int(trial_num) * TS.GOLDEN) % (1 << 64)
+        seed = _trial_seed(self.seed, trial_num)
         acq_info = {'seed': seed, 'n_features': self.n_features}
         return TS.FunctionInstance(model, desired_extremum, seed, self.n_features), acq_info
 
@@ -535,10 +542,7 @@ class TS(AcquisitionFunction):
             if prefetch_seed is not None:
                 raise NotImplementedError('TS: no prefetched batch (the overlap starts an EI / UCB sweep inside the fit)')
             ctx = self._ctx()
-            if lhs_total is not None:
-                ctx.gen_candidates_lhs(seed, first_candidate, num_points, lhs_total, low, high)
-            else:
-                ctx.gen_candidates(seed, first_candidate, num_points, low, high)
+            ctx.generate(seed, first_candidate, num_points, low, high, lhs_total)
             res = ctx.ts_sweep(self.scale_factor)
             self.last_sweep_ms = res.get('sweep_ms')
             return res['x'][0].copy(), self.scale_factor * float(res['val'][0]), int(res['idx'][0])
@@ -598,14 +602,12 @@ class MES(AcquisitionFunction):
     (no MES inside the batch strategies or the one-launch optimiser); an arg-max-only MES sweep is never pruned."""
 
     def __init__(self, n_samples=8, seed=None, n_features=2048):
-        n_samples, n_features = int(n_samples), int(n_features)
+        n_samples = int(n_samples)
         if n_samples < 1 or n_samples > 64:
             raise ValueError('n_samples must be in [1, 64]')
-        if n_features < 64 or n_features > 16384 or n_features % 64 != 0:
-            raise ValueError('n_features must be a multiple of 64 in [64, 16384]')
         self.n_samples = n_samples
         self.seed = seed
-        self.n_features = n_features
+        self.n_features = _checked_n_features(n_features)
 
     def get_type(self):
         return 'optimism'
@@ -615,8 +617,7 @@ class MES(AcquisitionFunction):
         if not _is_native(model):
             raise ValueError('MES serves native models only: it needs a model built by HipGPSurrogate (got {!r}) for the '
                              'noise level and the sample paths its maxima come from'.format(type(model)))
-        base = int(np.random.randint(0, 2**63)) if self.seed is None else int(self.seed)
-        seed = (base + int(trial_num) * TS.GOLDEN) % (1 << 64)
+        seed = _trial_seed(self.seed, trial_num)
         acq_info = {'seed': seed, 'n_samples': self.n_samples, 'n_features': self.n_features}
         return MES.FunctionInstance(model, desired_extremum, seed, self.n_samples, self.n_features), acq_info
 
@@ -644,8 +645,11 @@ class MES(AcquisitionFunction):
             return X
 
         def _prepare(self, X=None):
-            """the model's context with THIS instance's maxima in it.  First use: they are drawn over X (None: the batch
-            already resident).  Later: re-sent only when the handle holds another fit or another instance's maxima."""
+            """the base class's hook: THIS instance's maxima into the model's context.  First use: they are drawn over X
+            (None: the batch already resident).  Later: re-sent only when the handle holds another fit or another
+            instance's maxima.  Returns X as points."""
+            if X is not None:
+                X = self._as_points(X)
             ctx = self.model._ensure_resident()
             key = (self._token, getattr(ctx, 'fit_gen', 0))
             if self.maxima is None:
@@ -663,61 +667,16 @@ class MES(AcquisitionFunction):
                 ctx._mes_owner = None
                 ctx.mes_set_maxima(self.maxima)
                 ctx._mes_owner = key
-            return ctx
-
-        def __call__(self, X):
-            X = self._as_points(X)
-            if X.shape[0] > 0:
-                self._prepare(X)
-            return super().__call__(X)
-
-        def maximise(self, X):
-            X = self._as_points(X)
-            self._prepare(X)
-            return super().maximise(X)
-
-        def maximise_topk(self, X, k):
-            X = self._as_points(X)
-            self._prepare(X)
-            return super().maximise_topk(X, k)
-
-        def value_and_grad(self, X):
-            X = self._as_points(X)
-            self._prepare(X)
-            return super().value_and_grad(X)
-
-        def lbfgsb(self, starting_points, bounds, max_iter=15000):
-            self._prepare(self._as_points(starting_points))
-            return super().lbfgsb(starting_points, bounds, max_iter)
+            return X
 
         def maximise_generated(self, num_points, low, high, seed, first_candidate=0, lhs_total=None, prefetch_seed=None):
+            # Not folded into the hook: the first use draws the batch BEFORE the maxima (they are drawn over it; the base
+            # method then finds it by its key and does not draw it again), every later use sends the maxima before the
+            # base method draws -- the hook's one place in the base method cannot give both orders.
             if self.maxima is None:
-                # the first use: the batch has to be resident before the maxima can be drawn over it (the base method
-                # then finds it there, by its key, and does not draw it again)
-                ctx = self.model._ensure_resident()
-                if lhs_total is not None:
-                    ctx.gen_candidates_lhs(seed, first_candidate, num_points, lhs_total, low, high)
-                else:
-                    ctx.gen_candidates(seed, first_candidate, num_points, low, high)
+                self.model._ensure_resident().generate(seed, first_candidate, num_points, low, high, lhs_total)
             self._prepare(None)
             return super().maximise_generated(num_points, low, high, seed, first_candidate, lhs_total, prefetch_seed)
-
-        def maximise_host_stream(self, num_points, low, high, topk=0, first=0, count=None):
-            ctx = self.model._ensure_resident()
-            if not hasattr(ctx, 'set_candidates_numpy_stream') or not ctx.set_candidates_numpy_stream(num_points, low, high, first=first, count=count):
-                return None
-            self._prepare(None)
-            acq, incumbent, param = self._native_args()
-            if topk > 0:
-                idx, vals = ctx.sweep_topk(min(int(topk), 64), acq, self.scale_factor, incumbent, param)
-                keep = idx >= 0
-                top = (idx[keep], vals[keep])
-                if len(top[0]) > 0:
-                    return ctx, int(top[0][0]), float(top[1][0]), top
-                return ctx, 0, -np.inf, top
-            res = ctx.sweep(acq, self.scale_factor, incumbent, param)
-            self.last_sweep_ms = res.get('sweep_ms')
-            return ctx, res['best_idx'], res['best_val'], None
 
         def _refuse(self, what):
             raise NotImplementedError('MES: {} is not available for max-value entropy search (use CandidateSweep with '
