@@ -541,6 +541,47 @@ int tgp_sweep_integrated(tgp_handle h, const double *X, int64_t N, int64_t D, co
                          double *mu, double *sigma, double *acq_out,
                          double *best_val, int64_t *best_idx, int64_t *n_clamped);
 
+/* The knowledge gradient (Frazier, Powell & Dayanik 2009) over the RESIDENT candidates, against a discretisation set
+ * Xa (A, D), 1 <= A <= 256: the one acquisition here that needs the posterior covariance between every candidate and
+ * other points.  With the fitted model in normalised units (c the constant, u = x / l, K = c k0(X, X) + (noise + jitter) I):
+ *   mu(.)     raw posterior mean, y_mean + y_std c k0(., X) alpha
+ *   C(a, x)   raw LATENT posterior covariance, y_std^2 (c k0(a, x) - c k0(a, X) K^-1 c k0(X, x))
+ *   v(x)      raw latent variance, max(sigma(x)^2 - noise y_std^2, 0), sigma the sweep's own (TGP_ACQ_MES's sigma_f^2)
+ *   s(x)^2    v(x) + (noise + jitter) y_std^2: the deviation of the OBSERVATION a refit would condition on
+ *   lines     i < A: a_i = sf mu(Xa_i), b_i = C(Xa_i, x) / s(x);   i = A (x itself): a_A = sf mu(x), b_A = v(x) / s(x)
+ *   KG(x)     E_Z[max_i (a_i + b_i Z)] - max_i a_i, Z ~ N(0, 1): raw units, >= 0; 0 where s(x)^2 <= 0 or not finite
+ * -- what a literal refit on (X + {x}, y + {mu(x) + s(x) Z}) predicts at Xa and x, with the hyper-parameters, the jitter,
+ * y_mean and y_std held (tgp_sweep_batch's conditioning rule).  KG(x) is evaluated in the cancellation-free form: over the
+ * upper envelope's consecutive lines KG = sum (b_next - b_i) f(-|c_i|), c_i = (a_i - a_next) / (b_next - b_i),
+ * f(z) = phi(z) + z Phi(z) through the scaled complementary error function TGP_ACQ_MES uses; of lines with equal slope only
+ * the one with the largest intercept counts.  Finite for every finite input; may underflow to exactly 0.
+ *   tgp_kg_set_points  stores in the handle, on the device and always in float64: the scaled points, mu(Xa) (mu_out (A),
+ *                      nullable) and W = K^-1 c k0(X, Xa) as (Apad, Np) rows, Apad = A in whole 128s.  Like the MES maxima
+ *                      the points belong to ONE fit: any later fit, append, factor import or state import drops them.
+ *                      Non-finite Xa or A outside [1, 256]: TGP_BAD_ARG; no model: TGP_NOT_FITTED.  Duplicates are legal.
+ *                      Device memory kept: 3 Apad Np + Apad (Dp + 1) + A D doubles.
+ *   tgp_sweep_kg       (1) the unpruned predict-only sweep in the handle's arithmetic (its clamp count is n_clamped);
+ *                      where that arithmetic is not float64 the MEAN is re-formed in float64 from step (2)'s cross-kernel
+ *                      (y_mean + y_std Ks alpha, one wave a candidate, fixed order) and is what the lines and `mu` hold;
+ *                      sigma, and with it v(x), stays the sweep's own;
+ *                      (2) per chunk of candidates C = y_std^2 (c k0(Xc, Xa) - Ks W^T) in float64 on v_mfma_f64_16x16x4,
+ *                      the sum over the training points in ascending 16-wide tiles whatever M, the chunk or the row;
+ *                      (3) per candidate the A + 1 lines and KG(x), one wave a candidate, lines taken in ascending slope;
+ *                      (4) the library-wide arg-max (lowest index on ties, NaN never wins), the winner record
+ *                      (tgp_set_winner_out / tgp_winner_wait) and the completion of tgp_sweep.
+ *                      kg_out (M), mu (M), sigma (M), cov_out (M, A) = C(Xa_j, x_i) raw and latent; all outputs nullable.
+ *                      Without points for the resident fit, without candidates, or sf not +-1: TGP_BAD_ARG.
+ * Properties: float64 from step (2) on, whatever the handle's dtype; the same bits from run to run; on float64 handles a
+ * candidate's kg_out and cov_out bits depend neither on M, nor on its row index, nor on the chunk it falls in (no atomics on
+ * floating-point data, no split of a sum).  The call leaves the fit, the candidates, a Thompson draw, the MES maxima and
+ * later tgp_sweep results untouched.  Every fitted GPU handle is served: the one-workgroup fits, 128 < N <= 256, the
+ * blocked fit, an appended fit, a received factor.  GPU only: TGP_BAD_ARG on host handles for both entries.  The chunk's
+ * workspace (rows (Np + Dp + Apad + 1) doubles, rows <= 16384 candidates or TGP_CHUNK) is grown on first use and released with
+ * the handle.  tgp_last_timings slot [20] holds the device time of the call's own kernels. */
+int tgp_kg_set_points(tgp_handle h, const double *Xa, int64_t A, double *mu_out);
+int tgp_sweep_kg(tgp_handle h, double sf, double *kg_out, double *mu, double *sigma, double *cov_out,
+                 double *best_val, int64_t *best_idx, int64_t *n_clamped);
+
 /* The gradient stage itself on the device: R <= 4096 restarts X0 (R, D) are refined together by a
  * projected L-BFGS (memory 8; a line search that asks for sufficient decrease 1e-4 and the curvature
  * condition 0.9 as L-BFGS-B's does, lengthening a step whose slope is still steep; bounds lo / hi
@@ -745,7 +786,9 @@ int tgp_profile_reset(tgp_handle h);
  * tgp_profile_read's cross-kernel and contraction times.  Slot [18] (not a time): that screen's arithmetic, 0 none,
  * 1 the f32 matrix pipe, 2 fp16 planes with the k-weighted error (TGP_SCREEN_ARITH).
  * Slot [19]: device time (ms) of the kernels of the last tgp_loo, the copies back left out (0 on host handles).  After
- * tgp_fit_loo_grad slot [2] holds everything up to B = A A^T (K^-1, kappa, b, A, B), slots [3] and [4] as for tgp_fit_grad. */
+ * tgp_fit_loo_grad slot [2] holds everything up to B = A A^T (K^-1, kappa, b, A, B), slots [3] and [4] as for tgp_fit_grad.
+ * Slot [20]: device time (ms) of the last tgp_sweep_kg's own kernels -- cross-covariance and envelope, chunk by chunk; the
+ * predict-only sweep in front of them and the copies left out (0 on host handles). */
 int tgp_last_timings(tgp_handle h, double *out, int64_t n);
 /* Candidates per trmm launch (chunk) and padded N used by the sweep, for the roofline maths. */
 int tgp_sweep_geometry(tgp_handle h, int64_t *chunk, int64_t *n_padded);

@@ -43,7 +43,7 @@ SYMBOLS = (
     "tgp_read_candidates", "tgp_get_candidate",
     "tgp_sweep", "tgp_sweep_batch", "tgp_sweep_batch_mc", "tgp_ts_draw", "tgp_ts_sweep", "tgp_ts_eval", "tgp_ts_read", "tgp_mes_set_maxima", "tgp_mes_draw", "tgp_predict_cov", "tgp_sample_joint", "tgp_sweep_topk", "tgp_set_winner_out", "tgp_winner_wait", "tgp_acq_grad", "tgp_acq_refine", "tgp_acq_lbfgsb",
     "tgp_evaluate", "tgp_predict_batch", "tgp_predict", "tgp_profile_enable", "tgp_profile_read", "tgp_profile_reset",
-    "tgp_sweep_geometry", "tgp_last_timings", "tgp_hyper_sample", "tgp_sweep_integrated",
+    "tgp_sweep_geometry", "tgp_last_timings", "tgp_hyper_sample", "tgp_sweep_integrated", "tgp_kg_set_points", "tgp_sweep_kg",
     "tgp_multi_create", "tgp_multi_destroy", "tgp_multi_last_error", "tgp_multi_size", "tgp_multi_handle",
     "tgp_multi_fit", "tgp_multi_set_candidates", "tgp_multi_gen_candidates", "tgp_multi_sweep",
 )
@@ -150,6 +150,8 @@ def _argtypes():
         "tgp_ts_read": [_vp, _dp, _dp, _dp, _dp],
         "tgp_mes_set_maxima": [_vp, _dp, c.c_int64],
         "tgp_mes_draw": [_vp, c.c_uint64, c.c_int64, c.c_int64, c.c_double, c.c_double, _dp],
+        "tgp_kg_set_points": [_vp, _dp, c.c_int64, _dp],
+        "tgp_sweep_kg": [_vp, c.c_double, _dp, _dp, _dp, _dp, _dp, _i64p, _i64p],
         "tgp_predict_cov": [_vp, _dp, c.c_int64, c.c_int, _dp, _dp, _i64p],
         "tgp_sample_joint": [_vp, _dp, c.c_int64, c.c_int64, c.c_int, c.c_double, c.c_uint64, _dp, _dp, _dp, _dp],
         "tgp_acq_refine": [_vp, _dp, c.c_int64, _dp, _dp, c.c_int, c.c_double, c.c_double, c.c_double,
@@ -871,6 +873,31 @@ class NativeGP:
                                           _ptr(out)))
         self.ts_S, self.ts_F = int(S), int(F)
         return out[:int(S)]
+
+    def kg_set_points(self, Xa):
+        """``tgp_kg_set_points``: the 1 <= A <= 256 finite discretisation points Xa (A, D) of the knowledge gradient; they
+        belong to the resident fit (any later fit, append or import drops them).  Returns the raw posterior mean at
+        them (A,).  GPU handles only."""
+        Xa = _f64c(np.atleast_2d(Xa))
+        assert Xa.ndim == 2 and Xa.shape[1] == self.D, "points must be (A, %d)" % self.D
+        mu = np.empty(max(Xa.shape[0], 1))
+        self._check(self.lib.tgp_kg_set_points(self._h, _ptr(Xa), Xa.shape[0], _ptr(mu)))
+        self.kg_A = Xa.shape[0]
+        return mu[:Xa.shape[0]]
+
+    def sweep_kg(self, sf=1.0, want_kg=False, want_mu=False, want_sigma=False, want_cov=False):
+        """``tgp_sweep_kg``: the knowledge gradient of every resident candidate against the stored points, float64
+        behind the predict-only sweep.  Returns ``sweep``'s dict (``acq`` is the knowledge gradient (M,)) plus ``kg``
+        (the same array), ``cov`` (M, A) -- the raw latent covariance between candidate i and point j -- or None, and
+        ``kg_ms`` (``tgp_last_timings`` slot 20)."""
+        M = getattr(self, "M", 0)
+        out = _SweepOut(M, want_mu, want_sigma, want_kg)
+        cov = np.empty((M, getattr(self, "kg_A", 0))) if want_cov else None
+        self._check(self.lib.tgp_sweep_kg(self._h, float(sf), _ptr(out.aq), _ptr(out.mu), _ptr(out.sg), _ptr(cov),
+                                          ctypes.byref(out.bv), ctypes.byref(out.bi), ctypes.byref(out.nc)))
+        v = np.zeros(21)
+        self._check(self.lib.tgp_last_timings(self._h, _ptr(v), 21))
+        return out.result(kg=out.aq, cov=cov, kg_ms=float(v[20]))
 
     def predict_cov(self, Xq, latent=False):
         """``tgp_predict_cov``: the joint posterior over m <= 4096 points -- mu (m,), cov (m, m) in raw units (symmetric

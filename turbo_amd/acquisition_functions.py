@@ -690,6 +690,162 @@ class MES(AcquisitionFunction):
             self._refuse('the on-device optimiser (on_device=True, tgp_acq_refine)')
 
 
+class KG(AcquisitionFunction):
+    """The knowledge gradient (Frazier, Powell & Dayanik 2009): the expected gain of the best posterior mean over a
+    discretisation set ``points`` (A, D), A <= 256, and the candidate itself from ONE more observation at the candidate
+    (``tgp_kg_set_points`` / ``tgp_sweep_kg``, csrc/kg_kernels.hip):
+
+        lines  a_i = sf mu(Xa_i), b_i = C(Xa_i, x) / s(x);  a_A = sf mu(x), b_A = v(x) / s(x)
+        KG(x)  = E_Z[max_i (a_i + b_i Z)] - max_i a_i >= 0,  raw units
+
+    with C the raw latent posterior covariance, v the latent variance at x and s^2 = v + (noise + jitter) y_std^2 (the
+    hyper-parameters held, as the batch strategies condition).  ``points`` None: the ``min(n_points, N, 256)`` training
+    inputs with the best observed y in the direction of the extremum, the earlier trial on ties -- deterministic, no
+    random number drawn.  Native models only; a marginalised model is refused.  ``maximise_batch``, ``refine``,
+    ``lbfgsb`` and ``value_and_grad`` are refused: the gradient of KG is not implemented."""
+
+    def __init__(self, points=None, n_points=64):
+        n_points = int(n_points)
+        if n_points < 1 or n_points > 256:
+            raise ValueError('n_points must be in [1, 256]')
+        if points is not None:
+            points = np.array(points, dtype=np.float64)
+            if points.ndim != 2 or points.shape[0] < 1 or points.shape[0] > 256:
+                raise ValueError('points must be (A, D) with 1 <= A <= 256')
+            if not np.all(np.isfinite(points)):
+                raise ValueError('points must be finite')
+        self.points = points
+        self.n_points = n_points
+
+    def get_type(self):
+        return 'optimism'
+
+    @staticmethod
+    def default_points(X, y, desired_extremum, n_points=64):
+        """the ``min(n_points, N, 256)`` rows of X with the best y ('max': largest), the earlier row on ties"""
+        X = np.asarray(X, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64).reshape(-1)
+        sf = 1.0 if desired_extremum == 'max' else -1.0
+        k = min(int(n_points), X.shape[0], 256)
+        order = np.argsort(-sf * y, kind='stable')[:k]
+        return np.ascontiguousarray(X[order])
+
+    def construct_function(self, trial_num, model, desired_extremum):
+        _refuse_marginalised(model, 'KG (its discretisation points belong to one fitted model)')
+        if not _is_native(model):
+            raise ValueError('KG serves native models only: it needs a model built by HipGPSurrogate (got {!r}) for the '
+                             'posterior covariance between the candidates and its points'.format(type(model)))
+        if self.points is None:
+            points = KG.default_points(model.X, model.y, desired_extremum, self.n_points)
+        else:
+            points = self.points
+            if points.shape[1] != np.asarray(model.X).shape[1]:
+                raise ValueError('points must be (A, {})'.format(np.asarray(model.X).shape[1]))
+        acq_info = {'n_points': int(points.shape[0]), 'default_points': self.points is None}
+        return KG.FunctionInstance(model, desired_extremum, points), acq_info
+
+    class FunctionInstance(AcquisitionFunction.FunctionInstance):
+        """KG(x) over ``points`` (A, D)"""
+
+        sweep_dtype = 'f64'      # the cross-covariance and the envelope are f64 whatever the handle's dtype
+
+        def __init__(self, model, desired_extremum, points):
+            super().__init__(model, desired_extremum)
+            self.points = np.ascontiguousarray(points, dtype=np.float64)
+            self._token = object()
+
+        def get_name(self):
+            return 'KG'
+
+        def _native_args(self):
+            raise NotImplementedError('KG has no posterior-formula arguments: it needs the cross-covariance sweep')
+
+        def _as_points(self, X):
+            X = np.asarray(X, dtype=np.float64)
+            if X.ndim == 1:
+                X = X.reshape(1, -1)
+            assert X.ndim == 2 and X.shape[1] == self.model.X.shape[1], \
+                'X must have shape (num_points, {})'.format(self.model.X.shape[1])
+            return X
+
+        def _ctx(self):
+            """the model's context holding THIS instance's points: re-sent when the handle holds another fit or another
+            instance's points"""
+            ctx = self.model._ensure_resident()
+            if getattr(ctx, 'host', False):
+                raise ValueError('KG runs on the GPU only; the model is served by the host backend')
+            key = (self._token, getattr(ctx, 'fit_gen', 0))
+            if getattr(ctx, '_kg_owner', None) != key:
+                ctx._kg_owner = None
+                ctx.kg_set_points(self.points)
+                ctx._kg_owner = key
+            return ctx
+
+        def _sweep(self, ctx, **want):
+            res = ctx.sweep_kg(self.scale_factor, **want)
+            self.last_sweep_ms = res.get('kg_ms')
+            return res
+
+        def __call__(self, X):
+            X = self._as_points(X)
+            if X.shape[0] == 0:
+                return np.empty(0)
+            ctx = self._ctx()
+            ctx.set_candidates(X)
+            return self._sweep(ctx, want_kg=True)['kg']
+
+        def maximise(self, X):
+            """arg-max of KG over the rows of X: (index, value); lowest index wins ties"""
+            ctx = self._ctx()
+            ctx.set_candidates(self._as_points(X))
+            res = self._sweep(ctx)
+            return res['best_idx'], res['best_val']
+
+        def maximise_topk(self, X, k):
+            """the k best rows of X: (indices (k,), values (k,)), best first (a host argsort of the (M,) values)"""
+            v = self(X)
+            v = np.where(np.isnan(v), -np.inf, v)
+            order = np.argsort(-v, kind='stable')[:min(int(k), 64)]
+            return order.astype(np.int64), v[order]
+
+        def maximise_generated(self, num_points, low, high, seed, first_candidate=0, lhs_total=None, prefetch_seed=None):
+            """draw ``num_points`` candidates on the GPU and return the best: (x (D,), value, index)"""
+            if prefetch_seed is not None:
+                raise NotImplementedError('KG: no prefetched batch (the overlap starts an EI / UCB sweep inside the fit)')
+            ctx = self._ctx()
+            ctx.generate(seed, first_candidate, num_points, low, high, lhs_total, reuse=True)
+            res = self._sweep(ctx)
+            return ctx.get_candidate(res['best_idx']), res['best_val'], res['best_idx']
+
+        def maximise_host_stream(self, num_points, low, high, topk=0, first=0, count=None):
+            return None     # nothing drawn: the caller draws on the host and calls maximise / maximise_topk
+
+        def winner_record(self, global_offset):
+            self._ctx()
+            return super().winner_record(global_offset)
+
+        def _refuse(self, what, instead):
+            raise NotImplementedError('KG: {} is not available for the knowledge gradient (its gradient is not '
+                                      'implemented): use {}'.format(what, instead))
+
+        def maximise_batch(self, X, q, strategy='kriging_believer', lie='min', pending=None, want_posterior=False,
+                           n_sim=16, seed=None):
+            self._refuse('batch selection (tgp_sweep_batch / tgp_sweep_batch_mc)',
+                         'maximise_topk for q rows of one sweep, or EI / UCB with select_batch')
+
+        def refine(self, starting_points, bounds, max_iter=200):
+            self._refuse('the on-device optimiser (on_device=True, tgp_acq_refine)',
+                         'CandidateSweep with grad_restarts=0 (maximise over the candidates)')
+
+        def lbfgsb(self, starting_points, bounds, max_iter=15000):
+            self._refuse('the in-library L-BFGS-B (lockstep=True, tgp_acq_lbfgsb)',
+                         'CandidateSweep with grad_restarts=0 (maximise over the candidates)')
+
+        def value_and_grad(self, X):
+            self._refuse('value_and_grad',
+                         'CandidateSweep with grad_restarts=0, or __call__ for values and finite differences')
+
+
 def joint_ei(model, Xb, desired_extremum, incumbent, xi=0.01, n_samples=512, seed=None, eps=None, latent=False,
              nugget=1e-10):
     """The Monte Carlo q-EI of a batch: the expected improvement of the BEST of the q points of ``Xb`` (q, D), q <= 4096,

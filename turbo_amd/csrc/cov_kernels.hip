@@ -331,6 +331,21 @@ int64_t cov_ws_doubles(const Context &c, int64_t m, int64_t S, CovWs *out) {
     return off;
 }
 
+// the first three steps of launch_cov_posterior for rows given on the DEVICE (kg_kernels.hip: the discretisation points,
+// a chunk of the resident candidates): Us = Xq / l, Ks = c k0(Xq, X), and (mu != null) the raw mean
+hipError_t launch_cov_cross(Context &c, const double *Xq, int m, int mpad, double *Us, double *Ks, double *mu, long long *cnt) {
+    hipStream_t s = c.stream;
+    const int N = (int)c.N, Np = (int)c.Np, D = (int)c.D, Dp = (int)c.Dp;
+    hipLaunchKernelGGL(cov_scale_kernel, dim3((unsigned)(((long)mpad * Dp + 255) / 256)), dim3(256), 0, s, Xq, c.d_ls, Us, m, mpad, D, Dp, cnt);
+    TGP_TRY(hipGetLastError());
+    auto k = by_kind(c.kernel, [](auto K) { return cov_ks_kernel<K()>; });
+    hipLaunchKernelGGL(k, dim3(Np / PW_T, mpad / PW_T), dim3(256), 0, s, Us, c.d_Xs, Ks, m, N, Np, Dp, c.constant);
+    TGP_TRY(hipGetLastError());
+    if (!mu) return hipSuccess;
+    hipLaunchKernelGGL(cov_mu_kernel, dim3(mpad / 4), dim3(256), 0, s, Ks, c.d_alpha, mu, m, mpad, N, Np, c.y_mean, c.y_std);
+    return hipGetLastError();
+}
+
 hipError_t launch_cov_posterior(Context &c, double *ws, const CovWs &w, int latent, double nugget, bool for_sample) {
     hipStream_t s = c.stream;
     const int m = (int)w.m, mpad = (int)w.mpad, N = (int)c.N, Np = (int)c.Np, D = (int)c.D, Dp = (int)c.Dp, NV = (int)w.NV;

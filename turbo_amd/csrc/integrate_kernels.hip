@@ -99,12 +99,27 @@ hipError_t launch_integrate_accumulate(Context &c, const SweepCall &s, int k) {
     return hipGetLastError();
 }
 
+static hipError_t launch_final(Context &c, const SweepCall &s, IntFinal f);
+
 // s.mu / s.sigma / s.acqv: where the averaged outputs go (device memory, nullable); s.res, s.winner as for a plain sweep
 hipError_t launch_integrate_final(Context &c, const SweepCall &s, int S) {
     IntFinal f{};
     f.sum_a = c.d_int_a; f.sum_mu = c.d_int_mu; f.sum_m2 = c.d_int_m2;
-    f.M = (long)c.M; f.S = S; f.acq = s.acq;
+    f.S = S;
     f.mu = s.mu; f.sigma = s.sigma; f.acqv = s.acqv;
+    return launch_final(c, s, f);
+}
+
+// one "sample" whose sums are the values themselves (a / 1 is exact) and no (M,) output: the arg-max and the records alone
+hipError_t launch_argmax_of(Context &c, const SweepCall &s, const double *vals) {
+    IntFinal f{};
+    f.sum_a = f.sum_mu = f.sum_m2 = vals;
+    f.S = 1;
+    return launch_final(c, s, f);
+}
+
+static hipError_t launch_final(Context &c, const SweepCall &s, IntFinal f) {
+    f.M = (long)c.M; f.acq = s.acq;
     f.bval = c.d_bval; f.bidx = c.d_bidx;
     const long nblk = (f.M + INT_BLOCK - 1) / INT_BLOCK;
     f.nblk = s.acq != TGP_ACQ_NONE ? nblk : 0;

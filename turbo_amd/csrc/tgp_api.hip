@@ -2829,6 +2829,124 @@ int tgp_sweep_integrated(tgp_handle h, const double *X, int64_t N, int64_t D, co
     return TGP_OK;
 } TGP_CATCH
 
+// ---- the knowledge gradient over the resident batch (include/turbogp.h; kg_kernels.hip) ----
+// candidates per chunk of tgp_sweep_kg: a cross-kernel slab of about 512 MiB, a multiple of 1024, at most 16384
+// (TGP_CHUNK replaces it, as it does the sweep's); a batch that fits one chunk takes what it needs, in whole 128-tiles.
+// The chunk is what fills the chip: the cross-covariance launches (rows / 128) (Apad / 128) workgroups, and at 128 MiB
+// (4096 rows at Np = 4096: 32 or 64 workgroups on 256 CUs) C3's call spent 39 ms in its own kernels whatever A was.
+static int64_t kg_chunk_rows(const Context &c) {
+    int64_t chunk = (int64_t)((512ull << 20) / ((size_t)c.Np * sizeof(double)));
+    chunk = std::min<int64_t>(std::max<int64_t>(1024, (chunk / 1024) * 1024), 16384);
+    if (const long v = tuning_chunk_now(); v >= 1024) chunk = (v / 1024) * 1024;
+    const int64_t mpad = (c.M + 127) / 128 * 128;
+    return std::min(chunk, mpad);
+}
+
+int tgp_kg_set_points(tgp_handle h, const double *Xa, int64_t A, double *mu_out) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_kg_set_points");
+    Context &c = h->c;
+    if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_kg_set_points: no fitted model (the points belong to one fit)");
+    if (!Xa || A < 1 || A > 256) return fail(c, TGP_BAD_ARG, "tgp_kg_set_points: need Xa and 1 <= A <= 256 points");
+    for (int64_t e = 0; e < A * c.D; ++e)
+        if (!std::isfinite(Xa[e])) return fail(c, TGP_BAD_ARG, "tgp_kg_set_points: Xa must be finite");
+    API_HIP(hipSetDevice(c.device), "hipSetDevice");
+    API_HIP(pre_join(c), "hipStreamWaitEvent");
+    c.kg_gen = -1;
+    KgPoints p;
+    const int64_t nd = kg_points_doubles(c, A, &p);
+    API_MEM(grow(c, c.d_kgp, (size_t)nd * sizeof(double), "hipMalloc knowledge-gradient points"));
+    API_HIP(hipMemcpyAsync(c.d_kgp + p.o_Xa, Xa, (size_t)(A * c.D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D Xa");
+    hipError_t le = launch_kg_points(c, c.d_kgp, p);
+    if (le != hipSuccess) return hip_fail(c, le, "launch_kg_points");
+    if (mu_out) API_HIP(hipMemcpyAsync(mu_out, c.d_kgp + p.o_mu, (size_t)A * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H mu");
+    API_HIP(hipStreamSynchronize(c.stream), "kg_set_points sync");
+    c.kg_A = (int)A;
+    c.kg_gen = c.fit_gen;
+    return TGP_OK;
+} TGP_CATCH
+
+int tgp_sweep_kg(tgp_handle h, double sf, double *kg_out, double *mu, double *sigma, double *cov_out, double *best_val,
+                 int64_t *best_idx, int64_t *n_clamped) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_sweep_kg");
+    Context &c = h->c;
+    if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_sweep_kg: no fitted model");
+    if (!c.d_cand || c.M < 1) return fail(c, TGP_BAD_ARG, "tgp_sweep_kg: no candidates set");
+    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_sweep_kg: sf must be +1 or -1");
+    if (c.kg_gen < 0 || c.kg_gen != c.fit_gen || c.kg_A < 1)
+        return fail(c, TGP_BAD_ARG, "tgp_sweep_kg: needs discretisation points for the resident fit (tgp_kg_set_points after the last fit)");
+    API_HIP(hipSetDevice(c.device), "hipSetDevice");
+    API_HIP(pre_join(c), "hipStreamWaitEvent");
+    int rc = ensure_outputs(c, true, true, true);
+    if (rc != TGP_OK) return rc;
+    KgPoints p;
+    (void)kg_points_doubles(c, c.kg_A, &p);
+    const int64_t rows = kg_chunk_rows(c);
+    KgChunk k;
+    const int64_t nd = kg_chunk_doubles(c, rows, p.Apad, &k);
+    API_MEM(grow(c, c.d_kgw, (size_t)nd * sizeof(double), "hipMalloc knowledge-gradient workspace"));
+    const size_t nchunks = (size_t)((c.M + rows - 1) / rows);
+    while (c.ev_kg.size() < 2 * nchunks) {
+        Ev e;
+        API_HIP(e.create(hipEventDefault), "hipEventCreate");
+        c.ev_kg.push_back(std::move(e));
+    }
+    // step 1: the unpruned predict-only sweep in the handle's arithmetic: no record, no winner, no bell; its clamp
+    // count stays in the counter for the final kernel
+    SweepCall s;
+    s.mu = c.d_mu; s.sigma = c.d_sigma;
+    CallClock clk;
+    if ((rc = run_sweep(c, s, clk)) != TGP_OK) return rc;
+    // a failure from here on hands the clamp counter back at zero, as every sweep does
+    auto bail = [&](int code) {
+        (void)hipMemsetAsync(c.d_besti + 1, 0, sizeof(long long), c.stream);
+        (void)hipStreamSynchronize(c.stream);
+        (void)hipGetLastError();
+        return code;
+    };
+    // steps 2 and 3, chunk by chunk in f64: the cross-covariance, then the envelope into c.d_acq.  Where the sweep ran in
+    // the handle's f32 arithmetic the mean is re-formed in f64 from the chunk's cross-kernel (one more pass over a slab
+    // that is there anyway) and replaces the sweep's in c.d_mu: the f32 mean was the larger half of kg_out's error
+    const bool remean = c.last_sweep_f64 == 0;
+    const size_t d8 = sizeof(double);
+    for (size_t ch = 0; ch < nchunks; ++ch) {
+        const int64_t i0 = (int64_t)ch * rows;
+        const int m = (int)std::min<int64_t>(rows, c.M - i0);
+        hipError_t e = hipEventRecord(c.ev_kg[2 * ch], c.stream);
+        if (e == hipSuccess) e = launch_kg_chunk(c, c.d_kgw, k, c.d_kgp, p, i0, m, sf, c.d_acq, remean);
+        if (e == hipSuccess) e = hipEventRecord(c.ev_kg[2 * ch + 1], c.stream);
+        if (e == hipSuccess && cov_out)
+            e = hipMemcpy2DAsync(cov_out + i0 * c.kg_A, (size_t)c.kg_A * d8, c.d_kgw + k.o_C, (size_t)p.Apad * d8, (size_t)c.kg_A * d8,
+                                 (size_t)m, hipMemcpyDeviceToHost, c.stream);
+        if (e != hipSuccess) return bail(hip_fail(c, e, "launch_kg_chunk"));
+    }
+    // step 4: the shared arg-max, record and winner record
+    SweepCall fin;
+    fin.acq = TGP_ACQ_EI;                 // (any acquisition: the final kernel only asks whether there is one)
+    fin.winner = c.d_winner;
+    const bool zc = tuning().sweep_zc != 0;
+    if (zc && (rc = ensure_pinned(c, 0, 8 * sizeof(double))) != TGP_OK) return bail(rc);
+    fin.res = zc ? c.h_pin_out.dev() : nullptr;
+    {
+        const hipError_t le = launch_argmax_of(c, fin, c.d_acq);
+        if (le != hipSuccess) return bail(hip_fail(c, le, "launch_argmax_of"));
+    }
+    if ((rc = winner_mark(c, fin)) != TGP_OK) return rc;
+    SweepRecord rec;
+    if ((rc = sweep_queue_return(c, zc, fin.acq, rec, nullptr, mu, sigma, kg_out)) != TGP_OK) return rc;
+    API_HIP(hipStreamSynchronize(c.stream), "kg sweep sync");
+    sweep_read_record(c, zc, fin.acq, rec, best_val, best_idx, n_clamped);
+    double total = 0.0;
+    for (size_t ch = 0; ch < nchunks; ++ch) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, c.ev_kg[2 * ch], c.ev_kg[2 * ch + 1]) == hipSuccess) total += ms;
+        else (void)hipGetLastError();
+    }
+    c.last_kg_ms = total;
+    return TGP_OK;
+} TGP_CATCH
+
 int tgp_evaluate(tgp_handle h, const double *Xc, int64_t M, int acq, double sf, double incumbent,
                  double param, double *mu, double *sigma, double *acq_out, double *best_val,
                  int64_t *best_idx, int64_t *n_clamped) try {
@@ -3030,15 +3148,16 @@ int tgp_last_timings(tgp_handle h, double *out, int64_t n) try {
     // the screen's launches since tgp_profile_reset (ms; apart from the cross-kernel's and the contraction's); [18]: that
     // screen's arithmetic, 0 none, 1 f32, 2 fp16 planes (TGP_SCREEN_ARITH)
     // [19]: device time of the last tgp_loo's three kernels (ms; the copies back left out)
-    double v[20] = {c.last_fit_ms, c.last_sweep_ms, c.last_grad_ms[0], c.last_grad_ms[1], c.last_grad_ms[2], c.trmm_flops,
+    // [20]: device time of the last tgp_sweep_kg's own kernels (ms; cross-covariance + envelope, the copies left out)
+    double v[21] = {c.last_fit_ms, c.last_sweep_ms, c.last_grad_ms[0], c.last_grad_ms[1], c.last_grad_ms[2], c.trmm_flops,
                     (double)c.last_sweep_f64, 0.0, 0.0, 0.0, 0.0, 0.0, (double)c.prune_state, (double)c.prune_lbset,
-                    (double)c.prune_surv, c.last_cov_ms, (double)c.prune_screen, c.screen_ms, (double)c.prune_arith, c.last_loo_ms};
+                    (double)c.prune_surv, c.last_cov_ms, (double)c.prune_screen, c.screen_ms, (double)c.prune_arith, c.last_loo_ms, c.last_kg_ms};
     if (c.h_bell && c.h_bell[1]) {
         const unsigned long long t0 = c.h_bell[1];
         const int src[5] = {3, 4, 5, 6, 2};
         for (int k = 0; k < 5; ++k) v[7 + k] = c.h_bell[src[k]] >= t0 ? (double)(c.h_bell[src[k]] - t0) * 1e-2 : 0.0;
     }
-    for (int64_t i = 0; i < n; ++i) out[i] = i < 20 ? v[i] : 0.0;
+    for (int64_t i = 0; i < n; ++i) out[i] = i < 21 ? v[i] : 0.0;
     return TGP_OK;
 } TGP_CATCH
 

@@ -117,6 +117,12 @@ struct WsMem {                     // the sweeps' and the acquisition entries' w
     int mes_S = 0;
     long mes_gen = -1;             // the fit_gen the maxima belong to (-1: none)
     Dev<double> d_int_a, d_int_mu, d_int_m2;   // tgp_sweep_integrated: (M,) sums over the samples of acq, mu, sigma^2 + mu^2
+    Dev<double> d_kgp;             // tgp_kg_set_points: the stored points (kg_kernels.hip, KgPoints) and the workspace they were built in
+    int kg_A = 0;
+    long kg_gen = -1;              // the fit_gen the points belong to (-1: none)
+    Dev<double> d_kgw;             // tgp_sweep_kg: a chunk's scaled candidates, cross-kernel slab and cross-covariance (KgChunk)
+    std::vector<Ev> ev_kg;         // brackets of the last tgp_sweep_kg's own kernels, a pair per chunk (the copies between them are not timed)
+    double last_kg_ms = 0.0;
 };
 
 struct OutMem {                    // the sweep's optional (M,) outputs: created lazily at ONE size, released together
@@ -453,5 +459,33 @@ hipError_t launch_ts_eval(Context &c, const TsDraw &t, const double *Xq, int m, 
 // (device memory, nullable), their arg-max, the record s.res and the winner record s.winner as a plain sweep leaves them
 hipError_t launch_integrate_accumulate(Context &c, const SweepCall &s, int k);
 hipError_t launch_integrate_final(Context &c, const SweepCall &s, int S);
+// the same final kernel over ONE (M,) vector of values that is already the acquisition (tgp_sweep_kg: c.d_acq): its
+// arg-max, the record s.res and the winner record s.winner; writes no (M,) output
+hipError_t launch_argmax_of(Context &c, const SweepCall &s, const double *vals);
+
+// the cov path's scaling, cross-kernel and mean for m rows Xq (m, D) on the device (cov_kernels.hip): Us (mpad, Dp),
+// Ks (mpad, Np), mu (mpad) or null; mpad a multiple of 64; cnt: two counters the first kernel clears
+hipError_t launch_cov_cross(Context &c, const double *Xq, int m, int mpad, double *Us, double *Ks, double *mu, long long *cnt);
+
+// The knowledge gradient (kg_kernels.hip).  KgPoints: c.d_kgp for A discretisation points, offsets in doubles
+struct KgPoints {
+    int64_t A, Apad;               // Apad: A in whole 128-tiles
+    int64_t o_cnt, o_Xa, o_Ua, o_mu, o_W;   // counters, raw (A, D) and scaled (Apad, Dp) points, mu(Xa) (Apad), W = K^-1 c k0(X, Xa) as (Apad, Np)
+    int64_t o_Ka, o_Z;             // workspace: c k0(Xa, X) and Linv of it, (Apad, Np) each
+};
+int64_t kg_points_doubles(const Context &c, int64_t A, KgPoints *out);
+hipError_t launch_kg_points(Context &c, double *ws, const KgPoints &p);   // Xa is in the workspace
+// KgChunk: c.d_kgw for chunks of `rows` candidates (a multiple of 128)
+struct KgChunk {
+    int64_t rows, Apad;
+    int64_t o_cnt, o_Us, o_Ks, o_C;   // counters, (rows, Dp), (rows, Np), (rows, Apad)
+    int64_t o_mu;                  // (rows) the chunk's raw mean re-formed in f64 (handles whose sweep is not f64)
+};
+int64_t kg_chunk_doubles(const Context &c, int64_t rows, int64_t Apad, KgChunk *out);
+// candidates [i0, i0 + m) of the resident batch: the raw latent cross-covariance into the chunk's C and the knowledge
+// gradient into kg[i0 ..) from c.d_mu / c.d_sigma; remean: the mean of these rows is first re-formed in f64 from the
+// chunk's cross-kernel (y_mean + y_std Ks alpha, the cov path's kernel) and replaces c.d_mu[i0 ..)
+hipError_t launch_kg_chunk(Context &c, double *ws, const KgChunk &k, const double *pts, const KgPoints &p, int64_t i0, int m,
+                           double sf, double *kg, bool remean);
 
 }  // namespace tgp
