@@ -788,7 +788,10 @@ int tgp_profile_reset(tgp_handle h);
  * Slot [19]: device time (ms) of the kernels of the last tgp_loo, the copies back left out (0 on host handles).  After
  * tgp_fit_loo_grad slot [2] holds everything up to B = A A^T (K^-1, kappa, b, A, B), slots [3] and [4] as for tgp_fit_grad.
  * Slot [20]: device time (ms) of the last tgp_sweep_kg's own kernels -- cross-covariance and envelope, chunk by chunk; the
- * predict-only sweep in front of them and the copies left out (0 on host handles). */
+ * predict-only sweep in front of them and the copies left out (0 on host handles).
+ * Slot [21] (not a time): the speculative round of the last tgp_sweep's pruned schedule (TGP_PRUNE_SPEC; DESIGN.md section
+ * 4) -- 0 not tried, 1 hit: the runner-ups contracted beside the lb set covered every survivor, so the sweep made one exact
+ * round; 2 miss: the survivors' round ran as well.  Slots [12..14] and [16] read the same either way. */
 int tgp_last_timings(tgp_handle h, double *out, int64_t n);
 /* Candidates per trmm launch (chunk) and padded N used by the sweep, for the roofline maths. */
 int tgp_sweep_geometry(tgp_handle h, int64_t *chunk, int64_t *n_padded);

@@ -1052,6 +1052,14 @@ class NativeGP:
         self._check(self.lib.tgp_last_timings(self._h, _ptr(v), 19))
         return dict(state=int(v[12]), lb_set=int(v[13]), survivors=int(v[14]), screen=int(v[16]), screen_arith=int(v[18]))
 
+    def last_prune_spec(self):
+        """the speculative round of the last ``sweep``'s pruned schedule (``tgp_last_timings`` slot 21, TGP_PRUNE_SPEC):
+        0 = not tried, 1 = hit (the runner-ups contracted beside the lb set covered every survivor: one exact round),
+        2 = miss (the survivors' round ran as well).  ``last_prune()`` reads the same either way."""
+        v = np.zeros(22)
+        self._check(self.lib.tgp_last_timings(self._h, _ptr(v), 22))
+        return int(v[21])
+
     def sweep_geometry(self):
         ch, npad = ctypes.c_int64(), ctypes.c_int64()
         self._check(self.lib.tgp_sweep_geometry(self._h, ctypes.byref(ch), ctypes.byref(npad)))

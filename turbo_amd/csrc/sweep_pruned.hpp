@@ -76,15 +76,94 @@ __global__ __launch_bounds__(256) void prune_pick_kernel(const double *__restric
     if (threadIdx.x == 0) pick[blockIdx.x] = b.i == IDX_NONE ? g0 : b.i;   // (all bounds -inf: the group's first)
 }
 
-// rows idx[0..n) of the scaled candidates into a dense block of `rows` rows (rows >= n zero)
+// The speculative round's lb set (sweep_pruned below): prune_pick_kernel's pick AND the next three bounds of each group, in
+// `better`'s order (larger bound first, lower index on ties), into runner[3 g ..]; IDX_NONE where the group has no more
+// members.  A thread keeps the best four of its own candidates, then four block arg-max rounds take them off the threads'
+// heads.  pick[g] is prune_pick_kernel's: the largest bound at its lowest index, the group's first when every bound is -inf.
+__global__ __launch_bounds__(256) void prune_pick4_kernel(const double *__restrict__ ub, long m, long gs, long long *__restrict__ pick,
+                                                          long long *__restrict__ runner) {
+    __shared__ double sv[256];
+    __shared__ long long si[256];
+    const long g0 = (long)blockIdx.x * gs;
+    const long g1 = g0 + gs < m ? g0 + gs : m;
+    double v[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    long long ix[4] = {IDX_NONE, IDX_NONE, IDX_NONE, IDX_NONE};
+    for (long c = g0 + threadIdx.x; c < g1; c += 256) {
+        const double u = ub[c];
+        if (better(u, c, v[3], ix[3])) {
+            v[3] = u; ix[3] = c;
+#pragma unroll
+            for (int k = 3; k > 0; --k)
+                if (better(v[k], ix[k], v[k - 1], ix[k - 1])) {
+                    const double tv = v[k]; v[k] = v[k - 1]; v[k - 1] = tv;
+                    const long long ti = ix[k]; ix[k] = ix[k - 1]; ix[k - 1] = ti;
+                }
+        }
+    }
+#pragma unroll
+    for (int round = 0; round < 4; ++round) {
+        Best b;
+        b.v = v[0]; b.i = ix[0];
+        b = block_argmax<256>(b, sv, si);
+        __syncthreads();   // (every thread has read the result before the next round stages its head)
+        if (b.i != IDX_NONE && b.i == ix[0]) {
+            v[0] = v[1]; v[1] = v[2]; v[2] = v[3]; v[3] = -INFINITY;
+            ix[0] = ix[1]; ix[1] = ix[2]; ix[2] = ix[3]; ix[3] = IDX_NONE;
+        }
+        if (threadIdx.x == 0) {
+            if (round == 0) pick[blockIdx.x] = b.i == IDX_NONE ? g0 : b.i;
+            else runner[3 * (long)blockIdx.x + round - 1] = b.i;
+        }
+    }
+}
+
+// The extras of the speculative round: of the R runner-ups (IDX_NONE: none) the first `cap` in `better`'s order of their
+// bounds, written in that order (larger bound first, lower index on ties: the runner-ups are distinct candidates, so the
+// order is total and the gathered rows, and every byte behind them, are the same on every run).  One wave per runner-up:
+// every workgroup stages all R (bound, index) pairs in LDS (R <= SPEC_MAXR), a wave counts the pairs in front of its own
+// with ballots, and a runner-up whose rank is below `cap` is written to extras[rank] and marked in sel.  An infinite bound
+// ranks first; an IDX_NONE place is in front of nothing.  words[1] = 0: the survivors' scatter counts there the survivors
+// that are not among the extras; words[2] = nx, the number of extras (the smaller of cap and the real runner-ups).
+constexpr int SPEC_MAXR = 3072;
+__global__ __launch_bounds__(256) void prune_extras_kernel(const double *__restrict__ ub, const long long *__restrict__ runner, int R,
+                                                           int cap, long long nx, long long *__restrict__ extras,
+                                                           int *__restrict__ sel, long long *__restrict__ words) {
+    __shared__ double sv[SPEC_MAXR];
+    __shared__ long long si[SPEC_MAXR];
+    for (int k = threadIdx.x; k < R; k += 256) {
+        const long long i = runner[k];
+        si[k] = i;
+        sv[k] = i == IDX_NONE ? -INFINITY : ub[i];
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && threadIdx.x == 0) { words[1] = 0; words[2] = nx; }
+    const int lane = threadIdx.x & 63;
+    const int k = (int)blockIdx.x * 4 + (threadIdx.x >> 6);   // (one value per wave)
+    if (k >= R) return;
+    const double vk = sv[k];
+    const long long ik = si[k];
+    int rank = 0;
+    for (int j0 = 0; j0 < R; j0 += 64) {
+        const int j = j0 + lane;
+        rank += __popcll(__ballot(j < R && better(sv[j], si[j], vk, ik)));
+    }
+    if (lane == 0) {
+        const int take = ik != IDX_NONE && rank < cap;
+        sel[k] = take;
+        if (take) extras[rank] = ik;
+    }
+}
+
+// rows idx[0..n), then idx1[0..n1), of the scaled candidates into a dense block of `rows` rows (rows >= n + n1 zero)
 template <typename T>
 __global__ __launch_bounds__(256) void prune_gather_kernel(const T *__restrict__ Cs, int Dp, const long long *__restrict__ idx,
-                                                           long n, long rows, T *__restrict__ out) {
+                                                           long n, const long long *__restrict__ idx1, long n1, long rows,
+                                                           T *__restrict__ out) {
     const long total = rows * Dp;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const long r = i / Dp;
         const int d = (int)(i - r * Dp);
-        out[i] = r < n ? Cs[idx[r] * Dp + d] : (T)0;
+        out[i] = r < n ? Cs[idx[r] * Dp + d] : (r < n + n1 ? Cs[idx1[r - n] * Dp + d] : (T)0);
     }
 }
 
@@ -95,6 +174,9 @@ struct SurvArgs {
     int *bcnt; const int *boff;       // survivors per 256-candidate block / exclusive offsets
     long long *sidx;                  // survivors' batch indices, in order
     const long long *src;             // null, or ub is over a gathered set (already clear of the lb set): src[c] is row c's batch index
+    const long long *runner;          // null, or the speculative round's runner-ups (three places per group of the lb set), ...
+    const int *sel;                   // ... which of them are its extras, ...
+    int *leftover;                    // ... and where the scatter counts the survivors that are not among the extras
 };
 
 __device__ __forceinline__ bool prune_survives(const SurvArgs &s, long c) {
@@ -143,7 +225,16 @@ __global__ __launch_bounds__(256) void prune_scatter_kernel(SurvArgs s) {
     __syncthreads();
     int off = s.boff[blockIdx.x];
     for (int k = 0; k < w; ++k) off += wsum[k];
-    if (keep) s.sidx[off + __popcll(bal & ((1ull << lane) - 1ull))] = s.src ? s.src[c] : c;
+    if (keep) {
+        const long long gc = s.src ? s.src[c] : c;
+        s.sidx[off + __popcll(bal & ((1ull << lane) - 1ull))] = gc;
+        if (s.runner) {   // an extra is one of its own group's runner-ups (an integer count: the same on every run)
+            const long g3 = 3 * (long)(gc / s.gs);
+            bool found = false;
+            for (int k = 0; k < 3; ++k) found = found || (s.runner[g3 + k] == gc && s.sel[g3 + k] != 0);
+            if (!found) atomicAdd(s.leftover, 1);
+        }
+    }
 }
 
 // the pruned sweep's own workspace (grow-only): bounds, lb set, survivors, block counts, the gathered scaled rows; for the
@@ -153,6 +244,7 @@ struct PruneWs {
     double *ub; long long *pick, *sidx, *misc; int *bcnt, *boff; void *cs;
     double *err, *ub1; long long *sidx1; float *nx;
     double *wcoef; unsigned char *xh; float *nxp, *absa; long ncap;
+    long long *runner, *extras; int *sel;   // the speculative round: three runner-ups per group, the extras taken from them, which they are
 };
 static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -170,7 +262,7 @@ struct Carver {
 };
 
 template <typename T>
-static void prune_carve(const Context &c, int64_t npick, int64_t rows_cap, bool screen, bool h2, Carver &k, PruneWs &w) {
+static void prune_carve(const Context &c, int64_t npick, int64_t rows_cap, bool screen, bool h2, bool spec, Carver &k, PruneWs &w) {
     const size_t M = (size_t)c.M, nb = (size_t)((c.M + 255) / 256), Mpad = (size_t)c.ws_Mpad;
     w.ncap = (long)((c.N + SCR_T - 1) / SCR_T + 1) * SCR_T;
     const size_t ncap = (size_t)w.ncap, nch = (size_t)((c.Dp + SCR_DC - 1) / SCR_DC);
@@ -189,15 +281,18 @@ static void prune_carve(const Context &c, int64_t npick, int64_t rows_cap, bool 
     w.xh = k.take<unsigned char>(nch * ncap * 128, h2);
     w.nxp = k.take<float>(ncap, h2);
     w.absa = k.take<float>(ncap, h2);
+    w.runner = k.take<long long>(3 * (size_t)npick, spec);
+    w.extras = k.take<long long>(3 * (size_t)npick, spec);
+    w.sel = k.take<int>(3 * (size_t)npick, spec);
 }
 
 template <typename T>
-static hipError_t prune_workspace(Context &c, int64_t npick, int64_t rows_cap, bool screen, bool h2, PruneWs &w) {
+static hipError_t prune_workspace(Context &c, int64_t npick, int64_t rows_cap, bool screen, bool h2, bool spec, PruneWs &w) {
     Carver count;
-    prune_carve<T>(c, npick, rows_cap, screen, h2, count, w);
+    prune_carve<T>(c, npick, rows_cap, screen, h2, spec, count, w);
     TGP_TRY(c.d_prune.reserve(count.off, [&] { return hipStreamSynchronize(c.stream); }));
     Carver k{c.d_prune};
-    prune_carve<T>(c, npick, rows_cap, screen, h2, k, w);
+    prune_carve<T>(c, npick, rows_cap, screen, h2, spec, k, w);
     return hipSuccess;
 }
 
@@ -271,6 +366,7 @@ struct PruneRun {
     int64_t gs, npick, keep;   // candidates per group of the lb set; its size; the most survivors taken (-1: none)
     bool screen, h2;           // the screen runs; on the fp16 matrix pipe
     ProfCursor cur;
+    int64_t nx = 0;            // the speculative round's extras (0: this sweep does not speculate)
 };
 
 // The tight bound of `rows` scaled candidates (a multiple of 16 KAR; m of them real) into ub.
@@ -358,21 +454,23 @@ static hipError_t bound_all(PruneRun<T> &r) {
     return hipSuccess;
 }
 
-// rows idx[0, n) of the scaled candidates into the dense block cs (zero rows up to a multiple of 128)
+// rows idx[0, n), then idx1[0, n1), of the scaled candidates into the dense block cs (zero rows up to a multiple of 128)
 template <typename T>
-static hipError_t gather_rows(PruneRun<T> &r, const long long *idx, int64_t n) {
+static hipError_t gather_rows(PruneRun<T> &r, const long long *idx, int64_t n, const long long *idx1 = nullptr, int64_t n1 = 0) {
     const int Dp = (int)r.c.Dp;
-    const long total = (long)pad128(n) * Dp;
+    const long total = (long)pad128(n + n1) * Dp;
     const long blocks = (total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192;
-    hipLaunchKernelGGL(prune_gather_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, r.c.stream, r.Cs, Dp, idx, (long)n,
-                       (long)pad128(n), r.cs);
+    hipLaunchKernelGGL(prune_gather_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, r.c.stream, r.Cs, Dp, idx, (long)n, idx1,
+                       (long)n1, (long)pad128(n + n1), r.cs);
     return hipGetLastError();
 }
 
-// value and block arg-max of the n contracted rows idx[0, n), their partials from block blk0 on
+// value and block arg-max of the n contracted rows idx[0, n): their partial sums from column col0 of part / mupart on (the
+// rows' place in the gathered block), their block partials from block blk0 on
 template <typename T>
-static hipError_t finalize_rows(PruneRun<T> &r, const long long *idx, int64_t n, int64_t blk0) {
+static hipError_t finalize_rows(PruneRun<T> &r, const long long *idx, int64_t n, int64_t blk0, int64_t col0 = 0) {
     FinArgs f = fin_args<T>(r.c, r.p, r.call);
+    f.part += col0; f.mupart += col0;
     f.base_pairs = r.p.nunits;   // 128-row tiles throughout
     f.njs = 1;
     f.off = blk0 * FIN_BLOCK; f.m = n;
@@ -394,23 +492,56 @@ static hipError_t lb_set(PruneRun<T> &r, int64_t &nblk) {
     return launch_argmax(c, c.stream, (long)nblk, nullptr, nullptr, Bell{nullptr, 0, nullptr});
 }
 
-// 3. the candidates of ub[0, m) that reach the bar, compacted in order into out; their number comes back to the host
-// (the launches behind it are sized by the count)
+// 2 (speculating). the lb set AND the r.nx extras in ONE exact round: the picks with three runner-ups per group
+// (prune_pick4_kernel), the extras chosen from the runner-ups (prune_extras_kernel), both gathered into one block -- picks
+// first -- and contracted together; the picks finalized into blocks [0, nblk) as lb_set does, the extras into the nblk_x
+// blocks behind them.  The bar is lb_set's: the arg-max over the PICKS' blocks alone.
 template <typename T>
-static hipError_t survivors(PruneRun<T> &r, const double *ub, int64_t m, const long long *src, long long *out, long long &n) {
+static hipError_t lb_set_with_extras(PruneRun<T> &r, int64_t &nblk, int64_t &nblk_x) {
+    Context &c = r.c;
+    const PruneWs &w = r.w;
+    hipLaunchKernelGGL(prune_pick4_kernel, dim3((unsigned)r.npick), dim3(256), 0, c.stream, w.ub, (long)c.M, (long)r.gs, w.pick, w.runner);
+    TGP_TRY(hipGetLastError());
+    const int R = (int)(3 * r.npick);
+    hipLaunchKernelGGL(prune_extras_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, c.stream, w.ub, w.runner, R, (int)r.nx,
+                       (long long)r.nx, w.extras, w.sel, w.misc);
+    TGP_TRY(hipGetLastError());
+    TGP_TRY(gather_rows(r, w.pick, r.npick, w.extras, r.nx));
+    TGP_TRY(contract_rows<T>(c, r.p, r.cs, r.npick + r.nx, r.cur));
+    TGP_TRY(finalize_rows(r, w.pick, r.npick, 0));
+    nblk = (r.npick + FIN_BLOCK - 1) / FIN_BLOCK;
+    TGP_TRY(finalize_rows(r, w.extras, r.nx, nblk, r.npick));
+    nblk_x = (r.nx + FIN_BLOCK - 1) / FIN_BLOCK;
+    return launch_argmax(c, c.stream, (long)nblk, nullptr, nullptr, Bell{nullptr, 0, nullptr});
+}
+
+// 3. the candidates of ub[0, m) that reach the bar, compacted in order into out; their number comes back to the host
+// (the launches behind it are sized by the count).  leftover (the speculative round): with it comes the number of them that
+// are not among the extras
+template <typename T>
+static hipError_t survivors(PruneRun<T> &r, const double *ub, int64_t m, const long long *src, long long *out, long long &n,
+                            long long *leftover = nullptr) {
     Context &c = r.c;
     const PruneWs &w = r.w;
     hipStream_t st = c.stream;
     const int64_t nb = (m + 255) / 256;
-    SurvArgs s{ub, (long)m, w.pick, (long)r.gs, c.d_best, r.b.margin, w.bcnt, w.boff, out, src};
+    SurvArgs s{ub, (long)m, w.pick, (long)r.gs, c.d_best, r.b.margin, w.bcnt, w.boff, out, src, nullptr, nullptr, nullptr};
+    if (leftover) { s.runner = w.runner; s.sel = w.sel; s.leftover = reinterpret_cast<int *>(w.misc + 1); }
     hipLaunchKernelGGL(prune_count_kernel, dim3((unsigned)nb), dim3(256), 0, st, s);
     TGP_TRY(hipGetLastError());
     hipLaunchKernelGGL(prune_scan_kernel, dim3(1), dim3(1024), 0, st, w.bcnt, (int)nb, w.boff, w.misc);
     TGP_TRY(hipGetLastError());
     hipLaunchKernelGGL(prune_scatter_kernel, dim3((unsigned)nb), dim3(256), 0, st, s);
     TGP_TRY(hipGetLastError());
-    TGP_TRY(hipMemcpyAsync(&n, w.misc, sizeof(long long), hipMemcpyDeviceToHost, st));
-    return hipStreamSynchronize(st);
+    if (!leftover) {
+        TGP_TRY(hipMemcpyAsync(&n, w.misc, sizeof(long long), hipMemcpyDeviceToHost, st));
+        return hipStreamSynchronize(st);
+    }
+    long long back[2] = {0, 0};   // [0] the count, [1] the leftover count (prune_extras_kernel zeroed it)
+    TGP_TRY(hipMemcpyAsync(back, w.misc, sizeof back, hipMemcpyDeviceToHost, st));
+    TGP_TRY(hipStreamSynchronize(st));
+    n = back[0]; *leftover = back[1];
+    return hipSuccess;
 }
 
 // 4. behind the screen, by the number of its survivors S0 (in w.sidx): more than `keep` -- the screen was too loose for this
@@ -483,6 +614,24 @@ static BoundArgs bound_args(const Context &c, const SweepCall &call, double marg
 // contracted candidate goes through the full sweep's arithmetic, the one arg-max sees batch indices, and no skipped
 // candidate can clamp (the gate above): value, index and n_clamped are the full sweep's.  The screen's own values and
 // its looseness never reach a result; they only move work between "skipped" and "contracted".
+//
+// The speculative round (TGP_PRUNE_SPEC).  Steps 2 and 5 are two exact rounds in series only because the survivors are
+// named by lb, and a small round lasts as long as its heaviest workgroup's k-chain however few rows it holds: the second
+// round's rows cost next to nothing as more workgroups of the first.  So the survivors are guessed: the runner-ups -- the
+// second to fourth bound of each group -- ranked by bound, the first TGP_PRUNE_SPEC_CAP of them (the extras, in that
+// order) gathered behind the picks and contracted in the lb set's round; the picks' blocks alone give lb, as in step 2;
+// step 3 runs unchanged and also counts the survivors that are no extras.  None left over (a hit): the arg-max over the
+// picks' and the extras' blocks ends the sweep.  Otherwise (a miss) steps 4 and 5 run as if the extras had never been.
+// Mode 1 speculates only when the handle's previous pruned sweep ended pruned with 1 .. cap survivors of its first filter:
+// a handle's first sweep, and every sweep after one without survivors, makes today's launches one for one.  The history
+// and the guess choose a schedule, never a value.
+// Why the result is still the full sweep's, byte for byte: (a) lb is the same value -- the same picks (prune_pick4_kernel's
+// first place is prune_pick_kernel's), each contracted by the full sweep's arithmetic, and a contracted candidate's value
+// does not depend on which row of which launch it sat in (contract_variant); (b) every candidate with ub >= lb - margin
+// |lb| is contracted before the final arg-max -- on a hit the survivors are all extras, on a miss by steps 4 and 5; (c) an
+// extra that is no survivor has a value <= ub < lb - margin |lb| <= lb and cannot win or tie (lb = -inf: every candidate
+// survives; the arg-max sees batch indices, so the lowest index still wins a tie among survivors); (d) under the clamp gate
+// no candidate clamps, so the extras add nothing to the counter.  last_prune() reports what the two-round schedule would.
 template <typename T>
 static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCall &call, bool front_usable, bool &done) {
     done = false;
@@ -492,28 +641,55 @@ static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCal
     const int64_t gs = (M + top - 1) / top, npick = (M + gs - 1) / gs;
     const double frac = tuning_prune_frac_now();
     const int64_t keep = frac < 0.0 ? -1 : (frac >= 1.0 ? M : (int64_t)(frac * (double)M));   // most survivors taken
-    const int64_t rows_cap = pad128(npick > keep ? npick : keep);
+    // the speculative round (the comment above): this many extras ride in the lb set's exact round
+    const int spec_mode = tuning_prune_spec_now();
+    const int64_t cap = tuning_prune_spec_cap_now();
+    const int64_t last = M - (npick - 1) * gs;   // members of the last group
+    const int64_t nrunner = (npick - 1) * (gs - 1 < 3 ? gs - 1 : 3) + (last - 1 < 3 ? last - 1 : 3);
+    const int64_t nx_max = spec_mode != 0 && cap > 0 && 3 * npick <= SPEC_MAXR ? (cap < nrunner ? cap : nrunner) : 0;
+    const bool spec = nx_max > 0 && (spec_mode >= 2 || (c.prune_hist >= 1 && c.prune_hist <= cap));
+    const int64_t rows_cap = pad128(npick + nx_max > keep ? npick + nx_max : keep);
     const bool screen = sizeof(T) == 4 && c.kernel == TGP_RBF && c.D <= SCR_MAXD && tuning_prune_screen_now() != 0;
     // the screen's arithmetic: fp16 planes and the weighted error where its closed form is no looser than the f32 screen's
     const bool h2 = screen && tuning_screen_arith_now() == 2 && c.D >= SCRH_MIN_D;
     PruneRun<T> r{c, p, call, PruneWs{}, BoundArgs{}, reinterpret_cast<const T *>(c.d_Cs.get()), train_points<T>(c), nullptr,
                   gs, npick, keep, screen, h2, ProfCursor{c, c.stream, -1}};
-    TGP_TRY(prune_workspace<T>(c, npick, rows_cap, screen, h2, r.w));
+    TGP_TRY(prune_workspace<T>(c, npick, rows_cap, screen, h2, nx_max > 0, r.w));
     TGP_TRY(lds_opt_in(c, p.early.kern, p.early.lds));   // (the request the fit's early row tiles make of the same kernel)
     r.cs = reinterpret_cast<T *>(r.w.cs);
     c.prune_screen = -1;
     c.prune_arith = 0;
+    c.prune_hist = -1;   // (what this sweep leaves for the next one's choice: set where it ends in state 0)
     if (!front_usable) TGP_TRY(issue_prep<T>(c, c.stream));   // (a fit's front has scaled them already)
     r.cur.restart();
     r.b = bound_args(c, call, tu.prune_margin);
+    r.nx = spec ? nx_max : 0;
 
     TGP_TRY(bound_all(r));                                                   // 1. the bound of every candidate
-    int64_t nblk_lb = 0;
-    TGP_TRY(lb_set(r, nblk_lb));                                             // 2. the lb set, exactly: the bar
-    long long nsurv = 0;
+    int64_t nblk_lb = 0, nblk_x = 0;
+    long long nsurv = 0, leftover = 0;
     const long long *sidx = r.w.sidx;
-    TGP_TRY(survivors(r, r.w.ub, M, nullptr, r.w.sidx, nsurv));              // 3. the survivors, in index order
+    if (spec) {
+        TGP_TRY(lb_set_with_extras(r, nblk_lb, nblk_x));                     // 2. the lb set and the extras, exactly: the bar
+        TGP_TRY(survivors(r, r.w.ub, M, nullptr, r.w.sidx, nsurv, &leftover));   // 3. the survivors; how many the extras miss
+    } else {
+        TGP_TRY(lb_set(r, nblk_lb));                                         // 2. the lb set, exactly: the bar
+        TGP_TRY(survivors(r, r.w.ub, M, nullptr, r.w.sidx, nsurv));          // 3. the survivors, in index order
+    }
     c.prune_lbset = npick;
+    const long long nsurv0 = nsurv;   // the first filter's survivors
+    if (spec && leftover == 0 && nsurv <= r.nx && nsurv <= keep && (!screen || nsurv <= tuning_prune_direct_now())) {
+        // hit: every survivor is an extra and already contracted -- ONE arg-max over the picks' and the extras' blocks
+        if (screen) c.prune_screen = nsurv;
+        c.prune_surv = nsurv;
+        c.prune_spec = 1;
+        TGP_TRY(launch_argmax(c, c.stream, (long)(nblk_lb + nblk_x), call.winner, call.res, Bell{nullptr, 0, nullptr}));
+        c.prune_state = 0;
+        c.prune_hist = nsurv0;
+        done = true;
+        return hipSuccess;
+    }
+    if (spec) c.prune_spec = 2;   // miss: on as if the extras had never been (their blocks are overwritten or not read)
     if (screen) {
         c.prune_screen = nsurv;
         TGP_TRY(narrow_after_screen(r, nsurv, sidx));                        // 4. the screen's survivors, narrowed
@@ -526,6 +702,7 @@ static hipError_t sweep_pruned(Context &c, const SweepPlan<T> &p, const SweepCal
     }
     TGP_TRY(contract_survivors_and_pick(r, sidx, nsurv, nblk_lb));           // 5. contract them; one arg-max over both sets
     c.prune_state = 0;
+    c.prune_hist = nsurv0;
     done = true;
     return hipSuccess;
 }

@@ -1601,6 +1601,7 @@ static int run_sweep(Context &c, const SweepCall &call, CallClock &clk) {
     c.prune_lbset = c.prune_surv = 0;
     c.prune_screen = -1;
     c.prune_arith = 0;
+    c.prune_spec = 0;
     if ((rc = call_begin(c, clk)) != TGP_OK) return rc;
     hipError_t le;
     if (path == SweepPath::OneLaunch) {
@@ -3149,15 +3150,18 @@ int tgp_last_timings(tgp_handle h, double *out, int64_t n) try {
     // screen's arithmetic, 0 none, 1 f32, 2 fp16 planes (TGP_SCREEN_ARITH)
     // [19]: device time of the last tgp_loo's three kernels (ms; the copies back left out)
     // [20]: device time of the last tgp_sweep_kg's own kernels (ms; cross-covariance + envelope, the copies left out)
-    double v[21] = {c.last_fit_ms, c.last_sweep_ms, c.last_grad_ms[0], c.last_grad_ms[1], c.last_grad_ms[2], c.trmm_flops,
+    // [21]: the speculative round of the last tgp_sweep's pruned schedule (TGP_PRUNE_SPEC): 0 not tried, 1 hit (the runner-ups
+    // covered every survivor: one exact round), 2 miss (the survivors' round ran as well)
+    double v[22] = {c.last_fit_ms, c.last_sweep_ms, c.last_grad_ms[0], c.last_grad_ms[1], c.last_grad_ms[2], c.trmm_flops,
                     (double)c.last_sweep_f64, 0.0, 0.0, 0.0, 0.0, 0.0, (double)c.prune_state, (double)c.prune_lbset,
-                    (double)c.prune_surv, c.last_cov_ms, (double)c.prune_screen, c.screen_ms, (double)c.prune_arith, c.last_loo_ms, c.last_kg_ms};
+                    (double)c.prune_surv, c.last_cov_ms, (double)c.prune_screen, c.screen_ms, (double)c.prune_arith, c.last_loo_ms, c.last_kg_ms,
+                    (double)c.prune_spec};
     if (c.h_bell && c.h_bell[1]) {
         const unsigned long long t0 = c.h_bell[1];
         const int src[5] = {3, 4, 5, 6, 2};
         for (int k = 0; k < 5; ++k) v[7 + k] = c.h_bell[src[k]] >= t0 ? (double)(c.h_bell[src[k]] - t0) * 1e-2 : 0.0;
     }
-    for (int64_t i = 0; i < n; ++i) out[i] = i < 21 ? v[i] : 0.0;
+    for (int64_t i = 0; i < n; ++i) out[i] = i < 22 ? v[i] : 0.0;
     return TGP_OK;
 } TGP_CATCH
 

@@ -196,6 +196,9 @@ struct Context : FitMem, WsMem, OutMem {
     int64_t prune_lbset = 0, prune_surv = 0;   // ... candidates in its lb set / survivors
     int64_t prune_screen = -1;    // ... survivors of its screen (prune_screen.hpp); -1: the screen did not apply (f64, Matern, TGP_PRUNE_SCREEN=0, not pruned)
     int prune_arith = 0;          // ... and the screen's arithmetic: 0 no screen, 1 f32 (prune_screen.hpp), 2 fp16 planes (prune_screen_h2.hpp)
+    int prune_spec = 0;           // ... and its speculative round (sweep_pruned.hpp): 0 not tried, 1 hit, 2 miss
+    int64_t prune_hist = -1;      // the handle's PREVIOUS pruned sweep: the survivors of its first filter when it ended in state 0, else -1.
+                                  // Survives a refit; only ever chooses the schedule (TGP_PRUNE_SPEC=1), never a result
     double screen_ms = 0.0;       // profiling: the screen's launches since tgp_profile_reset
     Dev<double> d_bval;           // per finalize block arg-max value
     Dev<long long> d_bidx;        // per finalize block arg-max index

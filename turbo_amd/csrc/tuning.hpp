@@ -43,6 +43,8 @@ namespace tgp {
     X(INT, prune_screen, "TGP_PRUNE_SCREEN", 1, "1 = the pruned sweep of an f32 RBF handle screens every candidate on the matrix cores first (prune_screen.hpp) and runs its tight bound pass only on the screen's survivors; 0 = the tight bound pass over all candidates [per call]") \
     X(STR, screen_arith, "TGP_SCREEN_ARITH", "h2", "arithmetic of that screen: h2 = two fp16 planes per operand on v_mfma_f32_32x32x16_f16 and a k-weighted error (prune_screen_h2.hpp; D >= 15, else f32), f32 = prune_screen.hpp's kernel and closed form; the A/B switch [per call]") \
     X(INT, prune_direct, "TGP_PRUNE_DIRECT", 1024, "screen survivors up to this many are contracted as they are; more (up to TGP_PRUNE_FRAC of the batch) go through the tight bound pass first [per call]") \
+    X(INT, prune_spec, "TGP_PRUNE_SPEC", 1, "the pruned sweep contracts its groups' runner-ups in the lb set's round and skips the survivors' round when they cover every survivor: 0 = never, 1 = after a sweep that kept 1 .. TGP_PRUNE_SPEC_CAP survivors, 2 = always [per call]") \
+    X(INT, prune_spec_cap, "TGP_PRUNE_SPEC_CAP", 128, "runner-ups taken into that round at most (the largest bounds among the second to fourth of each group) [per call]") \
     X(DBL, prune_margin, "TGP_PRUNE_MARGIN", 1e-6, "relative slack of the pruned sweep's bounds against the bar (rounding of the acquisition formulas)") \
     X(INT, mid, "TGP_MID", 1, "0 = 128 < N <= 256 down the general sweep instead of the one-launch kernel")                      \
     X(INT, mid_maxm, "TGP_MID_MAXM", 0, "largest batch that takes the one-launch sweep for 256 < N <= 512 (0 = never) [per call]") \
@@ -165,6 +167,8 @@ inline int tuning_prune_screen_now() { return TGP_NOW(int, prune_screen); }
 inline int tuning_screen_arith_now() { return TGP_NOW(str, screen_arith) == "f32" ? 1 : 2; }   // 1 = f32, 2 = h2
 inline int tuning_prune_direct_now() { return TGP_NOW(int, prune_direct); }
 inline double tuning_prune_min_work_now() { return TGP_NOW(dbl, prune_min_work); }
+inline int tuning_prune_spec_now() { return TGP_NOW(int, prune_spec); }
+inline int tuning_prune_spec_cap_now() { return TGP_NOW(int, prune_spec_cap); }
 #undef TGP_NOW
 
 }  // namespace tgp
