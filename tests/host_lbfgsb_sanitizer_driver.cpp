@@ -2,9 +2,11 @@
 // -fsanitize=address,undefined and walked over objectives that reach every branch -- memory wrap-around (more than 10
 // pairs), active bounds at the Cauchy point, the subspace step's projection and back-tracking, a wall of +inf, a start
 // inside the wall, lo == hi, no bounds at all, the iteration limit (GPU sanitizers are not available on this pool: CPU
-// build only).
+// build only).  Then three of the walks again in lock-step -- a plain one, one whose first trial hits the wall (it ends on
+// a step from the cache), one stopped by max_iter = 1 -- which must print what each prints alone.
 #include <cmath>
 #include <cstdio>
+#include <string>
 #include <vector>
 
 #include "host_lbfgsb.hpp"
@@ -23,26 +25,59 @@ static double rosen(const std::vector<double> &x, std::vector<double> &g, double
     return f;
 }
 
+struct Case { int P; double lo, hi, x0, wall; int max_iter; };
+
+struct Run {
+    Case c;
+    std::vector<double> lo, hi, gt;
+    tgp::LbfgsbWalk walk;
+    static std::vector<double> bound(const Case &c, double v, int open, double inf) {
+        std::vector<double> b((size_t)c.P, v);
+        if (c.P == 20) b[(size_t)open] = inf;                              // half-open coordinates among boxed ones
+        return b;
+    }
+    explicit Run(const Case &c_)
+        : c(c_), lo(bound(c_, c_.lo, 7, -INFINITY)), hi(bound(c_, c_.hi, 3, INFINITY)), gt((size_t)c_.P),
+          walk(std::vector<double>((size_t)c_.P, c_.x0).data(), lo.data(), hi.data(), c_.P, c_.max_iter, 1e-5, 2.220446049250313e-09) {}
+    bool advance() {                                                       // one evaluation, if the walk wants one
+        if (!walk.wants_eval()) return false;
+        const double f = rosen(walk.xt, gt, c.wall);
+        walk.tell(f, gt);
+        return true;
+    }
+    std::string line() const {
+        const tgp::HostLbfgsb &opt = walk.opt;
+        bool inside = true;
+        for (int k = 0; k < c.P; ++k) inside = inside && opt.x[(size_t)k] >= lo[(size_t)k] && opt.x[(size_t)k] <= hi[(size_t)k];
+        char buf[160];
+        snprintf(buf, sizeof buf, "P=%d status=%d iters=%d evals=%d f=%.6g inside=%d", c.P, opt.status, opt.iters, (int)walk.evals,
+                 opt.phi, (int)inside);
+        return buf;
+    }
+};
+
 int main() {
-    struct Case { int P; double lo, hi, x0, wall; int max_iter; };
     const Case cases[] = {{2, -5, 5, -1.2, 1e9, 15000}, {66, -5, 5, -1.2, 1e9, 15000}, {20, -0.5, 0.8, 0.0, 1e9, 15000},
                           {5, -2, 2, -1.5, 0.3, 15000}, {3, -2, 2, 1.0, 0.5, 15000}, {8, -INFINITY, INFINITY, -1.2, 1e9, 15000},
                           {12, -5, 5, -1.2, 1e9, 7}, {4, 0.5, 0.5, 0.5, 1e9, 15000}};
     for (const Case &c : cases) {
-        std::vector<double> lo((size_t)c.P, c.lo), hi((size_t)c.P, c.hi), xt((size_t)c.P, c.x0), gt((size_t)c.P);
-        if (c.P == 20) { hi[3] = INFINITY; lo[7] = -INFINITY; }            // half-open coordinates among boxed ones
-        tgp::HostLbfgsb opt(lo.data(), hi.data(), c.P);
-        int evals = 0, it = 0;
-        for (; opt.iters < c.max_iter && it < 15000; ++it) {
-            double f;
-            if (it > 0 && opt.evaluated(xt)) { f = opt.f_eval; gt = opt.g_eval; }
-            else { f = rosen(xt, gt, c.wall); ++evals; }
-            opt.step(xt, gt, f, it == 0, 1e-5, 2.220446049250313e-09);
-            if (opt.status != 0) break;
-        }
-        bool inside = true;
-        for (int k = 0; k < c.P; ++k) inside = inside && opt.x[(size_t)k] >= lo[(size_t)k] && opt.x[(size_t)k] <= hi[(size_t)k];
-        printf("P=%d status=%d iters=%d evals=%d f=%.6g inside=%d\n", c.P, opt.status, opt.iters, evals, opt.phi, (int)inside);
+        Run r(c);
+        while (r.advance()) {}
+        printf("%s\n", r.line().c_str());
     }
-    return 0;
+    // lock-step: the walks finish at different rounds
+    const Case three[] = {{2, -5, 5, -1.2, 1e9, 15000}, {2, -2, 2, 0.0, 0.1, 15000}, {12, -5, 5, -1.2, 1e9, 1}};
+    std::vector<Run> together(three, three + 3);
+    for (bool any = true; any;) {
+        any = false;
+        for (Run &r : together) any = r.advance() || any;
+    }
+    int differ = 0;
+    for (int i = 0; i < 3; ++i) {
+        Run alone(three[i]);
+        while (alone.advance()) {}
+        printf("alone %s\nlockstep %s\n", alone.line().c_str(), together[(size_t)i].line().c_str());
+        differ += alone.line() != together[(size_t)i].line();
+    }
+    return differ;
 }

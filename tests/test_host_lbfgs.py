@@ -43,6 +43,31 @@ def minimise(tmp_path_factory):
         st = lib.host_lbfgs_minimise(CB(cb), None, P, x.ctypes.data_as(DP), lo.ctypes.data_as(DP), hi.ctypes.data_as(DP),
                                      max_iter, 1e-5, 2.220446049250313e-09, ctypes.byref(fo), ctypes.byref(ev), ctypes.byref(it))
         return x, fo.value, st, ev.value, it.value
+
+    IP = ctypes.POINTER(ctypes.c_int)
+    lib.host_lbfgs_lockstep.argtypes = [CB, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, DP, DP, DP, IP, ctypes.c_double,
+                                        ctypes.c_double, DP, IP, IP, IP]
+    lib.host_lbfgs_lockstep.restype = None
+
+    def lockstep(f, X0, lo, hi, max_iter):
+        """R walks advanced together: [(x, f, status, evaluations, iterations)] as `run` returns them"""
+        R, P = np.shape(X0)
+
+        def cb(xp, gp, _):
+            v, g = f(np.array([xp[i] for i in range(P)]))
+            for i in range(P):
+                gp[i] = g[i]
+            return float(v)
+        x = np.array(X0, dtype=np.float64)
+        lo, hi = np.array(lo, dtype=np.float64), np.array(hi, dtype=np.float64)
+        mi = np.array(max_iter, dtype=np.int32)
+        fo = np.zeros(R)
+        ev, it, st = (np.zeros(R, dtype=np.int32) for _ in range(3))
+        lib.host_lbfgs_lockstep(CB(cb), None, P, R, x.ctypes.data_as(DP), lo.ctypes.data_as(DP), hi.ctypes.data_as(DP),
+                                mi.ctypes.data_as(IP), 1e-5, 2.220446049250313e-09, fo.ctypes.data_as(DP), ev.ctypes.data_as(IP),
+                                it.ctypes.data_as(IP), st.ctypes.data_as(IP))
+        return [(x[r], float(fo[r]), int(st[r]), int(ev[r]), int(it[r])) for r in range(R)]
+    run.lockstep = lockstep
     return run
 
 
@@ -127,6 +152,28 @@ def test_degenerate_objectives(minimise):
         _same_walk_as_scipy(minimise, walled_later, np.array(x0), np.full(2, -2.0), np.full(2, 2.0))
 
 
+def test_walks_in_lock_step_are_the_walks_alone(minimise):
+    """three walks advanced together, as tgp_acq_lbfgsb advances its restarts -- a Rosenbrock start, a start whose first
+    trial hits the wall of +inf (it stops where it stands, on a step answered from the cache) and a start limited by
+    max_iter = 1: they end at different rounds, each with the x, f, status, evaluations and iterations of the same walk alone"""
+    def walled(x):
+        if x[1] > 1.5:
+            return np.inf, np.zeros_like(x)
+        return _rosen(x)
+    lo, hi = np.full(2, -2.0), np.full(2, 2.0)
+    X0 = np.array([[0.5, 1.4], [-1.5, 1.45], [0.0, 0.0]])
+    max_iter = [15000, 15000, 1]
+    alone = [minimise(walled, x0, lo, hi, max_iter=mi) for x0, mi in zip(X0, max_iter)]
+    together = minimise.lockstep(walled, X0, lo, hi, max_iter)
+    for r, (a, t) in enumerate(zip(alone, together)):
+        assert np.array_equal(a[0], t[0]) and a[1:] == t[1:], (r, a, t)
+    (_, _, st0, ev0, it0), (x1, _, st1, ev1, it1), (_, _, st2, ev2, it2) = together
+    assert st0 == 1 and it0 > 5
+    assert np.array_equal(x1, X0[1]) and st1 == 1 and ev1 < ev0        # the wall at its first trial: it stops where it stands
+    assert (st2, it2) == (0, 1)
+    assert len({ev0, ev1, ev2}) == 3
+
+
 @pytest.mark.parametrize("kind,N,D,ard", [("rbf", 40, 2, False), ("matern52", 60, 3, True), ("matern32", 90, 4, False),
                                           ("matern12", 50, 2, True)])
 def test_log_marginal_likelihood_of_the_oracle(minimise, kind, N, D, ard):
@@ -165,6 +212,14 @@ def test_lbfgsb_under_sanitizers(tmp_path):
     run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert run.returncode == 0 and "ERROR" not in run.stderr and "runtime error" not in run.stderr, run.stderr[-3000:]
     lines = run.stdout.strip().splitlines()
+    # behind the eight walks: three of them in lock-step, each line beside the line of the same walk alone
+    pairs, lines = lines[8:], lines[:8]
+    assert len(pairs) == 6 and all("inside=1" in ln for ln in pairs), run.stdout
+    for alone, together in zip(pairs[0::2], pairs[1::2]):
+        assert alone.startswith("alone ") and together == "lockstep " + alone[len("alone "):], run.stdout
+    ev = [int(ln.split("evals=")[1].split()[0]) for ln in pairs[0::2]]
+    assert ev[0] > 2 * max(ev[1:]), run.stdout                                           # the first walks on long after the others ended
+    assert "status=0 iters=1 " in pairs[4] and "status=1 iters=1 evals=3 f=1 " in pairs[2], run.stdout  # max_iter = 1 | stopped by the wall, where it stood (f(0, 0) = 1)
     assert len(lines) == 8 and all("inside=1" in ln for ln in lines), run.stdout
     st = [int(ln.split("status=")[1].split()[0]) for ln in lines]
     assert st[:6] == [1] * 6 and st[6] == 0 and st[7] == 1, run.stdout        # converged ... | stopped by max_iter | nothing to move

@@ -166,30 +166,11 @@ int tgp_hyper_sample(tgp_handle h, const double *X, int64_t N, int64_t D, const 
                      int64_t burn, int64_t thin, const double *width, uint64_t seed, double *theta_out, double *lml_out,
                      int64_t *evaluations, int64_t *not_pd) {
     if (!h) return TGP_BAD_ARG;
-    static_assert(tgp::SLICE_OK == TGP_OK && tgp::SLICE_NOT_PD == TGP_NOT_PD, "host_slice.hpp's statuses are tgp_status values");
-    try {
-        if (const char *msg = tgp::slice_check_args(X, N, D, y, kernel, theta0, n_ls, log_lo, log_hi, jitter, S, burn, thin,
-                                                    width, theta_out, lml_out)) {
-            h->g.err = std::string("tgp_hyper_sample: ") + msg;
-            return TGP_BAD_ARG;
-        }
-        std::vector<double> ls((size_t)n_ls);
-        auto eval = [&](const double *theta, double *lml) {
-            double constant, noise;
-            tgp::slice_unpack(theta, n_ls, constant, ls.data(), noise);
-            return h->g.fit(X, N, D, y, kernel, constant, ls.data(), n_ls, noise, jitter, normalize_y, lml, nullptr, nullptr);
-        };
-        const int rc = tgp::slice_sample(eval, (int)(2 + n_ls), theta0, log_lo, log_hi, width, S, burn, thin, seed, theta_out,
-                                         lml_out, evaluations, not_pd);
-        if (rc != TGP_OK) h->g.err = "tgp_hyper_sample: " + std::string(rc == TGP_NOT_PD ? "at theta0: " : "") + h->g.err;
-        return rc;
-    } catch (const std::bad_alloc &) {
-        h->g.err = "out of host memory";
-        return TGP_NO_MEMORY;
-    } catch (...) {
-        h->g.err = "unexpected C++ exception";
-        return TGP_HIP_ERROR;
-    }
+    auto fit = [&](double constant, const double *ls, double noise, double *lml) {
+        return h->g.fit(X, N, D, y, kernel, constant, ls, n_ls, noise, jitter, normalize_y, lml, nullptr, nullptr);
+    };
+    HOST_TRY(tgp::hyper_sample(fit, h->g.err, X, N, D, y, kernel, theta0, n_ls, log_lo, log_hi, jitter, S, burn, thin, width, seed,
+                               theta_out, lml_out, evaluations, not_pd))
 }
 
 int tgp_mt19937_uniform_columns(uint32_t *key624, int32_t *pos, int64_t M, int64_t D, const double *lo, const double *hi,

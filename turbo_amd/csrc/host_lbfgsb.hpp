@@ -12,6 +12,7 @@
 // tests/test_host_lbfgs.py holds it against SciPy on the CPU: equal iterates, evaluation and iteration counts.
 #pragma once
 #include <math.h>
+#include <stdint.h>
 
 #include <algorithm>
 #include <vector>
@@ -52,18 +53,10 @@ struct HostLbfgsb {
     double finit = 0, ginit = 0, gtest = 0, width = 0, width1 = 0, stx = 0, fx = 0, gx = 0, sty = 0, fy = 0, gy = 0, stmin = 0, stmax = 0;
 
     // ---- the last point handed to step(): a search that ends on "no further progress" asks for its best point once
-    // more; SciPy answers that from its cache of the last evaluation (ScalarFunction), and so can the caller
+    // more; SciPy answers that from its cache of the last evaluation (ScalarFunction), and so does LbfgsbWalk below
     std::vector<double> x_eval, g_eval;
     double f_eval = 0;
     bool evaluated(const std::vector<double> &xt) const { return !x_eval.empty() && xt == x_eval; }
-    // ... in one place: when xt is that point, take the step from the stored evaluation and say so (false: xt is a new
-    // point, or the first one, and wants evaluating)
-    bool step_from_cache(std::vector<double> &xt) {
-        if (!evaluated(xt)) return false;
-        const std::vector<double> gt = g_eval;      // (step() stores its arguments over the cache)
-        step(xt, gt, f_eval, false);
-        return true;
-    }
 
     HostLbfgsb(const double *lo_, const double *hi_, int P_)
         : P(P_), lo(lo_, lo_ + P_), hi(hi_, hi_ + P_), x(P_), g(P_), z(P_), d(P_), gt_prev(P_), where(P_) {
@@ -572,6 +565,68 @@ struct HostLbfgsb {
             if (!factor_T()) refresh_memory();
         }
         begin_iteration(xt);
+    }
+};
+
+// One start's walk, the reverse-communication loop around HostLbfgsb in the one place it is written:
+//     LbfgsbWalk w(x0, lo, hi, P, max_iter);
+//     while (w.wants_eval()) w.tell(f(w.xt), gradient at w.xt);
+// after which w.opt.x / phi / status / iters are the result and w.evals the evaluations made.  Several walks advance in
+// lock-step by asking each of them in turn and answering those that want a point from one batched evaluation.
+// max_iter bounds ACCEPTED iterations (opt.iters), as in the one-launch path and as SciPy's maxiter does; the line
+// searches' trial evaluations have a cap of their own, SciPy's maxfun (LBFGSB_MAXFUN; round-4 advisor: every trial used
+// to count against max_iter, so an ARD fit could stop early with status 0)
+struct LbfgsbWalk {
+    HostLbfgsb opt;
+    std::vector<double> xt;                // the point the walk wants evaluated next
+    int64_t max_iter, rounds = 0, evals = 0;
+    double pgtol, ftol;
+    bool live = true;
+
+    // (the start is clipped into the box first, as SciPy does)
+    LbfgsbWalk(const double *x0, const double *lo, const double *hi, int P, int64_t max_iter_, double pgtol_ = LBFGSB_PGTOL,
+               double ftol_ = LBFGSB_FTOL)
+        : opt(lo, hi, P), xt((size_t)P), max_iter(max_iter_), pgtol(pgtol_), ftol(ftol_) {
+        for (int k = 0; k < P; ++k) xt[(size_t)k] = HostLbfgsb::clip(x0[k], lo[k], hi[k]);
+    }
+    // the stop rule, after every step: the optimiser's own verdict, max_iter iterations, LBFGSB_MAXFUN steps
+    void stepped() {
+        if (opt.status != 0 || opt.iters >= max_iter || ++rounds >= LBFGSB_MAXFUN) live = false;
+    }
+    // Does the walk want f and g at xt?  While xt is the point evaluated last (a search giving up on "no further
+    // progress") the step is taken from that evaluation, as SciPy answers it from its cache.  False: the walk has ended.
+    bool wants_eval() {
+        while (live && opt.evaluated(xt)) {
+            const std::vector<double> gt = opt.g_eval;      // (step() stores its arguments over the cache)
+            opt.step(xt, gt, opt.f_eval, false, pgtol, ftol);
+            stepped();
+        }
+        return live;
+    }
+    // f and g at xt: one step (the first evaluation opens the walk), leaving the next point in xt
+    void tell(double f, const std::vector<double> &g) {
+        opt.step(xt, g, f, evals++ == 0, pgtol, ftol);
+        stepped();
+    }
+};
+
+// an entry with log_lo == log_hi is FIXED at that value: the optimiser works on the other entries only, as
+// scikit-learn leaves a fixed hyper-parameter out of theta (kernels.py: Hyperparameter(..., "fixed")) -- not as a
+// coordinate of the box that cannot move, whose gradient would still enter the quasi-Newton pairs
+struct FreeMask {
+    std::vector<int> fr;                   // the free entries' places in the full vector
+    std::vector<double> lo_f, hi_f;        // ... and their bounds
+    int Pf = 0;
+    FreeMask(const double *log_lo, const double *log_hi, int P) {
+        for (int k = 0; k < P; ++k)
+            if (log_lo[k] < log_hi[k]) { fr.push_back(k); lo_f.push_back(log_lo[k]); hi_f.push_back(log_hi[k]); }
+        Pf = (int)fr.size();
+    }
+    void gather(const double *full, double *free_, double sign = 1.0) const {
+        for (int k = 0; k < Pf; ++k) free_[k] = sign * full[fr[(size_t)k]];
+    }
+    void scatter(const double *free_, double *full) const {
+        for (int k = 0; k < Pf; ++k) full[fr[(size_t)k]] = free_[k];
     }
 };
 

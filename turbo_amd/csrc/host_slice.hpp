@@ -24,7 +24,10 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <string>
 #include <vector>
+
+#include "../../include/turbogp.h"
 
 namespace tgp {
 
@@ -161,6 +164,33 @@ inline void slice_unpack(const double *theta, int64_t n_ls, double &constant, do
     constant = exp(theta[0]);
     for (int64_t d = 0; d < n_ls; ++d) ls[d] = exp(theta[1 + d]);
     noise = exp(theta[1 + n_ls]);
+}
+
+static_assert(SLICE_OK == TGP_OK && SLICE_NOT_PD == TGP_NOT_PD, "host_slice.hpp's statuses are tgp_status values");
+
+// tgp_hyper_sample itself, for both libraries: the argument rules, the walk and the texts.  Every evaluation is
+// fit(constant, ls, noise, &lml) -> tgp_status: the handle's own tgp_fit, taken for its LML.  err: the handle's message
+// (a fit that fails has left its own there).
+template <class Fit>
+int hyper_sample(Fit &&fit, std::string &err, const double *X, int64_t N, int64_t D, const double *y, int kernel,
+                 const double *theta0, int64_t n_ls, const double *log_lo, const double *log_hi, double jitter, int64_t S,
+                 int64_t burn, int64_t thin, const double *width, uint64_t seed, double *theta_out, double *lml_out,
+                 int64_t *evaluations, int64_t *not_pd) {
+    if (const char *msg = slice_check_args(X, N, D, y, kernel, theta0, n_ls, log_lo, log_hi, jitter, S, burn, thin, width,
+                                           theta_out, lml_out)) {
+        err = std::string("tgp_hyper_sample: ") + msg;
+        return TGP_BAD_ARG;
+    }
+    std::vector<double> ls((size_t)n_ls);
+    auto eval = [&](const double *theta, double *lml) {
+        double constant, noise;
+        slice_unpack(theta, n_ls, constant, ls.data(), noise);
+        return fit(constant, ls.data(), noise, lml);
+    };
+    const int rc = slice_sample(eval, (int)(2 + n_ls), theta0, log_lo, log_hi, width, S, burn, thin, seed, theta_out, lml_out,
+                                evaluations, not_pd);
+    if (rc != TGP_OK) err = "tgp_hyper_sample: " + std::string(rc == TGP_NOT_PD ? "at theta0: " : "") + err;
+    return rc;
 }
 
 }  // namespace tgp

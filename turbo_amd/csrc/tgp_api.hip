@@ -2350,301 +2350,33 @@ int tgp_sweep_topk(tgp_handle h, int acq, double sf, double incumbent, double pa
     return TGP_OK;
 } TGP_CATCH
 
+}  // extern "C"
+#include "api_optimise.hpp"
+extern "C" {
+
 int tgp_acq_refine(tgp_handle h, const double *X0, int64_t R, const double *lo, const double *hi,
                    int acq, double sf, double incumbent, double param, int64_t max_iter,
                    double *x_out, double *val_out, int64_t *status_out, int64_t *iterations) try {
     if (!h) return TGP_BAD_ARG;
     HOST_NA("tgp_acq_refine");
     Context &c = h->c;
-    const char *own = (!X0 || !lo || !hi || !x_out || !val_out || R < 1 || R > 4096) ? "need X0, lo, hi, x_out, val_out and 1 <= R <= 4096" : nullptr;
-    if (int arc = acq_check_args(c, "tgp_acq_refine", own, acq, TGP_ACQ_SIGMA, sf); arc != TGP_OK) return arc;
-    if (max_iter < 1) return fail(c, TGP_BAD_ARG, "tgp_acq_refine: max_iter >= 1");
-    if (int brc = box_check(c, "tgp_acq_refine", lo, hi); brc != TGP_OK) return brc;
-    API_HIP(hipSetDevice(c.device), "hipSetDevice");
-    API_HIP(pre_join(c), "hipStreamWaitEvent");
-    const int64_t D = c.D, m = R;
-    if (small_refine_fits(c) && small_path_enabled()) {
-        // small problems: one launch, one workgroup per restart running its whole optimisation; starts and
-        // bounds are read from, results written to, device-mapped host memory (no memcpy)
-        const size_t n_in = (size_t)(R * D + 2 * D), n_out = (size_t)(8 + R * D + 4 * R);
-        int prc = ensure_pinned(c, n_in * sizeof(double), n_out * sizeof(double));
-        if (prc != TGP_OK) return prc;
-        memcpy(c.h_pin_in, X0, (size_t)(R * D) * sizeof(double));
-        memcpy(c.h_pin_in + R * D, lo, (size_t)D * sizeof(double));
-        memcpy(c.h_pin_in + R * D + D, hi, (size_t)D * sizeof(double));
-        double *o_x = c.h_pin_out.dev() + 8, *o_v = o_x + R * D, *o_info = o_v + R;
-        CallClock clk;
-        if ((prc = call_begin(c, clk)) != TGP_OK) return prc;
-        hipError_t le = launch_small_refine(c, c.h_pin_in.dev(), c.h_pin_in.dev() + R * D, c.h_pin_in.dev() + R * D + D, (int)R, acq, sf,
-                                            incumbent, param, (int)std::min<int64_t>(max_iter, 1 << 30), LBFGSB_PGTOL,
-                                            LBFGSB_FTOL, o_x, o_v, o_info);
-        if (le != hipSuccess) return hip_fail(c, le, "launch_small_refine");
-        if ((prc = call_finish(c, clk, c.last_sweep_ms, "refine sync")) != TGP_OK) return prc;
-        const double *h_x = c.h_pin_out + 8, *h_v = h_x + R * D, *h_info = h_v + R;
-        memcpy(x_out, h_x, (size_t)(R * D) * sizeof(double));
-        memcpy(val_out, h_v, (size_t)R * sizeof(double));
-        int64_t ev = 0;
-        for (int64_t r = 0; r < R; ++r) {
-            if (status_out) status_out[r] = (int64_t)h_info[3 * r];
-            ev = std::max<int64_t>(ev, (int64_t)h_info[3 * r + 2]);
-        }
-        if (iterations) *iterations = ev;      // evaluations of the slowest restart (what the lock-step path counts)
-        return TGP_OK;
-    }
-    API_MEM(grow(c, c.d_qws, query_ws(c, (int)m).bytes, "hipMalloc query workspace"));   // as tgp_acq_grad
-    // optimiser state: [state (R stride) | history of the eight-wave teams (D > 1024) | lo (D) | hi (D) | x_out (R D) |
-    //                   v_out (R) | info (2 R) | active (int)]
-    const int64_t stride = refine_state_stride((int)D);
-    const int64_t hist = refine_hist_doubles((int)D, (int)R);
-    const size_t rf_need = (size_t)(R * stride + hist + 2 * D + R * D + R + 2 * R + 2) * sizeof(double);
-    int rc = grow(c, c.d_rf, rf_need, "hipMalloc refine state");
-    if (rc != TGP_OK) return rc;
-    const QueryWs q = query_ws(c, (int)m);
-    double *d_Xq = q.Xq, *d_val = q.val, *d_grad = q.grad, *d_ws = q.ws;
-    double *d_state = c.d_rf, *d_lo = d_state + R * stride + hist, *d_hi = d_lo + D, *d_xo = d_hi + D;
-    double *d_vo = d_xo + R * D, *d_info = d_vo + R;
-    int *d_active = reinterpret_cast<int *>(d_info + 2 * R);
-    CallClock clk;
-    if ((rc = call_begin(c, clk)) != TGP_OK) return rc;
-    API_HIP(hipMemcpyAsync(d_Xq, X0, (size_t)(R * D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D X0");
-    API_HIP(hipMemcpyAsync(d_lo, lo, (size_t)D * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D lo");
-    API_HIP(hipMemcpyAsync(d_hi, hi, (size_t)D * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D hi");
-    hipError_t le = launch_refine_clip(c, d_Xq, d_lo, d_hi, (int)R);
-    if (le != hipSuccess) return hip_fail(c, le, "launch_refine_clip");
-    // every iteration: one batched value + gradient evaluation of all R trial points (the closed-form
-    // kernels of tgp_acq_grad), then one optimiser step for all restarts.  The host only looks at
-    // the count of unfinished restarts, every 4th iteration.
-    int64_t it = 0;
-    int active = (int)R;
-    for (; it <= max_iter; ++it) {
-        // (the wave step turns the evaluation's sums into value + gradient itself, one launch fewer)
-        const bool fused = true;
-        le = launch_query(c, d_Xq, (int)m, acq, sf, incumbent, param, d_ws, fused ? nullptr : d_val, d_grad);
-        if (le != hipSuccess) return hip_fail(c, le, "launch_query");
-        le = launch_refine_step(c, d_state, d_Xq, d_val, d_grad, d_lo, d_hi, (int)R, (int)it, LBFGSB_PGTOL, LBFGSB_FTOL, d_active,
-                                fused ? q.red : nullptr, acq, sf, incumbent, param);
-        if (le != hipSuccess) return hip_fail(c, le, "launch_refine_step");
-        if ((it & 3) == 3 || it == max_iter) {
-            API_HIP(hipMemcpyAsync(&active, d_active + (it & 1), sizeof(int), hipMemcpyDeviceToHost, c.stream), "D2H active");
-            API_HIP(hipStreamSynchronize(c.stream), "refine sync");
-            if (active == 0) { ++it; break; }
-        }
-    }
-    le = launch_refine_collect(c, d_state, (int)R, d_xo, d_vo, d_info);
-    if (le != hipSuccess) return hip_fail(c, le, "launch_refine_collect");
-    std::vector<double> info((size_t)(2 * R));
-    API_HIP(hipMemcpyAsync(x_out, d_xo, (size_t)(R * D) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H x");
-    API_HIP(hipMemcpyAsync(val_out, d_vo, (size_t)R * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H values");
-    API_HIP(hipMemcpyAsync(info.data(), d_info, (size_t)(2 * R) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H info");
-    if ((rc = call_finish(c, clk, c.last_sweep_ms, "refine sync")) != TGP_OK) return rc;
-    if (status_out)
-        for (int64_t r = 0; r < R; ++r) status_out[r] = (int64_t)info[(size_t)(2 * r)];
-    if (iterations) *iterations = it;
-    return TGP_OK;
+    const RefineArgs a{X0, R, lo, hi, acq, sf, incumbent, param, max_iter};
+    const RefineOut out{x_out, val_out, status_out, iterations};
+    if (int rc = check_refine_args(c, "tgp_acq_refine", a, out, TGP_ACQ_SIGMA); rc != TGP_OK) return rc;
+    return acq_refine(c, a, out);
 } TGP_CATCH
 
-// The gradient stage as the reference runs it -- scipy.optimize.minimize(method='L-BFGS-B', default limits) on the
-// negated acquisition from every start (turbo/modules/auxiliary_optimisers.py:80-99) -- inside the library: one
-// host_lbfgsb.hpp optimiser per restart, all of them in LOCK-STEP on the calling thread (reverse communication needs no
-// threads): every round gathers the trial points of the restarts still running, ONE batched closed-form value +
-// gradient evaluation serves them all (tgp_acq_grad: a point's value does not depend on the batch it travels in), and
-// every optimiser takes its step.  What turbo_amd/auxiliary_optimisers.py did with a Python thread and a SciPy
-// optimiser per restart meeting at a rendezvous; same walk per restart, no interpreter between two rounds.
 int tgp_acq_lbfgsb(tgp_handle h, const double *X0, int64_t R, const double *lo, const double *hi,
                    int acq, double sf, double incumbent, double param, int64_t max_iter,
                    double *x_out, double *val_out, int64_t *status_out, int64_t *evaluations) try {
     if (!h) return TGP_BAD_ARG;
     HOST_NA("tgp_acq_lbfgsb");
     Context &c = h->c;
-    const char *own = (!X0 || !lo || !hi || !x_out || !val_out || R < 1 || R > 4096) ? "need X0, lo, hi, x_out, val_out and 1 <= R <= 4096" : nullptr;
-    if (int arc = acq_check_args(c, "tgp_acq_lbfgsb", own, acq, TGP_ACQ_MES, sf); arc != TGP_OK) return arc;
-    if (max_iter < 1) return fail(c, TGP_BAD_ARG, "tgp_acq_lbfgsb: max_iter >= 1");
-    if (int brc = box_check(c, "tgp_acq_lbfgsb", lo, hi); brc != TGP_OK) return brc;
-    const int D = (int)c.D;
-    std::vector<HostLbfgsb> opts;
-    opts.reserve((size_t)R);
-    std::vector<std::vector<double>> xt((size_t)R, std::vector<double>((size_t)D));
-    std::vector<char> started((size_t)R, 0), live((size_t)R, 1);
-    std::vector<int64_t> rounds((size_t)R, 0);
-    for (int64_t r = 0; r < R; ++r) {
-        opts.emplace_back(lo, hi, D);
-        for (int d = 0; d < D; ++d) xt[(size_t)r][(size_t)d] = HostLbfgsb::clip(X0[r * D + d], lo[d], hi[d]);
-    }
-    std::vector<double> Xq((size_t)R * D), val((size_t)R), grad((size_t)R * D), gt((size_t)D);
-    std::vector<int64_t> who((size_t)R);
-    int64_t ev = 0, n_live = R;
-    while (n_live > 0) {
-        // restarts whose next point is the one they evaluated last (a search giving up on "no further progress") are
-        // answered from that evaluation, as SciPy answers them from its cache; the others go into this round's batch
-        int64_t m = 0;
-        for (int64_t r = 0; r < R; ++r) {
-            if (!live[(size_t)r]) continue;
-            HostLbfgsb &o = opts[(size_t)r];
-            while (live[(size_t)r] && o.step_from_cache(xt[(size_t)r]))
-                if (o.status != 0 || o.iters >= max_iter || ++rounds[(size_t)r] >= LBFGSB_MAXFUN) { live[(size_t)r] = 0; --n_live; }
-            if (!live[(size_t)r]) continue;
-            memcpy(&Xq[(size_t)(m * D)], xt[(size_t)r].data(), (size_t)D * sizeof(double));
-            who[(size_t)m++] = r;
-        }
-        if (m == 0) break;
-        const int rc = tgp_acq_grad(h, Xq.data(), m, acq, sf, incumbent, param, val.data(), grad.data());
-        if (rc != TGP_OK) return rc;
-        ev += m;
-        for (int64_t i = 0; i < m; ++i) {
-            const int64_t r = who[(size_t)i];
-            HostLbfgsb &o = opts[(size_t)r];
-            for (int d = 0; d < D; ++d) gt[(size_t)d] = -grad[(size_t)(i * D + d)];     // maximise = minimise the negation
-            o.step(xt[(size_t)r], gt, -val[(size_t)i], !started[(size_t)r]);
-            started[(size_t)r] = 1;
-            if (o.status != 0 || o.iters >= max_iter || ++rounds[(size_t)r] >= LBFGSB_MAXFUN) { live[(size_t)r] = 0; --n_live; }
-        }
-    }
-    for (int64_t r = 0; r < R; ++r) {
-        const HostLbfgsb &o = opts[(size_t)r];
-        for (int d = 0; d < D; ++d) x_out[r * D + d] = o.x[(size_t)d];
-        val_out[r] = -o.phi;
-        if (status_out) status_out[r] = o.status;
-    }
-    if (evaluations) *evaluations = ev;
-    return TGP_OK;
+    const RefineArgs a{X0, R, lo, hi, acq, sf, incumbent, param, max_iter};
+    const RefineOut out{x_out, val_out, status_out, evaluations};
+    if (int rc = check_refine_args(c, "tgp_acq_lbfgsb", a, out, TGP_ACQ_MES); rc != TGP_OK) return rc;
+    return acq_lbfgsb_lockstep(h, a, out);
 } TGP_CATCH
-
-// tgp_fit_optimise above the one-launch sizes: every start is a host_lbfgsb.hpp optimiser (SciPy's L-BFGS-B restated:
-// the iterates scikit-learn's fit walks) driving tgp_fit_grad
-// (fit + LML gradient on the GPU); the starts run side by side, a C++ thread and a handle on a stream of its own
-// each (start j of a thread's share after the other: thread t takes starts t, t + T, ...), with no interpreter
-// between two evaluations.  Every start walks the iterates it walks alone -- its own optimiser state, its own
-// handle -- so the result does not depend on the number of threads.
-static int fit_optimise_streams(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
-                                const double *theta0, int64_t S, int64_t n_ls, const double *log_lo, const double *log_hi,
-                                double jitter, int normalize_y, int64_t max_iter, double *theta_out, double *f_out,
-                                int64_t *status_out, int64_t *evaluations) {
-    Context &c = h->c;
-    API_HIP(pre_join(c), "hipStreamWaitEvent");
-    const int P = (int)(2 + n_ls);
-    // measured through the plugin path (tools/bench_latency.py): one evaluation is a serial chain of ~35 launches that
-    // leaves the chip idle up to N ~ 1000; beyond, two chains already share the CUs
-    const int threads_env = tuning().hyper_threads;
-    // (round 4, late, with the workers' inverses in line and every start on a worker: three starts at N = 700 / 1000 / 1500
-    // take 18.6 / 27.1 / 36.8 ms on three threads against 32 / 42 / 53 on one; at 2048 the chains fill the chip: 120 vs 117)
-    // (round 5, late, re-measured with L-BFGS-B in the library and the one-outer-block fits: three starts side by side
-    // now pay well beyond 1536 -- N = 2048 55.8 -> 42.2 ms, 3000 110 -> 82, 4096 240 -> 206, 6144 482 -> 440, 8192 984 ->
-    // 911 -- two threads never do (2 + 1); the limit is the workers' workspaces, 4 N^2 doubles each: 2 GiB at 8192)
-    int T = threads_env > 0 ? threads_env : (N <= 1536 ? 4 : (N <= 8192 ? 3 : 1));
-    T = (int)std::min<int64_t>(T, S);
-    // With more than one thread EVERY start runs on a worker handle (a private stream each) and the caller's handle sits
-    // out: on its shared main stream it ended up serialised with one of the workers in the first factory of a fresh
-    // process (an evaluation 0.35 -> 0.83 ms on both; N = 500, three starts: 23-27 ms instead of 11.6; tools/diag_streams.py
-    // shows the pairing).  No probe saw it -- one launch on each stream, chains of memory-dependent launches from one
-    // thread, launch + wait cycles from two threads all ran side by side -- so re-creating streams until a probe passes
-    // is no cure; the workers do not show it among themselves.
-    std::vector<tgp_handle> workers((size_t)T, nullptr);
-    struct Borrowed {   // the pool is this call's from here to the return
-        tgp_handle h; bool held = false;
-        ~Borrowed() { if (held) (void)tgp_workers_release(h); }
-    } borrowed{h};
-    if (T > 1) {
-        const int rc = tgp_workers_acquire(h, T, workers.data());
-        if (rc != TGP_OK) return rc;
-        borrowed.held = true;
-    }
-    std::vector<int> status((size_t)S, 0), rcs((size_t)T, TGP_OK);
-    std::vector<int64_t> evals((size_t)S, 0);
-    std::vector<std::string> errs((size_t)T);
-    // an entry with log_lo == log_hi is FIXED at that value: the optimiser works on the other entries only, as
-    // scikit-learn leaves a fixed hyper-parameter out of theta (kernels.py: Hyperparameter(..., "fixed")) -- not as a
-    // coordinate of the box that cannot move, whose gradient would still enter the quasi-Newton pairs
-    std::vector<int> fr;
-    std::vector<double> lo_f, hi_f;
-    for (int k = 0; k < P; ++k)
-        if (log_lo[k] < log_hi[k]) { fr.push_back(k); lo_f.push_back(log_lo[k]); hi_f.push_back(log_hi[k]); }
-    const int Pf = (int)fr.size();
-    auto run_share = [&](int t) {
-      try {
-        tgp_handle hw = T == 1 ? h : workers[(size_t)t];
-        std::vector<double> ls((size_t)n_ls), grad((size_t)P), th((size_t)P), xt((size_t)Pf), gt((size_t)Pf);
-        for (int64_t s = t; s < S; s += T) {
-            // th = the full vector log(constant, length scale(s), noise); the optimiser sees its free entries only
-            for (int k = 0; k < P; ++k) th[(size_t)k] = HostLbfgsb::clip(theta0[s * P + k], log_lo[k], log_hi[k]);
-            HostLbfgsb opt(lo_f.data(), hi_f.data(), Pf);
-            for (int k = 0; k < Pf; ++k) xt[(size_t)k] = th[(size_t)fr[(size_t)k]];
-            // max_iter bounds ACCEPTED iterations (opt.iters), as in the one-launch path and as SciPy's maxiter does;
-            // the line searches' trial evaluations have a cap of their own, SciPy's maxfun (LBFGSB_MAXFUN; round-4 advisor:
-            // every trial used to count against max_iter, so an ARD fit could stop early with status 0)
-            int64_t it = 0;
-            for (; opt.iters < max_iter && it < LBFGSB_MAXFUN; ++it) {
-                if (opt.step_from_cache(xt)) {      // the search's best point once more: answered from the last evaluation
-                    if (opt.status != 0) break;
-                    continue;
-                }
-                for (int k = 0; k < Pf; ++k) th[(size_t)fr[(size_t)k]] = xt[(size_t)k];
-                const double constant = exp(th[0]), noise = exp(th[(size_t)(P - 1)]);
-                for (int64_t d = 0; d < n_ls; ++d) ls[(size_t)d] = exp(th[(size_t)(1 + d)]);
-                double lml = 0.0, phit;
-                const int rc = fit_grad_entry(hw, FitArgs{X, N, D, y, kernel, constant, ls.data(), n_ls, noise, jitter, normalize_y},
-                                              FitOut{&lml, nullptr, nullptr}, grad.data());
-                if (rc == TGP_NOT_PD) {            // -inf likelihood, zero gradient (_gpr.py:586-589)
-                    phit = INFINITY;
-                    for (int k = 0; k < Pf; ++k) gt[(size_t)k] = 0.0;
-                } else if (rc != TGP_OK) {
-                    rcs[(size_t)t] = rc;
-                    errs[(size_t)t] = tgp_last_error(hw);
-                    return;
-                } else {
-                    phit = -lml;
-                    for (int k = 0; k < Pf; ++k) gt[(size_t)k] = -grad[(size_t)fr[(size_t)k]];
-                }
-                ++evals[(size_t)s];
-                if (Pf == 0) {                     // nothing is free: the one evaluation is the answer
-                    opt.phi = phit;
-                    opt.status = 1;
-                    break;
-                }
-                opt.step(xt, gt, phit, it == 0);
-                if (opt.status != 0) break;
-            }
-            status[(size_t)s] = opt.status;
-            for (int k = 0; k < Pf; ++k) th[(size_t)fr[(size_t)k]] = opt.x[(size_t)k];
-            for (int k = 0; k < P; ++k) theta_out[s * P + k] = th[(size_t)k];
-            f_out[s] = opt.phi;
-        }
-      } catch (const std::bad_alloc &) {    // (no exception leaves a worker thread: that would be std::terminate)
-        rcs[(size_t)t] = TGP_NO_MEMORY;
-        errs[(size_t)t] = "out of host memory";
-      } catch (...) {
-        rcs[(size_t)t] = TGP_HIP_ERROR;
-        errs[(size_t)t] = "unexpected exception in a start's thread";
-      }
-    };
-    (void)run_on_start_threads(T, run_share);   // (the library's parked start threads; shares no thread could be had for run on this one)
-    for (int t = 0; t < T; ++t)
-        if (rcs[(size_t)t] != TGP_OK) return fail(c, rcs[(size_t)t], "tgp_fit_optimise: " + errs[(size_t)t]);
-    int64_t ev = 0;
-    for (int64_t s = 0; s < S; ++s) {
-        if (status_out) status_out[s] = status[(size_t)s];
-        ev += evals[(size_t)s];
-    }
-    if (evaluations) *evaluations = ev;
-    return TGP_OK;
-}
-
-static int check_optimise_args(Context &c, const char *fn, const double *X, int64_t N, int64_t D, const double *y, int kernel,
-                               const double *theta0, int64_t S, int64_t n_ls, const double *log_lo, const double *log_hi,
-                               int64_t max_iter, const double *theta_out, const double *f_out) {
-    const std::string name(fn);
-    if (!X || !y || !theta0 || !log_lo || !log_hi || !theta_out || !f_out)
-        return fail(c, TGP_BAD_ARG, name + ": need X, y, theta0, log_lo, log_hi, theta_out, f_out");
-    if (kernel < 0 || kernel > 3) return fail(c, TGP_BAD_ARG, name + ": unknown kernel");
-    if (N < 1 || D < 1 || D > 4096 || (n_ls != 1 && n_ls != D) || S < 1 || S > 64 || max_iter < 1)
-        return fail(c, TGP_BAD_ARG, name + ": needs N >= 1, 1 <= D <= 4096, n_ls 1 or D, 1 <= S <= 64, max_iter >= 1");
-    for (int64_t i = 0; i < 2 + n_ls; ++i) {
-        // (the noise entry fixed at log 0: a kernel without a noise term)
-        if (i == 1 + n_ls && log_lo[i] == -INFINITY && log_hi[i] == -INFINITY) continue;
-        if (!(log_lo[i] <= log_hi[i]) || !isfinite(log_lo[i]) || !isfinite(log_hi[i]))
-            return fail(c, TGP_BAD_ARG, name + ": bounds must be finite with lo <= hi (the noise entry may be fixed at -inf: no noise term)");
-    }
-    return TGP_OK;
-}
 
 int tgp_fit_lbfgsb(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
                    const double *theta0, int64_t S, int64_t n_ls, const double *log_lo, const double *log_hi,
@@ -2653,11 +2385,10 @@ int tgp_fit_lbfgsb(tgp_handle h, const double *X, int64_t N, int64_t D, const do
     if (!h) return TGP_BAD_ARG;
     HOST_NA("tgp_fit_lbfgsb");
     Context &c = h->c;
-    const int rc = check_optimise_args(c, "tgp_fit_lbfgsb", X, N, D, y, kernel, theta0, S, n_ls, log_lo, log_hi, max_iter, theta_out, f_out);
-    if (rc != TGP_OK) return rc;
-    API_HIP(hipSetDevice(c.device), "hipSetDevice");
-    return fit_optimise_streams(h, X, N, D, y, kernel, theta0, S, n_ls, log_lo, log_hi, jitter, normalize_y, max_iter,
-                                theta_out, f_out, status_out, evaluations);
+    const HyperOptArgs a{X, N, D, y, kernel, theta0, S, n_ls, log_lo, log_hi, jitter, normalize_y, max_iter};
+    const HyperOptOut out{theta_out, f_out, status_out, evaluations};
+    if (int rc = check_optimise_args(c, "tgp_fit_lbfgsb", a, out); rc != TGP_OK) return rc;
+    return fit_lbfgsb(h, a, out);
 } TGP_CATCH
 
 int tgp_fit_optimise(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
@@ -2667,87 +2398,24 @@ int tgp_fit_optimise(tgp_handle h, const double *X, int64_t N, int64_t D, const 
     if (!h) return TGP_BAD_ARG;
     HOST_NA("tgp_fit_optimise");
     Context &c = h->c;
-    const int rc0 = check_optimise_args(c, "tgp_fit_optimise", X, N, D, y, kernel, theta0, S, n_ls, log_lo, log_hi, max_iter, theta_out, f_out);
-    if (rc0 != TGP_OK) return rc0;
-    const int64_t Dp = ((D + 3) / 4) * 4, P = 2 + n_ls;
-    if (N > 2 * NB || Dp > 64 || P > 64 || !small_path_enabled() || log_lo[P - 1] == -INFINITY)
-        return fit_optimise_streams(h, X, N, D, y, kernel, theta0, S, n_ls, log_lo, log_hi, jitter, normalize_y, max_iter,
-                                    theta_out, f_out, status_out, evaluations);
-    API_HIP(hipSetDevice(c.device), "hipSetDevice");
-    API_HIP(pre_join(c), "hipStreamWaitEvent");
-    double mean = 0.0, sd = 1.0;
-    std::vector<double> yn((size_t)N, 0.0);
-    normalise_targets(y, N, normalize_y, yn, mean, sd);
-    // inputs through device-mapped host memory (each start copies X and the targets once), results the same way
-    const size_t n_in = (size_t)(N * D + N + S * P + 2 * P), n_out = (size_t)(8 + S * P + S + 3 * S);
-    int rc = ensure_pinned(c, n_in * sizeof(double), n_out * sizeof(double));
-    if (rc != TGP_OK) return rc;
-    double *in = c.h_pin_in;
-    memcpy(in, X, (size_t)(N * D) * sizeof(double));
-    memcpy(in + N * D, yn.data(), (size_t)N * sizeof(double));
-    memcpy(in + N * D + N, theta0, (size_t)(S * P) * sizeof(double));
-    memcpy(in + N * D + N + S * P, log_lo, (size_t)P * sizeof(double));
-    memcpy(in + N * D + N + S * P + P, log_hi, (size_t)P * sizeof(double));
-    const size_t ws_need = (size_t)S * (size_t)small_hyper_workspace_doubles((int)N, (int)D, (int)Dp) * sizeof(double);
-    rc = grow(c, c.d_rf, ws_need, "hipMalloc hyper workspace");
-    if (rc != TGP_OK) return rc;
-    const double *d_in = c.h_pin_in.dev();
-    double *o_theta = c.h_pin_out.dev() + 8, *o_f = o_theta + S * P, *o_info = o_f + S;
-    const double *h_theta = c.h_pin_out + 8, *h_f = h_theta + S * P, *h_info = h_f + S;
-    bool timed_out = false;
-    // A start whose three workgroups never met (status 3: the barrier's time budget ran out, e.g. CUs taken
-    // away by HSA_CU_MASK or by another process on the card) invalidates the launch: nothing of it reaches
-    // the caller, and the fit runs once more with one workgroup per start -- no barrier, no way to wait.
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        CallClock clk;
-        if ((rc = call_begin(c, clk)) != TGP_OK) return rc;
-        hipError_t le = launch_small_hyper(c, kernel, d_in, d_in + N * D, d_in + N * D + N, d_in + N * D + N + S * P,
-                                           d_in + N * D + N + S * P + P, (int)S, (int)N, (int)D, (int)Dp, (int)n_ls,
-                                           (int)std::min<int64_t>(max_iter, 1 << 30), jitter, c.d_rf, o_theta, o_f, o_info,
-                                           attempt > 0);
-        if (le != hipSuccess) return hip_fail(c, le, "launch_small_hyper");
-        if ((rc = call_finish(c, clk, c.last_fit_ms, "hyper sync")) != TGP_OK) return rc;
-        timed_out = false;
-        for (int64_t s = 0; s < S; ++s) timed_out = timed_out || (int64_t)h_info[3 * s] == 3;
-        if (!timed_out) break;
-    }
-    if (timed_out) return fail(c, TGP_HIP_ERROR, "tgp_fit_optimise: the barrier between a start's workgroups timed out, and so did the relaunch with one workgroup per start");
-    memcpy(theta_out, h_theta, (size_t)(S * P) * sizeof(double));
-    memcpy(f_out, h_f, (size_t)S * sizeof(double));
-    int64_t ev = 0;
-    for (int64_t s = 0; s < S; ++s) {
-        if (status_out) status_out[s] = (int64_t)h_info[3 * s];
-        ev += (int64_t)h_info[3 * s + 2];
-    }
-    if (evaluations) *evaluations = ev;
-    return TGP_OK;
+    const HyperOptArgs a{X, N, D, y, kernel, theta0, S, n_ls, log_lo, log_hi, jitter, normalize_y, max_iter};
+    const HyperOptOut out{theta_out, f_out, status_out, evaluations};
+    if (int rc = check_optimise_args(c, "tgp_fit_optimise", a, out); rc != TGP_OK) return rc;
+    return fit_optimise(h, a, out);
 } TGP_CATCH
 
 // ---- marginalised hyper-parameters: the slice sampler and the integrated sweep ------------------------------------
-static_assert(SLICE_OK == TGP_OK && SLICE_NOT_PD == TGP_NOT_PD, "host_slice.hpp's statuses are tgp_status values");
-
 int tgp_hyper_sample(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel, const double *theta0,
                      int64_t n_ls, const double *log_lo, const double *log_hi, double jitter, int normalize_y, int64_t S,
                      int64_t burn, int64_t thin, const double *width, uint64_t seed, double *theta_out, double *lml_out,
                      int64_t *evaluations, int64_t *not_pd) try {
     if (!h) return TGP_BAD_ARG;
-    std::string &err = h->host ? h->host->err : h->c.err;
-    if (const char *msg = slice_check_args(X, N, D, y, kernel, theta0, n_ls, log_lo, log_hi, jitter, S, burn, thin, width,
-                                           theta_out, lml_out)) {
-        err = std::string("tgp_hyper_sample: ") + msg;
-        return TGP_BAD_ARG;
-    }
     // every evaluation is the handle's own tgp_fit, taken for its LML: whichever fit path N selects, or the host backend
-    std::vector<double> ls((size_t)n_ls);
-    auto eval = [&](const double *theta, double *lml) {
-        double constant, noise;
-        slice_unpack(theta, n_ls, constant, ls.data(), noise);
-        return fit_entry(h, FitArgs{X, N, D, y, kernel, constant, ls.data(), n_ls, noise, jitter, normalize_y}, FitOut{lml, nullptr, nullptr});
+    auto fit = [&](double constant, const double *ls, double noise, double *lml) {
+        return fit_entry(h, FitArgs{X, N, D, y, kernel, constant, ls, n_ls, noise, jitter, normalize_y}, FitOut{lml, nullptr, nullptr});
     };
-    const int rc = slice_sample(eval, (int)(2 + n_ls), theta0, log_lo, log_hi, width, S, burn, thin, seed, theta_out, lml_out,
-                                evaluations, not_pd);
-    if (rc != TGP_OK) err = "tgp_hyper_sample: " + std::string(rc == TGP_NOT_PD ? "at theta0: " : "") + err;
-    return rc;
+    return hyper_sample(fit, h->host ? h->host->err : h->c.err, X, N, D, y, kernel, theta0, n_ls, log_lo, log_hi, jitter, S, burn,
+                        thin, width, seed, theta_out, lml_out, evaluations, not_pd);
 } TGP_CATCH
 
 int tgp_sweep_integrated(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
