@@ -582,6 +582,45 @@ int tgp_kg_set_points(tgp_handle h, const double *Xa, int64_t A, double *mu_out)
 int tgp_sweep_kg(tgp_handle h, double sf, double *kg_out, double *mu, double *sigma, double *cov_out,
                  double *best_val, int64_t *best_idx, int64_t *n_clamped);
 
+/* The knowledge gradient AND its gradient w.r.t. the query point at m <= 4096 points Xq (m, D), in closed form and in
+ * float64 whatever the handle's dtype: val (m) is tgp_sweep_kg's kg_out for the same point (same lines, same envelope
+ * order: ascending slope, of equal slopes the largest intercept), grad (m, D) its derivative.  Notation as above.  Let the
+ * upper envelope, left to right, be the lines j_0 .. j_n-1 with breakpoints -inf = z_0 < z_1 < .. < z_n = +inf, line j_k the
+ * maximum on (z_k, z_k+1), P_k = Phi(z_k+1) - Phi(z_k), E_k = phi(z_k) - phi(z_k+1).  By the envelope theorem the
+ * breakpoints' own derivatives cancel, and a line leaving the envelope takes P_k, E_k -> 0 with it (KG is C1 there):
+ *   grad KG(x) = sum_k E_k grad b_jk(x) + sf grad mu(x) ([A on the envelope] P_A - [a_A > max_{i<A} a_i])
+ *   grad b_i = grad C(Xa_i, x) / s - C(Xa_i, x) grad s / s^2 (i < A),  grad b_A = grad v / s - v grad s / s^2,  grad s = grad v / (2 s)
+ *   grad_d C(Xa_i, x) = y_std^2 (d_d c k0(x, Xa_i) - sum_j d_d c k0(x, X_j) W_ji),  d_d c k0(x, X_j) = -c h(r_j) (u_d - xs_jd) / l_d
+ * (h as in the LML gradient and tgp_acq_grad; grad mu and grad v are tgp_acq_grad's).  With e_i = E_k / s for i = j_k < A the
+ * training points' part is ONE reduction per (point, dimension), sum_j omega_j c h_j (u_d - xs_jd) / l_d, against
+ *   omega = c_mu alpha + c_v K^-1 k(x) + y_std^2 sum_k e_jk W_jk
+ * -- the sum a gather of the few rows of W the envelope holds, not a dense product -- plus the prior term
+ * y_std^2 sum_k e_jk d_d c k0(x, Xa_jk) over the same lines.  Conventions:
+ *   the only kink lies where a_A crosses max_{i<A} a_i; the indicator is a STRICT >: at a tie the derivative is the one-sided
+ *     one of "the candidate's line is not the maximum".  Where it is the maximum, P_A - 1 is never formed: the term is
+ *     -(Phi(z_lo) + Phi(-z_hi)), the two tails outside the line's interval, through the scaled complementary error function;
+ *   dead points (s^2 <= 0 or not finite, a non-finite mean): value 0 and gradient 0, as tgp_sweep_kg's value;
+ *   a clamped latent variance: grad v = 0 and b_A = 0;
+ *   h(0) = 0 for Matern-1/2 as everywhere: a query ON a discretisation or training point takes part with a zero kernel
+ *     derivative (for the other kernels h(0) (u - xs) is zero anyway).
+ * The posterior the lines are formed from is the predict-only sweep's of these m points wherever that sweep runs in
+ * float64 -- every float64 handle, and the one-workgroup / one-launch sizes of the others -- so that val is tgp_sweep_kg's
+ * kg_out bit for bit; elsewhere mu and sigma are formed in float64 from the query vectors (never the float32 sweep's).
+ * Kernels: the query front of tgp_acq_grad (x / l, c k0, c h, K^-1 k on the matrix cores), the cross-covariance of
+ * tgp_sweep_kg's step (2), the envelope walk with its record, omega, the (point, dimension) reductions.  No atomics on
+ * floating-point data, no split sums, every order fixed: a point's value and gradient bits depend neither on m, nor on its
+ * row, nor on what travels with it, and are the same from run to run.
+ *   Needs a fitted GPU handle with points set for the resident fit (else TGP_BAD_ARG; no model: TGP_NOT_FITTED; a host
+ *   handle: TGP_BAD_ARG); sf not +-1, m outside [1, 4096] or a non-finite Xq: TGP_BAD_ARG.  Leaves the fit, the resident
+ *   candidates, the winner record, a Thompson draw, the MES maxima and later tgp_sweep / tgp_sweep_kg results untouched.
+ *   Serves every fitted GPU handle tgp_sweep_kg serves.  tgp_last_timings slot [20]: the device time of its own kernels
+ *   (the predict-only sweep in front of them and the copies left out).
+ * tgp_kg_lbfgsb is tgp_acq_lbfgsb with KG as the objective: the same L-BFGS-B walks in lock-step, one batched tgp_kg_grad
+ * per round; arguments, outputs and checks as tgp_acq_lbfgsb's, without the acquisition's. */
+int tgp_kg_grad(tgp_handle h, const double *Xq, int64_t m, double sf, double *val, double *grad);
+int tgp_kg_lbfgsb(tgp_handle h, const double *X0, int64_t R, const double *lo, const double *hi, double sf,
+                  int64_t max_iter, double *x_out, double *val_out, int64_t *status_out, int64_t *evaluations);
+
 /* The gradient stage itself on the device: R <= 4096 restarts X0 (R, D) are refined together by a
  * projected L-BFGS (memory 8; a line search that asks for sufficient decrease 1e-4 and the curvature
  * condition 0.9 as L-BFGS-B's does, lengthening a step whose slope is still steep; bounds lo / hi
@@ -788,7 +827,8 @@ int tgp_profile_reset(tgp_handle h);
  * Slot [19]: device time (ms) of the kernels of the last tgp_loo, the copies back left out (0 on host handles).  After
  * tgp_fit_loo_grad slot [2] holds everything up to B = A A^T (K^-1, kappa, b, A, B), slots [3] and [4] as for tgp_fit_grad.
  * Slot [20]: device time (ms) of the last tgp_sweep_kg's own kernels -- cross-covariance and envelope, chunk by chunk; the
- * predict-only sweep in front of them and the copies left out (0 on host handles).
+ * predict-only sweep in front of them and the copies left out (0 on host handles); after tgp_kg_grad, that call's own
+ * kernels likewise.
  * Slot [21] (not a time): the speculative round of the last tgp_sweep's pruned schedule (TGP_PRUNE_SPEC; DESIGN.md section
  * 4) -- 0 not tried, 1 hit: the runner-ups contracted beside the lb set covered every survivor, so the sweep made one exact
  * round; 2 miss: the survivors' round ran as well.  Slots [12..14] and [16] read the same either way. */

@@ -44,6 +44,7 @@ SYMBOLS = (
     "tgp_sweep", "tgp_sweep_batch", "tgp_sweep_batch_mc", "tgp_ts_draw", "tgp_ts_sweep", "tgp_ts_eval", "tgp_ts_read", "tgp_mes_set_maxima", "tgp_mes_draw", "tgp_predict_cov", "tgp_sample_joint", "tgp_sweep_topk", "tgp_set_winner_out", "tgp_winner_wait", "tgp_acq_grad", "tgp_acq_refine", "tgp_acq_lbfgsb",
     "tgp_evaluate", "tgp_predict_batch", "tgp_predict", "tgp_profile_enable", "tgp_profile_read", "tgp_profile_reset",
     "tgp_sweep_geometry", "tgp_last_timings", "tgp_hyper_sample", "tgp_sweep_integrated", "tgp_kg_set_points", "tgp_sweep_kg",
+    "tgp_kg_grad", "tgp_kg_lbfgsb",
     "tgp_multi_create", "tgp_multi_destroy", "tgp_multi_last_error", "tgp_multi_size", "tgp_multi_handle",
     "tgp_multi_fit", "tgp_multi_set_candidates", "tgp_multi_gen_candidates", "tgp_multi_sweep",
 )
@@ -152,6 +153,8 @@ def _argtypes():
         "tgp_mes_draw": [_vp, c.c_uint64, c.c_int64, c.c_int64, c.c_double, c.c_double, _dp],
         "tgp_kg_set_points": [_vp, _dp, c.c_int64, _dp],
         "tgp_sweep_kg": [_vp, c.c_double, _dp, _dp, _dp, _dp, _dp, _i64p, _i64p],
+        "tgp_kg_grad": [_vp, _dp, c.c_int64, c.c_double, _dp, _dp],
+        "tgp_kg_lbfgsb": [_vp, _dp, c.c_int64, _dp, _dp, c.c_double, c.c_int64, _dp, _dp, _i64p, _i64p],
         "tgp_predict_cov": [_vp, _dp, c.c_int64, c.c_int, _dp, _dp, _i64p],
         "tgp_sample_joint": [_vp, _dp, c.c_int64, c.c_int64, c.c_int, c.c_double, c.c_uint64, _dp, _dp, _dp, _dp],
         "tgp_acq_refine": [_vp, _dp, c.c_int64, _dp, _dp, c.c_int, c.c_double, c.c_double, c.c_double,
@@ -898,6 +901,32 @@ class NativeGP:
         v = np.zeros(21)
         self._check(self.lib.tgp_last_timings(self._h, _ptr(v), 21))
         return out.result(kg=out.aq, cov=cov, kg_ms=float(v[20]))
+
+    def kg_grad(self, Xq, sf=1.0):
+        """``tgp_kg_grad``: the knowledge gradient (m,) -- ``sweep_kg``'s value for the same point -- and its gradient
+        (m, D) at m <= 4096 points, against the stored points; float64 whatever the handle's dtype"""
+        Xq = _f64c(np.atleast_2d(Xq))
+        assert Xq.ndim == 2 and Xq.shape[1] == self.D, "points must be (m, %d)" % self.D
+        val = np.empty(Xq.shape[0])
+        grad = np.empty(Xq.shape)
+        self._check(self.lib.tgp_kg_grad(self._h, _ptr(Xq), Xq.shape[0], float(sf), _ptr(val), _ptr(grad)))
+        return val, grad
+
+    def kg_lbfgsb(self, X0, lo, hi, sf=1.0, max_iter=15000):
+        """``tgp_kg_lbfgsb``: ``acq_refine(lbfgsb=True)`` with the knowledge gradient as the objective -- L-BFGS-B from
+        every start in lock-step, one batched ``tgp_kg_grad`` per round; returns (x (R, D), values (R,), status (R,),
+        evaluations)"""
+        X0 = _f64c(np.atleast_2d(X0))
+        assert X0.ndim == 2 and X0.shape[1] == self.D, "start points must be (R, %d)" % self.D
+        lo, hi = _bounds(lo, hi, self.D)
+        R = X0.shape[0]
+        x = np.empty((R, self.D))
+        v = np.empty(R)
+        st = np.empty(R, dtype=np.int64)
+        its = ctypes.c_int64(0)
+        self._check(self.lib.tgp_kg_lbfgsb(self._h, _ptr(X0), R, _ptr(lo), _ptr(hi), float(sf), int(max_iter), _ptr(x), _ptr(v),
+                                           st.ctypes.data_as(_i64p), ctypes.byref(its)))
+        return x, v, st, its.value
 
     def predict_cov(self, Xq, latent=False):
         """``tgp_predict_cov``: the joint posterior over m <= 4096 points -- mu (m,), cov (m, m) in raw units (symmetric

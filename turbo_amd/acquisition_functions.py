@@ -702,9 +702,15 @@ class KG(AcquisitionFunction):
     hyper-parameters held, as the batch strategies condition).  ``points`` None: the ``min(n_points, N, 256)`` training
     inputs with the best observed y in the direction of the extremum, the earlier trial on ties -- deterministic, no
     random number drawn.  Native models only; a marginalised model is refused.  ``maximise_batch``, ``refine``,
-    ``lbfgsb`` and ``value_and_grad`` are refused: the gradient of KG is not implemented."""
+    ``lbfgsb`` and ``value_and_grad`` are refused by the default instance.
 
-    def __init__(self, points=None, n_points=64):
+    ``gradient=True``: the instance offers ``value_and_grad`` (``tgp_kg_grad``: KG and its closed-form gradient, the
+    envelope theorem over the same lines) and ``lbfgsb`` (``tgp_kg_lbfgsb``), so that ``CandidateSweep(grad_restarts>0)``
+    / ``RandomAndQuasiNewton`` refine a KG trial as they refine EI; ``refine`` (the on-device optimiser) and
+    ``maximise_batch`` stay refused."""
+
+    def __init__(self, points=None, n_points=64, gradient=False):
+        self.gradient = bool(gradient)
         n_points = int(n_points)
         if n_points < 1 or n_points > 256:
             raise ValueError('n_points must be in [1, 256]')
@@ -742,6 +748,9 @@ class KG(AcquisitionFunction):
             if points.shape[1] != np.asarray(model.X).shape[1]:
                 raise ValueError('points must be (A, {})'.format(np.asarray(model.X).shape[1]))
         acq_info = {'n_points': int(points.shape[0]), 'default_points': self.points is None}
+        if self.gradient:
+            acq_info['gradient'] = True
+            return KG.GradientInstance(model, desired_extremum, points), acq_info
         return KG.FunctionInstance(model, desired_extremum, points), acq_info
 
     class FunctionInstance(AcquisitionFunction.FunctionInstance):
@@ -844,6 +853,28 @@ class KG(AcquisitionFunction):
         def value_and_grad(self, X):
             self._refuse('value_and_grad',
                          'CandidateSweep with grad_restarts=0, or __call__ for values and finite differences')
+
+    class GradientInstance(FunctionInstance):
+        """KG(x) over ``points`` with its closed-form gradient (``KG(gradient=True)``)"""
+
+        def value_and_grad(self, X):
+            """KG (m,) -- ``__call__``'s value for the same point -- and its gradient (m, D) at m <= 4096 points
+            (``tgp_kg_grad``)"""
+            return self._ctx().kg_grad(self._as_points(X), self.scale_factor)
+
+        def lbfgsb(self, starting_points, bounds, max_iter=15000):
+            """L-BFGS-B from every start inside the library (``tgp_kg_lbfgsb``): the restarts in lock-step, one batched
+            ``tgp_kg_grad`` per round; returns (x (R, D), values (R,), status (R,): 1 = SciPy's success, evaluations)"""
+            low, high = zip(*bounds)
+            return self._ctx().kg_lbfgsb(self._as_points(starting_points), low, high, self.scale_factor, max_iter)
+
+        def _refuse(self, what, instead):
+            raise NotImplementedError('KG: {} is not available for the knowledge gradient (gradient=True serves '
+                                      'value_and_grad and the in-library L-BFGS-B only): use {}'.format(what, instead))
+
+        def refine(self, starting_points, bounds, max_iter=200):
+            self._refuse('the on-device optimiser (on_device=True, tgp_acq_refine)',
+                         'CandidateSweep with the default lockstep=True gradient stage (tgp_kg_lbfgsb)')
 
 
 def joint_ei(model, Xb, desired_extremum, incumbent, xi=0.01, n_samples=512, seed=None, eps=None, latent=False,

@@ -2,6 +2,7 @@
 //
 //   tgp_acq_refine    check_refine_args -> acq_refine:  refine_small | refine_general (refine_iterate)
 //   tgp_acq_lbfgsb    check_refine_args -> acq_lbfgsb_lockstep:  R walks, one batched tgp_acq_grad per round
+//   tgp_kg_lbfgsb     check_refine_args -> acq_lbfgsb_lockstep:  the same walks, one batched tgp_kg_grad per round
 //   tgp_fit_lbfgsb    check_optimise_args -> fit_optimise_streams:  hyper_thread_count, Borrowed, HyperRun, run_start
 //   tgp_fit_optimise  check_optimise_args -> hyper_one_launch | fit_optimise_streams
 //
@@ -154,7 +155,9 @@ static int acq_refine(Context &c, const RefineArgs &a, const RefineOut &out) {
 // every optimiser takes its step.  What turbo_amd/auxiliary_optimisers.py did with a Python thread and a SciPy
 // optimiser per restart meeting at a rendezvous; same walk per restart, no interpreter between two rounds.
 // (No hipSetDevice, no pre_join here: every tgp_acq_grad makes its own.)
-static int acq_lbfgsb_lockstep(tgp_handle h, const RefineArgs &a, const RefineOut &out) {
+// eval(Xq, m, val, grad): the round's batched evaluation -- tgp_acq_grad, or tgp_kg_grad for the knowledge gradient.
+template <class Eval>
+static int acq_lbfgsb_lockstep(tgp_handle h, const RefineArgs &a, const RefineOut &out, Eval &&eval) {
     const int D = (int)h->c.D;
     const int64_t R = a.R;
     std::vector<LbfgsbWalk> walks;
@@ -173,7 +176,7 @@ static int acq_lbfgsb_lockstep(tgp_handle h, const RefineArgs &a, const RefineOu
             who[(size_t)m++] = r;
         }
         if (m == 0) break;
-        const int rc = tgp_acq_grad(h, Xq.data(), m, a.acq, a.sf, a.incumbent, a.param, val.data(), grad.data());
+        const int rc = eval(Xq.data(), m, val.data(), grad.data());
         if (rc != TGP_OK) return rc;
         ev += m;
         for (int64_t i = 0; i < m; ++i) {

@@ -539,12 +539,13 @@ hipError_t launch_query(Context &c, const double *d_Xq, int m, int acq, double s
     return hipGetLastError();
 }
 
-// The front of launch_query for ONE point, its vectors left where the caller wants them (tgp_sweep_batch: the point
-// conditioned on next, batch_kernels.hip): uq = x / l (Dp), ks = c k0(x, X) (Np, 0 from N on), v = Linv ks,
-// w = Linv^T v = K^-1 k* -- on the matrix-core products whatever TGP_QUERY_MFMA says (one split of w, nothing to add).
-hipError_t launch_query_front(Context &c, const double *d_xq, double *uq, double *ks, double *hw, double *v, double *w) {
-    TGP_TRY(launch_q_kvec(c, d_xq, 1, uq, ks, hw, nullptr));
-    return launch_linv_solve(c, ks, v, w, 1);
+// The front of launch_query for m points (ONE for tgp_sweep_batch: the point conditioned on next, batch_kernels.hip; the
+// batch of tgp_kg_grad), its vectors left where the caller wants them: uq = x / l (Dp), ks = c k0(x, X) (Np, 0 from N on),
+// v = Linv ks, w = Linv^T v = K^-1 k* -- on the matrix-core products whatever TGP_QUERY_MFMA says (one split of w, nothing
+// to add).
+hipError_t launch_query_front(Context &c, const double *d_xq, double *uq, double *ks, double *hw, double *v, double *w, int m) {
+    TGP_TRY(launch_q_kvec(c, d_xq, m, uq, ks, hw, nullptr));
+    return launch_linv_solve(c, ks, v, w, m);
 }
 
 }  // namespace tgp

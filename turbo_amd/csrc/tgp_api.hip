@@ -1597,6 +1597,8 @@ static int run_sweep(Context &c, const SweepCall &call, CallClock &clk) {
                        c.pre.M == c.M && c.pre.Mpad == c.ws_Mpad && c.pre.launch_rows == c.launch_rows && c.pre.chunk == c.chunk;
     c.pre.front = false;   // one sweep per front: the slab it filled is overwritten from here on
     c.last_sweep_f64 = path != SweepPath::General || c.dtype == TGP_F64;   // (the one-workgroup / one-launch kernels only exist in f64)
+    // (kg_grad_sweep_posterior sweeps query points in the resident batch's place and puts back what is set from here on
+    // and in ensure_workspace: a field added here goes into its list)
     c.prune_state = -1;
     c.prune_lbset = c.prune_surv = 0;
     c.prune_screen = -1;
@@ -2375,7 +2377,9 @@ int tgp_acq_lbfgsb(tgp_handle h, const double *X0, int64_t R, const double *lo, 
     const RefineArgs a{X0, R, lo, hi, acq, sf, incumbent, param, max_iter};
     const RefineOut out{x_out, val_out, status_out, evaluations};
     if (int rc = check_refine_args(c, "tgp_acq_lbfgsb", a, out, TGP_ACQ_MES); rc != TGP_OK) return rc;
-    return acq_lbfgsb_lockstep(h, a, out);
+    return acq_lbfgsb_lockstep(h, a, out, [&](const double *Xq, int64_t m, double *val, double *grad) {
+        return tgp_acq_grad(h, Xq, m, a.acq, a.sf, a.incumbent, a.param, val, grad);
+    });
 } TGP_CATCH
 
 int tgp_fit_lbfgsb(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
@@ -2614,6 +2618,90 @@ int tgp_sweep_kg(tgp_handle h, double sf, double *kg_out, double *mu, double *si
     }
     c.last_kg_ms = total;
     return TGP_OK;
+} TGP_CATCH
+
+// The posterior tgp_sweep_kg's lines are formed from, for the m query points in the workspace: its step 1 -- the
+// predict-only sweep -- with the points standing in for the resident batch, so that a point's mu and sigma (and with
+// them its value) are the bits tgp_sweep_kg returns for it.  The handle's candidates, its sweep geometry and what the
+// last sweep reported are put back; the clamp counter is handed back at zero.
+static int kg_grad_sweep_posterior(Context &c, const double *d_Xq, int64_t m, double *d_mu, double *d_sigma) {
+    struct Kept {
+        Context &c;
+        const double *cand; int64_t M, chunk, launch_rows, ws_Mpad, lbset, surv, screen;
+        int f64, state, arith, spec;
+        explicit Kept(Context &c_) : c(c_), cand(c_.d_cand), M(c_.M), chunk(c_.chunk), launch_rows(c_.launch_rows), ws_Mpad(c_.ws_Mpad),
+                                     lbset(c_.prune_lbset), surv(c_.prune_surv), screen(c_.prune_screen),
+                                     f64(c_.last_sweep_f64), state(c_.prune_state), arith(c_.prune_arith), spec(c_.prune_spec) {}
+        ~Kept() {
+            c.d_cand = cand; c.M = M; c.chunk = chunk; c.launch_rows = launch_rows; c.ws_Mpad = ws_Mpad;
+            c.prune_lbset = lbset; c.prune_surv = surv; c.prune_screen = screen;
+            c.last_sweep_f64 = f64; c.prune_state = state; c.prune_arith = arith; c.prune_spec = spec;
+        }
+    } kept(c);
+    c.d_cand = d_Xq; c.M = m;
+    SweepCall s;
+    s.mu = d_mu; s.sigma = d_sigma;
+    CallClock clk;
+    const int rc = run_sweep(c, s, clk);
+    (void)hipMemsetAsync(c.d_besti, 0, 4 * sizeof(long long), c.stream);   // zero between calls, as every sweep leaves them
+    return rc;
+}
+
+int tgp_kg_grad(tgp_handle h, const double *Xq, int64_t m, double sf, double *val, double *grad) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_kg_grad");
+    Context &c = h->c;
+    if (!c.fitted) return fail(c, TGP_NOT_FITTED, "tgp_kg_grad: no fitted model");
+    if (!Xq || !val || !grad || m < 1 || m > 4096) return fail(c, TGP_BAD_ARG, "tgp_kg_grad: need Xq, val, grad and 1 <= m <= 4096");
+    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, "tgp_kg_grad: sf must be +1 or -1");
+    if (c.kg_gen < 0 || c.kg_gen != c.fit_gen || c.kg_A < 1)
+        return fail(c, TGP_BAD_ARG, "tgp_kg_grad: needs discretisation points for the resident fit (tgp_kg_set_points after the last fit)");
+    for (int64_t e = 0; e < m * c.D; ++e)
+        if (!std::isfinite(Xq[e])) return fail(c, TGP_BAD_ARG, "tgp_kg_grad: Xq must be finite");
+    API_HIP(hipSetDevice(c.device), "hipSetDevice");
+    API_HIP(pre_join(c), "hipStreamWaitEvent");
+    KgPoints p;
+    (void)kg_points_doubles(c, c.kg_A, &p);
+    KgGradWs g;
+    const int64_t nd = kg_grad_doubles(c, m, p.Apad, &g);
+    API_MEM(grow(c, c.d_kgw, (size_t)nd * sizeof(double), "hipMalloc knowledge-gradient workspace"));
+    while (c.ev_kg.size() < 2) {
+        Ev e;
+        API_HIP(e.create(hipEventDefault), "hipEventCreate");
+        c.ev_kg.push_back(std::move(e));
+    }
+    double *ws = c.d_kgw;
+    API_HIP(hipMemcpyAsync(ws + g.o_Xq, Xq, (size_t)(m * c.D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D Xq");
+    // the lines' posterior: the sweep's own where the sweep of these points runs in f64 (the value is then tgp_sweep_kg's,
+    // bit for bit); else formed in f64 from the query front's vectors -- never the f32 sweep's
+    const bool sweep_f64 = sweep_path(c, m) != SweepPath::General || c.dtype == TGP_F64;
+    if (sweep_f64)
+        if (int rc = kg_grad_sweep_posterior(c, ws + g.o_Xq, m, ws + g.o_mu, ws + g.o_sigma); rc != TGP_OK) return rc;
+    API_HIP(hipEventRecord(c.ev_kg[0], c.stream), "hipEventRecord");
+    if (hipError_t le = launch_kg_grad(c, ws, g, c.d_kgp, p, (int)m, sf, !sweep_f64); le != hipSuccess) return hip_fail(c, le, "launch_kg_grad");
+    API_HIP(hipEventRecord(c.ev_kg[1], c.stream), "hipEventRecord");
+    API_HIP(hipMemcpyAsync(val, ws + g.o_val, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H val");
+    API_HIP(hipMemcpyAsync(grad, ws + g.o_grad, (size_t)(m * c.D) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H grad");
+    API_HIP(hipStreamSynchronize(c.stream), "kg grad sync");
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, c.ev_kg[0], c.ev_kg[1]) != hipSuccess) { (void)hipGetLastError(); ms = 0.f; }
+    c.last_kg_ms = ms;
+    return TGP_OK;
+} TGP_CATCH
+
+int tgp_kg_lbfgsb(tgp_handle h, const double *X0, int64_t R, const double *lo, const double *hi, double sf, int64_t max_iter,
+                  double *x_out, double *val_out, int64_t *status_out, int64_t *evaluations) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_kg_lbfgsb");
+    Context &c = h->c;
+    const RefineArgs a{X0, R, lo, hi, TGP_ACQ_NONE, sf, 0.0, 0.0, max_iter};
+    const RefineOut out{x_out, val_out, status_out, evaluations};
+    if (int rc = check_refine_args(c, "tgp_kg_lbfgsb", a, out, TGP_ACQ_MES); rc != TGP_OK) return rc;
+    if (c.kg_gen < 0 || c.kg_gen != c.fit_gen || c.kg_A < 1)
+        return fail(c, TGP_BAD_ARG, "tgp_kg_lbfgsb: needs discretisation points for the resident fit (tgp_kg_set_points after the last fit)");
+    return acq_lbfgsb_lockstep(h, a, out, [&](const double *Xq, int64_t m, double *val, double *grad) {
+        return tgp_kg_grad(h, Xq, m, sf, val, grad);
+    });
 } TGP_CATCH
 
 int tgp_evaluate(tgp_handle h, const double *Xc, int64_t M, int acq, double sf, double incumbent,

@@ -388,8 +388,8 @@ struct BatchWs {
     long long *seli, *clampw, *flagw, *bidx;          // d_bti: clampw and flagw right behind seli (one copy back)
     unsigned char *mask;           // ... and the selection mask last
 };
-// launch_query's front for one point: uq = x / l, ks = k*(x), v = Linv ks, w = Linv^T v (query_kernels.hip)
-hipError_t launch_query_front(Context &c, const double *d_xq, double *uq, double *ks, double *hw, double *v, double *w);
+// launch_query's front for m points (rows of stride D in, Dp / Np out): uq = x / l, ks = k*(x), v = Linv ks, w = Linv^T v (query_kernels.hip)
+hipError_t launch_query_front(Context &c, const double *d_xq, double *uq, double *ks, double *hw, double *v, double *w, int m = 1);
 int bt_pass_splits(const Context &c, int64_t M);   // training-point splits of the pass = rows of its partials
 hipError_t launch_bt_prep(Context &c, double *Cs, int64_t Mpad);
 hipError_t launch_bt_init(Context &c, double *mu, double *var, unsigned char *mask);   // from c.d_mu / c.d_sigma of the first sweep
@@ -490,5 +490,22 @@ int64_t kg_chunk_doubles(const Context &c, int64_t rows, int64_t Apad, KgChunk *
 // chunk's cross-kernel (y_mean + y_std Ks alpha, the cov path's kernel) and replaces c.d_mu[i0 ..)
 hipError_t launch_kg_chunk(Context &c, double *ws, const KgChunk &k, const double *pts, const KgPoints &p, int64_t i0, int m,
                            double sf, double *kg, bool remean);
+// tgp_kg_grad: c.d_kgw for m <= 4096 query points -- the chunk's buffers (k: rows = m in whole 128-tiles) and behind them
+// the query front's vectors, the envelope's record and the results
+constexpr int KG_ENV_LD = 264;     // row stride of env_e / env_idx: the A + 1 <= 257 lines an envelope can hold
+struct KgGradWs {
+    KgChunk k;
+    int64_t o_Xq, o_uq, o_ks, o_hw, o_v, o_w;   // (m, D), (m, Dp), then (m, Np) each: x, x / l, c k0, c h, Linv ks (then omega), K^-1 ks
+    int64_t o_mu, o_sigma;         // (m) the posterior the lines are formed from: the predict-only sweep's, or kg_posterior_kernel's
+    int64_t o_coef;                // (m, 2) c_mu, c_v: the weights of alpha and w in omega
+    int64_t o_env_e, o_env_idx, o_env_n;   // (m, KG_ENV_LD) E_k / s of the envelope's lines i < A, their indices (int), (m) their number (int)
+    int64_t o_env_eh;              // (m, KG_ENV_LD) the prior term's weights e_k c h(|u - ua_k|)
+    int64_t o_val, o_grad;         // (m), (m, D)
+};
+int64_t kg_grad_doubles(const Context &c, int64_t m, int64_t Apad, KgGradWs *out);
+// Xq is in the workspace.  own_posterior: mu and sigma are formed here from the front's vectors (handles whose sweep is not
+// f64); else the caller has left the sweep's in o_mu / o_sigma.  Leaves val and grad in the workspace
+hipError_t launch_kg_grad(Context &c, double *ws, const KgGradWs &g, const double *pts, const KgPoints &p, int m, double sf,
+                          bool own_posterior);
 
 }  // namespace tgp
