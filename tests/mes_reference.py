@@ -9,17 +9,37 @@ backend and the MES plugin are held to.
 h goes through scipy.special.erfcx at z = |gamma| / sqrt 2, e = erfcx(z):
     gamma <= 0:  log Phi = log(e / 2) - z^2,  r = phi / Phi = sqrt(2 / pi) / e
     gamma >  0:  q = e exp(-z^2) / 2 = 1 - Phi,  log Phi = log1p(-q),  r = exp(-z^2) / (sqrt(2 pi) (1 - q))
-    gamma < -50: with t = 1 / gamma^2 (Mills' ratio expanded; the two halves of h are each gamma^2 / 2 there and cancel,
-                 and 1 + gamma^2 + gamma r loses gamma^4 ulps)
-                 h = log(-gamma) + (log(2 pi) - 1) / 2 + 2 t - 15/2 t^2 + 148/3 t^3,
-                 dh = (1 - 4 t + 30 t^2 - 296 t^3) / gamma          (next terms ~ 4e2 t^4: below 1e-10 there)
-and dh/dgamma = -(r / 2)(1 + gamma^2 + gamma r) elsewhere (0 where r has underflowed to 0)."""
+    gamma < -50: with t = 1 / gamma^2 (Mills' ratio expanded; the two halves of h are each gamma^2 / 2 there and cancel)
+                 h = log(-gamma) + (log(2 pi) - 1) / 2 + 2 t - 15/2 t^2 + 148/3 t^3      (next term ~ 4e2 t^4)
+dh/dgamma = -(r / 2)(1 + gamma^2 + gamma r) on gamma >= DH_SEAM = -10 (0 where r has underflowed to 0).  Below the seam
+that form loses gamma^4 ulps (8.9e-10 of dh at gamma = -49.4), so there, with x = -gamma and Laplace's continued fraction
+T_k = x + k / T_(k+1) evaluated backwards from T_17 = x (DH_DEPTH = 16):  dh = -T_1 / (T_2 T_3)  -- r = T_1 and
+1 + gamma^2 + gamma r = 2 / (T_2 T_3), every term positive -- without a division per level (dh_tail).  This is the f64 restatement of csrc/mes_math.hpp, operation
+for operation; tests/mes_reference_hp.py is the independent 80-bit statement both are judged by."""
 import numpy as np
 from scipy.special import erfcx
 
 SQRT_2_OVER_PI = 0.79788456080286536
 INV_SQRT_2PI = 0.3989422804014327
 H_TAIL_CONST = 0.41893853320467274      # (log(2 pi) - 1) / 2
+DH_SEAM, DH_DEPTH = -10.0, 16
+
+
+def dh_tail(g):
+    """dh/dgamma below DH_SEAM as the device forms it: T_k = x a_k / a_(k+1) with a_k = a_(k+1) + k t a_(k+2), t = 1 / x^2,
+    a_17 = 1, a_16 = 1 + 16 t (T_17 = x), and dh = -T_1 / (T_2 T_3) = -a_1 a_4 / (x a_2^2)"""
+    x = -np.asarray(g, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        ix = 1.0 / x
+        t = np.where(x > 50.0, ix * ix, 1.0 / (x * x))          # (below -50 the device reuses the t of h's series)
+        hi, lo = np.ones_like(x), 1.0 + DH_DEPTH * t
+        a4 = lo
+        for k in range(DH_DEPTH - 1, 1, -1):
+            hi, lo = lo, lo + (k * t) * hi
+            if k == 4:
+                a4 = lo
+        a1 = lo + t * hi
+        return -(a1 * a4) / (x * lo * lo)
 
 
 def h_and_dh(gamma):
@@ -34,7 +54,6 @@ def h_and_dh(gamma):
         ig = 1.0 / g[tail]
         t = ig * ig
         h[tail] = np.log(-g[tail]) + H_TAIL_CONST + t * (2.0 + t * (-7.5 + t * (148.0 / 3.0)))
-        dh[tail] = ig * (1.0 + t * (-4.0 + t * (30.0 - 296.0 * t)))
     z = np.abs(g) * 0.70710678118654752440
     e = erfcx(z)
     r = np.zeros_like(g)
@@ -50,6 +69,8 @@ def h_and_dh(gamma):
     h[live] = 0.5 * g[live] * r[live] - lp[live]
     with np.errstate(all="ignore"):
         dh[live] = np.where(r[live] == 0.0, 0.0, -0.5 * r[live] * (1.0 + g[live] * g[live] + g[live] * r[live]))
+    low = g < DH_SEAM
+    dh[low] = dh_tail(g[low])
     return h, dh
 
 

@@ -11,7 +11,9 @@ Gradient: the bar for tgp_acq_grad's ACQ_NONE / ACQ_SIGMA / UCB / PI / EI gradie
 tests/test_gpu_acq_grad_edges.py's (an 80-bit closed form, 64 max(e_ref, N u) of the batch maximum under a cap of 1e-9).
 The MES gradient is held here to its closed form over the device's own ACQ_NONE / ACQ_SIGMA gradients -- which that
 file pins -- and to central differences at tests/test_gpu_parity.py's bar (rtol 2e-4, atol max(2e-6 scale, 2e-9),
-h = 1e-6)."""
+h = 1e-6).
+Row by row, on every branch of h and dh (gamma from -1e300 to the underflow) and at bars built from an 80-bit reference:
+tests/test_gpu_mes_edges.py."""
 import numpy as np
 import pytest
 

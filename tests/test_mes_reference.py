@@ -33,12 +33,18 @@ def test_dh_matches_central_differences():
 
 
 def test_the_tail_branch_joins_the_erfcx_branch():
-    """the expansion used below gamma = -50 continues the erfcx route: the series' next term there is 4e2 / 50^8 = 1e-11
-    (h) and 3e3 / 50^9 (dh), the erfcx route's cancellation 50^2 / 2 ulps (h) and 50^4 / 2 ulps of 1 / 50 (dh)"""
+    """the expansion of h used below gamma = -50 continues the erfcx route: the series' next term there is 4e2 / 50^8 = 1e-11
+    (2.6e-12 of h, measured against the 80-bit reference), the erfcx route's cancellation 50^2 / 2 ulps.  dh/dgamma is the
+    continued fraction on both sides of -50 (below -10), so it does not see that seam at all; the form it replaced,
+    -(r / 2)(1 + gamma^2 + gamma r), was off by 8.9e-10 of dh at gamma = -49.4 (measured; 50^4 ulps would be 7e-10), and
+    the series that served below -50 by 9e-11.  At its own seam, -10, the two forms of dh agree to the cancelling form's
+    10^4 ulps.  tests/test_mes_reference_hp.py holds both branches to the 80-bit reference class by class."""
     a, da = mr.h_and_dh(np.array([-50.0]))                   # the erfcx route's last point
     b, db = mr.h_and_dh(np.array([np.nextafter(-50.0, -np.inf)]))
     assert abs(a[0] - b[0]) <= 1e-10
-    assert abs(da[0] - db[0]) <= 1e-10
+    assert abs(da[0] - db[0]) <= 1e-17                       # (dh = -0.02 there: three of its ulps)
+    _, dc = mr.h_and_dh(np.array([mr.DH_SEAM, np.nextafter(mr.DH_SEAM, -np.inf)]))
+    assert abs(dc[0] - dc[1]) <= 2e-12 * abs(dc[0])
     g = np.array([-1e4, -1e6, -1e12, -1e150, -1e300])
     v = mr.h(g)
     np.testing.assert_allclose(v, np.log(-g) + 0.5 * np.log(2 * np.pi) - 0.5, rtol=0, atol=1e-7)
