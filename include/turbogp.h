@@ -621,6 +621,91 @@ int tgp_kg_grad(tgp_handle h, const double *Xq, int64_t m, double sf, double *va
 int tgp_kg_lbfgsb(tgp_handle h, const double *X0, int64_t R, const double *lo, const double *hi, double sf,
                   int64_t max_iter, double *x_out, double *val_out, int64_t *status_out, int64_t *evaluations);
 
+/* ---- learned input warping (Snoek, Swersky, Zemel, Adams, ICML 2014) -----------------------------------------------
+ * Every input dimension goes through a monotone map of the unit interval, the Kumaraswamy CDF, whose two shape parameters
+ * are learned with the kernel's hyper-parameters from the same marginal likelihood: a warped model is an ordinary fit on
+ * w(X), its sweep an ordinary sweep over w(Xc).  Per dimension d, with the box [lo_d, hi_d] and shapes a_d, b_d > 0:
+ *   u = clip((x - lo) / (hi - lo), 0, 1),   w = 1 - (1 - u^a)^b,   evaluated as -expm1(b log(1 - u^a)) with
+ *   log(1 - u^a) = log1p(-exp(a log u)) up to u^a = 1/2 and log(-expm1(a log u)) above (csrc/warp_math.hpp: one header
+ *   for the device kernels and the host backend).  u = 0 gives 0 and u = 1 gives 1 exactly; a == 1 and b == 1 give w = u
+ *   exactly, a plain rescale to the unit cube.
+ *   dw/du = a b u^(a-1) (1-u^a)^(b-1),   dw/da = b (1-u^a)^(b-1) u^a log u,   dw/db = -(1-u^a)^b log(1-u^a);
+ *   dw/da and dw/db are 0 at both endpoints (their limit); dw/du at u = 0 with a < 1 and at u = 1 with b < 1 is +inf and
+ *   is returned as such.   Inverse: u = (1 - (1 - w)^(1/b))^(1/a).
+ * All of it is float64 whatever the handle's dtype.
+ *
+ * tgp_fit_input_grad is tgp_fit_grad (same arguments, same `grad`) plus dX (N, D) = d LML / d X in RAW X units:
+ *   d LML / d x_id = -(c / l_d) sum_{j != i} G_ij h_ij (s_id - s_jd),   s = x / l,  G = alpha alpha^T - K^-1,
+ *   h the length-scale weight of tgp_fit_grad (dK_ij / dlog l_d = c h_ij (s_id - s_jd)^2); a pair with d2 = 0 (the diagonal,
+ *   a duplicated training row) contributes nothing, under Matern-1/2 too.  So sum_i dX[i][d] = 0 and
+ *   sum_i x_id dX[i][d] = -d LML / d log l_d.  It is what any parametric input transform differentiates through.
+ *   The fit takes the BLOCKED route for every N, as tgp_fit_loo_grad does and for its reason (the pass reads K^-1 from the
+ *   workspace only that route's gradient fills): `lml` and `grad` are byte for byte tgp_fit_grad's under TGP_SMALL=0.  One
+ *   pass over the lower triangle of 64 x 64 tiles; nothing N x N is written, no atomics, every sum in a fixed order: the
+ *   same bits from run to run.  dX may be NULL: the call is then tgp_fit_grad on that route.  N = 1 gives zeros.  GPU only:
+ *   a host handle answers TGP_BAD_ARG.  The model is left fitted.  Status as tgp_fit_grad.
+ *   Memory: the pass keeps ceil(N / 64) N Dp doubles of partial sums (Dp = D rounded up to 4) in a workspace of the handle's
+ *   that only grows, like the fit's: 64 MiB at N = 4096, D = 32; 1 GiB at N = 16384, D = 32; 16 GiB at N = 65536, D = 32 --
+ *   an allocation that fails answers TGP_HIP_ERROR with the fit intact.
+ *
+ * tgp_warp_points: w_out (m, D) = w(X) for host points X (m, D) and, where the pointers are non-NULL, dw_du, dw_da, dw_db
+ *   (m, D each; dw/dx = dw_du / (hi - lo)).  A GPU handle runs the device kernel, a TGP_DEVICE_HOST handle (and
+ *   libturbogp_host.so) the same header on the host.  Needs no fitted model.  m < 1, D outside [1, 4096], a box without
+ *   hi > lo (finite), an a or b that is not finite and > 0, a NULL X / w_out / lo / hi / a / b: TGP_BAD_ARG.
+ * tgp_warp_inverse: x_out (m, D) = lo + u(W) (hi - lo), the closed-form inverse, W clipped to [0, 1]; host arithmetic on
+ *   every handle (m is the gradient stage's few results).  Arguments checked as tgp_warp_points'.
+ *
+ * tgp_warp_candidates warps the RESIDENT batch, however it got there (uploaded, a borrowed device pointer, generated, LHS,
+ *   the MT19937 stream), on the device: the result goes into a library-owned buffer that BECOMES the resident batch, so
+ *   from the next call on every entry that reads the resident batch -- the sweeps, tgp_sweep_topk, the batch entries,
+ *   tgp_read_candidates, tgp_get_candidate, the winner record's row -- sees the warped rows exactly as if the caller had
+ *   handed them to tgp_set_candidates_dev.  A borrowed buffer is never written to.  The raw rows are kept as a copy of the
+ *   library's own and stay readable through tgp_warp_read_raw(first, count, out) until the next call that makes another
+ *   batch resident (tgp_set_candidates*, tgp_gen_candidates*, tgp_set_candidates_mt19937, tgp_evaluate, a fit with
+ *   another D), which drops both; tgp_warp_read_raw then answers TGP_BAD_ARG.  A second tgp_warp_candidates without a
+ *   new batch warps the RAW rows again with the new parameters (a hyper-parameter fit changes a and b between trials
+ *   while a prefetched batch may stay).  A row's bits depend neither on M nor on the row's position, and equal what
+ *   tgp_warp_points gives for that row on the same handle (one kernel serves both).  D is the resident model's.  GPU
+ *   only; no resident batch or a bad box or shape: TGP_BAD_ARG.
+ *   Memory: the warped rows and the raw copy are 2 M D doubles of the handle's own, grow-only and kept for the next batch
+ *   after the warp is dropped (as the owned candidate buffer is); tgp_destroy releases them.
+ *
+ * tgp_fit_warp_grad warps X (N, D) on the device, fits on w(X) as tgp_fit_input_grad does, and returns `grad` with
+ *   2 + n_ls + 2 D entries: tgp_fit_grad's layout, then d LML / d log a_0..D-1, then d LML / d log b_0..D-1, by the chain rule
+ *   d LML / d log a_d = a_d sum_i (d LML / d w(X)_id) (dw/da)(u_id), i = 0, 1, ... per thread and a fixed tree (one small
+ *   kernel).  The length scales are in WARPED units.  `lml` and the first 2 + n_ls entries are byte for byte what
+ *   tgp_fit_input_grad returns when handed tgp_warp_points' own output as X: the composite is the composition of its parts.
+ *   The handle is left fitted on w(X), ready to sweep a warped batch.  GPU only.
+ *
+ * tgp_fit_warp_lbfgsb is tgp_fit_lbfgsb over theta' = [log constant, log ls.., log noise, log a_0.., log b_0..], P' =
+ *   2 + n_ls + 2 D entries per start (theta0 (S, P'), log_lo / log_hi (P'), theta_out (S, P')): the same L-BFGS-B walk, free
+ *   mask (log_lo == log_hi fixes an entry), worker handles, thread rule and TGP_NOT_PD rule, every evaluation a
+ *   tgp_fit_warp_grad in the box lo / hi (D each).  prior_sigma > 0 adds sum over the FREE warp entries of
+ *   theta^2 / (2 prior_sigma^2) to the minimised objective and its gradient -- a log-normal prior centred on the identity
+ *   warp; 0: none.  f_out (S) is the MINIMISED OBJECTIVE at theta_out, -LML plus that penalty, not -LML alone.  The
+ *   caller's handle is left as the last evaluation that ran on it left it (with several starts: untouched) -- fit at
+ *   the chosen theta afterwards. */
+int tgp_fit_input_grad(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y,
+                       int kernel, double constant, const double *ls, int64_t n_ls,
+                       double noise, double jitter, int normalize_y,
+                       double *lml, double *y_mean, double *y_std, double *grad, double *dX);
+int tgp_warp_points(tgp_handle h, const double *X, int64_t m, int64_t D, const double *lo, const double *hi,
+                    const double *a, const double *b, double *w_out, double *dw_du, double *dw_da, double *dw_db);
+int tgp_warp_inverse(tgp_handle h, const double *W, int64_t m, int64_t D, const double *lo, const double *hi,
+                     const double *a, const double *b, double *x_out);
+int tgp_warp_candidates(tgp_handle h, const double *lo, const double *hi, const double *a, const double *b);
+int tgp_warp_read_raw(tgp_handle h, int64_t first, int64_t count, double *out);
+int tgp_fit_warp_grad(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y,
+                      int kernel, double constant, const double *ls, int64_t n_ls,
+                      double noise, double jitter, int normalize_y,
+                      const double *lo, const double *hi, const double *a, const double *b,
+                      double *lml, double *y_mean, double *y_std, double *grad);
+int tgp_fit_warp_lbfgsb(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
+                        const double *lo, const double *hi, const double *theta0, int64_t S, int64_t n_ls,
+                        const double *log_lo, const double *log_hi, double prior_sigma, double jitter,
+                        int normalize_y, int64_t max_iter, double *theta_out, double *f_out,
+                        int64_t *status_out, int64_t *evaluations);
+
 /* The gradient stage itself on the device: R <= 4096 restarts X0 (R, D) are refined together by a
  * projected L-BFGS (memory 8; a line search that asks for sufficient decrease 1e-4 and the curvature
  * condition 0.9 as L-BFGS-B's does, lengthening a step whose slope is still steep; bounds lo / hi

@@ -15,12 +15,13 @@ unmodified reference Optimiser (settings_preset=None):
 from .kernels import GPKernel
 from .bounds import Bounds
 from .surrogates import Surrogate, HipGPSurrogate, MarginalisedHipGPSurrogate, MarginalisedModel
+from .warped import WarpedHipGPSurrogate, WarpedModel
 from .acquisition_functions import AcquisitionFunction, UCB, PI, EI, TS, MES, KG, joint_ei
 from .auxiliary_optimisers import CandidateSweep, RandomAndQuasiNewton
 from .naive_selectors import random_selector, LHS_selector
 from ._lib import TurboGPLibraryError, NativeGP, LIB_PATH
 
 __all__ = ['GPKernel', 'Bounds', 'Surrogate', 'HipGPSurrogate', 'MarginalisedHipGPSurrogate',
-           'MarginalisedModel', 'AcquisitionFunction', 'UCB', 'PI',
+           'MarginalisedModel', 'WarpedHipGPSurrogate', 'WarpedModel', 'AcquisitionFunction', 'UCB', 'PI',
            'EI', 'TS', 'MES', 'KG', 'joint_ei', 'CandidateSweep', 'RandomAndQuasiNewton', 'random_selector', 'LHS_selector',
            'TurboGPLibraryError', 'NativeGP', 'LIB_PATH']

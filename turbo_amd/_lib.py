@@ -45,6 +45,8 @@ SYMBOLS = (
     "tgp_evaluate", "tgp_predict_batch", "tgp_predict", "tgp_profile_enable", "tgp_profile_read", "tgp_profile_reset",
     "tgp_sweep_geometry", "tgp_last_timings", "tgp_hyper_sample", "tgp_sweep_integrated", "tgp_kg_set_points", "tgp_sweep_kg",
     "tgp_kg_grad", "tgp_kg_lbfgsb",
+    "tgp_fit_input_grad", "tgp_warp_points", "tgp_warp_inverse", "tgp_warp_candidates", "tgp_warp_read_raw", "tgp_fit_warp_grad",
+    "tgp_fit_warp_lbfgsb",
     "tgp_multi_create", "tgp_multi_destroy", "tgp_multi_last_error", "tgp_multi_size", "tgp_multi_handle",
     "tgp_multi_fit", "tgp_multi_set_candidates", "tgp_multi_gen_candidates", "tgp_multi_sweep",
 )
@@ -118,6 +120,14 @@ def _argtypes():
         "tgp_fit_grad": fit + [_dp],
         "tgp_loo": [_vp, _dp, _dp, _dp, _dp],
         "tgp_fit_loo_grad": fit + [_dp, _dp],
+        "tgp_fit_input_grad": fit + [_dp, _dp],
+        "tgp_warp_points": [_vp, _dp, c.c_int64, c.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
+        "tgp_warp_inverse": [_vp, _dp, c.c_int64, c.c_int64, _dp, _dp, _dp, _dp, _dp],
+        "tgp_warp_candidates": [_vp, _dp, _dp, _dp, _dp],
+        "tgp_warp_read_raw": [_vp, c.c_int64, c.c_int64, _dp],
+        "tgp_fit_warp_grad": fit[:12] + [_dp, _dp, _dp, _dp] + fit[12:] + [_dp],
+        "tgp_fit_warp_lbfgsb": [_vp, _dp, c.c_int64, c.c_int64, _dp, c.c_int, _dp, _dp, _dp, c.c_int64, c.c_int64, _dp, _dp,
+                                c.c_double, c.c_double, c.c_int, c.c_int64, _dp, _dp, _i64p, _i64p],
         "tgp_fit_append": fit + [c.POINTER(c.c_int)],
         "tgp_fit_optimise": [_vp, _dp, c.c_int64, c.c_int64, _dp, c.c_int, _dp, c.c_int64, c.c_int64, _dp, _dp,
                              c.c_double, c.c_int, c.c_int64, _dp, _dp, _i64p, _i64p],
@@ -554,6 +564,91 @@ class NativeGP:
         self._check(self.lib.tgp_fit_loo_grad(*args, ctypes.byref(loo), _ptr(grad)))
         self.N, self.D = X.shape
         return lml.value, loo.value, grad
+
+    def fit_input_grad(self, X, y, kind, constant, length_scale, noise, jitter, normalize_y, want_dX=True):
+        """``tgp_fit_input_grad``: fit + d LML / d log(theta) on the blocked route + d LML / d X (N, D) in raw X units:
+        returns (lml, grad [c, ls..., noise], dX); ``want_dX=False``: dX is None and the call is ``fit_grad`` on that route"""
+        X, n_ls, args, (lml, _, _) = self._fit_args(X, y, kind, constant, length_scale, noise, jitter, normalize_y)
+        grad = np.zeros(2 + n_ls)
+        dX = np.zeros(X.shape) if want_dX else None
+        self.fit_gen += 1
+        self._check(self.lib.tgp_fit_input_grad(*args, _ptr(grad), _ptr(dX)))
+        self.N, self.D = X.shape
+        return lml.value, grad, dX
+
+    @staticmethod
+    def _warp_box(lo, hi, a, b, D):
+        lo, hi = _bounds(lo, hi, D)
+        a, b = _bounds(np.broadcast_to(np.asarray(a, dtype=np.float64), (D,)), np.broadcast_to(np.asarray(b, dtype=np.float64), (D,)), D)
+        return lo, hi, a, b
+
+    def warp_points(self, X, lo, hi, a, b, derivatives=False):
+        """``tgp_warp_points``: the Kumaraswamy warp w (m, D) of the points X (m, D) in the box lo / hi with shapes a, b (D
+        each, or scalars); ``derivatives=True``: (w, dw/du, dw/da, dw/db).  Needs no fitted model; a host handle
+        computes it on the host"""
+        X = _f64c(np.atleast_2d(X))
+        lo, hi, a, b = self._warp_box(lo, hi, a, b, X.shape[1])
+        out = [np.empty(X.shape) for _ in range(4 if derivatives else 1)]
+        ptrs = [_ptr(o) for o in out] + [None] * (4 - len(out))
+        self._check(self.lib.tgp_warp_points(self._h, _ptr(X), X.shape[0], X.shape[1], _ptr(lo), _ptr(hi), _ptr(a), _ptr(b), *ptrs))
+        return tuple(out) if derivatives else out[0]
+
+    def warp_inverse(self, W, lo, hi, a, b):
+        """``tgp_warp_inverse``: the raw points x (m, D) whose warp is W (m, D), in closed form on the host"""
+        W = _f64c(np.atleast_2d(W))
+        lo, hi, a, b = self._warp_box(lo, hi, a, b, W.shape[1])
+        out = np.empty(W.shape)
+        self._check(self.lib.tgp_warp_inverse(self._h, _ptr(W), W.shape[0], W.shape[1], _ptr(lo), _ptr(hi), _ptr(a), _ptr(b), _ptr(out)))
+        return out
+
+    def warp_candidates(self, lo, hi, a, b):
+        """``tgp_warp_candidates``: the RESIDENT batch through the warp on the device; the warped rows become the resident
+        batch (a borrowed buffer is not written to), the raw rows stay readable through ``warp_read_raw`` until another
+        batch is made resident.  Called again without a new batch it warps the raw rows with the new shapes"""
+        lo, hi, a, b = self._warp_box(lo, hi, a, b, self.D)
+        self._check(self.lib.tgp_warp_candidates(self._h, _ptr(lo), _ptr(hi), _ptr(a), _ptr(b)))
+
+    def warp_read_raw(self, first=0, count=None):
+        """``tgp_warp_read_raw``: rows [first, first + count) of the batch as it was before ``warp_candidates``"""
+        count = int(self.M) - int(first) if count is None else int(count)
+        out = np.empty((max(count, 0), self.D))
+        self._check(self.lib.tgp_warp_read_raw(self._h, int(first), count, _ptr(out)))
+        return out
+
+    def fit_warp_grad(self, X, y, kind, constant, length_scale, noise, jitter, normalize_y, lo, hi, a, b):
+        """``tgp_fit_warp_grad``: fit on w(X) + the gradient of the LML in log(constant, length scale(s), noise, a (D), b (D));
+        returns (lml, grad (2 + n_ls + 2 D,)).  The handle is left fitted on w(X)"""
+        X, n_ls, args, (lml, _, _) = self._fit_args(X, y, kind, constant, length_scale, noise, jitter, normalize_y)
+        lo, hi, a, b = self._warp_box(lo, hi, a, b, X.shape[1])
+        grad = np.zeros(2 + n_ls + 2 * X.shape[1])
+        self.fit_gen += 1
+        self._check(self.lib.tgp_fit_warp_grad(*args[:12], _ptr(lo), _ptr(hi), _ptr(a), _ptr(b), *args[12:], _ptr(grad)))
+        self.N, self.D = X.shape
+        return lml.value, grad
+
+    def fit_warp_optimise(self, X, y, kind, lo, hi, theta0, n_ls, log_bounds, jitter, normalize_y, prior_sigma=0.0, max_iter=500):
+        """``tgp_fit_warp_lbfgsb``: ``fit_optimise(lbfgsb=True)`` over theta' = log(constant, length scale(s), noise, a (D),
+        b (D)) in the box lo / hi: every row of theta0 (S, P') is optimised inside log_bounds (P', 2), P' = 2 + n_ls + 2 D;
+        ``prior_sigma > 0`` adds theta^2 / (2 prior_sigma^2) over the free warp entries.  Returns (theta (S, P'), the
+        minimised objective (S,), status (S,), evaluations)"""
+        X = _f64c(X)
+        y = _f64c(y).reshape(-1)
+        D = X.shape[1]
+        lo, hi = _bounds(lo, hi, D)
+        theta0 = _f64c(np.atleast_2d(theta0))
+        S, P = theta0.shape
+        assert P == 2 + n_ls + 2 * D, "theta0 must be (S, 2 + n_ls + 2 D)"
+        lb = _f64c(np.asarray(log_bounds, dtype=np.float64).reshape(P, 2))
+        blo, bhi = _f64c(lb[:, 0]), _f64c(lb[:, 1])
+        theta, f = np.empty((S, P)), np.empty(S)
+        st = np.empty(S, dtype=np.int64)
+        ev = ctypes.c_int64(0)
+        self.fit_gen += 1
+        self._check(self.lib.tgp_fit_warp_lbfgsb(
+            self._h, _ptr(X), X.shape[0], D, _ptr(y), KERNELS[kind], _ptr(lo), _ptr(hi), _ptr(theta0), S, int(n_ls), _ptr(blo),
+            _ptr(bhi), float(prior_sigma), float(jitter), 1 if normalize_y else 0, int(max_iter), _ptr(theta), _ptr(f),
+            st.ctypes.data_as(_i64p), ctypes.byref(ev)))
+        return theta, f, st, ev.value
 
     def set_private_stream(self, on=True):
         """submit this handle's work to a stream of its own (handles of a device share one by default),

@@ -37,6 +37,13 @@ def _refuse_marginalised(model, what):
                          'fitted model'.format(what))
 
 
+def _refuse_warped(model, what):
+    """a ``WarpedModel`` (turbo_amd/warped.py) serves UCB / PI / EI over one batch or a gradient stage: the rest is refused"""
+    if getattr(model, 'is_warped', False):
+        raise ValueError('{} is not available for a warped model (WarpedHipGPSurrogate): input warping serves UCB / PI / EI '
+                         'through CandidateSweep and RandomAndQuasiNewton on one GPU'.format(what))
+
+
 def _require_native(model, what):
     _refuse_marginalised(model, what)
     if not _is_native(model):
@@ -205,6 +212,7 @@ class AcquisitionFunction:
             ``want_posterior`` asks for sigma alone (the S means differ).  The other strategies ignore ``n_sim`` and
             ``seed``."""
             _refuse_marginalised(self.model, 'maximise_batch')
+            _refuse_warped(self.model, 'maximise_batch')
             if not _is_native(self.model):
                 raise NotImplementedError('maximise_batch runs on the GPU only: it needs a model built by HipGPSurrogate '
                                           '(got {!r})'.format(type(self.model)))
@@ -276,6 +284,7 @@ class AcquisitionFunction:
             if _is_marginalised(self.model):     # tgp_sweep_integrated packs the record as a plain sweep does
                 ctx = self.model._resident_context()
             else:
+                _refuse_warped(self.model, 'winner_record (the sharded multi-GPU sweep)')
                 _require_native(self.model, 'winner_record')
                 ctx = self.model._ensure_resident()
             D = self.model.X.shape[1]
@@ -447,6 +456,7 @@ class TS(AcquisitionFunction):
         return 'optimism'
 
     def construct_function(self, trial_num, model, desired_extremum):
+        _refuse_warped(model, 'TS')
         _refuse_marginalised(model, 'TS (a sample path belongs to one fitted model)')
         if not _is_native(model):
             raise NotImplementedError('TS draws its sample paths on the GPU: it needs a model built by HipGPSurrogate '
@@ -613,6 +623,7 @@ class MES(AcquisitionFunction):
         return 'optimism'
 
     def construct_function(self, trial_num, model, desired_extremum):
+        _refuse_warped(model, 'MES')
         _refuse_marginalised(model, 'MES (its maxima belong to one fitted model)')
         if not _is_native(model):
             raise ValueError('MES serves native models only: it needs a model built by HipGPSurrogate (got {!r}) for the '
@@ -737,6 +748,7 @@ class KG(AcquisitionFunction):
         return np.ascontiguousarray(X[order])
 
     def construct_function(self, trial_num, model, desired_extremum):
+        _refuse_warped(model, 'KG')
         _refuse_marginalised(model, 'KG (its discretisation points belong to one fitted model)')
         if not _is_native(model):
             raise ValueError('KG serves native models only: it needs a model built by HipGPSurrogate (got {!r}) for the '

@@ -51,6 +51,12 @@ def _marginalised(acq):
     return bool(getattr(getattr(acq, 'model', None), 'is_marginalised', False))
 
 
+def _warped(acq):
+    """an acquisition over a ``WarpedModel`` (turbo_amd/warped.py): its context warps every batch made resident and reads the
+    chosen row back raw; what needs more than one sweep of one batch on one GPU is refused"""
+    return bool(getattr(getattr(acq, 'model', None), 'is_warped', False))
+
+
 class _collect_warnings(warnings.catch_warnings):
     """``with _collect_warnings() as caught``: whatever the block warns about goes to the list ``caught``, every time it
     is raised, and not to the caller"""
@@ -236,6 +242,9 @@ class CandidateSweep:
         if _marginalised(acq):
             raise ValueError('select_batch is not available for a marginalised model: batch strategies over a mixture of '
                              'hyper-parameter samples are out of scope')
+        if _warped(acq):
+            raise ValueError('select_batch is not available for a warped model (WarpedHipGPSurrogate): batch strategies '
+                             'condition on fantasies in the warped space, which is out of scope')
         thompson = bool(getattr(acq, 'is_thompson', False))
         if strategy == 'thompson' and not thompson:
             raise ValueError("strategy='thompson' needs a TS acquisition (got {!r})".format(type(acq)))
@@ -296,6 +305,9 @@ class CandidateSweep:
             raise ValueError('on_device=True is not available for a marginalised model: the on-device gradient stage '
                              'refines ONE fitted model (the SciPy path serves the integrated acquisition)')
         rank, world = dist_info() if self.shard else (0, 1)
+        if world > 1 and _warped(acq):
+            raise ValueError('a warped model (WarpedHipGPSurrogate) is swept by one process only: the sharded multi-GPU sweep '
+                             'is out of scope')
         m_local, offset, _ = shard_plan(self.num_random, world, rank)
         if world > 1 and getattr(acq, 'is_thompson', False):
             raise NotImplementedError('TS: one process only (the sharded multi-rank sweep is not available for sample paths)')

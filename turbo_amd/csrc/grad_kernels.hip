@@ -19,6 +19,7 @@
 #include "lds_opt_in.hpp"
 #include "mfma_gemm.hpp"
 #include "nt_product.hpp"
+#include "pair_weight.hpp"
 #include "pairwise.hpp"
 #include "small_grad.hpp"
 #include "tgp_internal.hpp"
@@ -38,22 +39,8 @@ namespace tgp {
 // GEMM: 0.36 ms of a 3.4 ms evaluation at N = 4096, mostly the 256 MiB of writes and a 64-workgroup
 // GEMM; this way nothing N x N leaves the kernel.)
 //
-// The pair weight G_ij is a compile-time policy: everything after it (distances, ls_weight, the ARD passes, the sums)
-// is one spelling for both traces 1/2 tr(G dK).
-struct LmlPairWeight {      // G = alpha alpha^T - K^-1: the log marginal likelihood
-    const double *__restrict__ alpha;
-    const double *__restrict__ Kinv;      // lower triangle read
-    __device__ double row(int i) const { return alpha[i]; }
-    __device__ double G(double ai, int, int j, long lower) const { return ai * alpha[j] - Kinv[lower]; }
-};
-struct LooPairWeight {      // G = b alpha^T + alpha b^T - 2 B: the leave-one-out score (loo_kernels.hip)
-    const double *__restrict__ alpha;
-    const double *__restrict__ b;
-    const double *__restrict__ B;         // lower triangle read
-    __device__ double row(int i) const { return alpha[i]; }
-    __device__ double G(double ai, int i, int j, long lower) const { return (b[i] * alpha[j] + ai * b[j]) - 2.0 * B[lower]; }
-};
-
+// The pair weight G_ij is a compile-time policy (pair_weight.hpp: LmlPairWeight, LooPairWeight): everything after it
+// (distances, ls_weight, the ARD passes, the sums) is one spelling for both traces 1/2 tr(G dK).
 template <int KIND, class PW>
 __global__ __launch_bounds__(256) void lml_weights_kernel(const double *__restrict__ Xs, const PW pw,
                                                           double *__restrict__ partial, int N,

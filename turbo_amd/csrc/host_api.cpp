@@ -184,6 +184,18 @@ int tgp_mt19937_uniform_columns(uint32_t *key624, int32_t *pos, int64_t M, int64
     }
 }
 
+int tgp_warp_points(tgp_handle h, const double *X, int64_t m, int64_t D, const double *lo, const double *hi, const double *a,
+                    const double *b, double *w_out, double *dw_du, double *dw_da, double *dw_db) {
+    if (!h) return TGP_BAD_ARG;
+    HOST_TRY(tgp_host::warp_points(h->g.err, X, m, D, lo, hi, a, b, w_out, dw_du, dw_da, dw_db))
+}
+
+int tgp_warp_inverse(tgp_handle h, const double *W, int64_t m, int64_t D, const double *lo, const double *hi, const double *a,
+                     const double *b, double *x_out) {
+    if (!h) return TGP_BAD_ARG;
+    HOST_TRY(tgp_host::warp_inverse(h->g.err, W, m, D, lo, hi, a, b, x_out))
+}
+
 int64_t tgp_tuning(char *buf, int64_t cap) {
     try {
         const std::string t = tgp::tuning().dump();

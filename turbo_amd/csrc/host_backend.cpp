@@ -1,6 +1,7 @@
 // host_backend.cpp -- see host_backend.hpp.  Plain C++17: no HIP header, no HIP call.
 #include "host_backend.hpp"
 #include "tuning.hpp"
+#include "warp_math.hpp"
 
 #include <math.h>
 #include <stdio.h>
@@ -659,6 +660,47 @@ int mt19937_uniform_columns(uint32_t *key, int32_t *pos, int64_t M, int64_t D, c
             }
         });
     }
+    return TGP_OK;
+}
+
+// ---- the input warp on the host (warp_math.hpp: the closed forms the device kernels use) ----
+static bool warp_args_ok(int64_t D, const double *lo, const double *hi, const double *a, const double *b) {
+    if (!lo || !hi || !a || !b || D < 1 || D > 4096) return false;
+    for (int64_t d = 0; d < D; ++d)
+        if (!tgp::warp_params_ok(lo[d], hi[d], a[d], b[d])) return false;
+    return true;
+}
+
+int warp_points(std::string &err, const double *X, int64_t m, int64_t D, const double *lo, const double *hi, const double *a,
+                const double *b, double *w_out, double *dw_du, double *dw_da, double *dw_db) {
+    if (!X || !w_out || m < 1 || !warp_args_ok(D, lo, hi, a, b)) {
+        err = "tgp_warp_points: need X, w_out, m >= 1, 1 <= D <= 4096, hi > lo and finite a, b > 0";
+        return TGP_BAD_ARG;
+    }
+    for (int64_t i = 0; i < m; ++i)
+        for (int64_t d = 0; d < D; ++d) {
+            const int64_t k = i * D + d;
+            const double u = tgp::warp_unit(X[k], lo[d], hi[d]);
+            tgp::WarpDerivs v;
+            w_out[k] = tgp::warp_value(u, a[d], b[d], dw_du != nullptr, dw_da != nullptr, dw_db != nullptr, v);
+            if (dw_du) dw_du[k] = v.du;
+            if (dw_da) dw_da[k] = v.da;
+            if (dw_db) dw_db[k] = v.db;
+        }
+    return TGP_OK;
+}
+
+int warp_inverse(std::string &err, const double *W, int64_t m, int64_t D, const double *lo, const double *hi, const double *a,
+                 const double *b, double *x_out) {
+    if (!W || !x_out || m < 1 || !warp_args_ok(D, lo, hi, a, b)) {
+        err = "tgp_warp_inverse: need W, x_out, m >= 1, 1 <= D <= 4096, hi > lo and finite a, b > 0";
+        return TGP_BAD_ARG;
+    }
+    for (int64_t i = 0; i < m; ++i)
+        for (int64_t d = 0; d < D; ++d) {
+            const int64_t k = i * D + d;
+            x_out[k] = lo[d] + tgp::warp_inverse_unit(W[k], a[d], b[d]) * (hi[d] - lo[d]);
+        }
     return TGP_OK;
 }
 

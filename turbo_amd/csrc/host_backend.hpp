@@ -88,4 +88,11 @@ void mt19937_fill(uint32_t *key, int32_t *pos, uint32_t *dst, int64_t n);
 // ... and n outputs passed over unread (the rows of a column that belong to other ranks' shards)
 void mt19937_skip(uint32_t *key, int32_t *pos, int64_t n);
 
+// The Kumaraswamy input warp at host points and its closed-form inverse (tgp_warp_points on a host handle, tgp_warp_inverse
+// on every handle; warp_math.hpp).  X / W (m, D); dw_du, dw_da, dw_db nullable.  Return a tgp_status, err the message
+int warp_points(std::string &err, const double *X, int64_t m, int64_t D, const double *lo, const double *hi, const double *a,
+                const double *b, double *w_out, double *dw_du, double *dw_da, double *dw_db);
+int warp_inverse(std::string &err, const double *W, int64_t m, int64_t D, const double *lo, const double *hi, const double *a,
+                 const double *b, double *x_out);
+
 }  // namespace tgp_host

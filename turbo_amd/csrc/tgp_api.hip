@@ -21,6 +21,8 @@
 #include "host_lbfgsb.hpp"
 #include "host_slice.hpp"
 #include "tgp_internal.hpp"
+#include "pairwise.hpp"
+#include "warp_math.hpp"
 
 using namespace tgp;
 
@@ -2406,6 +2408,90 @@ int tgp_fit_optimise(tgp_handle h, const double *X, int64_t N, int64_t D, const 
     const HyperOptOut out{theta_out, f_out, status_out, evaluations};
     if (int rc = check_optimise_args(c, "tgp_fit_optimise", a, out); rc != TGP_OK) return rc;
     return fit_optimise(h, a, out);
+} TGP_CATCH
+
+}  // extern "C"
+#include "api_warp.hpp"
+extern "C" {
+
+// ---- learned input warping (include/turbogp.h; api_warp.hpp, warp_kernels.hip) -------------------------------------
+int tgp_fit_input_grad(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
+                       double constant, const double *ls, int64_t n_ls, double noise, double jitter,
+                       int normalize_y, double *lml, double *y_mean, double *y_std, double *grad, double *dX) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_fit_input_grad");
+    Context &c = h->c;
+    if (!grad) return fail(c, TGP_BAD_ARG, "tgp_fit_input_grad: grad is NULL");
+    return fit_input_grad(h, FitArgs{X, N, D, y, kernel, constant, ls, n_ls, noise, jitter, normalize_y}, FitOut{lml, y_mean, y_std}, grad, dX, false);
+} TGP_CATCH
+
+int tgp_warp_points(tgp_handle h, const double *X, int64_t m, int64_t D, const double *lo, const double *hi, const double *a,
+                    const double *b, double *w_out, double *dw_du, double *dw_da, double *dw_db) try {
+    if (!h) return TGP_BAD_ARG;
+    if (h->host) return tgp_host::warp_points(h->host->err, X, m, D, lo, hi, a, b, w_out, dw_du, dw_da, dw_db);
+    Context &c = h->c;
+    if (!X || !w_out || m < 1) return fail(c, TGP_BAD_ARG, "tgp_warp_points: need X, w_out and m >= 1");
+    const WarpBox w{D, lo, hi, a, b};
+    if (int rc = check_warp_box(c, "tgp_warp_points", w); rc != TGP_OK) return rc;
+    return warp_points_device(c, X, m, w, w_out, dw_du, dw_da, dw_db);
+} TGP_CATCH
+
+int tgp_warp_inverse(tgp_handle h, const double *W, int64_t m, int64_t D, const double *lo, const double *hi, const double *a,
+                     const double *b, double *x_out) try {
+    if (!h) return TGP_BAD_ARG;
+    return tgp_host::warp_inverse(h->host ? h->host->err : h->c.err, W, m, D, lo, hi, a, b, x_out);
+} TGP_CATCH
+
+int tgp_warp_candidates(tgp_handle h, const double *lo, const double *hi, const double *a, const double *b) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_warp_candidates");
+    Context &c = h->c;
+    if (!c.d_cand || c.M < 1) return fail(c, TGP_BAD_ARG, "tgp_warp_candidates: no resident candidates");
+    const WarpBox w{c.D, lo, hi, a, b};
+    if (int rc = check_warp_box(c, "tgp_warp_candidates", w); rc != TGP_OK) return rc;
+    return warp_resident(c, w);
+} TGP_CATCH
+
+int tgp_warp_read_raw(tgp_handle h, int64_t first, int64_t count, double *out) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_warp_read_raw");
+    Context &c = h->c;
+    if (!warp_in_force(c)) return fail(c, TGP_BAD_ARG, "tgp_warp_read_raw: the resident batch is not a warped one (tgp_warp_candidates)");
+    if (!out || first < 0 || count < 1 || first + count > c.M) return fail(c, TGP_BAD_ARG, "tgp_warp_read_raw: bad range");
+    API_HIP(hipSetDevice(c.device), "hipSetDevice");
+    API_HIP(hipMemcpy(out, c.d_wraw + first * c.D, (size_t)(count * c.D) * sizeof(double), hipMemcpyDeviceToHost), "D2H raw candidates");
+    return TGP_OK;
+} TGP_CATCH
+
+int tgp_fit_warp_grad(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
+                      double constant, const double *ls, int64_t n_ls, double noise, double jitter, int normalize_y,
+                      const double *lo, const double *hi, const double *a, const double *b,
+                      double *lml, double *y_mean, double *y_std, double *grad) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_fit_warp_grad");
+    Context &c = h->c;
+    if (!grad) return fail(c, TGP_BAD_ARG, "tgp_fit_warp_grad: grad is NULL");
+    return fit_warp_grad(h, FitArgs{X, N, D, y, kernel, constant, ls, n_ls, noise, jitter, normalize_y}, WarpBox{D, lo, hi, a, b},
+                         FitOut{lml, y_mean, y_std}, grad);
+} TGP_CATCH
+
+int tgp_fit_warp_lbfgsb(tgp_handle h, const double *X, int64_t N, int64_t D, const double *y, int kernel,
+                        const double *lo, const double *hi, const double *theta0, int64_t S, int64_t n_ls,
+                        const double *log_lo, const double *log_hi, double prior_sigma, double jitter, int normalize_y,
+                        int64_t max_iter, double *theta_out, double *f_out, int64_t *status_out, int64_t *evaluations) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_fit_warp_lbfgsb");
+    Context &c = h->c;
+    const HyperOptArgs a{X, N, D, y, kernel, theta0, S, n_ls, log_lo, log_hi, jitter, normalize_y, max_iter};
+    const HyperOptOut out{theta_out, f_out, status_out, evaluations};
+    if (int rc = check_optimise_args(c, "tgp_fit_warp_lbfgsb", a, out); rc != TGP_OK) return rc;
+    bool ok = lo && hi && prior_sigma >= 0.0 && isfinite(prior_sigma);
+    for (int64_t d = 0; ok && d < D; ++d) ok = warp_params_ok(lo[d], hi[d], 1.0, 1.0);
+    for (int64_t i = 2 + n_ls; ok && i < 2 + n_ls + 2 * D; ++i) ok = log_lo[i] <= log_hi[i] && isfinite(log_lo[i]) && isfinite(log_hi[i]);
+    for (int64_t s = 0; ok && s < S; ++s)      // (check_optimise_args knows 2 + n_ls entries; a NaN warp start is not left to the clip)
+        for (int64_t i = 2 + n_ls; ok && i < 2 + n_ls + 2 * D; ++i) ok = isfinite(theta0[s * (2 + n_ls + 2 * D) + i]);
+    if (!ok) return fail(c, TGP_BAD_ARG, "tgp_fit_warp_lbfgsb: need lo, hi with hi > lo (finite), prior_sigma >= 0, finite bounds lo <= hi for the 2 D warp entries and finite warp entries in theta0");
+    return warp_optimise_streams(h, a, WarpOptArgs{lo, hi, prior_sigma}, out);
 } TGP_CATCH
 
 // ---- marginalised hyper-parameters: the slice sampler and the integrated sweep ------------------------------------

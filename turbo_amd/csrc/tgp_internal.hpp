@@ -86,6 +86,9 @@ struct FitMem {
     Dev<double> d_gpart;           // (tiles, 3 + Dp) partial sums: [S_c, S_iso, S_diag, gd[0..Dp)] per 64 x 64 tile
     Dev<double> d_gout;            // [S_c, S_iso, S_diag, gd[Dp]]
     int64_t g_cap_Np = 0, g_cap_Dp = 0;   // the geometry those two were allocated for
+    // input-gradient workspace (allocated on first tgp_fit_input_grad / tgp_fit_warp_grad; warp_kernels.hip)
+    Dev<double> d_xgpart;          // (tiles of 64 rows, N, Dp) the column slices' shares of d LML / d X, each entry written once
+    Dev<double> d_xgout;           // (N, D) d LML / d X, raw units of the fitted inputs
     // leave-one-out workspaces (allocated on first tgp_loo / tgp_fit_loo_grad)
     Dev<double> d_loov;            // the per-point vectors, the kappa kernel's partials and [L_LOO, bad count] (loo_vec_doubles + 2)
     Dev<double> d_looA;            // (Np, Np) A = K^-1 diag(sqrt(w)) of the LOO gradient
@@ -188,6 +191,14 @@ struct Context : FitMem, WsMem, OutMem {
     const double *d_cand = nullptr;   // (M, D) f64 row-major: borrowed -- the caller's, or a view of d_cand_owned / h_pin_cand
     Dev<double> d_cand_owned;
     int64_t M = 0;
+    // ---- the warped batch (tgp_warp_candidates): in force while d_cand == d_wcand and M == warp_M, i.e. until any entry
+    //      makes another batch resident; the raw rows are the library's own copy, so whoever owns the rows they came from
+    //      may overwrite or free them ----
+    Dev<double> d_wcand;              // (warp_M, D) the warped rows: the resident batch
+    Dev<double> d_wraw;               // (warp_M, D) the rows as they were before the warp (tgp_warp_read_raw; the source of a re-warp)
+    Dev<double> d_wpar;               // [lo | hi | a | b] (4 D) of the last tgp_warp_candidates
+    int64_t warp_M = 0, warp_D = 0;
+    Dev<double> d_wpts;               // tgp_warp_points / tgp_fit_warp_grad: [lo | hi | a | b | points | w | dw/du | dw/da | dw/db | 2 D sums]
 
     // ---- sweep workspace ----
     int64_t chunk = 0;            // candidates per GROUP of a trmm launch (the slab the caches re-serve: about 256 MiB)
@@ -235,6 +246,14 @@ hipError_t launch_lml_grad(Context &c, bool ard, double *gout, bool timed = true
 // tiles into d_W; the pairwise pass over d_W (loo_b == null: K^-1 and the LML's pair weight; else B and b, the LOO weight)
 hipError_t launch_kinv_product(Context &c);
 hipError_t launch_pair_sums(Context &c, bool ard, const double *loo_b, double *gout, bool timed);
+// learned input warping (warp_kernels.hip).  launch_input_grad: behind launch_lml_grad (K^-1 in d_W, alpha, Xs resident):
+// dX (N, D) = d LML / d X through partial (tiles of 64 rows, N, Dp).  launch_warp: `total` = m D elements of src through the
+// Kumaraswamy warp with par = [lo | hi | a | b] (4 D); raw (a copy of src), du, da, db nullable.  launch_warp_chain: out
+// (2 D) = [d LML / d log a | d LML / d log b] from dWx = d LML / d w(X) and the warp's derivatives, all (N, D)
+hipError_t launch_input_grad(Context &c, double *partial, double *dX);
+hipError_t launch_warp(Context &c, const double *src, int64_t total, int D, const double *par, double *raw, double *wout,
+                       double *du, double *da, double *db);
+hipError_t launch_warp_chain(Context &c, const double *dWx, const double *dwda, const double *dwdb, const double *par, double *out);
 // leave-one-out cross-validation (loo_kernels.hip).  c.d_loov: [kappa | resid | sigma | lpd | p | sqrt(w) | b] (Np each), then
 // the (Np / LOO_ROWS, Np) partial column sums and the (2, Np / 256) sums of the points' workgroups; scal (device or
 // device-mapped): [L_LOO, count of kappa_i <= 0 or not finite]
