@@ -706,6 +706,69 @@ int tgp_fit_warp_lbfgsb(tgp_handle h, const double *X, int64_t N, int64_t D, con
                         int normalize_y, int64_t max_iter, double *theta_out, double *f_out,
                         int64_t *status_out, int64_t *evaluations);
 
+/* ---- constrained and cost-aware acquisition ----------------------------------------------------------------------
+ * Scoring a candidate under SEVERAL models at once: the objective's EI / PI multiplied by the probability that every
+ * constraint model is satisfied (Gardner et al. 2014; Gelbart, Snoek & Adams 2014) and divided by a predicted cost ("EI per
+ * second", Snoek, Larochelle & Adams 2012, section 3.2: a GP on the LOG of the cost).  The reference has neither; its
+ * objective may return (cost, eval_info) and every listener receives evaluation_finished(trial_num, y, eval_info)
+ * (turbo/optimiser.py:243-256), which is where the plugin turbo_amd.Constrained collects the side values from.
+ * `h` is the objective's fitted GPU handle with a resident batch of M rows; sides[0..K), 0 <= K <= 8, each name another
+ * fitted GPU handle `g` on the same device with the same D (any dtype, kernel, N, training inputs and fit path; `h` itself
+ * and a handle named twice are TGP_BAD_ARG).  With mu_k, sigma_k what g_k's own unpruned predict-only sweep reports for a
+ * row, in raw units, and everything below in float64 whatever the dtypes:
+ *   TGP_SIDE_GE    log f_k = log Phi(z_k), z_k = (mu_k - level) / sigma_k         the side's value should be >= level
+ *   TGP_SIDE_LE    the same with z_k = (level - mu_k) / sigma_k
+ *                  sigma_k == 0: a step function, log f_k = 0 where the inequality holds (equality included), else -inf
+ *   TGP_SIDE_COST  log f_k = -mu_k: the side models the log of a cost; level must be 0
+ *   logw   = sum_k log f_k, summed in the order k = 0, 1, ...
+ *   a      = the objective's unweighted acquisition (acq_out)
+ *   value  = a exp(logw) for TGP_ACQ_EI / TGP_ACQ_PI, exactly 0 where a == 0 or logw == -inf;
+ *            logw itself for TGP_ACQ_NONE: the pure feasibility search of Gelbart et al. before any feasible observation
+ *            exists, kept in logs so that the order survives underflow.  UCB, SIGMA and MES are TGP_BAD_ARG: a weight on a
+ *            signed or entropy-valued acquisition has no meaning here.
+ * log Phi goes through the scaled complementary error function (csrc/weight_math.hpp, the route of TGP_ACQ_MES): finite for
+ * every finite z whose square is finite, so a 1e-400 feasibility still orders the candidates.  A NaN in any mu or sigma
+ * makes the row's value NaN, and such a row never wins.
+ * tgp_sweep_weighted
+ *   makes every g_k's resident batch a device-to-device COPY of h's M x D rows, owned by g_k (nothing is borrowed across
+ *   handles; a buffer g_k had borrowed with tgp_set_candidates_dev is released, never written): afterwards g_k behaves
+ *   exactly as after tgp_set_candidates with those rows.  h's fit, batch, Thompson draw, MES maxima and KG points are
+ *   untouched.  A batch on h that was warped with tgp_warp_candidates is TGP_BAD_ARG (each model would need its own warp).
+ *   The call enqueues the K side sweeps, the accumulation behind each, the objective's sweep -- the unpruned one: the pruned
+ *   sweep's bounds belong to the unweighted arg-max, as for tgp_sweep_integrated -- and the final step, and waits once, at
+ *   the end; handles on private streams (tgp_set_private_stream) are ordered with events.
+ *   mu, sigma, acq_out, logw_out, value_out (M) and side_mu, side_sigma (K, M): nullable host outputs; mu / sigma /
+ *   side_mu / side_sigma are the bits of the same handles' own predict-only tgp_sweep of the same rows.
+ *   best_val, best_idx: the arg-max of value under the library-wide rule (lowest index on ties, NaN never wins), for
+ *   TGP_ACQ_NONE too; the winner record (tgp_set_winner_out / tgp_winner_wait) is packed as by tgp_sweep.  n_clamped is
+ *   the sum over the K + 1 sweeps.
+ * tgp_weighted_grad
+ *   value (val, as defined above) and its gradient (grad (m, D)) at m <= 4096 host points Xq, formed from every handle's
+ *   value-with-partials -- mu, sigma and their gradients from the query kernels behind tgp_acq_grad; where a handle's
+ *   sweep of the points runs in f64 (every f64 handle, the one-workgroup and one-launch kernels of any handle) the VALUES
+ *   mu and sigma are that sweep's own bits, so val is what tgp_sweep_weighted returns for the same rows, as tgp_kg_grad
+ *   does for tgp_sweep_kg -- without a division by a quantity that can underflow:
+ *     EI / PI:  grad = (prod f) grad a + a sum_k (prod_{j != k} f_j) grad f_k,   NONE:  sum_k (phi / Phi)(z_k) grad z_k
+ *   summed in the order k = 0, 1, ...; a step-function side contributes no gradient.  A point's bits depend neither on m
+ *   nor on its row.  The resident batches are not touched.
+ * tgp_weighted_lbfgsb
+ *   tgp_acq_lbfgsb (below) with that evaluation: its arguments with (sides, K) after h, its contract, statuses and limits.
+ * Status: TGP_NOT_FITTED for an unfitted handle; TGP_BAD_ARG for a host handle, another device, another D, a duplicate
+ * side or g == h, K outside [0, 8], an unknown kind, a non-finite level, a cost side with level != 0, sf not +-1, no
+ * candidates on h; tgp_last_error names the side's index.
+ * Out of scope: pruning the objective's sweep under weights, batch selection (the tgp_sweep_batch entries) under weights,
+ * the sharded multi-GPU route, warped or marginalised sides, band constraints on one model, a host backend. */
+enum tgp_side_kind { TGP_SIDE_GE = 0, TGP_SIDE_LE = 1, TGP_SIDE_COST = 2 };
+typedef struct tgp_side { tgp_handle g; int32_t kind; int32_t reserved; double level; } tgp_side;
+int tgp_sweep_weighted(tgp_handle h, const tgp_side *sides, int64_t K, int acq, double sf, double incumbent, double param,
+                       double *mu, double *sigma, double *acq_out, double *logw_out, double *value_out,
+                       double *side_mu, double *side_sigma, double *best_val, int64_t *best_idx, int64_t *n_clamped);
+int tgp_weighted_grad(tgp_handle h, const tgp_side *sides, int64_t K, const double *Xq, int64_t m, int acq, double sf,
+                      double incumbent, double param, double *val, double *grad);
+int tgp_weighted_lbfgsb(tgp_handle h, const tgp_side *sides, int64_t K, const double *X0, int64_t R, const double *lo,
+                        const double *hi, int acq, double sf, double incumbent, double param, int64_t max_iter,
+                        double *x_out, double *val_out, int64_t *status_out, int64_t *evaluations);
+
 /* The gradient stage itself on the device: R <= 4096 restarts X0 (R, D) are refined together by a
  * projected L-BFGS (memory 8; a line search that asks for sufficient decrease 1e-4 and the curvature
  * condition 0.9 as L-BFGS-B's does, lengthening a step whose slope is still steep; bounds lo / hi

@@ -33,6 +33,8 @@ KERNELS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3}
 ACQ_NONE, ACQ_UCB, ACQ_PI, ACQ_EI, ACQ_SIGMA, ACQ_MES = 0, 1, 2, 3, 4, 5
 BUF_K, BUF_L, BUF_LINV, BUF_ALPHA = 0, 1, 2, 3
 BATCH_KB, BATCH_CL = 0, 1    # tgp_sweep_batch strategies: Kriging Believer, Constant Liar
+SIDE_GE, SIDE_LE, SIDE_COST = 0, 1, 2    # tgp_side kinds: value >= level, value <= level, the log of a cost
+SIDE_KINDS = {"ge": SIDE_GE, "le": SIDE_LE, "cost": SIDE_COST}
 
 # every symbol include/turbogp.h declares
 SYMBOLS = (
@@ -44,7 +46,7 @@ SYMBOLS = (
     "tgp_sweep", "tgp_sweep_batch", "tgp_sweep_batch_mc", "tgp_ts_draw", "tgp_ts_sweep", "tgp_ts_eval", "tgp_ts_read", "tgp_mes_set_maxima", "tgp_mes_draw", "tgp_predict_cov", "tgp_sample_joint", "tgp_sweep_topk", "tgp_set_winner_out", "tgp_winner_wait", "tgp_acq_grad", "tgp_acq_refine", "tgp_acq_lbfgsb",
     "tgp_evaluate", "tgp_predict_batch", "tgp_predict", "tgp_profile_enable", "tgp_profile_read", "tgp_profile_reset",
     "tgp_sweep_geometry", "tgp_last_timings", "tgp_hyper_sample", "tgp_sweep_integrated", "tgp_kg_set_points", "tgp_sweep_kg",
-    "tgp_kg_grad", "tgp_kg_lbfgsb",
+    "tgp_kg_grad", "tgp_kg_lbfgsb", "tgp_sweep_weighted", "tgp_weighted_grad", "tgp_weighted_lbfgsb",
     "tgp_fit_input_grad", "tgp_warp_points", "tgp_warp_inverse", "tgp_warp_candidates", "tgp_warp_read_raw", "tgp_fit_warp_grad",
     "tgp_fit_warp_lbfgsb",
     "tgp_multi_create", "tgp_multi_destroy", "tgp_multi_last_error", "tgp_multi_size", "tgp_multi_handle",
@@ -71,6 +73,12 @@ class Factor(ctypes.Structure):
                 ("constant", ctypes.c_double), ("noise", ctypes.c_double), ("jitter", ctypes.c_double),
                 ("y_mean", ctypes.c_double), ("y_std", ctypes.c_double), ("lml", ctypes.c_double), ("sumlog", ctypes.c_double),
                 ("Xs", ctypes.c_void_p), ("ls", ctypes.c_void_p), ("alpha", ctypes.c_void_p), ("Linv", ctypes.c_void_p)]
+
+
+class Side(ctypes.Structure):
+    """``tgp_side`` (include/turbogp.h): a side model of the weighted acquisition -- its handle, kind and level"""
+    _fields_ = [("g", ctypes.c_void_p), ("kind", ctypes.c_int32), ("reserved", ctypes.c_int32), ("level", ctypes.c_double)]
+
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _i64p = ctypes.POINTER(ctypes.c_int64)
@@ -165,6 +173,12 @@ def _argtypes():
         "tgp_sweep_kg": [_vp, c.c_double, _dp, _dp, _dp, _dp, _dp, _i64p, _i64p],
         "tgp_kg_grad": [_vp, _dp, c.c_int64, c.c_double, _dp, _dp],
         "tgp_kg_lbfgsb": [_vp, _dp, c.c_int64, _dp, _dp, c.c_double, c.c_int64, _dp, _dp, _i64p, _i64p],
+        "tgp_sweep_weighted": [_vp, c.POINTER(Side), c.c_int64, c.c_int, c.c_double, c.c_double, c.c_double, _dp, _dp, _dp, _dp,
+                               _dp, _dp, _dp, _dp, _i64p, _i64p],
+        "tgp_weighted_grad": [_vp, c.POINTER(Side), c.c_int64, _dp, c.c_int64, c.c_int, c.c_double, c.c_double, c.c_double,
+                              _dp, _dp],
+        "tgp_weighted_lbfgsb": [_vp, c.POINTER(Side), c.c_int64, _dp, c.c_int64, _dp, _dp, c.c_int, c.c_double, c.c_double,
+                                c.c_double, c.c_int64, _dp, _dp, _i64p, _i64p],
         "tgp_predict_cov": [_vp, _dp, c.c_int64, c.c_int, _dp, _dp, _i64p],
         "tgp_sample_joint": [_vp, _dp, c.c_int64, c.c_int64, c.c_int, c.c_double, c.c_uint64, _dp, _dp, _dp, _dp],
         "tgp_acq_refine": [_vp, _dp, c.c_int64, _dp, _dp, c.c_int, c.c_double, c.c_double, c.c_double,
@@ -1021,6 +1035,84 @@ class NativeGP:
         its = ctypes.c_int64(0)
         self._check(self.lib.tgp_kg_lbfgsb(self._h, _ptr(X0), R, _ptr(lo), _ptr(hi), float(sf), int(max_iter), _ptr(x), _ptr(v),
                                            st.ctypes.data_as(_i64p), ctypes.byref(its)))
+        return x, v, st, its.value
+
+    @staticmethod
+    def _sides(sides):
+        """``[(NativeGP, kind, level), ...]`` as a ``tgp_side`` array (None when empty) and its length; kind: SIDE_GE /
+        SIDE_LE / SIDE_COST or 'ge' / 'le' / 'cost'"""
+        sides = list(sides or ())
+        if not sides:
+            return None, 0
+        arr = (Side * len(sides))()
+        for k, (g, kind, level) in enumerate(sides):
+            arr[k].g = g._h if isinstance(g._h, int) or g._h is None else g._h.value
+            arr[k].kind = SIDE_KINDS[kind] if isinstance(kind, str) else int(kind)
+            arr[k].level = float(level)
+        return arr, len(sides)
+
+    @staticmethod
+    def _resident_rows_are(g, M):
+        """does handle g hold exactly M resident rows?  (tgp_read_candidates answers TGP_BAD_ARG past the batch)"""
+        row = np.empty(max(int(getattr(g, 'D', 0)), 1))
+        return M >= 1 and g.lib.tgp_read_candidates(g._h, M - 1, 1, _ptr(row)) == OK and \
+            g.lib.tgp_read_candidates(g._h, M, 1, _ptr(row)) != OK
+
+    def sweep_weighted(self, sides, acq=ACQ_EI, sf=1.0, incumbent=0.0, param=0.0, want_mu=False, want_sigma=False,
+                       want_acq=False, want_logw=False, want_value=False, want_sides=False):
+        """``tgp_sweep_weighted``: the resident batch scored under this (the objective's) model and the side models
+        ``sides = [(NativeGP, kind, level), ...]`` -- value = acq * prod_k f_k (EI / PI) or sum_k log f_k (ACQ_NONE) --
+        and its arg-max.  Every side's resident batch becomes its own copy of this handle's rows.  ``acq`` (M,) is the
+        unweighted acquisition; ``want_sides``: ``side_mu`` / ``side_sigma`` (K, M)."""
+        arr, K = self._sides(sides)
+        out = _SweepOut(self.M, want_mu, want_sigma, want_acq)
+        logw = np.empty(self.M) if want_logw else None
+        value = np.empty(self.M) if want_value else None
+        smu = np.empty((K, self.M)) if want_sides else None
+        ssg = np.empty((K, self.M)) if want_sides else None
+        try:
+            self._check(self.lib.tgp_sweep_weighted(self._h, arr, K, int(acq), float(sf), float(incumbent), float(param), _ptr(out.mu),
+                                                    _ptr(out.sg), _ptr(out.aq), _ptr(logw), _ptr(value), _ptr(smu), _ptr(ssg),
+                                                    ctypes.byref(out.bv), ctypes.byref(out.bi), ctypes.byref(out.nc)))
+        except Exception:
+            # a side the call reached before it failed owns a copy of these rows already: its row count is asked of the
+            # library (a probe of row M - 1 and of row M), so that a later sweep's (M,) outputs have the library's size
+            for g, _, _ in (sides or ()):
+                if isinstance(g, NativeGP) and g is not self and g._h is not None and not g.host and self._resident_rows_are(g, self.M):
+                    g._batch_is(self.M)
+            raise
+        for g, _, _ in (sides or ()):
+            g._batch_is(self.M)       # the side owns a copy of these rows now: nothing of a caller's to keep alive
+        return out.result(logw=logw, value=value, side_mu=smu, side_sigma=ssg)
+
+    def weighted_grad(self, Xq, sides, acq=ACQ_EI, sf=1.0, incumbent=0.0, param=0.0):
+        """``tgp_weighted_grad``: the weighted value (m,) -- ``sweep_weighted``'s formula -- and its gradient (m, D) at
+        m <= 4096 points; float64 whatever the handles' dtypes"""
+        Xq = _f64c(np.atleast_2d(Xq))
+        assert Xq.ndim == 2 and Xq.shape[1] == self.D, "points must be (m, %d)" % self.D
+        arr, K = self._sides(sides)
+        val = np.empty(Xq.shape[0])
+        grad = np.empty(Xq.shape)
+        self._check(self.lib.tgp_weighted_grad(self._h, arr, K, _ptr(Xq), Xq.shape[0], int(acq), float(sf), float(incumbent),
+                                               float(param), _ptr(val), _ptr(grad)))
+        return val, grad
+
+    def weighted_lbfgsb(self, X0, lo, hi, sides, acq=ACQ_EI, sf=1.0, incumbent=0.0, param=0.0, max_iter=15000):
+        """``tgp_weighted_lbfgsb``: ``acq_refine(lbfgsb=True)`` with the weighted value as the objective -- L-BFGS-B from
+        every start in lock-step, one batched ``tgp_weighted_grad`` per round; returns (x (R, D), values (R,), status
+        (R,), evaluations)"""
+        X0 = _f64c(np.atleast_2d(X0))
+        assert X0.ndim == 2 and X0.shape[1] == self.D, "start points must be (R, %d)" % self.D
+        lo, hi = _bounds(lo, hi, self.D)
+        arr, K = self._sides(sides)
+        R = X0.shape[0]
+        x = np.empty((R, self.D))
+        v = np.empty(R)
+        st = np.empty(R, dtype=np.int64)
+        its = ctypes.c_int64(0)
+        self._check(self.lib.tgp_weighted_lbfgsb(self._h, arr, K, _ptr(X0), R, _ptr(lo), _ptr(hi), int(acq), float(sf),
+                                                 float(incumbent), float(param), int(max_iter), _ptr(x), _ptr(v),
+                                                 st.ctypes.data_as(_i64p), ctypes.byref(its)))
         return x, v, st, its.value
 
     def predict_cov(self, Xq, latent=False):

@@ -889,6 +889,340 @@ class KG(AcquisitionFunction):
                          'CandidateSweep with the default lockstep=True gradient stage (tgp_kg_lbfgsb)')
 
 
+
+def _weighted_from_posteriors(acq, sf, incumbent, param, mu, sigma, sides):
+    """the weighted value on the host from every model's posterior -- ``tgp_sweep_weighted``'s definition in NumPy, float64:
+    sides = [(kind, level, mu_k, sigma_k)]; log Phi by ``scipy.special.log_ndtr`` (never log(ndtr(z)): finite for every
+    finite z), a step function where sigma_k == 0, value = a exp(logw) (EI / PI; exactly 0 where a == 0 or logw == -inf) or
+    logw itself (ACQ_NONE); NaN where any mu or sigma is NaN"""
+    from scipy.special import log_ndtr
+    mu = np.asarray(mu, dtype=np.float64).reshape(-1)
+    sigma = np.asarray(sigma, dtype=np.float64).reshape(-1)
+    logw = np.zeros_like(mu)
+    for k, (kind, level, mk, sk) in enumerate(sides):
+        mk = np.asarray(mk, dtype=np.float64).reshape(-1)
+        sk = np.asarray(sk, dtype=np.float64).reshape(-1)
+        if kind == _lib.SIDE_COST:
+            lf = -mk
+        else:
+            live = sk != 0
+            d = (mk - level) if kind == _lib.SIDE_GE else (level - mk)
+            with np.errstate(invalid='ignore', divide='ignore'):
+                lf = np.where(live, log_ndtr(d / np.where(live, sk, 1.0)), np.where(d >= 0, 0.0, -np.inf))
+        lf = np.where(np.isnan(mk) | np.isnan(sk), np.nan, lf)
+        logw = lf if k == 0 else logw + lf
+    bad = np.isnan(mu) | np.isnan(sigma) | np.isnan(logw)
+    if acq == _lib.ACQ_NONE:
+        return np.where(bad, np.nan, logw)
+    a = _from_mu_sigma(acq, sf, incumbent, param, mu, sigma)
+    with np.errstate(over='ignore', invalid='ignore'):
+        value = np.where((a == 0) | (logw == -np.inf), 0.0, a * np.exp(logw))
+    return np.where(bad | np.isnan(a), np.nan, value)
+
+
+class Constraint:
+    """An unknown constraint of ``Constrained``: the objective reports ``eval_info[name]`` for every trial, a GP (its OWN
+    ``HipGPSurrogate`` factory: one factory is one GPU handle, so the models do not displace each other) is fitted to
+    those values, and a candidate is feasible where the value is ``<= level`` (kind 'le') or ``>= level`` ('ge')"""
+
+    def __init__(self, name, surrogate, kind='le', level=0.0):
+        if kind not in ('le', 'ge'):
+            raise ValueError("kind must be 'le' or 'ge'")
+        if not np.isfinite(level):
+            raise ValueError('level must be finite')
+        self.name, self.surrogate, self.kind, self.level = name, surrogate, kind, float(level)
+
+    def holds(self, values):
+        values = np.asarray(values, dtype=np.float64)
+        return values <= self.level if self.kind == 'le' else values >= self.level
+
+
+class Cost:
+    """The evaluation cost of ``Constrained`` ("EI per second", Snoek, Larochelle & Adams 2012, section 3.2): a GP (its own
+    ``HipGPSurrogate`` factory) on the LOG of a positive cost per trial -- ``source='duration'``: the wall time between the
+    Optimiser's ``evaluation_started`` and ``evaluation_finished``; any other ``source``: ``eval_info[source]``"""
+    name = 'cost'
+
+    def __init__(self, surrogate, source='duration'):
+        self.surrogate, self.source = surrogate, source
+
+
+class Constrained(AcquisitionFunction):
+    """``base`` (``EI`` or ``PI``) weighted by the probability that every constraint model is satisfied (Gardner et al. 2014;
+    Gelbart, Snoek & Adams 2014) and divided by the predicted cost -- ``tgp_sweep_weighted`` and its gradient.  It is an
+    acquisition factory AND a listener (duck-typed: it imports nothing from ``turbo``), so with an unmodified reference
+    Optimiser it is put in both places::
+
+        acq = ta.Constrained(ta.EI(0.01), constraints=[ta.Constraint('g', ta.HipGPSurrogate(...), 'le', 0.0)])
+        op.acquisition = acq
+        op.register_listener(acq)          # evaluation_finished(trial_num, y, eval_info) brings eval_info['g']
+
+    The incumbent the base sees is the best observed y among the trials whose OBSERVED constraint values satisfy every
+    constraint; while there is none, the instance maximises the log feasibility alone (``TGP_ACQ_NONE``)."""
+
+    def __init__(self, base, constraints=(), cost=None):
+        if not isinstance(base, (EI, PI)):
+            raise TypeError('Constrained weights EI or PI (a weight on a signed or entropy-valued acquisition has no meaning); '
+                            'got {!r}'.format(type(base)))
+        self.base = base
+        self.constraints = list(constraints)
+        self.cost = cost
+        if len(self.constraints) + (cost is not None) > 8:
+            raise ValueError('at most 8 side models')
+        names = [c.name for c in self.constraints]
+        if len(set(names)) != len(names):
+            raise ValueError('constraint names must be distinct')
+        self.records = {}          # trial_num -> {constraint name: value, 'cost': log cost}
+        self._started = {}         # trial_num -> perf_counter() at evaluation_started
+        self.optimiser = None
+
+    def get_type(self):
+        return 'improvement'
+
+    # ---- listener callbacks (turbo/modules/listener.py) ----
+    def registered(self, optimiser):
+        self.optimiser = optimiser
+
+    def unregistered(self):
+        self.optimiser = None
+
+    def run_started(self, finished_trials, max_trials):
+        pass
+
+    def selection_started(self, trial_num):
+        pass
+
+    def surrogate_fitted(self, trial_num):
+        pass
+
+    def acquisition_maximised(self, trial_num):
+        pass
+
+    def selection_finished(self, trial_num, x, selection_info):
+        pass
+
+    def run_finished(self):
+        pass
+
+    def evaluation_started(self, trial_num):
+        import time
+        if self.cost is not None and self.cost.source == 'duration':      # (the only reader: evaluation_finished pops it)
+            self._started[trial_num] = time.perf_counter()
+
+    def evaluation_finished(self, trial_num, y, eval_info):
+        import time
+        now = time.perf_counter()
+        rec = {}
+        info = eval_info if isinstance(eval_info, dict) else {}
+        for c in self.constraints:
+            if c.name not in info:
+                raise KeyError('Constrained: trial {} reported no eval_info[{!r}] (the objective must return (cost, eval_info) '
+                               'with a value for every constraint)'.format(trial_num, c.name))
+            rec[c.name] = float(info[c.name])
+        if self.cost is not None:
+            if self.cost.source == 'duration':
+                if trial_num not in self._started:
+                    raise KeyError('Constrained: no evaluation_started for trial {}: the duration is unknown'.format(trial_num))
+                spent = max(now - self._started.pop(trial_num), 1e-9)
+            else:
+                if self.cost.source not in info:
+                    raise KeyError('Constrained: trial {} reported no eval_info[{!r}] (the cost)'.format(trial_num, self.cost.source))
+                spent = float(info[self.cost.source])
+                if not spent > 0:
+                    raise ValueError('Constrained: the cost of trial {} must be positive (it is modelled as its log)'.format(trial_num))
+            rec['cost'] = float(np.log(spent))
+        self.records[int(trial_num)] = rec
+
+    # ---- factory ----
+    def _side_values(self, n):
+        if len(self.records) != n:
+            raise ValueError('Constrained holds {} trial records for a model of {} observations: register it as a listener of '
+                             'the Optimiser (op.register_listener(acq)) before the first trial, one record per row of model.X'
+                             .format(len(self.records), n))
+        order = sorted(self.records)
+        return {c.name: np.array([self.records[t][c.name] for t in order]) for c in self.constraints}, \
+            (np.array([self.records[t]['cost'] for t in order]) if self.cost is not None else None)
+
+    def construct_function(self, trial_num, model, desired_extremum, incumbent_cost):
+        _refuse_warped(model, 'Constrained')
+        _refuse_marginalised(model, 'Constrained (each side is weighted under one fitted model)')
+        X = np.asarray(model.X, dtype=np.float64)
+        y = np.asarray(model.y, dtype=np.float64).reshape(-1)
+        values, cost = self._side_values(X.shape[0])
+        xi = self.base.xi(trial_num) if callable(self.base.xi) else self.base.xi
+        sides, side_info = [], {}
+        feasible = np.ones(X.shape[0], dtype=bool)
+        for c in self.constraints:
+            m, info = c.surrogate.construct_model(trial_num, X, values[c.name])
+            sides.append((c.name, m, _lib.SIDE_LE if c.kind == 'le' else _lib.SIDE_GE, c.level))
+            side_info[c.name] = info
+            feasible &= c.holds(values[c.name])
+        if self.cost is not None:
+            m, info = self.cost.surrogate.construct_model(trial_num, X, cost)
+            sides.append(('cost', m, _lib.SIDE_COST, 0.0))
+            side_info['cost'] = info
+        for name, m, _, _ in sides:
+            _refuse_warped(m, 'Constrained (side {!r})'.format(name))
+            _refuse_marginalised(m, 'Constrained (side {!r})'.format(name))
+        n_feasible = int(feasible.sum())
+        if n_feasible > 0:
+            incumbent = float(y[feasible].max() if desired_extremum == 'max' else y[feasible].min())
+            acq = self.base.FunctionInstance.ACQ
+        else:          # no feasible observation yet: the pure feasibility search
+            incumbent, acq = None, _lib.ACQ_NONE
+        acq_info = {'xi': xi, 'feasible_incumbent': incumbent, 'n_feasible': n_feasible, 'side_fitting_info': side_info}
+        return Constrained.FunctionInstance(model, desired_extremum, acq, incumbent, xi, sides, self.base.FunctionInstance.NAME), acq_info
+
+    class FunctionInstance(AcquisitionFunction.FunctionInstance):
+        """value(x) = base(x) prod_k f_k(x) -- or sum_k log f_k(x) while no feasible trial exists -- over ``sides``
+        [(name, model, kind, level)]"""
+
+        sweep_dtype = 'f64'      # the weight and the product are f64 whatever the handles' dtypes
+
+        def __init__(self, model, desired_extremum, acq, incumbent, xi, sides, base_name):
+            super().__init__(model, desired_extremum)
+            self.acq = acq
+            self.incumbent_cost = incumbent
+            self.xi = xi
+            self.sides = list(sides)
+            self.base_name = base_name
+
+        def get_name(self):
+            return 'feasibility' if self.acq == _lib.ACQ_NONE else 'constrained ' + self.base_name
+
+        def _native_args(self):
+            return self.acq, (0.0 if self.incumbent_cost is None else self.incumbent_cost), (0.0 if self.acq == _lib.ACQ_NONE else self.xi)
+
+        def _as_points(self, X):
+            X = np.asarray(X, dtype=np.float64)
+            if X.ndim == 1:
+                X = X.reshape(1, -1)
+            assert X.ndim == 2 and X.shape[1] == np.asarray(self.model.X).shape[1], \
+                'X must have shape (num_points, {})'.format(np.asarray(self.model.X).shape[1])
+            return X
+
+        def _on_gpu(self):
+            """(the objective's context, [(side context, kind, level)]) with every model resident in its own handle, or
+            None where the formula is served on the host: a foreign objective or side model, or a reloaded model where
+            no GPU is visible (the Recorder's plot path)"""
+            if not _is_native(self.model) or not all(_is_native(m) for _, m, _, _ in self.sides):
+                return None
+            ctx = self.model._ensure_resident()
+            if getattr(ctx, 'host', False):
+                return None
+            specs, seen = [], [ctx]
+            for name, m, kind, level in self.sides:
+                g = m._ensure_resident()
+                if getattr(g, 'host', False):
+                    return None
+                if any(g is s for s in seen):
+                    raise ValueError('Constrained: side {!r} shares its HipGPSurrogate factory (one GPU handle) with the objective '
+                                     'or another side: give every Constraint / Cost its own factory'.format(name))
+                seen.append(g)
+                specs.append((g, kind, level))
+            return ctx, specs
+
+        def _require_gpu(self, what):
+            on = self._on_gpu()
+            if on is None:
+                raise TypeError('Constrained: {} runs on the GPU only: it needs models built by HipGPSurrogate and a visible '
+                                'device'.format(what))
+            return on
+
+        def _weighted(self, ctx, specs, **want):
+            acq, incumbent, param = self._native_args()
+            res = ctx.sweep_weighted(specs, acq, self.scale_factor, incumbent, param, **want)
+            return res
+
+        def __call__(self, X):
+            X = self._as_points(X)
+            if X.shape[0] == 0:
+                return np.empty(0)
+            on = self._on_gpu()
+            if on is None:       # the formula from model.predict of every model, in NumPy
+                acq, incumbent, param = self._native_args()
+                mu, sigma = self.model.predict(X, return_std_dev=True)
+                sides = [(kind, level) + tuple(m.predict(X, return_std_dev=True)) for _, m, kind, level in self.sides]
+                return _weighted_from_posteriors(acq, self.scale_factor, incumbent, param, mu, sigma, sides)
+            ctx, specs = on
+            ctx.set_candidates(X)
+            return self._weighted(ctx, specs, want_value=True)['value']
+
+        def maximise(self, X):
+            """arg-max of the weighted value over the rows of X: (index, value); lowest index wins ties"""
+            on = self._on_gpu()
+            if on is None:
+                vals = self(X)
+                vals = np.where(np.isnan(vals), -np.inf, vals)
+                i = int(np.argmax(vals))
+                return i, float(vals[i])
+            ctx, specs = on
+            ctx.set_candidates(self._as_points(X))
+            res = self._weighted(ctx, specs)
+            return res['best_idx'], res['best_val']
+
+        def maximise_generated(self, num_points, low, high, seed, first_candidate=0, lhs_total=None, prefetch_seed=None):
+            """draw ``num_points`` candidates on the GPU and return the best: (x (D,), value, index)"""
+            if prefetch_seed is not None:
+                raise NotImplementedError('Constrained: no prefetched batch (the overlap starts an unweighted sweep inside the fit)')
+            ctx, specs = self._require_gpu('maximise_generated')
+            ctx.generate(seed, first_candidate, num_points, low, high, lhs_total, reuse=True)
+            res = self._weighted(ctx, specs)
+            return ctx.get_candidate(res['best_idx']), res['best_val'], res['best_idx']
+
+        def maximise_host_stream(self, num_points, low, high, topk=0, first=0, count=None):
+            """the reference's host draw finished on the GPU, then the weighted sweep; None -- nothing drawn -- where the
+            library cannot promise NumPy's numbers, or a top-k is asked for (the caller then draws on the host)"""
+            if topk > 0:
+                return None
+            on = self._on_gpu()
+            if on is None:
+                return None
+            ctx, specs = on
+            if not hasattr(ctx, 'set_candidates_numpy_stream') or not ctx.set_candidates_numpy_stream(num_points, low, high, first=first, count=count):
+                return None
+            res = self._weighted(ctx, specs)
+            return ctx, res['best_idx'], res['best_val'], None
+
+        def value_and_grad(self, X):
+            """the weighted value (m,) and its gradient (m, D) at m <= 4096 points (``tgp_weighted_grad``)"""
+            ctx, specs = self._require_gpu('value_and_grad')
+            acq, incumbent, param = self._native_args()
+            return ctx.weighted_grad(self._as_points(X), specs, acq, self.scale_factor, incumbent, param)
+
+        def lbfgsb(self, starting_points, bounds, max_iter=15000):
+            """L-BFGS-B from every start inside the library (``tgp_weighted_lbfgsb``): the restarts in lock-step, one batched
+            ``tgp_weighted_grad`` per round; returns (x (R, D), values (R,), status (R,): 1 = SciPy's success, evaluations)"""
+            ctx, specs = self._require_gpu('lbfgsb')
+            acq, incumbent, param = self._native_args()
+            low, high = zip(*bounds)
+            return ctx.weighted_lbfgsb(self._as_points(starting_points), low, high, specs, acq, self.scale_factor, incumbent,
+                                       param, max_iter)
+
+        def _refuse(self, what, instead):
+            raise NotImplementedError('Constrained: {} is not available for the weighted acquisition: use {}'.format(what, instead))
+
+        # maximise_topk is a PROPERTY that raises AttributeError, not a method that raises NotImplementedError: CandidateSweep asks
+        # ``hasattr(acq, 'maximise_topk')`` (auxiliary_optimisers._offers) before it takes the tgp_sweep_topk route, and the base
+        # class defines the method, so the only way for this instance not to offer it is for the attribute not to be there.
+        # CandidateSweep then ranks the values of __call__ on the host; a direct call still fails with the text below.
+        @property
+        def maximise_topk(self):
+            raise AttributeError('Constrained: maximise_topk (tgp_sweep_topk) is not available for the weighted acquisition: '
+                                 'use __call__ and a host argsort')
+
+        def maximise_batch(self, X, q, strategy='kriging_believer', lie='min', pending=None, want_posterior=False,
+                           n_sim=16, seed=None):
+            self._refuse('batch selection (tgp_sweep_batch / tgp_sweep_batch_mc)', 'one selection at a time')
+
+        def refine(self, starting_points, bounds, max_iter=200):
+            self._refuse('the on-device optimiser (on_device=True, tgp_acq_refine)',
+                         'the default lockstep=True gradient stage (tgp_weighted_lbfgsb)')
+
+        def winner_record(self, global_offset):
+            self._refuse('winner_record (the sharded multi-GPU sweep)', 'one process per optimisation')
+
+
 def joint_ei(model, Xb, desired_extremum, incumbent, xi=0.01, n_samples=512, seed=None, eps=None, latent=False,
              nugget=1e-10):
     """The Monte Carlo q-EI of a batch: the expected improvement of the BEST of the q points of ``Xb`` (q, D), q <= 4096,

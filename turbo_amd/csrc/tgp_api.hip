@@ -2588,6 +2588,227 @@ int tgp_sweep_integrated(tgp_handle h, const double *X, int64_t N, int64_t D, co
     return TGP_OK;
 } TGP_CATCH
 
+// ---- constrained and cost-aware acquisition (include/turbogp.h; weight_kernels.hip) -------------------------------
+// the checks the three entries share, in the order they report; a side's index is named
+static int weighted_check(tgp_handle h, const char *fn, const tgp_side *sides, int64_t K, int acq, double sf) {
+    Context &c = h->c;
+    const std::string f = std::string(fn) + ": ";
+    if (K < 0 || K > WT_MAX_SIDES) return fail(c, TGP_BAD_ARG, f + "need 0 <= K <= 8 sides");
+    if (K > 0 && !sides) return fail(c, TGP_BAD_ARG, f + "sides is NULL with K > 0");
+    if (!c.fitted) return fail(c, TGP_NOT_FITTED, f + "no fitted model");
+    if (acq != TGP_ACQ_NONE && acq != TGP_ACQ_PI && acq != TGP_ACQ_EI)
+        return fail(c, TGP_BAD_ARG, f + "the acquisition must be TGP_ACQ_EI, TGP_ACQ_PI or TGP_ACQ_NONE (a weight on a signed or entropy-valued acquisition has no meaning)");
+    if (sf != 1.0 && sf != -1.0) return fail(c, TGP_BAD_ARG, f + "sf must be +1 or -1");
+    for (int64_t k = 0; k < K; ++k) {
+        const std::string sk = f + "side " + std::to_string((long long)k) + ": ";
+        const tgp_side &s = sides[k];
+        if (!s.g) return fail(c, TGP_BAD_ARG, sk + "the handle is NULL");
+        if (s.g->host) return fail(c, TGP_BAD_ARG, sk + "a TGP_DEVICE_HOST handle cannot be a side");
+        if (s.g == h) return fail(c, TGP_BAD_ARG, sk + "the objective's own handle cannot be a side");
+        for (int64_t j = 0; j < k; ++j)
+            if (sides[j].g == s.g) return fail(c, TGP_BAD_ARG, sk + "the same handle as side " + std::to_string((long long)j));
+        if (s.kind != TGP_SIDE_GE && s.kind != TGP_SIDE_LE && s.kind != TGP_SIDE_COST) return fail(c, TGP_BAD_ARG, sk + "unknown kind");
+        if (!std::isfinite(s.level)) return fail(c, TGP_BAD_ARG, sk + "the level must be finite");
+        if (s.kind == TGP_SIDE_COST && s.level != 0.0) return fail(c, TGP_BAD_ARG, sk + "a cost side's level must be 0");
+        const Context &g = s.g->c;
+        if (!g.fitted) return fail(c, TGP_NOT_FITTED, sk + "no fitted model");
+        if (g.device != c.device) return fail(c, TGP_BAD_ARG, sk + "the handle is on another device");
+        if (g.D != c.D) return fail(c, TGP_BAD_ARG, sk + "D differs from the objective's");
+    }
+    return TGP_OK;
+}
+
+// a side's stream is ordered in front of the objective's by an event (nothing to do where both use the device's shared
+// main stream: one queue, in order)
+static int weighted_join(Context &c, Context &g, Ev &ev) {
+    if (g.stream == c.stream) return TGP_OK;
+    API_HIP(ev.create(hipEventDisableTiming), "hipEventCreate");
+    API_HIP(hipEventRecord(ev, g.stream), "hipEventRecord");
+    API_HIP(hipStreamWaitEvent(c.stream, ev, 0), "hipStreamWaitEvent");
+    return TGP_OK;
+}
+
+int tgp_sweep_weighted(tgp_handle h, const tgp_side *sides, int64_t K, int acq, double sf, double incumbent, double param,
+                       double *mu, double *sigma, double *acq_out, double *logw_out, double *value_out, double *side_mu,
+                       double *side_sigma, double *best_val, int64_t *best_idx, int64_t *n_clamped) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_sweep_weighted");
+    Context &c = h->c;
+    if (int rc = weighted_check(h, "tgp_sweep_weighted", sides, K, acq, sf); rc != TGP_OK) return rc;
+    if (!c.d_cand || c.M < 1) return fail(c, TGP_BAD_ARG, "tgp_sweep_weighted: no candidates set");
+    if (warp_in_force(c))
+        return fail(c, TGP_BAD_ARG, "tgp_sweep_weighted: the resident batch is a warped one (tgp_warp_candidates): each model would need its own warp");
+    API_HIP(hipSetDevice(c.device), "hipSetDevice");
+    API_HIP(pre_join(c), "hipStreamWaitEvent");
+    const int64_t M = c.M, D = c.D;
+    const size_t mb = (size_t)M * sizeof(double);
+    int rc = ensure_outputs(c, true, true, true);
+    if (rc != TGP_OK) return rc;
+    API_MEM(grow(c, c.d_wt_logw, mb, "hipMalloc weighted logw"));
+    API_MEM(grow(c, c.d_wt_val, mb, "hipMalloc weighted value"));
+    if (side_mu && K > 0) API_MEM(grow(c, c.d_wt_smu, (size_t)K * mb, "hipMalloc weighted side mu"));
+    if (side_sigma && K > 0) API_MEM(grow(c, c.d_wt_ssg, (size_t)K * mb, "hipMalloc weighted side sigma"));
+    if (c.ev_wt.size() < (size_t)K) c.ev_wt.resize((size_t)K);
+    // a failure between the first sweep and the final kernel leaves clamp counts in the counters of the handles swept so
+    // far: they are handed back at zero, as every sweep does
+    std::vector<Context *> swept;
+    auto bail = [&](int code) {
+        for (Context *g : swept) {
+            (void)hipMemsetAsync(g->d_besti + 1, 0, sizeof(long long), g->stream);
+            (void)hipStreamSynchronize(g->stream);
+        }
+        // (the accumulation behind every side's sweep has moved that side's count into the objective's counter)
+        (void)hipMemsetAsync(c.d_besti + 1, 0, sizeof(long long), c.stream);
+        (void)hipStreamSynchronize(c.stream);
+        (void)hipGetLastError();
+        return code;
+    };
+    auto side_fail = [&](int64_t k, int code, const Context &g) {
+        const std::string why = g.err;
+        return bail(fail(c, code, "tgp_sweep_weighted: side " + std::to_string((long long)k) + ": " + why));
+    };
+    for (int64_t k = 0; k < K; ++k) {
+        Context &g = sides[k].g->c;
+        // the side's batch becomes its OWN device-to-device copy of the objective's rows -- what tgp_set_candidates with
+        // those rows leaves: a front is dropped, a borrowed buffer is released (never written), a warped batch is gone
+        if (const hipError_t e = pre_join(g); e != hipSuccess) { (void)hip_fail(g, e, "hipStreamWaitEvent"); return side_fail(k, TGP_HIP_ERROR, g); }
+        if ((rc = grow_candidates(g, M * D)) != TGP_OK) return side_fail(k, rc, g);
+        if (const hipError_t e = hipMemcpyAsync(g.d_cand_owned, c.d_cand, (size_t)(M * D) * sizeof(double), hipMemcpyDeviceToDevice, g.stream);
+            e != hipSuccess) { (void)hip_fail(g, e, "D2D candidates"); return side_fail(k, TGP_HIP_ERROR, g); }
+        g.d_cand = g.d_cand_owned;
+        g.M = M;
+        if ((rc = ensure_outputs(g, true, true, false)) != TGP_OK) return side_fail(k, rc, g);
+        // its unpruned predict-only sweep, in its own arithmetic and on its own stream: no record, no winner, no bell
+        SweepCall s;
+        s.mu = g.d_mu; s.sigma = g.d_sigma;
+        CallClock clk;
+        swept.push_back(&g);
+        if ((rc = run_sweep(g, s, clk)) != TGP_OK) return side_fail(k, rc, g);
+        if ((rc = weighted_join(c, g, c.ev_wt[(size_t)k])) != TGP_OK) return bail(rc);
+        const hipError_t le = launch_weight_accumulate(c, g, (int)k, sides[k].kind, sides[k].level, c.d_wt_logw,
+                                                       side_mu ? c.d_wt_smu + k * M : nullptr, side_sigma ? c.d_wt_ssg + k * M : nullptr);
+        if (le != hipSuccess) return bail(hip_fail(c, le, "launch_weight_accumulate"));
+    }
+    // the objective's unpruned predict-only sweep (the pruned sweep's bounds belong to the unweighted arg-max), the value
+    // and the shared arg-max, record and winner record
+    swept.push_back(&c);
+    {
+        SweepCall s;
+        s.mu = c.d_mu; s.sigma = c.d_sigma;
+        CallClock clk;
+        if ((rc = run_sweep(c, s, clk)) != TGP_OK) return bail(rc);
+    }
+    SweepCall w;
+    w.acq = acq; w.sf = sf; w.incumbent = incumbent; w.param = param;
+    if (const hipError_t le = launch_weight_value(c, w, (int)K, c.d_wt_logw, c.d_wt_val); le != hipSuccess)
+        return bail(hip_fail(c, le, "launch_weight_value"));
+    SweepCall fin;
+    fin.acq = TGP_ACQ_EI;                 // (any acquisition: the final kernel only asks whether there is one)
+    fin.winner = c.d_winner;
+    const bool zc = tuning().sweep_zc != 0;
+    if (zc && (rc = ensure_pinned(c, 0, 8 * sizeof(double))) != TGP_OK) return bail(rc);
+    fin.res = zc ? c.h_pin_out.dev() : nullptr;
+    if (const hipError_t le = launch_argmax_of(c, fin, c.d_wt_val); le != hipSuccess) return bail(hip_fail(c, le, "launch_argmax_of"));
+    if ((rc = winner_mark(c, fin)) != TGP_OK) return rc;
+    SweepRecord rec;
+    if ((rc = sweep_queue_return(c, zc, fin.acq, rec, nullptr, mu, sigma, acq_out)) != TGP_OK) return rc;
+    if (logw_out) API_HIP(hipMemcpyAsync(logw_out, c.d_wt_logw, mb, hipMemcpyDeviceToHost, c.stream), "D2H logw");
+    if (value_out) API_HIP(hipMemcpyAsync(value_out, c.d_wt_val, mb, hipMemcpyDeviceToHost, c.stream), "D2H value");
+    if (side_mu && K > 0) API_HIP(hipMemcpyAsync(side_mu, c.d_wt_smu, (size_t)K * mb, hipMemcpyDeviceToHost, c.stream), "D2H side mu");
+    if (side_sigma && K > 0) API_HIP(hipMemcpyAsync(side_sigma, c.d_wt_ssg, (size_t)K * mb, hipMemcpyDeviceToHost, c.stream), "D2H side sigma");
+    API_HIP(hipStreamSynchronize(c.stream), "weighted sweep sync");     // the one wait: every side's stream is ordered in front of it
+    sweep_read_record(c, zc, fin.acq, rec, best_val, best_idx, n_clamped);
+    return TGP_OK;
+} TGP_CATCH
+
+static int kg_grad_sweep_posterior(Context &c, const double *d_Xq, int64_t m, double *d_mu, double *d_sigma);
+
+// the VALUES of a model's posterior at the query points: its own unpruned predict-only sweep of them where that sweep runs
+// in f64 (every f64 handle, and the one-workgroup / one-launch kernels of any handle), so that val is, for such handles,
+// what tgp_sweep_weighted returns for the same rows; an f32 sweep is not used (the query sums' f64 posterior stands)
+static bool weighted_sweep_is_f64(const Context &c, int64_t m) { return sweep_path(c, m) != SweepPath::General || c.dtype == TGP_F64; }
+
+int tgp_weighted_grad(tgp_handle h, const tgp_side *sides, int64_t K, const double *Xq, int64_t m, int acq, double sf,
+                      double incumbent, double param, double *val, double *grad) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_weighted_grad");
+    Context &c = h->c;
+    if (int rc = weighted_check(h, "tgp_weighted_grad", sides, K, acq, sf); rc != TGP_OK) return rc;
+    if (!Xq || !val || !grad || m < 1 || m > 4096) return fail(c, TGP_BAD_ARG, "tgp_weighted_grad: need Xq, val, grad and 1 <= m <= 4096");
+    API_HIP(hipSetDevice(c.device), "hipSetDevice");
+    API_HIP(pre_join(c), "hipStreamWaitEvent");
+    const int64_t D = c.D;
+    API_MEM(grow(c, c.d_wt_q, (size_t)(2 * m * D + m + 2 * (K + 1) * m) * sizeof(double), "hipMalloc weighted query"));
+    API_MEM(grow(c, c.d_qws, query_ws(c, (int)m).bytes, "hipMalloc query workspace"));
+    if (c.ev_wt.size() < (size_t)K) c.ev_wt.resize((size_t)K);
+    double *d_Xq = c.d_wt_q, *d_val = d_Xq + m * D, *d_grad = d_val + m, *d_mu = d_grad + m * D, *d_sg = d_mu + (K + 1) * m;
+    API_HIP(hipMemcpyAsync(d_Xq, Xq, (size_t)(m * D) * sizeof(double), hipMemcpyHostToDevice, c.stream), "H2D Xq");
+    bool in_marked = false;
+    WtGrad w{};
+    w.K = (int)K; w.m = (int)m; w.D = (int)D; w.acq = acq; w.sf = sf; w.incumbent = incumbent; w.param = param;
+    w.val = d_val; w.grad = d_grad;
+    // every model's sums [k.alpha, v.v, gm, gv] per point from the query kernels behind tgp_acq_grad, each on its handle's
+    // stream and in its handle's workspace; the combination reads them all on the objective's
+    {
+        const QueryWs q = query_ws(c, (int)m);
+        const hipError_t le = launch_query(c, d_Xq, (int)m, TGP_ACQ_NONE, sf, 0.0, 0.0, q.ws, nullptr, nullptr);
+        if (le != hipSuccess) return hip_fail(c, le, "launch_query");
+        const bool own = weighted_sweep_is_f64(c, m);
+        if (own)
+            if (int rc = kg_grad_sweep_posterior(c, d_Xq, m, d_mu, d_sg); rc != TGP_OK) return rc;
+        w.mdl[0] = WtModel{q.red, c.d_ls, c.constant + c.noise, c.y_mean, c.y_std, 0.0, 0, own ? d_mu : nullptr, own ? d_sg : nullptr};
+    }
+    for (int64_t k = 0; k < K; ++k) {
+        Context &g = sides[k].g->c;
+        auto side_fail = [&](int code) {
+            const std::string why = g.err;
+            (void)hipStreamSynchronize(c.stream);
+            (void)hipStreamSynchronize(g.stream);
+            (void)hipGetLastError();
+            return fail(c, code, "tgp_weighted_grad: side " + std::to_string((long long)k) + ": " + why);
+        };
+        if (const hipError_t e = pre_join(g); e != hipSuccess) { (void)hip_fail(g, e, "hipStreamWaitEvent"); return side_fail(TGP_HIP_ERROR); }
+        if (const int rc = grow(g, g.d_qws, query_ws(g, (int)m).bytes, "hipMalloc query workspace"); rc != TGP_OK) return side_fail(rc);
+        if (g.stream != c.stream) {          // the points are on the device before a private stream reads them
+            if (!in_marked) {
+                API_HIP(c.ev_wt_in.create(hipEventDisableTiming), "hipEventCreate");
+                API_HIP(hipEventRecord(c.ev_wt_in, c.stream), "hipEventRecord");
+                in_marked = true;
+            }
+            API_HIP(hipStreamWaitEvent(g.stream, c.ev_wt_in, 0), "hipStreamWaitEvent");
+        }
+        const QueryWs q = query_ws(g, (int)m);
+        const hipError_t le = launch_query(g, d_Xq, (int)m, TGP_ACQ_NONE, sf, 0.0, 0.0, q.ws, nullptr, nullptr);
+        if (le != hipSuccess) { (void)hip_fail(g, le, "launch_query"); return side_fail(TGP_HIP_ERROR); }
+        const bool own = weighted_sweep_is_f64(g, m);
+        if (own)
+            if (const int rc = kg_grad_sweep_posterior(g, d_Xq, m, d_mu + (1 + k) * m, d_sg + (1 + k) * m); rc != TGP_OK) return side_fail(rc);
+        if (const int rc = weighted_join(c, g, c.ev_wt[(size_t)k]); rc != TGP_OK) return rc;
+        w.mdl[1 + k] = WtModel{q.red, g.d_ls, g.constant + g.noise, g.y_mean, g.y_std, sides[k].level, sides[k].kind,
+                               own ? d_mu + (1 + k) * m : nullptr, own ? d_sg + (1 + k) * m : nullptr};
+    }
+    if (const hipError_t le = launch_weight_grad(c, w); le != hipSuccess) return hip_fail(c, le, "launch_weight_grad");
+    API_HIP(hipMemcpyAsync(val, d_val, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H val");
+    API_HIP(hipMemcpyAsync(grad, d_grad, (size_t)(m * D) * sizeof(double), hipMemcpyDeviceToHost, c.stream), "D2H grad");
+    API_HIP(hipStreamSynchronize(c.stream), "weighted grad sync");
+    return TGP_OK;
+} TGP_CATCH
+
+int tgp_weighted_lbfgsb(tgp_handle h, const tgp_side *sides, int64_t K, const double *X0, int64_t R, const double *lo,
+                        const double *hi, int acq, double sf, double incumbent, double param, int64_t max_iter, double *x_out,
+                        double *val_out, int64_t *status_out, int64_t *evaluations) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_weighted_lbfgsb");
+    Context &c = h->c;
+    const RefineArgs a{X0, R, lo, hi, acq, sf, incumbent, param, max_iter};
+    const RefineOut out{x_out, val_out, status_out, evaluations};
+    if (int rc = check_refine_args(c, "tgp_weighted_lbfgsb", a, out, TGP_ACQ_EI); rc != TGP_OK) return rc;
+    if (int rc = weighted_check(h, "tgp_weighted_lbfgsb", sides, K, acq, sf); rc != TGP_OK) return rc;
+    return acq_lbfgsb_lockstep(h, a, out, [&](const double *Xq, int64_t m, double *val, double *grad) {
+        return tgp_weighted_grad(h, sides, K, Xq, m, a.acq, a.sf, a.incumbent, a.param, val, grad);
+    });
+} TGP_CATCH
+
 // ---- the knowledge gradient over the resident batch (include/turbogp.h; kg_kernels.hip) ----
 // candidates per chunk of tgp_sweep_kg: a cross-kernel slab of about 512 MiB, a multiple of 1024, at most 16384
 // (TGP_CHUNK replaces it, as it does the sweep's); a batch that fits one chunk takes what it needs, in whole 128-tiles.

@@ -124,6 +124,11 @@ struct WsMem {                     // the sweeps' and the acquisition entries' w
     int kg_A = 0;
     long kg_gen = -1;              // the fit_gen the points belong to (-1: none)
     Dev<double> d_kgw;             // tgp_sweep_kg: a chunk's scaled candidates, cross-kernel slab and cross-covariance (KgChunk)
+    Dev<double> d_wt_logw, d_wt_val;   // tgp_sweep_weighted: (M,) summed log weight and weighted value
+    Dev<double> d_wt_smu, d_wt_ssg;    // ... and the sides' (K, M) mu / sigma rows, when asked for
+    Dev<double> d_wt_q;            // tgp_weighted_grad: [Xq (m D) | val (m) | grad (m D) | mu, sigma ((K + 1) m each)] on the objective's handle
+    std::vector<Ev> ev_wt;         // ... and, per side on another stream, "its sweep / its query sums are out" (no timing)
+    Ev ev_wt_in;                   // tgp_weighted_grad: the query points are on the device (what a side's private stream waits for)
     std::vector<Ev> ev_kg;         // brackets of the last tgp_sweep_kg's own kernels, a pair per chunk (the copies between them are not timed)
     double last_kg_ms = 0.0;
 };
@@ -484,6 +489,30 @@ hipError_t launch_integrate_final(Context &c, const SweepCall &s, int S);
 // the same final kernel over ONE (M,) vector of values that is already the acquisition (tgp_sweep_kg: c.d_acq): its
 // arg-max, the record s.res and the winner record s.winner; writes no (M,) output
 hipError_t launch_argmax_of(Context &c, const SweepCall &s, const double *vals);
+
+// tgp_sweep_weighted / tgp_weighted_grad (weight_kernels.hip), all on c.stream -- the OBJECTIVE's.
+constexpr int WT_MAX_SIDES = 8;    // most side models of one call
+// launch_weight_accumulate: behind side k's predict-only sweep into g.d_mu / g.d_sigma (the side's handle), logw (M,) on the
+// objective's handle takes (k == 0) or adds log f_k; the side's rows go to side_mu / side_sigma (nullable) and its clamp
+// count into c's counter.  launch_weight_value: behind the objective's predict-only sweep into c.d_mu / c.d_sigma, the
+// unweighted acquisition into c.d_acq and the weighted value into val (K == 0: logw is written as 0)
+hipError_t launch_weight_accumulate(Context &c, const Context &g, int k, int kind, double level, double *logw, double *side_mu,
+                                    double *side_sigma);
+hipError_t launch_weight_value(Context &c, const SweepCall &s, int K, double *logw, double *val);
+// the K + 1 models' value-with-partials at m query points combined: mdl[0] the objective, mdl[1 + k] side k; red: where
+// launch_query(d_val == nullptr) left that model's sums (QueryWs::red)
+struct WtModel {
+    const double *red, *ls; double kss, y_mean, y_std, level; int kind;
+    const double *mu, *sigma;      // (m) the model's own predict-only sweep of the points where that sweep is f64 (the VALUES are then the
+                                   // sweep's bits; the partials always come from the sums), else null
+};
+struct WtGrad {
+    WtModel mdl[1 + WT_MAX_SIDES];
+    int K, m, D, acq;
+    double sf, incumbent, param;
+    double *val, *grad;            // (m), (m, D) device memory
+};
+hipError_t launch_weight_grad(Context &c, const WtGrad &g);
 
 // the cov path's scaling, cross-kernel and mean for m rows Xq (m, D) on the device (cov_kernels.hip): Us (mpad, Dp),
 // Ks (mpad, Np), mu (mpad) or null; mpad a multiple of 64; cnt: two counters the first kernel clears
