@@ -769,6 +769,70 @@ int tgp_weighted_lbfgsb(tgp_handle h, const tgp_side *sides, int64_t K, const do
                         const double *hi, int acq, double sf, double incumbent, double param, int64_t max_iter,
                         double *x_out, double *val_out, int64_t *status_out, int64_t *evaluations);
 
+/* ---- two-objective expected hypervolume improvement (EHVI) --------------------------------------------------------
+ * Two competing objectives and a Pareto front: the expected growth of the area the front dominates over a reference
+ * point, under two INDEPENDENT GPs -- an exact closed form, a sum over the P + 1 strips of the front (Emmerich, Giannakoglou
+ * & Naujoks 2006; the strip form of Emmerich, Yang, Deutz, Wang & Fonseca 2016).  The reference has no second objective; the
+ * plugin turbo_amd.EHVI collects it from eval_info as turbo_amd.Constrained collects its side values.
+ * `h` is objective 1's fitted GPU handle with a resident batch of M rows, `g` objective 2's, on the same device with the
+ * same D (any dtype, kernel, N, training inputs and fit path).  Each has a direction sf_j in {+1, -1}, +1 = maximise as
+ * everywhere in the library.  Everything below is float64 whatever the dtypes.  In the oriented coordinates u_j = sf_j y_j:
+ *   r = (sf_1 ref_1, sf_2 ref_2) is the reference point; the front is the set of non-dominated observed pairs with
+ *   u_1 > r_1 and u_2 > r_2, sorted by u_1 ascending (u_2 is then strictly descending): (u_1^(i), u_2^(i)), i = 1 .. P,
+ *   0 <= P <= 256.  Breakpoints a_0 = r_1, a_i = u_1^(i), a_{P+1} = +inf; levels c_i = u_2^(i+1) for i < P, c_P = r_2.
+ * With (mu_j, sigma_j) the raw-unit posterior the handle's own unpruned predict-only sweep reports for the row, m_j = sf_j mu_j:
+ *   e_j(t) = sigma_j H((m_j - t) / sigma_j),  H(z) = phi(z) + z Phi(z);   sigma_j == 0: max(m_j - t, 0);   e_j(+inf) = 0
+ *   EHVI   = sum_{i = 0 .. P} max(e_1(a_i) - e_1(a_{i+1}), 0) e_2(c_i),   summed in the order i = 0, 1, ...
+ * the expectation of sum_i (min(V_1, a_{i+1}) - a_i)_+ (V_2 - c_i)_+, the improvement of the dominated area.  P = 0: the
+ * product e_1(r_1) e_2(r_2) of the two plain EIs at incumbent ref_j, xi = 0.  The partials, z_j(t) = (m_j - t) / sigma_j:
+ *   d/dm_1 = sum_i [Phi(z_1(a_i)) - Phi(z_1(a_{i+1}))] e_2(c_i)     d/dsigma_1 = sum_i [phi(z_1(a_i)) - phi(z_1(a_{i+1}))] e_2(c_i)
+ *   d/dm_2 = sum_i [e_1(a_i) - e_1(a_{i+1})] Phi(z_2(c_i))          d/dsigma_2 = sum_i [e_1(a_i) - e_1(a_{i+1})] phi(z_2(c_i))
+ * every term at t = +inf being 0.  H(z) for z <= 0 goes through the scaled complementary error function
+ * (csrc/ehvi_math.hpp, the route of TGP_ACQ_MES and of the weighted entries), never as phi + z ndtr(z) with the two tails
+ * formed separately.  H leaves the double range near z = -38.4: such a candidate's value is exactly 0 (there is no log
+ * form).  A NaN in any mu or sigma makes the row's value NaN, and such a row never wins.
+ * tgp_ehvi_set_front
+ *   Y (n, 2) raw observed pairs, n >= 0 (Y may be NULL when n == 0); ref: 2 finite raw values.  Every pair that does not
+ *   strictly beat ref in both oriented coordinates is dropped, duplicates merge, the non-dominated rest is kept (weak
+ *   dominance removes a point; equal u_1 keeps the larger u_2) and sorted (csrc/host_front.hpp, O(n log n)).  The front
+ *   is stored on h -- host copy and device breakpoints, with sf and r -- and survives refits, batches and every other
+ *   call until the next tgp_ehvi_set_front or tgp_destroy; it needs no fitted model.  Nullable outputs: P_out; front_out,
+ *   room for 2 TGP_EHVI_MAX_FRONT doubles, raw units, sorted order; hv_out, the front's dominated area over ref.
+ *   TGP_BAD_ARG for a non-finite Y or ref, an sf other than +-1, P > 256: the previous front is untouched.
+ * tgp_sweep_ehvi
+ *   makes g's resident batch a device-to-device COPY of h's M x D rows, owned by g (nothing is borrowed across handles; a
+ *   buffer g had borrowed with tgp_set_candidates_dev is released, never written): afterwards g behaves exactly as after
+ *   tgp_set_candidates with those rows.  h's fit, batch, Thompson draw, MES maxima and KG points are untouched.  A batch
+ *   on h that was warped with tgp_warp_candidates is TGP_BAD_ARG (each model would need its own warp).  The call enqueues
+ *   g's unpruned predict-only sweep on g's stream, orders that stream in front of h's (an event, where g has a private
+ *   stream), h's unpruned predict-only sweep, the value kernel and the final step, and waits once, at the end.
+ *   mu, sigma, mu2, sigma2, ehvi_out (M): nullable host outputs; mu / sigma / mu2 / sigma2 are the bits of the handles'
+ *   own predict-only tgp_sweep of the same rows.  best_val, best_idx: the arg-max of the value under the library-wide
+ *   rule (lowest index on ties, NaN never wins); the winner record (tgp_set_winner_out / tgp_winner_wait) is packed as by
+ *   tgp_sweep.  n_clamped is the sum of both sweeps.
+ * tgp_ehvi_grad
+ *   the value and its gradient (grad (m, D)) at m <= 4096 host points Xq, formed from both handles' value-with-partials --
+ *   mu, sigma and their gradients from the query kernels behind tgp_acq_grad, each on its own stream and workspace; where
+ *   a handle's sweep of the points runs in f64 (every f64 handle, the one-workgroup and one-launch kernels of any handle)
+ *   the VALUES mu and sigma are that sweep's own bits, so on such handles val is tgp_sweep_ehvi's ehvi_out for the same
+ *   rows, bit for bit:   grad = sf_1 C_m1 grad mu_1 + C_s1 grad sigma_1 + sf_2 C_m2 grad mu_2 + C_s2 grad sigma_2
+ *   with the four coefficients the strip sums above.  A model with sigma_j == 0 at the point contributes no sigma term; a
+ *   NaN value gives a NaN gradient.  A point's bits depend neither on m nor on its row.  The resident batches are not touched.
+ * tgp_ehvi_lbfgsb
+ *   tgp_acq_lbfgsb (below) with that evaluation: its contract, statuses and limits (no acq, sf, incumbent, param).
+ * Status: TGP_NOT_FITTED for an unfitted handle; TGP_BAD_ARG for no front set on h, g == h, a host handle, another device,
+ * another D, a warped batch on h, no candidates.  GPU only: the host-only library does not export these entries.
+ * Out of scope: more than two objectives, correlated objectives, a log form below the underflow, pruning either sweep,
+ * batch selection under EHVI, the sharded multi-GPU route, warped or marginalised models. */
+#define TGP_EHVI_MAX_FRONT 256
+int tgp_ehvi_set_front(tgp_handle h, const double *Y, int64_t n, double sf1, double sf2, const double *ref,
+                       int64_t *P_out, double *front_out, double *hv_out);
+int tgp_sweep_ehvi(tgp_handle h, tgp_handle g, double *mu, double *sigma, double *mu2, double *sigma2,
+                   double *ehvi_out, double *best_val, int64_t *best_idx, int64_t *n_clamped);
+int tgp_ehvi_grad(tgp_handle h, tgp_handle g, const double *Xq, int64_t m, double *val, double *grad);
+int tgp_ehvi_lbfgsb(tgp_handle h, tgp_handle g, const double *X0, int64_t R, const double *lo, const double *hi,
+                    int64_t max_iter, double *x_out, double *val_out, int64_t *status_out, int64_t *evaluations);
+
 /* The gradient stage itself on the device: R <= 4096 restarts X0 (R, D) are refined together by a
  * projected L-BFGS (memory 8; a line search that asks for sufficient decrease 1e-4 and the curvature
  * condition 0.9 as L-BFGS-B's does, lengthening a step whose slope is still steep; bounds lo / hi

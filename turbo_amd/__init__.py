@@ -16,12 +16,12 @@ from .kernels import GPKernel
 from .bounds import Bounds
 from .surrogates import Surrogate, HipGPSurrogate, MarginalisedHipGPSurrogate, MarginalisedModel
 from .warped import WarpedHipGPSurrogate, WarpedModel
-from .acquisition_functions import AcquisitionFunction, UCB, PI, EI, TS, MES, KG, Constraint, Cost, Constrained, joint_ei
+from .acquisition_functions import AcquisitionFunction, UCB, PI, EI, TS, MES, KG, Constraint, Cost, Constrained, Objective, EHVI, joint_ei
 from .auxiliary_optimisers import CandidateSweep, RandomAndQuasiNewton
 from .naive_selectors import random_selector, LHS_selector
 from ._lib import TurboGPLibraryError, NativeGP, LIB_PATH
 
 __all__ = ['GPKernel', 'Bounds', 'Surrogate', 'HipGPSurrogate', 'MarginalisedHipGPSurrogate',
            'MarginalisedModel', 'WarpedHipGPSurrogate', 'WarpedModel', 'AcquisitionFunction', 'UCB', 'PI',
-           'EI', 'TS', 'MES', 'KG', 'Constraint', 'Cost', 'Constrained', 'joint_ei', 'CandidateSweep', 'RandomAndQuasiNewton', 'random_selector', 'LHS_selector',
+           'EI', 'TS', 'MES', 'KG', 'Constraint', 'Cost', 'Constrained', 'Objective', 'EHVI', 'joint_ei', 'CandidateSweep', 'RandomAndQuasiNewton', 'random_selector', 'LHS_selector',
            'TurboGPLibraryError', 'NativeGP', 'LIB_PATH']

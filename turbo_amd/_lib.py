@@ -35,6 +35,7 @@ BUF_K, BUF_L, BUF_LINV, BUF_ALPHA = 0, 1, 2, 3
 BATCH_KB, BATCH_CL = 0, 1    # tgp_sweep_batch strategies: Kriging Believer, Constant Liar
 SIDE_GE, SIDE_LE, SIDE_COST = 0, 1, 2    # tgp_side kinds: value >= level, value <= level, the log of a cost
 SIDE_KINDS = {"ge": SIDE_GE, "le": SIDE_LE, "cost": SIDE_COST}
+EHVI_MAX_FRONT = 256    # TGP_EHVI_MAX_FRONT: most points of a front (tgp_ehvi_set_front)
 
 # every symbol include/turbogp.h declares
 SYMBOLS = (
@@ -47,6 +48,7 @@ SYMBOLS = (
     "tgp_evaluate", "tgp_predict_batch", "tgp_predict", "tgp_profile_enable", "tgp_profile_read", "tgp_profile_reset",
     "tgp_sweep_geometry", "tgp_last_timings", "tgp_hyper_sample", "tgp_sweep_integrated", "tgp_kg_set_points", "tgp_sweep_kg",
     "tgp_kg_grad", "tgp_kg_lbfgsb", "tgp_sweep_weighted", "tgp_weighted_grad", "tgp_weighted_lbfgsb",
+    "tgp_ehvi_set_front", "tgp_sweep_ehvi", "tgp_ehvi_grad", "tgp_ehvi_lbfgsb",
     "tgp_fit_input_grad", "tgp_warp_points", "tgp_warp_inverse", "tgp_warp_candidates", "tgp_warp_read_raw", "tgp_fit_warp_grad",
     "tgp_fit_warp_lbfgsb",
     "tgp_multi_create", "tgp_multi_destroy", "tgp_multi_last_error", "tgp_multi_size", "tgp_multi_handle",
@@ -179,6 +181,10 @@ def _argtypes():
                               _dp, _dp],
         "tgp_weighted_lbfgsb": [_vp, c.POINTER(Side), c.c_int64, _dp, c.c_int64, _dp, _dp, c.c_int, c.c_double, c.c_double,
                                 c.c_double, c.c_int64, _dp, _dp, _i64p, _i64p],
+        "tgp_ehvi_set_front": [_vp, _dp, c.c_int64, c.c_double, c.c_double, _dp, _i64p, _dp, _dp],
+        "tgp_sweep_ehvi": [_vp, _vp, _dp, _dp, _dp, _dp, _dp, _dp, _i64p, _i64p],
+        "tgp_ehvi_grad": [_vp, _vp, _dp, c.c_int64, _dp, _dp],
+        "tgp_ehvi_lbfgsb": [_vp, _vp, _dp, c.c_int64, _dp, _dp, c.c_int64, _dp, _dp, _i64p, _i64p],
         "tgp_predict_cov": [_vp, _dp, c.c_int64, c.c_int, _dp, _dp, _i64p],
         "tgp_sample_joint": [_vp, _dp, c.c_int64, c.c_int64, c.c_int, c.c_double, c.c_uint64, _dp, _dp, _dp, _dp],
         "tgp_acq_refine": [_vp, _dp, c.c_int64, _dp, _dp, c.c_int, c.c_double, c.c_double, c.c_double,
@@ -1113,6 +1119,71 @@ class NativeGP:
         self._check(self.lib.tgp_weighted_lbfgsb(self._h, arr, K, _ptr(X0), R, _ptr(lo), _ptr(hi), int(acq), float(sf),
                                                  float(incumbent), float(param), int(max_iter), _ptr(x), _ptr(v),
                                                  st.ctypes.data_as(_i64p), ctypes.byref(its)))
+        return x, v, st, its.value
+
+    def ehvi_set_front(self, Y, ref, sf=(1.0, 1.0)):
+        """``tgp_ehvi_set_front``: the Pareto front of the observed pairs ``Y`` (n, 2) over the reference point ``ref``
+        (2,), raw units, under the directions ``sf`` (+1 maximise, -1 minimise), kept on this (objective 1's) handle
+        until the next call.  Returns (front (P, 2) raw units, sorted by the oriented first objective ascending;
+        hypervolume).  Needs no fitted model."""
+        Y = _f64c(Y).reshape(-1, 2)
+        ref = _f64c(ref).reshape(-1)
+        assert ref.shape == (2,), "ref must have 2 entries"
+        P = ctypes.c_int64(0)
+        hv = ctypes.c_double(0.0)
+        front = np.empty((EHVI_MAX_FRONT, 2))
+        self._check(self.lib.tgp_ehvi_set_front(self._h, _ptr(Y) if Y.shape[0] else None, Y.shape[0], float(sf[0]), float(sf[1]),
+                                                _ptr(ref), ctypes.byref(P), _ptr(front), ctypes.byref(hv)))
+        return front[:P.value].copy(), hv.value
+
+    @staticmethod
+    def _handle_of(g):
+        return g._h if isinstance(g._h, int) or g._h is None else g._h.value
+
+    def sweep_ehvi(self, g, want_mu=False, want_sigma=False, want_second=False, want_value=False):
+        """``tgp_sweep_ehvi``: the resident batch scored by the two-objective expected hypervolume improvement under
+        this (objective 1's) model and ``g`` (objective 2's, a NativeGP) over the front of ``ehvi_set_front``, and its
+        arg-max.  ``g``'s resident batch becomes its own copy of this handle's rows.  ``want_second``: ``mu2`` /
+        ``sigma2`` (M,); ``want_value``: ``value`` (M,)."""
+        out = _SweepOut(self.M, want_mu, want_sigma, False)
+        mu2 = np.empty(self.M) if want_second else None
+        sg2 = np.empty(self.M) if want_second else None
+        value = np.empty(self.M) if want_value else None
+        try:
+            self._check(self.lib.tgp_sweep_ehvi(self._h, self._handle_of(g), _ptr(out.mu), _ptr(out.sg), _ptr(mu2), _ptr(sg2),
+                                                _ptr(value), ctypes.byref(out.bv), ctypes.byref(out.bi), ctypes.byref(out.nc)))
+        except Exception:
+            # (as sweep_weighted: a second objective the call reached before it failed owns a copy of these rows already)
+            if isinstance(g, NativeGP) and g is not self and g._h is not None and not g.host and self._resident_rows_are(g, self.M):
+                g._batch_is(self.M)
+            raise
+        g._batch_is(self.M)           # g owns a copy of these rows now: nothing of a caller's to keep alive
+        return out.result(mu2=mu2, sigma2=sg2, value=value)
+
+    def ehvi_grad(self, Xq, g):
+        """``tgp_ehvi_grad``: the value (m,) -- ``sweep_ehvi``'s formula -- and its gradient (m, D) at m <= 4096 points;
+        float64 whatever the handles' dtypes"""
+        Xq = _f64c(np.atleast_2d(Xq))
+        assert Xq.ndim == 2 and Xq.shape[1] == self.D, "points must be (m, %d)" % self.D
+        val = np.empty(Xq.shape[0])
+        grad = np.empty(Xq.shape)
+        self._check(self.lib.tgp_ehvi_grad(self._h, self._handle_of(g), _ptr(Xq), Xq.shape[0], _ptr(val), _ptr(grad)))
+        return val, grad
+
+    def ehvi_lbfgsb(self, X0, lo, hi, g, max_iter=15000):
+        """``tgp_ehvi_lbfgsb``: ``acq_refine(lbfgsb=True)`` with the expected hypervolume improvement as the objective --
+        L-BFGS-B from every start in lock-step, one batched ``tgp_ehvi_grad`` per round; returns (x (R, D), values (R,),
+        status (R,), evaluations)"""
+        X0 = _f64c(np.atleast_2d(X0))
+        assert X0.ndim == 2 and X0.shape[1] == self.D, "start points must be (R, %d)" % self.D
+        lo, hi = _bounds(lo, hi, self.D)
+        R = X0.shape[0]
+        x = np.empty((R, self.D))
+        v = np.empty(R)
+        st = np.empty(R, dtype=np.int64)
+        its = ctypes.c_int64(0)
+        self._check(self.lib.tgp_ehvi_lbfgsb(self._h, self._handle_of(g), _ptr(X0), R, _ptr(lo), _ptr(hi), int(max_iter), _ptr(x),
+                                             _ptr(v), st.ctypes.data_as(_i64p), ctypes.byref(its)))
         return x, v, st, its.value
 
     def predict_cov(self, Xq, latent=False):

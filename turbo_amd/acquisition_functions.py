@@ -14,6 +14,7 @@ GPU-only extras ``maximise_topk`` / ``refine`` / ``value_and_grad`` / ``maximise
 Beyond the reference interface each instance has ``maximise(X) -> (index, value)``, which the
 ``CandidateSweep`` auxiliary optimiser uses to get the arg-max without copying M values back.
 """
+import uuid
 from math import isinf
 
 import numpy as np
@@ -1218,6 +1219,319 @@ class Constrained(AcquisitionFunction):
         def refine(self, starting_points, bounds, max_iter=200):
             self._refuse('the on-device optimiser (on_device=True, tgp_acq_refine)',
                          'the default lockstep=True gradient stage (tgp_weighted_lbfgsb)')
+
+        def winner_record(self, global_offset):
+            self._refuse('winner_record (the sharded multi-GPU sweep)', 'one process per optimisation')
+
+
+def pareto_front(Y, sf, ref):
+    """the front of ``tgp_ehvi_set_front`` in NumPy: the rows of Y (n, 2) that strictly beat ``ref`` in both oriented
+    coordinates u_j = sf_j y_j and that no other pair weakly dominates, duplicates merged, sorted by u_1 ascending ->
+    (front (P, 2) raw units, positions (P,) of each point's first row in Y, dominated area over ref)"""
+    Y = np.asarray(Y, dtype=np.float64).reshape(-1, 2)
+    sf = np.asarray(sf, dtype=np.float64)
+    r = sf * np.asarray(ref, dtype=np.float64)
+    U = Y * sf
+    order = sorted((i for i in range(U.shape[0]) if U[i, 0] > r[0] and U[i, 1] > r[1]), key=lambda i: (-U[i, 0], -U[i, 1], i))
+    keep, top = [], r[1]
+    for i in order:
+        if U[i, 1] > top:
+            keep.append(i)
+            top = U[i, 1]
+    keep.reverse()
+    hv, left = 0.0, r[0]
+    for i in keep:
+        hv += (U[i, 0] - left) * (U[i, 1] - r[1])
+        left = U[i, 0]
+    idx = np.array(keep, dtype=np.int64)
+    return Y[idx].reshape(-1, 2), idx, hv
+
+
+def _ehvi_from_posteriors(front, sf, ref, mu1, sigma1, mu2, sigma2):
+    """the expected hypervolume improvement on the host from both models' posteriors -- ``tgp_sweep_ehvi``'s definition in
+    NumPy, float64: ``front`` (P, 2) raw units sorted as ``pareto_front`` returns it; H(z) for z <= 0 through
+    ``scipy.special.erfcx``; e = max(m - t, 0) where sigma == 0; NaN where any mu or sigma is NaN"""
+    from scipy.special import erfcx, ndtr
+    sf = np.asarray(sf, dtype=np.float64)
+    F = np.asarray(front, dtype=np.float64).reshape(-1, 2) * sf
+    r = sf * np.asarray(ref, dtype=np.float64)
+    a = np.concatenate([[r[0]], F[:, 0]])
+    c = np.concatenate([F[:, 1], [r[1]]])
+    m = [sf[0] * np.asarray(mu1, dtype=np.float64).reshape(-1), sf[1] * np.asarray(mu2, dtype=np.float64).reshape(-1)]
+    s = [np.asarray(sigma1, dtype=np.float64).reshape(-1), np.asarray(sigma2, dtype=np.float64).reshape(-1)]
+
+    def e(j, t):
+        d = m[j] - t
+        live = s[j] != 0
+        sj = np.where(live, s[j], 1.0)
+        with np.errstate(over='ignore', under='ignore', invalid='ignore'):
+            z = d / sj
+            x = -np.minimum(z, 0.0) / np.sqrt(2.0)
+            left = np.exp(-x * x) * (1.0 / np.sqrt(2.0 * np.pi) - x * erfcx(x) / np.sqrt(2.0))
+            zp = np.maximum(z, 0.0)
+            right = np.exp(-0.5 * zp * zp) / np.sqrt(2.0 * np.pi) + zp * ndtr(zp)
+            return np.where(live, sj * np.where(z <= 0, left, right), np.maximum(d, 0.0))
+    value = np.zeros_like(m[0])
+    lo = e(0, a[0])
+    for i in range(len(c)):
+        hi = e(0, a[i + 1]) if i + 1 < len(a) else np.zeros_like(lo)
+        value = value + np.maximum(lo - hi, 0.0) * e(1, c[i])
+        lo = hi
+    bad = np.isnan(m[0]) | np.isnan(s[0]) | np.isnan(m[1]) | np.isnan(s[1])
+    return np.where(bad, np.nan, value)
+
+
+class Objective:
+    """The second objective of ``EHVI``: the objective function reports ``eval_info[name]`` for every trial, and a GP (its OWN
+    ``HipGPSurrogate`` factory: one factory is one GPU handle, so the two models do not displace each other) is fitted to
+    those values; ``extremum``: 'min' or 'max'"""
+
+    def __init__(self, name, surrogate, extremum='min'):
+        if extremum not in ('min', 'max'):
+            raise ValueError("extremum must be 'min' or 'max'")
+        self.name, self.surrogate, self.extremum = name, surrogate, extremum
+
+
+class EHVI(AcquisitionFunction):
+    """Two-objective expected hypervolume improvement -- ``tgp_sweep_ehvi`` and its gradient: the Optimiser's own objective is
+    objective 1, ``second`` (an ``Objective``) objective 2, and a candidate is scored by the expected growth of the area the
+    Pareto front of the observed pairs dominates over ``ref`` (2 raw values; None: per objective the worst observed value
+    moved away from the front by 0.1 of the observed range, a zero range counting as 1.0).  It is an acquisition factory AND a
+    listener (duck-typed: it imports nothing from ``turbo``), so with an unmodified reference Optimiser it is put in both
+    places::
+
+        acq = ta.EHVI(ta.Objective('latency', ta.HipGPSurrogate(...), 'min'))
+        op.acquisition = acq
+        op.register_listener(acq)          # evaluation_finished(trial_num, y, eval_info) brings eval_info['latency']
+    """
+
+    def __init__(self, second, ref=None):
+        if not isinstance(second, Objective):
+            raise TypeError('EHVI takes the second objective as an Objective; got {!r}'.format(type(second)))
+        if ref is not None:
+            ref = np.asarray(ref, dtype=np.float64).reshape(-1)
+            if ref.shape != (2,) or not np.all(np.isfinite(ref)):
+                raise ValueError('ref must be 2 finite values')
+        self.second = second
+        self.ref = ref
+        self.records = {}          # trial_num -> the second objective's value
+        self.optimiser = None
+
+    def get_type(self):
+        return 'optimism'          # the Optimiser's scalar incumbent plays no part
+
+    # ---- listener callbacks (turbo/modules/listener.py) ----
+    def registered(self, optimiser):
+        self.optimiser = optimiser
+
+    def unregistered(self):
+        self.optimiser = None
+
+    def run_started(self, finished_trials, max_trials):
+        pass
+
+    def selection_started(self, trial_num):
+        pass
+
+    def surrogate_fitted(self, trial_num):
+        pass
+
+    def acquisition_maximised(self, trial_num):
+        pass
+
+    def selection_finished(self, trial_num, x, selection_info):
+        pass
+
+    def run_finished(self):
+        pass
+
+    def evaluation_started(self, trial_num):
+        pass
+
+    def evaluation_finished(self, trial_num, y, eval_info):
+        info = eval_info if isinstance(eval_info, dict) else {}
+        name = self.second.name
+        if name not in info:
+            raise KeyError('EHVI: trial {} reported no eval_info[{!r}] (the objective must return (cost, eval_info) with the '
+                           'second objective\'s value)'.format(trial_num, name))
+        value = float(info[name])
+        if not np.isfinite(value):
+            raise ValueError('EHVI: the second objective of trial {} must be finite'.format(trial_num))
+        self.records[int(trial_num)] = value
+
+    # ---- factory ----
+    def _second_values(self, n):
+        if len(self.records) != n:
+            raise ValueError('EHVI holds {} trial records for a model of {} observations: register it as a listener of the '
+                             'Optimiser (op.register_listener(acq)) before the first trial, one record per row of model.X'
+                             .format(len(self.records), n))
+        order = sorted(self.records)
+        return order, np.array([self.records[t] for t in order])
+
+    @staticmethod
+    def default_ref(Y, sf):
+        """per objective the worst observed value moved away from the front by 0.1 of the observed range (zero range: 1.0)"""
+        sf = np.asarray(sf, dtype=np.float64)
+        U = np.asarray(Y, dtype=np.float64).reshape(-1, 2) * sf
+        span = U.max(0) - U.min(0)
+        span = np.where(span > 0, span, 1.0)
+        return sf * (U.min(0) - 0.1 * span)
+
+    def construct_function(self, trial_num, model, desired_extremum):
+        _refuse_warped(model, 'EHVI')
+        _refuse_marginalised(model, 'EHVI (each objective is scored under one fitted model)')
+        X = np.asarray(model.X, dtype=np.float64)
+        y = np.asarray(model.y, dtype=np.float64).reshape(-1)
+        trials, y2 = self._second_values(X.shape[0])
+        second_model, second_info = self.second.surrogate.construct_model(trial_num, X, y2)
+        _refuse_warped(second_model, 'EHVI (the second objective)')
+        _refuse_marginalised(second_model, 'EHVI (the second objective)')
+        Y = np.stack([y, y2], 1)
+        sf = (1.0 if desired_extremum == 'max' else -1.0, 1.0 if self.second.extremum == 'max' else -1.0)
+        ref = self.default_ref(Y, sf) if self.ref is None else self.ref.copy()
+        front, idx, hv = pareto_front(Y, sf, ref)
+        if front.shape[0] > _lib.EHVI_MAX_FRONT:
+            raise ValueError('EHVI: the front has {} points; at most {} are scored (tgp_ehvi_set_front)'.format(front.shape[0], _lib.EHVI_MAX_FRONT))
+        inst = EHVI.FunctionInstance(model, desired_extremum, second_model, self.second.name, sf, ref, Y, front)
+        if inst._on_gpu() is not None:          # the library's own builder is the one the sweep uses: its front and area are reported
+            front, hv = inst._library_front
+            inst.front = front
+        acq_info = {'ref': ref, 'pareto_front': front, 'pareto_trials': [trials[i] for i in idx], 'hypervolume': hv,
+                    'second_fitting_info': second_info}
+        return inst, acq_info
+
+    class FunctionInstance(AcquisitionFunction.FunctionInstance):
+        """value(x) = the expected growth of the area dominated over ``ref`` by ``front`` under the two models' independent
+        posteriors at x"""
+
+        sweep_dtype = 'f64'      # the closed form is f64 whatever the handles' dtypes
+
+        def __init__(self, model, desired_extremum, second_model, second_name, sf, ref, Y, front):
+            super().__init__(model, desired_extremum)
+            self.second_model = second_model
+            self.second_name = second_name
+            self.sf = tuple(float(v) for v in sf)
+            self.ref = np.asarray(ref, dtype=np.float64)
+            self.Y = np.asarray(Y, dtype=np.float64)
+            self.front = np.asarray(front, dtype=np.float64)
+            self._token = uuid.uuid4().hex      # which instance's front a handle holds (a handle serves one trial after another)
+            self._library_front = None          # (front, hypervolume) as tgp_ehvi_set_front reported them
+
+        def get_name(self):
+            return 'EHVI'
+
+        def _as_points(self, X):
+            X = np.asarray(X, dtype=np.float64)
+            if X.ndim == 1:
+                X = X.reshape(1, -1)
+            assert X.ndim == 2 and X.shape[1] == np.asarray(self.model.X).shape[1], \
+                'X must have shape (num_points, {})'.format(np.asarray(self.model.X).shape[1])
+            return X
+
+        def _on_gpu(self):
+            """(objective 1's context, objective 2's) with both models resident, each in its own handle, and this
+            instance's front on the first -- or None where the formula is served on the host: a foreign model, or a
+            reloaded one where no GPU is visible (the Recorder's plot path)"""
+            if not _is_native(self.model) or not _is_native(self.second_model):
+                return None
+            ctx = self.model._ensure_resident()
+            if getattr(ctx, 'host', False):
+                return None
+            g = self.second_model._ensure_resident()
+            if getattr(g, 'host', False):
+                return None
+            if g is ctx:
+                raise ValueError('EHVI: the second objective shares its HipGPSurrogate factory (one GPU handle) with the first: '
+                                 'give the Objective its own factory')
+            if getattr(ctx, '_ehvi_owner', None) != self._token:      # another instance's front (or none) is on the handle
+                self._library_front = ctx.ehvi_set_front(self.Y, self.ref, self.sf)
+                ctx._ehvi_owner = self._token
+            return ctx, g
+
+        def _require_gpu(self, what):
+            on = self._on_gpu()
+            if on is None:
+                raise TypeError('EHVI: {} runs on the GPU only: it needs models built by HipGPSurrogate and a visible '
+                                'device'.format(what))
+            return on
+
+        def __call__(self, X):
+            X = self._as_points(X)
+            if X.shape[0] == 0:
+                return np.empty(0)
+            on = self._on_gpu()
+            if on is None:       # the formula from model.predict of both models, in NumPy
+                mu1, s1 = self.model.predict(X, return_std_dev=True)
+                mu2, s2 = self.second_model.predict(X, return_std_dev=True)
+                return _ehvi_from_posteriors(self.front, self.sf, self.ref, mu1, s1, mu2, s2)
+            ctx, g = on
+            ctx.set_candidates(X)
+            return ctx.sweep_ehvi(g, want_value=True)['value']
+
+        def maximise(self, X):
+            """arg-max of the value over the rows of X: (index, value); lowest index wins ties"""
+            on = self._on_gpu()
+            if on is None:
+                vals = self(X)
+                vals = np.where(np.isnan(vals), -np.inf, vals)
+                i = int(np.argmax(vals))
+                return i, float(vals[i])
+            ctx, g = on
+            ctx.set_candidates(self._as_points(X))
+            res = ctx.sweep_ehvi(g)
+            return res['best_idx'], res['best_val']
+
+        def maximise_generated(self, num_points, low, high, seed, first_candidate=0, lhs_total=None, prefetch_seed=None):
+            """draw ``num_points`` candidates on the GPU and return the best: (x (D,), value, index)"""
+            if prefetch_seed is not None:
+                raise NotImplementedError('EHVI: no prefetched batch (the overlap starts a single-objective sweep inside the fit)')
+            ctx, g = self._require_gpu('maximise_generated')
+            ctx.generate(seed, first_candidate, num_points, low, high, lhs_total, reuse=True)
+            res = ctx.sweep_ehvi(g)
+            return ctx.get_candidate(res['best_idx']), res['best_val'], res['best_idx']
+
+        def maximise_host_stream(self, num_points, low, high, topk=0, first=0, count=None):
+            """the reference's host draw finished on the GPU, then the sweep; None -- nothing drawn -- where the library
+            cannot promise NumPy's numbers, or a top-k is asked for (the caller then draws on the host)"""
+            if topk > 0:
+                return None
+            on = self._on_gpu()
+            if on is None:
+                return None
+            ctx, g = on
+            if not hasattr(ctx, 'set_candidates_numpy_stream') or not ctx.set_candidates_numpy_stream(num_points, low, high, first=first, count=count):
+                return None
+            res = ctx.sweep_ehvi(g)
+            return ctx, res['best_idx'], res['best_val'], None
+
+        def value_and_grad(self, X):
+            """the value (m,) and its gradient (m, D) at m <= 4096 points (``tgp_ehvi_grad``)"""
+            ctx, g = self._require_gpu('value_and_grad')
+            return ctx.ehvi_grad(self._as_points(X), g)
+
+        def lbfgsb(self, starting_points, bounds, max_iter=15000):
+            """L-BFGS-B from every start inside the library (``tgp_ehvi_lbfgsb``): the restarts in lock-step, one batched
+            ``tgp_ehvi_grad`` per round; returns (x (R, D), values (R,), status (R,): 1 = SciPy's success, evaluations)"""
+            ctx, g = self._require_gpu('lbfgsb')
+            low, high = zip(*bounds)
+            return ctx.ehvi_lbfgsb(self._as_points(starting_points), low, high, g, max_iter)
+
+        def _refuse(self, what, instead):
+            raise NotImplementedError('EHVI: {} is not available for the expected hypervolume improvement: use {}'.format(what, instead))
+
+        # (a PROPERTY that raises AttributeError, as Constrained's: CandidateSweep asks hasattr(acq, 'maximise_topk'))
+        @property
+        def maximise_topk(self):
+            raise AttributeError('EHVI: maximise_topk (tgp_sweep_topk) is not available for the expected hypervolume improvement: '
+                                 'use __call__ and a host argsort')
+
+        def maximise_batch(self, X, q, strategy='kriging_believer', lie='min', pending=None, want_posterior=False,
+                           n_sim=16, seed=None):
+            self._refuse('batch selection (tgp_sweep_batch / tgp_sweep_batch_mc)', 'one selection at a time')
+
+        def refine(self, starting_points, bounds, max_iter=200):
+            self._refuse('the on-device optimiser (on_device=True, tgp_acq_refine)',
+                         'the default lockstep=True gradient stage (tgp_ehvi_lbfgsb)')
 
         def winner_record(self, global_offset):
             self._refuse('winner_record (the sharded multi-GPU sweep)', 'one process per optimisation')

@@ -2809,6 +2809,47 @@ int tgp_weighted_lbfgsb(tgp_handle h, const tgp_side *sides, int64_t K, const do
     });
 } TGP_CATCH
 
+}  // extern "C"
+#include "api_ehvi.hpp"
+extern "C" {
+
+// ---- two-objective expected hypervolume improvement (include/turbogp.h; api_ehvi.hpp, ehvi_kernels.hip) ------------
+int tgp_ehvi_set_front(tgp_handle h, const double *Y, int64_t n, double sf1, double sf2, const double *ref, int64_t *P_out,
+                       double *front_out, double *hv_out) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_ehvi_set_front");
+    return ehvi_set_front(h, Y, n, sf1, sf2, ref, P_out, front_out, hv_out);
+} TGP_CATCH
+
+int tgp_sweep_ehvi(tgp_handle h, tgp_handle g, double *mu, double *sigma, double *mu2, double *sigma2, double *ehvi_out,
+                   double *best_val, int64_t *best_idx, int64_t *n_clamped) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_sweep_ehvi");
+    if (int rc = ehvi_check(h, g, "tgp_sweep_ehvi"); rc != TGP_OK) return rc;
+    return ehvi_sweep(h, g, mu, sigma, mu2, sigma2, ehvi_out, best_val, best_idx, n_clamped);
+} TGP_CATCH
+
+int tgp_ehvi_grad(tgp_handle h, tgp_handle g, const double *Xq, int64_t m, double *val, double *grad) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_ehvi_grad");
+    if (int rc = ehvi_check(h, g, "tgp_ehvi_grad"); rc != TGP_OK) return rc;
+    return ehvi_grad(h, g, Xq, m, val, grad);
+} TGP_CATCH
+
+int tgp_ehvi_lbfgsb(tgp_handle h, tgp_handle g, const double *X0, int64_t R, const double *lo, const double *hi,
+                    int64_t max_iter, double *x_out, double *val_out, int64_t *status_out, int64_t *evaluations) try {
+    if (!h) return TGP_BAD_ARG;
+    HOST_NA("tgp_ehvi_lbfgsb");
+    Context &c = h->c;
+    const RefineArgs a{X0, R, lo, hi, TGP_ACQ_EI, 1.0, 0.0, 0.0, max_iter};
+    const RefineOut out{x_out, val_out, status_out, evaluations};
+    if (int rc = check_refine_args(c, "tgp_ehvi_lbfgsb", a, out, TGP_ACQ_EI); rc != TGP_OK) return rc;
+    if (int rc = ehvi_check(h, g, "tgp_ehvi_lbfgsb"); rc != TGP_OK) return rc;
+    return acq_lbfgsb_lockstep(h, a, out, [&](const double *Xq, int64_t m, double *val, double *grad) {
+        return ehvi_grad(h, g, Xq, m, val, grad);
+    });
+} TGP_CATCH
+
 // ---- the knowledge gradient over the resident batch (include/turbogp.h; kg_kernels.hip) ----
 // candidates per chunk of tgp_sweep_kg: a cross-kernel slab of about 512 MiB, a multiple of 1024, at most 16384
 // (TGP_CHUNK replaces it, as it does the sweep's); a batch that fits one chunk takes what it needs, in whole 128-tiles.

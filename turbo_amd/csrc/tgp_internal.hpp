@@ -129,6 +129,14 @@ struct WsMem {                     // the sweeps' and the acquisition entries' w
     Dev<double> d_wt_q;            // tgp_weighted_grad: [Xq (m D) | val (m) | grad (m D) | mu, sigma ((K + 1) m each)] on the objective's handle
     std::vector<Ev> ev_wt;         // ... and, per side on another stream, "its sweep / its query sums are out" (no timing)
     Ev ev_wt_in;                   // tgp_weighted_grad: the query points are on the device (what a side's private stream waits for)
+    // tgp_ehvi_set_front: the front of objective 1's handle -- kept until the next tgp_ehvi_set_front (no fit touches it)
+    int ehvi_P = -1;               // points of the front (-1: none set)
+    double ehvi_sf[2] = {1.0, 1.0};
+    std::vector<double> ehvi_a, ehvi_c;   // host copy: the P + 1 breakpoints and levels, oriented coordinates
+    Dev<double> d_ehvi_front;      // [a | c], TGP_EHVI_MAX_FRONT + 1 doubles each
+    Dev<double> d_ehvi_val;        // tgp_sweep_ehvi: (M,) values
+    Dev<double> d_ehvi_q;          // tgp_ehvi_grad: [Xq (m D) | val (m) | coef (4 m) | grad (m D) | mu, sigma (2 m each)]
+    Ev ev_ehvi, ev_ehvi_in;        // g's sweep / sums are out; the query points are on the device (no timing)
     std::vector<Ev> ev_kg;         // brackets of the last tgp_sweep_kg's own kernels, a pair per chunk (the copies between them are not timed)
     double last_kg_ms = 0.0;
 };
@@ -513,6 +521,25 @@ struct WtGrad {
     double *val, *grad;            // (m), (m, D) device memory
 };
 hipError_t launch_weight_grad(Context &c, const WtGrad &g);
+
+// tgp_sweep_ehvi / tgp_ehvi_grad (ehvi_kernels.hip), all on c.stream -- objective 1's.  front: c.d_ehvi_front,
+// [a_0 .. a_P | c_0 .. c_P] at a stride of TGP_EHVI_MAX_FRONT + 1, oriented coordinates.
+// launch_ehvi_value: behind g's and c's predict-only sweeps into their d_mu / d_sigma, the value into val (M,); g's clamp
+// count moves into c's counter
+hipError_t launch_ehvi_value(Context &c, const Context &g, const double *front, int P, double sf1, double sf2, double *val);
+// the two models' value-with-partials at m query points combined; the members as WtModel's
+struct EhviModel {
+    const double *red, *ls; double kss, y_mean, y_std;
+    const double *mu, *sigma;
+};
+struct EhviGrad {
+    EhviModel mdl[2];
+    const double *front;
+    int P, m, D;
+    double sf[2];
+    double *val, *coef, *grad;     // (m), (m, 4), (m, D) device memory
+};
+hipError_t launch_ehvi_grad(Context &c, const EhviGrad &g);
 
 // the cov path's scaling, cross-kernel and mean for m rows Xq (m, D) on the device (cov_kernels.hip): Us (mpad, Dp),
 // Ks (mpad, Np), mu (mpad) or null; mpad a multiple of 64; cnt: two counters the first kernel clears
